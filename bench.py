@@ -52,6 +52,12 @@ WORKLOADS = {
 }
 FP64_VECTOR_PEAK_TFLOPS = 78.6   # MI355X fp64 vector peak (MI355X_MICROARCH.md / SURVEY 8d)
 
+# --dump-outputs: the particle state after the last timed step, the free-path histograms and the run's counters
+DUMP_MAX_BYTES = 64 * 10**6                 # all files together (the .npy headers included, with room to spare)
+DUMP_SAMPLE_SEED = 20240607                 # the fixed particle sample taken when the whole state does not fit
+STATE_KEYS = ("x", "y", "z", "vx", "vy", "vz", "d", "dx", "dy", "dz")
+COUNTER_KEYS = ("n_pp", "n_wall", "n_oob_walls", "n_oob_pp", "n_paths")      # (algorithm-independent counters only)
+
 
 def make_workload(name, n_override=None, device=0):
     from argon_monte_carlo_amd import ic as IC
@@ -252,6 +258,40 @@ def committed_traffic(workload, kclass, tag):
     return None, None
 
 
+def timed_outputs(src, stats, energy_sums=None):
+    """What a caller of the timed path holds after its last step: the state (float64, `flag` as float32), the free-path
+    histograms (float64 counts, 4 x bins), the counters summed over the timed steps (float64, COUNTER_KEYS order) and, for
+    the energised walls, the last step's (momentum, energy_cold, energy_hot, had_momentum, had_cold, had_hot).  `src` is
+    the engine or the multi-GPU driver: every rank calls this (the download and the histograms are collectives there).
+    When the state is larger than DUMP_MAX_BYTES allows, a fixed seeded sample of particles is kept and its indices are
+    written as `sample_index` (float64)."""
+    st = src.download()
+    counts, _ = src.histograms()
+    out = {"hist_counts": counts.astype(np.float64),
+           "counters": np.array([stats[k] if stats else 0 for k in COUNTER_KEYS], dtype=np.float64)}
+    if energy_sums is not None:
+        out["energy_sums"] = np.array([float(v) for v in energy_sums], dtype=np.float64)
+    n = len(st["x"])
+    fixed = sum(a.nbytes for a in out.values()) + 64 * 1024          # room for headers and `sample_index`'s own
+    per_particle = 8 * len(STATE_KEYS) + 4
+    if n * per_particle + fixed > DUMP_MAX_BYTES:
+        m = (DUMP_MAX_BYTES - fixed) // (per_particle + 8)
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=m, replace=False))
+        out["sample_index"] = idx.astype(np.float64)
+    else:
+        idx = slice(None)
+    for k in STATE_KEYS:
+        out[k] = np.ascontiguousarray(st[k][idx], dtype=np.float64)
+    out["flag"] = np.ascontiguousarray(st["flag"][idx], dtype=np.float32)
+    return out
+
+
+def write_outputs(directory, outputs):
+    os.makedirs(directory, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(directory, f"{name}.npy"), a)
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` without a launcher: start N ranks (one per GPU) through torch.distributed.run as a CHILD
     process — this parent has made no HIP / torch.cuda call, and it never replaces itself with another program — and pass
@@ -295,7 +335,12 @@ def main():
                     help="temp workloads: opt-in NON-PARITY mode, re-emission directions / gap energies drawn on the GPU (Philox)")
     ap.add_argument("--force-sharded", action="store_true", help="rehearsal: run the sharded driver (and its collectives) even with one rank")
     ap.add_argument("--strong", action="store_true", help="N>1: keep the TOTAL particle count at the workload's size (strong scaling) instead of the per-GPU count")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what they computed (state after the last timed step, histograms, "
+                         "counters) as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(spawn_ranks(args.gpus))
     if args.gpus > 1 and int(os.environ.get("WORLD_SIZE", "1")) != args.gpus:
@@ -371,11 +416,15 @@ def main():
             from argon_monte_carlo_amd.energised import device_rng_config
             p_dev = device_rng_config(c, 17)
 
+        last_sums = []                                  # the last step's momentum / energy sums (--dump-outputs)
+
         def step(k):
             tot = None
             for _ in range(k):
-                st = (eng.temp_timestep_device(c["dt"], p_dev) if p_dev is not None else
-                      eng.temp_timestep(c["dt"], sampler, energies))[0]
+                r = (eng.temp_timestep_device(c["dt"], p_dev) if p_dev is not None else
+                     eng.temp_timestep(c["dt"], sampler, energies))
+                st = r[0]
+                last_sums[:] = r[1:]
                 tot = st if tot is None else {kk: tot[kk] + st[kk] for kk in st}
             return tot
         parallelism = ("single GPU" if not sharded else f"index-range shards x{world}, hits concatenated in index order, "
@@ -437,6 +486,12 @@ def main():
         t = torch.tensor([el], dtype=torch.float64, device="cuda" if args.backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
+    if args.dump_outputs:
+        # before the profiled repeat below moves the state on; outside the timed region
+        src = driver if driver is not None else engines[0]
+        outputs = timed_outputs(src, stats, last_sums if kind == "temp" else None)
+        if rank == 0:
+            write_outputs(args.dump_outputs, outputs)
 
     # per-kernel durations: the same K steps again with every launch bracketed by hipEvents on the launch stream
     eng0 = engines[0]

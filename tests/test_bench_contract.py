@@ -85,5 +85,36 @@ def test_bench_command_line_parses_without_a_gpu():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
     out = r.stdout.decode()
     assert r.returncode == 0, out
-    for flag in ("--gpus", "--steps", "--warmup", "--workload", "--strong", "--force-sharded", "--extra-workloads"):
+    for flag in ("--gpus", "--steps", "--warmup", "--workload", "--strong", "--force-sharded", "--extra-workloads", "--dump-outputs"):
         assert flag in out, flag
+
+
+def test_dump_outputs_keep_the_size_cap_and_a_fixed_sample():
+    """--dump-outputs: float32 / float64 arrays only, at most 64 MB in all, and a state too large for that is reduced to
+    the same seeded particle sample every time (no GPU: a stand-in for the engine's download / histograms)."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+
+    class Src:
+        def __init__(self, n):
+            self.n = n
+
+        def download(self):
+            r = np.random.default_rng(1)
+            st = {k: r.random(self.n) for k in bench.STATE_KEYS}
+            st["flag"] = (r.random(self.n) < 0.5).astype(np.uint8)
+            return st
+
+        def histograms(self):
+            return np.ones((4, 200), dtype=np.uint64), 800
+
+    stats = {k: 7 for k in bench.COUNTER_KEYS}
+    small = bench.timed_outputs(Src(1000), stats)
+    assert "sample_index" not in small and len(small["x"]) == 1000 and list(small["counters"]) == [7.0] * len(bench.COUNTER_KEYS)
+    big = bench.timed_outputs(Src(2_000_000), stats, energy_sums=(1.0, 2.0, 3.0, True, False, True))
+    assert all(a.dtype in (np.float32, np.float64) for a in big.values())
+    assert sum(a.nbytes for a in big.values()) + 128 * len(big) <= bench.DUMP_MAX_BYTES <= 64 * 10**6
+    idx = big["sample_index"].astype(np.int64)
+    assert np.array_equal(big["x"], Src(2_000_000).download()["x"][idx]) and np.all(np.diff(idx) > 0)
+    assert np.array_equal(idx, bench.timed_outputs(Src(2_000_000), stats)["sample_index"])
