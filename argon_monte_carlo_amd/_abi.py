@@ -82,6 +82,18 @@ class AmcTempRng(C.Structure):
                 ("gl_x", C.c_double * 32), ("gl_w", C.c_double * 32)]
 
 
+AMC_FIELDS_CARTESIAN = 0
+AMC_FIELDS_AXISYMMETRIC = 1
+AMC_FIELDS_MAX_BINS = 2048
+
+
+class AmcFieldGrid(C.Structure):
+    """amc_field_grid (include/argonmc.h): the bins of the sampled fields and the sampling cadence."""
+    _fields_ = [("struct_size", C.c_int32), ("kind", C.c_int32), ("n1", C.c_int32), ("n2", C.c_int32), ("n3", C.c_int32),
+                ("reserved", C.c_int32), ("every", C.c_int64), ("step_offset", C.c_int64),
+                ("lo", C.c_double * 3), ("hi", C.c_double * 3)]
+
+
 # numpy dtype with the same layout as amc_path_record
 def path_record_dtype():
     import numpy as np
@@ -91,4 +103,4 @@ def path_record_dtype():
 
 
 AMC_K_NAMES = ["drift_walls", "bin_count", "bin_scan", "bin_scatter", "detect", "resolve", "bounds", "validate",
-               "resolve_more", "commit", "clusters_wide", "fixup"]
+               "resolve_more", "commit", "clusters_wide", "fixup", "fields"]

@@ -8,7 +8,7 @@ import ctypes as C
 import os
 import subprocess
 
-from ._abi import (AMC_ABI_VERSION, AmcIcConfig, AmcParams, AmcPathRecord, AmcStepStats, AmcTempRng)
+from ._abi import (AMC_ABI_VERSION, AmcFieldGrid, AmcIcConfig, AmcParams, AmcPathRecord, AmcStepStats, AmcTempRng)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libargonmc.so")
@@ -72,6 +72,11 @@ SIGNATURES = {
     "amc_kernel_times": (C.c_int, [_ctx, _dp, _i64p]),
     "amc_kernel_name": (C.c_char_p, [C.c_int]),
     "amc_overlap_stats": (C.c_int, [_ctx, _i64p]),
+    "amc_fields_config": (C.c_int, [_ctx, C.POINTER(AmcFieldGrid)]),
+    "amc_fields_sample": (C.c_int, [_ctx]),
+    "amc_fields_read": (C.c_int, [_ctx, _i64p, _i64p, _i64p]),
+    "amc_fields_load": (C.c_int, [_ctx, _i64p, C.c_int64, C.c_int64]),
+    "amc_fields_reset": (C.c_int, [_ctx]),
 }
 
 

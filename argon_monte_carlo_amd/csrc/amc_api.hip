@@ -161,7 +161,8 @@ const char *amc_last_error(const amc_ctx *ctx) { return ctx ? ctx->err.c_str() :
 const char *amc_kernel_name(int k)
 {
     static const char *names[AMC_K_COUNT] = {"drift_walls", "bin_count", "bin_scan",     "bin_scatter", "detect",  "resolve",
-                                             "bounds",      "validate",  "resolve_more", "commit",      "clusters_wide", "fixup"};
+                                             "bounds",      "validate",  "resolve_more", "commit",      "clusters_wide", "fixup",
+                                             "fields"};
     return (k >= 0 && k < AMC_K_COUNT) ? names[k] : "?";
 }
 
@@ -184,6 +185,7 @@ void amc_destroy(amc_ctx *c)
     if (c->T.def_dir) hipFree(c->T.def_dir);
     { void *td[] = {c->TD.idx, c->TD.count, c->TD.t, c->TD.contact, c->TD.normal, c->TD.dir, c->TD.Es, c->TD.dpz, c->TD.dE, c->TD.ok};
       for (void *q : td) if (q) hipFree(q); }
+    amc_fields_free(c);
     if (c->cand_send) hipFree(c->cand_send);
     if (c->cand_recv) hipFree(c->cand_recv);
     if (c->kin_send) hipFree(c->kin_send);
@@ -244,6 +246,7 @@ int amc_create(amc_ctx **out, const amc_params *p)
     c->T.ok = nullptr; c->T.cap = 0; c->T.last_case = -1; c->T.last_n = 0; c->T.pre_case = -1; c->T.pin = nullptr;
     c->T.def_idx = nullptr; c->T.def_dir = nullptr; c->T.def_case = -1; c->T.def_n = 0;
     memset(&c->out, 0, sizeof c->out); memset(&c->h_prev, 0, sizeof c->h_prev);
+    memset(&c->F, 0, sizeof c->F);
     c->d_lay = nullptr; c->d_banks = nullptr; c->d_rec = nullptr; c->d_hist = nullptr; c->d_edges = nullptr;
     c->d_dbg = nullptr; c->w_slab = nullptr; c->s_slab = nullptr;
     c->cw_blocks_env = getenv("AMC_CW_BLOCKS") ? atoi(getenv("AMC_CW_BLOCKS")) : 0;
@@ -635,7 +638,8 @@ static int enqueue_step(amc_ctx *c, double dt, bool fold_prev_bounds = false, bo
         return amc_fail(c, AMC_ERR_INVALID, "energised walls need the host handshake: use the Python driver (amc_wall_hits/apply)");
     }
     c->out.step++;
-    return AMC_OK;
+    // (a step that leaves its post-sweep bounds check to the next pass is never sampled: amc_run does not defer it)
+    return amc_fields_step(c);
 }
 
 int amc_timestep(amc_ctx *c, double dt, amc_step_stats *out)
@@ -777,17 +781,23 @@ int amc_run(amc_ctx *c, double dt, int64_t nsteps, amc_step_stats *sum)
     if (!c->uploaded) return amc_fail(c, AMC_ERR_STATE, "amc_run before amc_upload");
     AMC_HIP(c, hipSetDevice(c->device));
     const bool whole = c->lo == 0 && c->hi == c->n && !c->allpairs;
-    if (c->overlap_mode && whole && nsteps >= 2 && !c->keep_prior && !c->detect_ap && c->n > 0 &&
+    // (sampled fields with a cadence: the plain loop, whose steps end with the state a sample reads)
+    const bool sampling = c->F.on && c->F.g.every > 0;
+    if (c->overlap_mode && whole && nsteps >= 2 && !c->keep_prior && !c->detect_ap && c->n > 0 && !sampling &&
         (c->P.geometry == AMC_GEOM_CUBE || c->P.geometry == AMC_GEOM_PORE)) {
         int rc = run_overlapped(c, dt, nsteps);
         if (rc) return rc;
         return amc_finish_stats(c, sum);
     }
-    // inside the run only the last step needs its own post-sweep bounds pass (needs the whole range in one context)
+    // inside the run only the last step needs its own post-sweep bounds pass (needs the whole range in one context) — and
+    // every step that is sampled: the sample sees the step's final state
     const bool fold = c->P.geometry == AMC_GEOM_PORE && whole;
+    bool deferred = false;
     for (int64_t s = 0; s < nsteps; s++) {
-        int rc = enqueue_step(c, dt, fold && s > 0, fold && s + 1 < nsteps);
+        const bool defer = fold && s + 1 < nsteps && !amc_fields_due(c, (int64_t)c->out.step + 1);
+        int rc = enqueue_step(c, dt, deferred, defer);
         if (rc) return rc;
+        deferred = defer;
     }
     return amc_finish_stats(c, sum);
 }

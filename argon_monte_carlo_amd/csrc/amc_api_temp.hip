@@ -362,6 +362,7 @@ int amc_temp_end(amc_ctx *c, amc_step_stats *out)
     if (rc) return rc;
     AMC_HIP(c, amc_launch_stream(c, 0.0, AMC_ST_BOUNDS, 1));        // Temp:844
     c->out.step++;
+    if ((rc = amc_fields_step(c))) return rc;
     return amc_finish_stats(c, out);
 }
 

@@ -55,3 +55,11 @@ AMC_INTERNAL int amc_finish_stats(amc_ctx *c, amc_step_stats *out);     // per-s
 AMC_INTERNAL int amc_publish_velocities(amc_ctx *c);                    // multi-GPU: vpub = current velocities (after an upload)
 AMC_INTERNAL int amc_flush(amc_ctx *c);                                 // write deferred sweep results to the particle arrays
 AMC_INTERNAL int amc_enqueue_sweep(amc_ctx *c, bool counted = false, bool defer_commit = false);   // bin (unless counted) + detect + resolve
+AMC_INTERNAL int amc_fields_step(amc_ctx *c);                         // the cadence hook after a completed step (amc_fields.hip)
+AMC_INTERNAL void amc_fields_free(amc_ctx *c);
+
+// a sample is due after the step that leaves the step counter at `step`
+static inline bool amc_fields_due(const amc_ctx *c, int64_t step)
+{
+    return c->F.on && c->F.g.every > 0 && (step + c->F.g.step_offset) % c->F.g.every == 0;
+}

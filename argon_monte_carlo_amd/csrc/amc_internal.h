@@ -180,6 +180,19 @@ struct amc_temp_dev_ws {
     std::vector<unsigned char> h_ok[7];
 };
 
+// sampled fields (amc_fields.hip): the grid, the per-workgroup slab rows of one sample and the 128-bit running totals
+struct amc_fields_ws {
+    bool on;
+    amc_field_grid g;
+    int bins;                   // n1 * n2 * n3
+    double w[3];                // bin widths (hi - lo) / n, fp64 like NumPy
+    int max_blocks;             // slab rows allocated (AMC_FIELDS_BLOCKS, else the number of CUs)
+    int blocks_env;             // AMC_FIELDS_BLOCKS at configuration (0: by particle count)
+    unsigned long long *slab;   // [max_blocks][bins * 7 + 1] one sample's sums per workgroup (+ particles outside)
+    unsigned long long *tot;    // [bins][7][2] running totals, (low, high) words
+    unsigned long long *meta;   // [0] samples, [1] particles outside, [2] lowest particle index out of range (~0: none)
+};
+
 struct amc_ctx {
     amc_params P;
     int device;
@@ -216,6 +229,7 @@ struct amc_ctx {
     char *s_slab;             // the one allocation the particle state arrays are carved from
     amc_temp_ws T;
     amc_temp_dev_ws TD;
+    amc_fields_ws F;
     bool allpairs;            // no detection grid at all (single cells, N <= 4096): all-pairs detector, brute-force validation
     bool detect_ap;           // candidates come from the LDS-tiled all-pairs kernel (always without a grid; with one when detect_mode == 2)
     // outputs

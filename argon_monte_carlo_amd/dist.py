@@ -215,6 +215,27 @@ class ShardedSimulation:
             out[k] = torch.cat(parts).numpy()
         return out
 
+    # ---- sampled fields (fields.py): every rank samples its own shard, the totals are summed exactly ---------------------
+    def enable_fields(self, grid=None, every=0):
+        from . import fields as FL
+        g = FL.default_grid(self.params) if grid is None else grid
+        self.engine.fields_config(FL.copy_grid(g, every=every))
+
+    def fields_sample(self):
+        self.engine.fields_sample()
+
+    def fields(self):
+        """Simulation.fields() of the whole system (a collective: every rank calls it).  The ranks' 128-bit totals are summed
+        as 32-bit limbs in int64 all-reduces — exact, never through floats — so the integers equal a single engine's."""
+        from . import fields as FL
+        tot, ns, no = self.engine.fields_read()
+        if self.world > 1:
+            limbs = FL.words_to_limbs(tot)
+            flat = self.comm.allreduce_sum_ints([int(v) for v in limbs.ravel()] + [int(no)])
+            tot = FL.limbs_to_words(np.array(flat[:-1], dtype=np.int64).reshape(limbs.shape))
+            no = flat[-1]
+        return FL.derive(self.engine.field_grid, tot, ns, no, float(self.params.argon_mass), FL.boltzmann_constant(self.params))
+
     def histograms(self):
         """Global free-path histograms = sum over ranks (every completed path is emitted by its particle's owner)."""
         counts, tot = self.engine.histograms()

@@ -6,9 +6,10 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._abi import (AMC_K_NAMES, AmcParams, AmcPathRecord, AmcStepStats, path_record_dtype)
+from ._abi import (AMC_K_NAMES, AmcFieldGrid, AmcParams, AmcPathRecord, AmcStepStats, path_record_dtype)
 
 _dp = C.POINTER(C.c_double)
+_i64p = C.POINTER(C.c_int64)
 
 
 def _d(a):
@@ -29,6 +30,7 @@ class Engine:
         self.lib = _lib.load()
         self.params = params
         self.n = int(params.n)
+        self.field_grid = None
         self._ctx = C.c_void_p()
         rc = self.lib.amc_create(C.byref(self._ctx), C.byref(params))
         if rc != 0:
@@ -144,6 +146,36 @@ class Engine:
 
     def reset_outputs(self):
         self._ck(self.lib.amc_reset_outputs(self._ctx))
+
+    # -- sampled fields (fields.py) --------------------------------------------------------------------------------
+    def fields_config(self, grid):
+        """Sample on ``grid`` (an ``AmcFieldGrid``, fields.make_grid); None switches sampling off.  Starts from zero totals."""
+        self._ck(self.lib.amc_fields_config(self._ctx, None if grid is None else C.byref(grid)))
+        self.field_grid = None if grid is None else AmcFieldGrid.from_buffer_copy(grid)
+
+    def fields_sample(self):
+        """One sample of the current state, enqueued on the context's stream."""
+        self._ck(self.lib.amc_fields_sample(self._ctx))
+
+    def fields_read(self):
+        """(int64[bins, 7, 2] totals as (low, high) words, samples, particles outside); synchronises."""
+        g = self.field_grid
+        if g is None:
+            raise _lib.ArgonMCError(-6, "fields_read before fields_config")
+        tot = np.zeros((int(g.n1) * int(g.n2) * int(g.n3), 7, 2), dtype=np.int64)
+        ns, no = C.c_int64(0), C.c_int64(0)
+        self._ck(self.lib.amc_fields_read(self._ctx, tot.ctypes.data_as(_i64p), C.byref(ns), C.byref(no)))
+        return tot, ns.value, no.value
+
+    def fields_load(self, totals, n_samples, n_outside):
+        tot = np.ascontiguousarray(totals, dtype=np.int64)
+        g = self.field_grid
+        if g is None or tot.size != int(g.n1) * int(g.n2) * int(g.n3) * 14:
+            raise ValueError("totals do not match the configured grid")
+        self._ck(self.lib.amc_fields_load(self._ctx, tot.ctypes.data_as(_i64p), int(n_samples), int(n_outside)))
+
+    def fields_reset(self):
+        self._ck(self.lib.amc_fields_reset(self._ctx))
 
     # -- measurement -----------------------------------------------------------------------------------------------
     def set_stream(self, stream_ptr):

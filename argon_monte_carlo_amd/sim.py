@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from . import fields as FL
 from . import ic as IC
 from . import outputs as OUT
 from . import params as PR
@@ -125,6 +126,51 @@ class Simulation:
         dens, edges = self.histograms()
         OUT.write_histograms(directory, dens, edges)
 
+    # ---- sampled fields (fields.py; the reference has no such output) ---------------------------------------
+    def enable_fields(self, grid=None, every=0):
+        """Sample number density, flow velocity and temperature per bin of ``grid`` (fields.make_grid; None = the geometry's
+        default, fields.default_grid) after every ``every``-th step (0: only on ``fields_sample()``).  Starts from zero."""
+        g = FL.default_grid(self.params) if grid is None else grid
+        # (the device's step counter restarts at a resumed checkpoint: the cadence counts from the run's first step)
+        self.engine.fields_config(FL.copy_grid(g, every=every, step_offset=getattr(self, "_step_base", 0)))
+
+    def disable_fields(self):
+        self.engine.fields_config(None)
+
+    def fields_sample(self):
+        """One sample of the current state now (asynchronous)."""
+        self.engine.fields_sample()
+
+    def fields_reset(self):
+        self.engine.fields_reset()
+
+    def fields(self):
+        """dict: count, number_density (m^-3), velocity and temperature (bins x 3: x, y, z components on a Cartesian grid,
+        r, theta, z on an axisymmetric one), T (mean of the three), edges, bin_volume, n_samples, n_outside and the raw
+        integer totals (int64[bins, 7, 2], 128-bit (low, high) words).  Bins in linear order (i1 * n2 + i2) * n3 + i3."""
+        tot, ns, no = self.engine.fields_read()
+        return FL.derive(self.engine.field_grid, tot, ns, no, float(self.params.argon_mass), FL.boltzmann_constant(self.params))
+
+    def write_fields(self, path):
+        """The dict of ``fields()`` as an .npz (edges as edges_1, edges_2[, edges_3])."""
+        f = self.fields()
+        e = f.pop("edges")
+        np.savez(path, **f, **{f"edges_{k + 1}": v for k, v in enumerate(e)})
+
+    def _fields_checkpoint(self):
+        if self.engine.field_grid is None:
+            return {}
+        tot, ns, no = self.engine.fields_read()
+        return dict(fields_grid=FL.grid_to_array(self.engine.field_grid), fields_totals=tot, fields_n_samples=int(ns),
+                    fields_n_outside=int(no))
+
+    def _fields_restore(self, z):
+        if "fields_grid" in z:
+            self.engine.fields_config(FL.copy_grid(FL.grid_from_array(z["fields_grid"]), step_offset=self._step_base))
+            self.engine.fields_load(z["fields_totals"], int(z["fields_n_samples"]), int(z["fields_n_outside"]))
+        elif self.engine.field_grid is not None:      # fields on here, not in the checkpoint: they start with the resumed run
+            self.engine.fields_config(FL.copy_grid(self.engine.field_grid, step_offset=self._step_base))
+
     # ---- checkpoint / resume (the reference has none: a 10^4-step run is one process lifetime there) ---------------
     def _checkpoint_extra(self):
         return {}
@@ -134,7 +180,8 @@ class Simulation:
 
     def save_checkpoint(self, path):
         """Everything a later ``load_checkpoint`` needs to continue bit-identically: the particle arrays, the
-        completed-path lists, the device histograms and the counters (+ RNG streams and per-step lists for Temp)."""
+        completed-path lists, the device histograms and the counters (+ RNG streams and per-step lists for Temp, + the
+        grid and the totals of the sampled fields when they are on)."""
         st = self.engine.download()
         self._collect()
         counts, _ = self.engine.histograms()
@@ -147,7 +194,7 @@ class Simulation:
                  completed_y_paths=np.array(self.completed_y_paths, dtype=np.float64),
                  completed_z_paths=np.array(self.completed_z_paths, dtype=np.float64),
                  total_cols=int(self.total_cols), steps_done=int(self.steps_done),
-                 **{f"state_{k}": v for k, v in st.items()}, **self._checkpoint_extra())
+                 **{f"state_{k}": v for k, v in st.items()}, **self._checkpoint_extra(), **self._fields_checkpoint())
 
     def load_checkpoint(self, path):
         z = np.load(path if str(path).endswith(".npz") else str(path) + ".npz", allow_pickle=False)
@@ -163,8 +210,10 @@ class Simulation:
         self.completed_y_paths = z["completed_y_paths"].tolist()
         self.completed_z_paths = z["completed_z_paths"].tolist()
         self.total_cols, self.steps_done = int(z["total_cols"]), int(z["steps_done"])
+        self._step_base = self.steps_done           # (reset_outputs restarted the device's step counter)
         self._cache = None
         self._restore_extra(z)
+        self._fields_restore(z)
 
     def close(self):
         self.engine.close()

@@ -354,7 +354,8 @@ int amc_mg_finish(amc_ctx *ctx, amc_step_stats *out);      /* out == NULL: no ho
 #define AMC_K_COMMIT 9           /* k_commit: a sweep's commit as a launch of its own (else it rides along with the next k_stream) */
 #define AMC_K_CLUSTERS_WIDE 10   /* k_clusters_wide: every small cluster emulated and validated wide, before the ordered workgroup */
 #define AMC_K_FIXUP 11           /* k_fixup: joins an overlapped run's early streaming pass with the sweep's results (below) */
-#define AMC_K_COUNT 12
+#define AMC_K_FIELDS 12          /* k_fields_accum + k_fields_reduce: one sample of the fields (below) */
+#define AMC_K_COUNT 13
 int amc_profile(amc_ctx *ctx, int enable);
 int amc_kernel_times(amc_ctx *ctx, double *total_ms /*[AMC_K_COUNT]*/, int64_t *launches /*[AMC_K_COUNT]*/);
 const char *amc_kernel_name(int k);
@@ -365,6 +366,46 @@ const char *amc_kernel_name(int k);
  * had already advanced them (advanced again from the sweep's result and filed under an extra list node), out[2] = mode,
  * out[3] = extra list nodes available per step. */
 int amc_overlap_stats(amc_ctx *ctx, int64_t *out /*[4]*/);
+
+/* ---- sampled fields: number density, flow velocity, temperature per spatial bin (opt-in) -----------
+ * The reference has no such output.  A sample bins every particle of the context's range [lo, hi) and adds, per bin,
+ * seven exact integers: count, sum q1(c_k) and sum q2(c_k) for the three components, with
+ *   q1(c) = llrint(c * 2^24),  q2(c) = llrint((c * c) * 2^10)      (round half to even, IEEE double, no FMA)
+ * Cartesian grid: c = (vx, vy, vz).  Axisymmetric grid (axis x = y = 0): r = sqrt(x*x + y*y) and, for r > 0,
+ * c = ((x*vx + y*vy) / r, (x*vy - y*vx) / r, vz), for r == 0 c = (vx, vy, vz).
+ * Bin per axis: w = (hi - lo) / n, i = floor((u - lo) / w); i == n with u <= hi counts as n - 1; i < 0, i >= n or NaN:
+ * the particle is outside (it only adds to n_outside).  Linear bin (i1 * n2 + i2) * n3 + i3.
+ * Valid range: |c| < 2^14 m/s for every binned particle and at most 2^24 particles per sample: one sample's sums then
+ * stay below 2^62.  They are added into signed 128-bit totals per (bin, quantity): (low 64 bits, high 64 bits signed).
+ * Everything is integer, so the totals do not depend on launch configuration or order.
+ * A binned particle out of range stops the accumulation: amc_fields_read fails with AMC_ERR_CAPACITY naming the
+ * lowest such particle index until amc_fields_reset / amc_fields_load / amc_fields_config. */
+#define AMC_FIELDS_CARTESIAN 0
+#define AMC_FIELDS_AXISYMMETRIC 1
+#define AMC_FIELDS_MAX_BINS 2048
+typedef struct amc_field_grid {
+    int32_t struct_size;          /* sizeof(amc_field_grid)                                                      */
+    int32_t kind;                 /* AMC_FIELDS_CARTESIAN | AMC_FIELDS_AXISYMMETRIC                              */
+    int32_t n1, n2, n3;           /* bins per axis, n1 * n2 * n3 <= AMC_FIELDS_MAX_BINS; axisymmetric: n3 == 1   */
+    int32_t reserved;             /* 0                                                                           */
+    int64_t every;                /* > 0: a sample after every completed step whose step counter (the one path
+                                     records carry) + step_offset is a multiple of `every`; 0: amc_fields_sample only */
+    int64_t step_offset;          /* steps before the counter's origin (a run resumed after amc_reset_outputs)   */
+    double lo[3], hi[3];          /* Cartesian: [lo_k, hi_k] per axis.  Axisymmetric: r in [0, hi[0]] (lo[0] == 0),
+                                     z in [lo[1], hi[1]]; lo[2], hi[2] unused                                    */
+} amc_field_grid;
+/* NULL disables sampling.  A (new) grid starts from zero totals.  The cadence hooks every completed step:
+ * amc_timestep, each step of amc_run (which then takes the plain, not the overlapped, loop), amc_temp_end and
+ * amc_mg_finish.  A sample sees the step's final state. */
+int amc_fields_config(amc_ctx *ctx, const amc_field_grid *grid);
+/* one sample of the current state, enqueued on the context's stream (no synchronisation) */
+int amc_fields_sample(amc_ctx *ctx);
+/* totals[bins][7][2] (quantities count, q1 x3, q2 x3; words low, high), samples taken, particles outside; synchronises */
+int amc_fields_read(amc_ctx *ctx, int64_t *totals, int64_t *n_samples, int64_t *n_outside);
+/* the inverse of amc_fields_read (checkpoints) */
+int amc_fields_load(amc_ctx *ctx, const int64_t *totals, int64_t n_samples, int64_t n_outside);
+/* zero totals and counters (amc_reset_outputs leaves them alone) */
+int amc_fields_reset(amc_ctx *ctx);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,77 @@
+"""Cost of the sampled fields on one GPU: the per-sample kernel time (kernel class "fields": k_fields_accum +
+k_fields_reduce, timed on the dispatch like every other class) and the overhead of run(100) with a sample every 10 steps
+against run(100) without sampling.  Prints one JSON line per workload.
+
+    python tools/fields_cost.py [--reps 5]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from argon_monte_carlo_amd import fields as FL  # noqa: E402
+from argon_monte_carlo_amd import ic as IC  # noqa: E402
+from argon_monte_carlo_amd import params as PR  # noqa: E402
+from argon_monte_carlo_amd.sim import Simulation  # noqa: E402
+
+WORKLOADS = [("pore", 1_000_000), ("cube", 100_000)]
+
+
+def measure(kind, n, reps, steps=100, every=10, samples=50):
+    # the benchmark's set-up (bench.py make_workload): count-and-continue on a degenerate solve, histograms only
+    if kind == "cube":
+        p, c = PR.cube_params_for_n(n)
+        init = IC.cube_ic(p, c, seed=127)
+    else:
+        p, c = PR.pore_params(n=n)
+        init = IC.pore_ic(p, c, seed=17)
+    p.reserved1 = 1
+    p.max_paths = -1
+    sim = Simulation(kind, params=p, consts=c)
+    sim.set_state(*init)
+    g = FL.default_grid(sim.params)
+    # 1. one sample, kernel time on the dispatch
+    sim.enable_fields(g)
+    for _ in range(5):
+        sim.fields_sample()
+    sim.engine.synchronize()
+    sim.engine.profile(True)
+    for _ in range(samples):
+        sim.fields_sample()
+    sim.engine.synchronize()
+    ms, launches = sim.engine.kernel_times()["fields"]
+    sim.engine.profile(False)
+    per_sample_us = 1e3 * ms / (launches / 2)
+    # 2. run(steps) with and without a sample every `every` steps, alternating
+    sim.run(10)
+    t_off, t_on = [], []
+    for _ in range(reps):
+        for on in (False, True):
+            if on:
+                sim.enable_fields(g, every=every)
+            else:
+                sim.disable_fields()
+            t0 = time.perf_counter()
+            sim.run(steps)
+            (t_on if on else t_off).append(time.perf_counter() - t0)
+    off, on = statistics.median(t_off), statistics.median(t_on)
+    sim.close()
+    return {"workload": f"{kind}_{n:.0e}".replace("+0", ""), "grid": [g.n1, g.n2, g.n3], "bins": FL.grid_bins(g),
+            "sample_us": round(per_sample_us, 2), "run_ms_off": round(1e3 * off, 3), "run_ms_on": round(1e3 * on, 3),
+            "every": every, "steps": steps, "overhead_pct": round(100.0 * (on - off) / off, 2), "reps": reps}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    args = ap.parse_args()
+    for kind, n in WORKLOADS:
+        print(json.dumps(measure(kind, n, args.reps)), flush=True)
+
+
+if __name__ == "__main__":
+    main()
