@@ -205,7 +205,8 @@ __global__ __launch_bounds__(256, AMC_DETECT_MINW) void k_detect_lists(amc_grid 
 // overlaps, its own cell included, and keeps the pairs whose partner has the lower index — so a pair is found exactly once
 // in the whole job, by the rank that owns its higher index.  The pairs go into the rank's block of a second, small
 // all-gather ([0] = count, then (i, j) as two 32-bit integers each); k_ingest_candidates then builds the candidate graph
-// from the blocks of all ranks, identically everywhere, and the (replicated) resolve proceeds as on one GPU.
+// from the blocks of all ranks, identically everywhere, and the (replicated) resolve proceeds as on one GPU.  A block that
+// overflows its cap is flagged here by its owner and again by every rank's ingest, so the step fails on all ranks alike.
 __global__ __launch_bounds__(256) void k_detect_own(amc_grid G, amc_lists B, long long lo, long long hi, double cr2i,
                                                     double cr_probe, int *__restrict__ out, int cap, amc_dev_counters *cnt)
 {
@@ -271,7 +272,12 @@ __global__ __launch_bounds__(256) void k_ingest_candidates(const int *__restrict
     for (int r = 0; r < world; r++) {
         const int *b = blocks + (size_t)r * block_ints;
         int nr = b[0];
-        if (nr > cap) nr = cap;
+        // a block that overflowed (its count runs past cap) is truncated everywhere: every rank reads every block, so every
+        // rank flags the same step and reports AMC_ERR_CAPACITY with its owner, none resolves a partial graph silently
+        if (nr > cap) {
+            nr = cap;
+            if (gtid == 0) atomicOr(&cnt->flags, 1ULL);
+        }
         for (int k = gtid; k < nr; k += gstride) amc_push_candidate(b[2 + 2 * k], b[3 + 2 * k], max_cand, cnt, D);
     }
     if (gtid == 0) own[0] = 0;          // (this rank's block has been gathered: its counter is cleared for the next step)

@@ -224,16 +224,44 @@ class ShardedSimulation:
     def fields_sample(self):
         self.engine.fields_sample()
 
+    def fields_reset(self):
+        self.engine.fields_reset()
+
     def fields(self):
         """Simulation.fields() of the whole system (a collective: every rank calls it).  The ranks' 128-bit totals are summed
-        as 32-bit limbs in int64 all-reduces — exact, never through floats — so the integers equal a single engine's."""
+        as 32-bit limbs in int64 all-reduces — exact, never through floats — so the integers equal a single engine's.
+        A read that fails on one rank (a particle out of the sampler's range lives on one shard) fails on every rank, from
+        this same call: the failing rank still takes part in the all-reduce, whose first ``world`` entries carry each rank's
+        status — 0, the bad particle's index + 1, or the (negative) error code of any other failure."""
         from . import fields as FL
-        tot, ns, no = self.engine.fields_read()
-        if self.world > 1:
-            limbs = FL.words_to_limbs(tot)
-            flat = self.comm.allreduce_sum_ints([int(v) for v in limbs.ravel()] + [int(no)])
-            tot = FL.limbs_to_words(np.array(flat[:-1], dtype=np.int64).reshape(limbs.shape))
-            no = flat[-1]
+        if self.world == 1:
+            tot, ns, no = self.engine.fields_read()
+            return FL.derive(self.engine.field_grid, tot, ns, no, float(self.params.argon_mass), FL.boltzmann_constant(self.params))
+        import re
+        from ._abi import AMC_ERR_CAPACITY
+        from ._lib import ArgonMCError
+        status = [0] * self.world
+        err = None
+        try:
+            tot, ns, no = self.engine.fields_read()
+        except ArgonMCError as e:
+            if self.engine.field_grid is None:      # (not configured: there is no shape to take part with)
+                raise
+            err = e
+            tot, ns, no = np.zeros((FL.grid_bins(self.engine.field_grid), 7, 2), dtype=np.int64), 0, 0
+            m = re.search(r"particle (\d+) ", str(e))
+            status[self.rank] = int(m.group(1)) + 1 if (m and e.code == AMC_ERR_CAPACITY) else min(int(e.code), -1)
+        limbs = FL.words_to_limbs(tot)
+        flat = self.comm.allreduce_sum_ints(status + [int(v) for v in limbs.ravel()] + [int(no)])
+        failed = [(r, s) for r, s in enumerate(flat[:self.world]) if s != 0]
+        if failed:
+            r, s = failed[0]
+            if s > 0:
+                raise ArgonMCError(AMC_ERR_CAPACITY, f"amc_fields: particle {s - 1} (rank {r}) has a velocity component outside "
+                                                     "|c| < 2^14 m/s (or NaN); sampling stopped until fields_reset") from err
+            raise ArgonMCError(s, f"fields_read failed on rank {r}") from err
+        tot = FL.limbs_to_words(np.array(flat[self.world:-1], dtype=np.int64).reshape(limbs.shape))
+        no = flat[-1]
         return FL.derive(self.engine.field_grid, tot, ns, no, float(self.params.argon_mass), FL.boltzmann_constant(self.params))
 
     def histograms(self):

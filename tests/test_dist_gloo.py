@@ -14,8 +14,11 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from argon_monte_carlo_amd import fields as FL
 from argon_monte_carlo_amd import params as PR
+from argon_monte_carlo_amd._lib import ArgonMCError
 from argon_monte_carlo_amd.dist import ShardedSimulation, TorchComm, shard_range
+from tests.test_gpu_dist import _assert_same_error, _outcome, _run_ranks_outcomes
 
 KEYS = ["x", "y", "z", "vx", "vy", "vz", "d", "dx", "dy", "dz"]
 
@@ -159,6 +162,31 @@ class NumpyShardEngine:
     def mg_finish(self, want_stats=True):
         return dict(n_pp=self.ncand if self.lo == 0 else 0, n_wall=self.hi - self.lo, n_oob_walls=0, n_oob_pp=0,
                     n_paths=0, n_candidates=self.ncand, n_clusters=0, n_rounds=1, n_fp_errors=0, flags=0)
+
+    # -- sampled fields (fake totals: the shard's particle count in bin 0).  As on the device, a sample that meets a velocity
+    # component outside |c| < 2^14 stops the sampling, and fields_read raises on the rank that owns the particle
+    def fields_config(self, grid):
+        self.field_grid = grid
+        self.fields_reset()
+
+    def fields_reset(self):
+        self.f_tot = np.zeros((FL.grid_bins(self.field_grid), 7, 2), dtype=np.int64)
+        self.f_samples, self.f_bad = 0, -1
+
+    def fields_sample(self):
+        v = np.stack([self.a[k][self.lo:self.hi] for k in ("vx", "vy", "vz")])
+        bad = np.flatnonzero(~(np.abs(v) < 2.0 ** 14).all(axis=0))
+        if self.f_bad < 0 and len(bad):
+            self.f_bad = self.lo + int(bad[0])
+        if self.f_bad < 0:
+            self.f_tot[0, 0, 0] += self.hi - self.lo
+            self.f_samples += 1
+
+    def fields_read(self):
+        if self.f_bad >= 0:
+            raise ArgonMCError(-4, f"amc_fields: particle {self.f_bad} has a velocity component outside |c| < 2^14 m/s (or NaN); "
+                                   "sampling stopped until amc_fields_reset")
+        return self.f_tot.copy(), self.f_samples, 0
 
 
 def make_state(n, seed=5):
@@ -330,3 +358,39 @@ def test_energised_walls_two_ranks_equal_one_rank():
     assert out == ref_out                                                       # per-step momentum / energy sums, bitwise
     for k in KEYS:
         assert np.array_equal(got[k].view(np.int64), ref[k].view(np.int64)), k
+
+
+# ---- an error on one shard is an error on every rank ---------------------------------------------------------------------------
+def _fields_body(at, rank, world, n, bad):
+    """fields() with a particle out of the sampler's range on one shard, after fields_reset, and of a clean state again."""
+    p, _ = PR.cube_params(n=n)
+    lo, hi = shard_range(n, rank, world)
+    sim = ShardedSimulation(p, rank, world, engine=NumpyShardEngine(n, lo, hi, 3.385137501286538e-10), comm=TorchComm(rank, world))
+    state = make_state(n)
+    state[3] = state[3].copy()
+    state[3][bad] = 2.0 ** 14
+    sim.upload(*state)
+    sim.enable_fields()
+    sim.fields_sample()
+    first = _outcome(lambda at: sim.fields())
+    sim.fields_reset()
+    second = _outcome(lambda at: sim.fields())
+    sim.upload(*make_state(n))
+    sim.fields_sample()
+    third = _outcome(lambda at: sim.fields())
+    return [(o if o[0] != "ok" else ("ok", o[1]["n_samples"], o[1]["count"].tolist())) for o in (first, second, third)]
+
+
+@pytest.mark.parametrize("n,world,bad", [(251, 2, 200), (251, 3, 90)])
+def test_field_sample_out_of_range_on_one_shard_raises_on_every_rank(n, world, bad):
+    """One rank's fields_read fails (a velocity component at 2^14 m/s in its shard): every rank must raise the same
+    ArgonMCError naming the particle from the same fields() call — not the owner raise while the others wait in the
+    all-reduce — and a fields() after fields_reset() must then succeed everywhere."""
+    assert shard_range(n, 1, world)[0] <= bad < shard_range(n, 1, world)[1]
+    outs = _run_ranks_outcomes(world, _fields_body, (n, bad), timeout=150.0)
+    assert all(o[0] == "ok" for o in outs), outs
+    _assert_same_error([o[1][0] for o in outs], -4, f"particle {bad} ")
+    counts = [0] * (8 * 8 * 8)
+    assert all(o[1][1] == ("ok", 0, counts) for o in outs), outs
+    counts[0] = n
+    assert all(o[1][2] == ("ok", 1, counts) for o in outs), outs

@@ -115,6 +115,93 @@ def _free_port():
     return port
 
 
+# ---- every rank's outcome: an error on one rank must be the same error on all of them, raised from the same call -----------
+COLLECTIVE_TIMEOUT_S = 60
+
+
+def _outcome(fn):
+    """("ok", fn(at)) or ("raised", step, code, message).  ``at`` is a one-element list in which ``fn`` keeps the step it is
+    in; a rank left waiting in a collective ends with gloo's own timeout error (code None) instead of waiting forever."""
+    at = [None]
+    try:
+        return ("ok", fn(at))
+    except Exception as e:
+        return ("raised", at[0], getattr(e, "code", None), str(e))
+
+
+def _outcome_worker(rank, world, port, body, args, q):
+    try:
+        from datetime import timedelta
+        os.environ["MASTER_ADDR"] = "127.0.0.1"
+        os.environ["MASTER_PORT"] = str(port)
+        dist.init_process_group("gloo", rank=rank, world_size=world, timeout=timedelta(seconds=COLLECTIVE_TIMEOUT_S))
+        try:
+            q.put((rank, _outcome(lambda at: body(at, rank, world, *args))))
+        finally:
+            dist.destroy_process_group()
+    except BaseException as e:
+        import traceback
+        q.put((rank, ("error", f"rank {rank}: {e!r}\n{traceback.format_exc()}")))
+        raise
+
+
+def _run_ranks_outcomes(world, body, args=(), timeout=300.0):
+    """Start `world` ranks, each running ``body(at, rank, world, *args)`` under _outcome; return EVERY rank's outcome, in
+    rank order.  A rank that dies without reporting, or ranks that have not all reported after `timeout` seconds, fail
+    the test; whatever happens, no child process outlives the call."""
+    import queue
+    import time
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_outcome_worker, args=(r, world, port, body, tuple(args), q)) for r in range(world)]
+    for pr in procs:
+        pr.start()
+    try:
+        got = {}
+        t0 = time.time()
+        while len(got) < world:
+            try:
+                r, out = q.get(timeout=1.0)
+                got[r] = out
+                continue
+            except queue.Empty:
+                pass
+            dead = [r for r, pr in enumerate(procs) if pr.exitcode not in (None, 0) and r not in got]
+            if dead:
+                try:
+                    r, out = q.get(timeout=2.0)         # its error message, if it got that far
+                    got[r] = out
+                    continue
+                except queue.Empty:
+                    pytest.fail(f"rank {dead[0]} exited with code {procs[dead[0]].exitcode} without a result")
+            if time.time() - t0 > timeout:
+                pytest.fail(f"ranks {sorted(set(range(world)) - set(got))} have no result after {timeout:.0f} s; the others: "
+                            f"{ {r: (o if o[0] != 'ok' else 'ok') for r, o in got.items()} }")
+        for r in range(world):
+            if got[r][0] == "error":
+                pytest.fail(got[r][1])
+        for pr in procs:
+            pr.join(timeout=60)
+            assert pr.exitcode == 0
+        return [got[r] for r in range(world)]
+    finally:
+        for pr in procs:
+            if pr.is_alive():
+                pr.terminate()
+        for pr in procs:
+            pr.join(timeout=10)
+            if pr.is_alive():
+                pr.kill()
+
+
+def _assert_same_error(outs, code, text):
+    """Every rank raised, from the same step, the same error code and message, which contains `text`."""
+    assert all(o[0] == "raised" for o in outs), outs
+    assert len({o[1:] for o in outs}) == 1, outs
+    assert outs[0][2] == code and text in outs[0][3], outs[0]
+
+
 @pytest.mark.parametrize("kind,n,steps,world", [("cube", 30000, 8, 2), ("pore", 60001, 6, 2), ("cube", 400000, 5, 2),   # equal / unequal shards; large-sweep plan
                                                 ("cube", 200000, 40, 2), ("pore", 500001, 30, 2),   # longer runs: deferred commits, slot release
                                                 ("cube", 100003, 10, 3)])                           # three ranks, unequal shards
@@ -264,3 +351,256 @@ def test_energised_walls_two_ranks_one_gpu_equal_single_engine(n, steps):
     assert rows == ref_rows, (rows, ref_rows)
     for k in KEYS:
         assert np.array_equal(full[k], ref[k]), (k, np.flatnonzero(full[k] != ref[k])[:5])
+
+
+# ---- tiny and empty shards (N < world: ranks that own nothing) against the CPU oracle --------------------------------------------
+TINY_NS = (0, 1, 2, 3, 17, 257)
+TINY_STEPS = 7                  # (the pore keeps its per-cell lists for 4 steps: the 7 cross a full rebuild)
+
+
+def _tiny_case(kind, n):
+    """Tiny systems packed so that they collide: a blob at ~20 % volume fraction (17 and 257 particles: clusters and
+    chains), 2 and 3 particles 0.7 collision ranges apart on a line.  The cube runs at dt = 2e-14 s (its own dt would
+    scatter the blob in one step), the pore at its own."""
+    from argon_monte_carlo_amd import params as PR
+    p, c = PR.cube_params(n=n) if kind == "cube" else PR.pore_params(n=n)
+    p.detect_mode = 1           # (the grid detector at any size: the multi-GPU path refuses the gridless one)
+    cr = p.collision_range
+    rng = np.random.default_rng(n + 5)
+    side = (max(n, 1) * (4.0 / 3.0) * np.pi * (cr / 2) ** 3 / 0.2) ** (1.0 / 3.0)
+    pos = rng.random((3, n)) * (side if n > 3 else 0.1 * cr)
+    if n <= 3:
+        pos[0] += 0.7 * cr * np.arange(n)
+    pos += np.array([[49e-9], [49e-9], [49e-9]]) if kind == "cube" else np.array([[0.0], [0.0], [1.5e-6]])
+    vel = rng.normal(size=(3, n)) * 300.0
+    dt = 2e-14 if kind == "cube" else c["dt"]
+    return p, dt, (pos[0], pos[1], pos[2], vel[0], vel[1], vel[2])
+
+
+def _tiny_shards_body(at, rank, world, cases):
+    """Every case on a fresh ShardedSimulation: the assembled state and the summed counters after every step, then the
+    global histograms."""
+    from argon_monte_carlo_amd.dist import ShardedSimulation
+    out = []
+    for kind, n, replicated in cases:
+        p, dt, init = _tiny_case(kind, n)
+        sim = ShardedSimulation(p, rank, world, backend="gloo", replicated_detect=replicated)
+        try:
+            sim.upload(*init)
+            steps = []
+            for s in range(TINY_STEPS):
+                at[0] = (kind, n, replicated, s)
+                st = sim.timestep(dt)
+                steps.append((sim.download(), {k: st[k] for k in ("n_pp", "n_wall", "n_paths")}))
+            out.append((steps, sim.histograms()))
+        finally:
+            sim.engine.close()
+    return out
+
+
+@pytest.fixture(scope="module")
+def tiny_reference():
+    """(kind, n) -> (the oracle's (state, counters) after every step, a single Engine's histograms)."""
+    from argon_monte_carlo_amd.engine import Engine
+    from oracle import oracle
+    ref = {}
+    for kind in ("cube", "pore"):
+        for n in TINY_NS:
+            p, dt, init = _tiny_case(kind, n)
+            orc = oracle.Oracle(p, mode="mul")
+            orc.upload(*init)
+            steps = []
+            for s in range(TINY_STEPS):
+                rc, so = orc.timestep(dt)
+                assert rc == 0, (kind, n, s)
+                steps.append((orc.state(), so))
+            eng = Engine(p)
+            eng.upload(*init)
+            eng.run(dt, TINY_STEPS)
+            ref[kind, n] = (steps, eng.histograms())
+            eng.close()
+        for n in TINY_NS[2:]:
+            assert sum(so["n_pp"] for _, so in ref[kind, n][0]) > 0, (kind, n)         # the particles do interact
+    return ref
+
+
+@pytest.mark.parametrize("world", [2, 3, 4])
+def test_tiny_and_empty_shards_equal_oracle(world, tiny_reference):
+    """N in {0, 1, 2, 3, 17, 257} over 2-4 ranks (N < world leaves ranks with an empty shard: nothing to detect, pack or
+    count, one-element exchange blocks), cube and pore (kept lists across a rebuild), detection replicated and sharded by
+    index: the state bit for bit and n_pp / n_wall / n_paths equal to the oracle's after every step, on every rank; the
+    histograms equal a single engine's."""
+    from tests.test_gpu_parity import assert_state_equal
+    cases = [(kind, n, rep) for kind in ("cube", "pore") for n in TINY_NS for rep in (True, False)]
+    outs = _run_ranks_outcomes(world, _tiny_shards_body, (cases,), timeout=600.0)
+    for rank, o in enumerate(outs):
+        assert o[0] == "ok", (rank, o)
+        for (kind, n, rep), (steps, (counts, npaths)) in zip(cases, o[1]):
+            ref_steps, (ref_counts, ref_npaths) = tiny_reference[kind, n]
+            for s, ((state, st), (orc_state, so)) in enumerate(zip(steps, ref_steps)):
+                ctx = (world, rank, kind, n, rep, s)
+                assert_state_equal(state, orc_state, ctx)
+                for k in ("n_pp", "n_wall", "n_paths"):
+                    assert st[k] == so[k], (ctx, k, st, so)
+            assert npaths == ref_npaths and np.array_equal(counts, ref_counts), (world, rank, kind, n, rep)
+
+
+# ---- the candidate block of sharded detection, exactly at its capacity ---------------------------------------------------------
+CAP_N, CAP_K, CAP_DT = 600, 12, 2e-14
+
+
+def _close_pairs_case():
+    """A cube whose close pairs all have their HIGHER index in the last shard (of 2 and of 3 ranks) and their partner in the
+    first shard of 3: particles on a lattice 3 nm apart (~9 collision ranges), then CAP_K of the last ones moved to half a
+    collision range from a partner.  dt = 2e-14 s moves a particle by ~0.01 nm: nothing else comes close."""
+    from argon_monte_carlo_amd import params as PR
+    p, c = PR.cube_params(n=CAP_N)
+    p.detect_mode = 1
+    rng = np.random.default_rng(3)
+    g = np.arange(9) * 3e-9 + 30e-9
+    lat = np.stack(np.meshgrid(g, g, g, indexing="ij"), -1).reshape(-1, 3)[:CAP_N]
+    pos = lat.copy()
+    for k in range(CAP_K):
+        i, j = CAP_N - 1 - 13 * k, 7 + 15 * k
+        u = rng.normal(size=3)
+        pos[i] = pos[j] + 0.5 * p.collision_range * u / np.linalg.norm(u)
+    vel = rng.normal(size=(CAP_N, 3)) * 300.0
+    return p, (pos[:, 0], pos[:, 1], pos[:, 2], vel[:, 0], vel[:, 1], vel[:, 2])
+
+
+def _numpy_close_pairs(init, r):
+    """(i, j), i > j, of every pair closer than r after the drift of step 1 (the cube's walls are ~30 nm away)."""
+    P = np.stack(init[:3], 1) + CAP_DT * np.stack(init[3:], 1)
+    d2 = ((P[:, None, :] - P[None, :, :]) ** 2).sum(-1)
+    i, j = np.nonzero(np.tril(d2 < r * r, -1))
+    return i, j
+
+
+def _candidate_cap_body(at, rank, world, caps):
+    """Step 1 of the sharded-detection driver once per candidate-block capacity (None: the default)."""
+    from argon_monte_carlo_amd.dist import ShardedSimulation
+    p, init = _close_pairs_case()
+    res = []
+    for cap in caps:
+        if cap is None:
+            os.environ.pop("AMC_MG_CANDIDATES", None)
+        else:
+            os.environ["AMC_MG_CANDIDATES"] = str(cap)      # (read when the engine creates its candidate buffers)
+        sim = ShardedSimulation(p, rank, world, backend="gloo", replicated_detect=False)
+        try:
+            sim.upload(*init)
+
+            def step1(at):
+                at[0] = 1
+                st = sim.timestep(CAP_DT)
+                return {k: st[k] for k in ("n_pp", "n_wall", "n_paths", "n_candidates")}, sim.download()
+            res.append(_outcome(step1))
+        finally:
+            sim.engine.close()
+    return res
+
+
+@pytest.mark.parametrize("world", [2, 3])
+def test_candidate_block_at_capacity_and_one_past_it(world):
+    """Sharded detection (AMC_MG_REPLICATED=0 form) where only the last rank finds pairs, CAP_K of them.  A block with room
+    for exactly CAP_K gives the oracle's and the single engine's step; with room for CAP_K - 1 EVERY rank raises
+    AMC_ERR_CAPACITY from the same timestep() — not the owner alone while the others resolve a truncated graph and then
+    wait for it in the counters' all-reduce."""
+    from argon_monte_carlo_amd.engine import Engine
+    from oracle import oracle
+    from tests.test_gpu_parity import assert_state_equal
+    p, init = _close_pairs_case()
+    i, j = _numpy_close_pairs(init, 4 * p.collision_range)
+    assert len(i) == CAP_K and len(_numpy_close_pairs(init, p.collision_range)[0]) == CAP_K
+    from argon_monte_carlo_amd.dist import shard_range
+    assert (i >= shard_range(CAP_N, world - 1, world)[0]).all() and (j < shard_range(CAP_N, 0, 3)[1]).all()
+    orc = oracle.Oracle(p, mode="mul")
+    orc.upload(*init)
+    rc, so = orc.timestep(CAP_DT)
+    assert rc == 0
+    eng = Engine(p)
+    eng.upload(*init)
+    est = eng.timestep(CAP_DT)
+    ref = eng.download()
+    eng.close()
+    assert est["n_candidates"] == CAP_K and so["n_pp"] > 0
+    outs = _run_ranks_outcomes(world, _candidate_cap_body, ([None, CAP_K, CAP_K - 1],), timeout=300.0)
+    assert all(o[0] == "ok" for o in outs), outs
+    for rank, o in enumerate(outs):
+        default, at_cap = o[1][0], o[1][1]
+        assert default[0] == "ok" and default[1][0]["n_candidates"] == CAP_K, (rank, default[:2])
+        assert at_cap[0] == "ok", (rank, at_cap)
+        st, state = at_cap[1]
+        assert st["n_candidates"] == CAP_K, (rank, st)
+        for k in ("n_pp", "n_wall", "n_paths"):
+            assert st[k] == so[k] == est[k], (rank, k, st, so, est)
+        assert_state_equal(state, orc.state(), ("cap", world, rank))
+        for k in KEYS:
+            assert np.array_equal(state[k], ref[k]), (rank, k)
+    _assert_same_error([o[1][2] for o in outs], -4, "flags=1:")
+    assert outs[0][1][2][1] == 1
+
+
+# ---- the velocity-change list of the exchange overflows: every rank reports it ------------------------------------------------
+def _velocity_list_body(at, rank, world):
+    from argon_monte_carlo_amd.dist import ShardedSimulation
+    os.environ["AMC_MG_VELOCITY_LIST"] = "2"            # (read when the engine creates its exchange buffers)
+    p, c, init = _case("cube", 50000)
+    sim = ShardedSimulation(p, rank, world, backend="gloo")
+    try:
+        sim.upload(*init)
+        for s in range(1, 4):
+            at[0] = s
+            sim.timestep(c["dt"])
+    finally:
+        sim.engine.close()
+
+
+def test_velocity_change_list_overflow_raises_on_every_rank():
+    """test_velocity_change_list_overflow_is_reported over two ranks through ShardedSimulation.timestep: the sender flags
+    its full bank in the pack kernel, the receivers in the unpack kernel, so both ranks raise from the same step."""
+    outs = _run_ranks_outcomes(2, _velocity_list_body, (), timeout=300.0)
+    _assert_same_error(outs, -4, "velocity changes")
+    assert "flags=16:" in outs[0][3], outs[0]
+
+
+# ---- a field sample out of range on one shard: every rank raises ---------------------------------------------------------------
+FIELDS_BAD = 617
+
+
+def _fields_out_of_range_body(at, rank, world):
+    from argon_monte_carlo_amd.dist import ShardedSimulation
+    p, c, init = _case("cube", 1000)
+    sim = ShardedSimulation(p, rank, world, backend="gloo")
+    try:
+        state = list(init)
+        state[3] = state[3].copy()
+        state[3][FIELDS_BAD] = 2.0 ** 14            # (a position inside the box: the particle is binned)
+        sim.upload(*state)
+        sim.enable_fields()
+        sim.fields_sample()
+        first = _outcome(lambda at: sim.fields())
+        sim.fields_reset()
+        second = _outcome(lambda at: sim.fields())
+        sim.upload(*init)
+        sim.fields_sample()
+        third = _outcome(lambda at: sim.fields())
+        return [o if o[0] != "ok" else ("ok", o[1]["n_samples"], o[1]["count"].tolist(), o[1]["n_outside"])
+                for o in (first, second, third)]
+    finally:
+        sim.engine.close()
+
+
+def test_field_sample_out_of_range_on_one_shard_raises_on_every_rank():
+    """test_gpu_fields.test_velocity_out_of_range_is_reported_not_summed over two ranks: the particle lives on shard 1, only
+    that rank's fields_read fails, yet every rank raises the same AMC_ERR_CAPACITY naming it from the same fields() call;
+    after fields_reset() fields() succeeds everywhere, and a clean sample counts every particle."""
+    from argon_monte_carlo_amd.dist import shard_range
+    assert shard_range(1000, 1, 2)[0] <= FIELDS_BAD
+    outs = _run_ranks_outcomes(2, _fields_out_of_range_body, (), timeout=300.0)
+    assert all(o[0] == "ok" for o in outs), outs
+    _assert_same_error([o[1][0] for o in outs], -4, f"particle {FIELDS_BAD} ")
+    for rank, o in enumerate(outs):
+        assert o[1][1] == ("ok", 0, [0] * 512, 0), (rank, o[1][1][:2])
+        assert o[1][2][0] == "ok" and o[1][2][1] == 1 and sum(o[1][2][2]) + o[1][2][3] == 1000, (rank, o[1][2][:2])
+    assert outs[0][1][2] == outs[1][1][2]
