@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — particle-steps/s of the hot path (drift -> walls -> bounds -> p-p sweep) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cube_1e5|pore_5e5|pore_1e6|cube_1e6]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cube_1e5|pore_5e5|pore_1e6|cube_1e6] [--full]
 
 A "step" is one full timestep(dt) over all particles (BASELINE.json metric: particle-steps/sec + achieved HBM GB/s).
 At N=1 the default workload is BASELINE configs[1]: Open_Air_Cube_MC geometry, N = 100,000 synthetic uniform-cube
@@ -11,8 +11,10 @@ RANK / WORLD_SIZE are in the environment) or `python bench.py --gpus N` starts t
 parent that has not touched the GPU — and relays rank 0's JSON line.  Particles are sharded by index range with a
 per-step all-gather of positions (argon_monte_carlo_amd/dist.py) and per-GPU work is fixed (weak scaling).
 
-Prints ONE JSON line on rank 0 with the contract keys plus `roofline` (dominant kernel, HIP-event timed on the
-launch stream) and `cpu_baseline` (the C oracle = single-thread port of the reference algorithm, bounded sample).
+Prints ONE JSON line on rank 0 with the contract keys.  A plain run sets up, warms up, times the K steps, writes
+--dump-outputs and prints the line: nothing else.  `--full` adds, after the timed steps, `roofline` (dominant kernel,
+HIP-event timed on the launch stream over a repeat of the K steps), `extra_workloads` and `cpu_baseline` (the C oracle =
+single-thread port of the reference algorithm, bounded sample) with its all-cores and NumPy + multiprocessing legs.
 """
 import argparse
 import json
@@ -258,6 +260,52 @@ def committed_traffic(workload, kclass, tag):
     return None, None
 
 
+def roofline(kt, workload, steps, n_total, n_local, world, value, profiled_ms_per_step, round_tag):
+    """`roofline` of a --full line: the dominant kernel class of the profiled repeat against the peak that bounds it (HBM
+    bytes, or fp64 flops for the all-pairs detector), with class_report's per-kernel figures beside it.  `kt` is the
+    engine's kernel_times() (class -> (total ms, launches)); None when no kernel was timed."""
+    dom = max(((k, v) for k, v in kt.items() if v[1] > 0 and k != "allgather"), key=lambda kv: kv[1][0], default=(None, (0, 0)))
+    roof = None
+    if dom[0] is not None and "allpairs" in workload and kt.get("detect", (0, 0))[1] > 0:
+        dom = ("detect", kt["detect"])      # these workloads exist to report the all-pairs detector, dominant or not
+    if dom[0] is not None:
+        k, (ms, cnt) = dom
+        avg_s = ms / cnt * 1e-3
+        allpairs = "allpairs" in workload
+        if k == "detect" and allpairs:
+            # the all-pairs detector: fp64 vector work, 9 flop per unordered pair (SURVEY 8d)
+            flops = 9.0 * n_total * (n_total - 1) / 2.0
+            ach = flops / avg_s / 1e12
+            tiled = n_total >= 16 * 1024
+            roof = {"kernel": "k_detect_allpairs_tiled" if tiled else "k_detect_allpairs", "kernel_class": k, "bound": "fp64_valu",
+                    "achieved": ach, "peak": FP64_VECTOR_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": ach / FP64_VECTOR_PEAK_TFLOPS,
+                    "traffic": None, "avg_launch_us": avg_s * 1e6, "algorithmic_flops_per_launch": flops}
+            if tiled:
+                # the tiled kernel tests d^2 in the expanded form |ri|^2 + |rj|^2 - 2 ri.rj: three fused multiply-adds
+                # and a comparison per pair — 7 floating-point operations issued in 4 instructions for the 9 the
+                # direct form counts.  Both figures, so that nobody has to guess which one a fraction means.
+                ex = 7.0 * n_total * (n_total - 1) / 2.0 / avg_s / 1e12
+                roof["executed"] = {"flop_per_pair": 7, "instructions_per_pair": 4, "TFLOP/s": ex, "frac_of_peak": ex / FP64_VECTOR_PEAK_TFLOPS,
+                                    "vector_instruction_issue_frac": 4.0 * n_total * (n_total - 1) / 2.0 / avg_s / (FP64_VECTOR_PEAK_TFLOPS * 1e12 / 2.0)}
+        else:
+            # algorithmic bytes of the dominant kernel: a complete timestep for the streaming pass, the positions
+            # (24 B per particle, SURVEY 8d) for every kernel of the pair sweep — whose wide-cluster / ordered-workgroup
+            # kernels touch a few hundred KB and are bound by LATENCY (chains of dependent round trips), so that this
+            # fraction prices their time against the sweep's data, not their own traffic
+            per_particle = ALGO_BYTES.get(k, 24)
+            units = n_local if k in ("drift_walls", "bounds") else n_total
+            ach = per_particle * units / avg_s / 1e9
+            roof = {"kernel": KERNEL_OF_CLASS.get(k, k), "kernel_class": k, "bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s", "frac": ach / HBM_PEAK_GBS, "traffic": None, "avg_launch_us": avg_s * 1e6,
+                    "algorithmic_bytes_per_launch": per_particle * units}
+            if k in ("clusters_wide", "resolve", "commit"):
+                roof["note"] = "latency-bound kernel (dependent scattered round trips on a few hundred candidates): priced at the pair sweep's 24 B per particle"
+        roof.update(class_report(kt, steps, n_total, n_local, value / world, profiled_ms_per_step))
+    if roof is not None and roof["bound"] == "hbm":
+        roof["traffic"], roof["traffic_source"] = committed_traffic(workload, roof["kernel_class"], round_tag)
+    return roof
+
+
 def timed_outputs(src, stats, energy_sums=None):
     """What a caller of the timed path holds after its last step: the state (float64, `flag` as float32), the free-path
     histograms (float64 counts, 4 x bins), the counters summed over the timed steps (float64, COUNTER_KEYS order) and, for
@@ -317,17 +365,21 @@ def spawn_ranks(n):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--round-tag", default="r03", help="prefix of the committed profile files to take `traffic` from")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline does not need: the per-kernel repeat of the "
+                         "timed steps (`roofline`), the extra workloads and the CPU baselines")
+    ap.add_argument("--round-tag", default="r03", help="--full: prefix of the committed profile files to take `traffic` from")
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--workload", default="cube_1e5", choices=sorted(WORKLOADS))
     ap.add_argument("--n", type=int, default=0, help="override the particle count per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--extra-workloads", default="auto",
-                    help="comma-separated single-GPU workloads timed after the headline one (GPU legs only) and attached as "
-                         "`extra_workloads`; auto = cube_1e6,pore_1e6 behind the default headline on one GPU; none = skip")
-    ap.add_argument("--no-python-mp-baseline", action="store_true", help="skip the NumPy + multiprocessing leg (~30 s)")
+                    help="--full: comma-separated single-GPU workloads timed after the headline one (GPU legs only) and "
+                         "attached as `extra_workloads`; auto = cube_1e6,pore_1e6 behind the default headline on one GPU; "
+                         "none = skip")
+    ap.add_argument("--no-python-mp-baseline", action="store_true", help="--full: skip the NumPy + multiprocessing leg (~30 s)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N>1 (nccl = RCCL; gloo only for rehearsals)")
     ap.add_argument("--same-device", action="store_true", help="rehearsal: all ranks share GPU 0")
     ap.add_argument("--sorted-ic", action="store_true", help="experiment: upload the particles in spatial (cell) order")
@@ -341,6 +393,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full and args.extra_workloads not in ("auto", "none"):
+        ap.error("--extra-workloads needs --full")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(spawn_ranks(args.gpus))
     if args.gpus > 1 and int(os.environ.get("WORLD_SIZE", "1")) != args.gpus:
@@ -487,69 +541,31 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
     if args.dump_outputs:
-        # before the profiled repeat below moves the state on; outside the timed region
+        # before the profiled repeat of --full moves the state on; outside the timed region
         src = driver if driver is not None else engines[0]
         outputs = timed_outputs(src, stats, last_sums if kind == "temp" else None)
         if rank == 0:
             write_outputs(args.dump_outputs, outputs)
 
-    # per-kernel durations: the same K steps again with every launch bracketed by hipEvents on the launch stream
-    eng0 = engines[0]
-    eng0.profile(True)
-    if driver is not None:
-        driver.profile_collective(True)
-    t0 = time.perf_counter()
-    step(args.steps)
-    sync()
-    el_prof = time.perf_counter() - t0
-    kt = eng0.kernel_times()
-    eng0.profile(False)
-    if driver is not None:
-        kt["allgather"] = driver.collective_times()       # the step's collective, same (total ms, count) form
-        driver.profile_collective(False)
+    if args.full:
+        # per-kernel durations: the same K steps again with every launch bracketed by hipEvents on the launch stream
+        eng0 = engines[0]
+        eng0.profile(True)
+        if driver is not None:
+            driver.profile_collective(True)
+        t0 = time.perf_counter()
+        step(args.steps)
+        sync()
+        el_prof = time.perf_counter() - t0
+        kt = eng0.kernel_times()
+        eng0.profile(False)
+        if driver is not None:
+            kt["allgather"] = driver.collective_times()       # the step's collective, same (total ms, count) form
+            driver.profile_collective(False)
 
     if rank == 0:
         value = n_total * args.steps / el
         n_local = n_total // world if world > 1 else n_total
-        dom = max(((k, v) for k, v in kt.items() if v[1] > 0 and k != "allgather"), key=lambda kv: kv[1][0], default=(None, (0, 0)))
-        roof = None
-        if dom[0] is not None and "allpairs" in args.workload and kt.get("detect", (0, 0))[1] > 0:
-            dom = ("detect", kt["detect"])      # these workloads exist to report the all-pairs detector, dominant or not
-        if dom[0] is not None:
-            k, (ms, cnt) = dom
-            avg_s = ms / cnt * 1e-3
-            allpairs = "allpairs" in args.workload
-            if k == "detect" and allpairs:
-                # the all-pairs detector: fp64 vector work, 9 flop per unordered pair
-                flops = 9.0 * n_total * (n_total - 1) / 2.0
-                ach = flops / avg_s / 1e12
-                tiled = n_total >= 16 * 1024
-                roof = {"kernel": "k_detect_allpairs_tiled" if tiled else "k_detect_allpairs", "kernel_class": k, "bound": "fp64_valu",
-                        "achieved": ach, "peak": FP64_VECTOR_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": ach / FP64_VECTOR_PEAK_TFLOPS,
-                        "traffic": None, "avg_launch_us": avg_s * 1e6, "algorithmic_flops_per_launch": flops}
-                if tiled:
-                    # the tiled kernel tests d^2 in the expanded form |ri|^2 + |rj|^2 - 2 ri.rj: three fused multiply-adds
-                    # and a comparison per pair — 7 floating-point operations issued in 4 instructions for the 9 the
-                    # direct form counts.  Both figures, so that nobody has to guess which one a fraction means.
-                    ex = 7.0 * n_total * (n_total - 1) / 2.0 / avg_s / 1e12
-                    roof["executed"] = {"flop_per_pair": 7, "instructions_per_pair": 4, "TFLOP/s": ex, "frac_of_peak": ex / FP64_VECTOR_PEAK_TFLOPS,
-                                        "vector_instruction_issue_frac": 4.0 * n_total * (n_total - 1) / 2.0 / avg_s / (FP64_VECTOR_PEAK_TFLOPS * 1e12 / 2.0)}
-            else:
-                # algorithmic bytes of the dominant kernel: a complete timestep for the streaming pass, the positions
-                # (24 B per particle) for every kernel of the pair sweep — whose wide-cluster / ordered-workgroup
-                # kernels touch a few hundred KB and are bound by LATENCY (chains of dependent round trips), so that this
-                # fraction prices their time against the sweep's data, not their own traffic
-                per_particle = ALGO_BYTES.get(k, 24)
-                units = n_local if k in ("drift_walls", "bounds") else n_total
-                ach = per_particle * units / avg_s / 1e9
-                roof = {"kernel": KERNEL_OF_CLASS.get(k, k), "kernel_class": k, "bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS,
-                        "unit": "GB/s", "frac": ach / HBM_PEAK_GBS, "traffic": None, "avg_launch_us": avg_s * 1e6,
-                        "algorithmic_bytes_per_launch": per_particle * units}
-                if k in ("clusters_wide", "resolve", "commit"):
-                    roof["note"] = "latency-bound kernel (dependent scattered round trips on a few hundred candidates): priced at the pair sweep's 24 B per particle"
-            roof.update(class_report(kt, args.steps, n_total, n_local, value / world, el_prof / args.steps * 1e3))
-        if roof is not None and roof["bound"] == "hbm":
-            roof["traffic"], roof["traffic_source"] = committed_traffic(args.workload, roof["kernel_class"], args.round_tag)
         out = {
             "metric": "particle-steps/sec", "value": value, "unit": "particle-steps/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": el / args.steps * 1e3,
@@ -557,17 +573,19 @@ def main():
             "config": {"workload": args.workload, "geometry": kind, "n_particles": n_total, "n_per_gpu": n_local,
                        "dt": c["dt"], "parallelism": parallelism,
                        "pp_collisions_per_step": stats["n_pp"] / args.steps if stats else None},
-            "roofline": roof,
         }
-        extras = args.extra_workloads
-        if extras == "auto":
-            extras = "cube_1e6,pore_1e6" if (world == 1 and not args.force_sharded and args.workload == "cube_1e5" and not args.n) else "none"
-        if extras != "none" and world == 1:
-            out["extra_workloads"] = [extra_workload(w, args.steps, args.warmup, local_rank, stream_ptr, sync) for w in extras.split(",") if w]
-        if world == 1 and not args.no_cpu_baseline:
-            out.update(cpu_baseline(args.workload))
-            if not args.no_python_mp_baseline:
-                out["cpu_baseline_python_mp"] = cpu_baseline_python_mp()
+        if args.full:
+            out["roofline"] = roofline(kt, args.workload, args.steps, n_total, n_local, world, value,
+                                       el_prof / args.steps * 1e3, args.round_tag)
+            extras = args.extra_workloads
+            if extras == "auto":
+                extras = "cube_1e6,pore_1e6" if (world == 1 and not args.force_sharded and args.workload == "cube_1e5" and not args.n) else "none"
+            if extras != "none" and world == 1:
+                out["extra_workloads"] = [extra_workload(w, args.steps, args.warmup, local_rank, stream_ptr, sync) for w in extras.split(",") if w]
+            if world == 1 and not args.no_cpu_baseline:
+                out.update(cpu_baseline(args.workload))
+                if not args.no_python_mp_baseline:
+                    out["cpu_baseline_python_mp"] = cpu_baseline_python_mp()
         sys.stdout.flush()
         os.dup2(real_stdout, 1)
         print(json.dumps(out), flush=True)

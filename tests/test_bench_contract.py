@@ -89,6 +89,39 @@ def test_bench_command_line_parses_without_a_gpu():
         assert flag in out, flag
 
 
+def test_extra_workloads_need_full():
+    """A plain run times the headline only: asking it for extra workloads is an error, raised before any GPU work."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--extra-workloads", "cube_1e6"],
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+    assert r.returncode == 2 and "--extra-workloads needs --full" in r.stdout.decode(), r.stdout.decode()
+
+
+def _bench_line(*extra):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", *extra],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    lines = r.stdout.decode().splitlines()
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["metric"] == "particle-steps/sec" and d["unit"] == "particle-steps/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f64" and d["steps"] == 5 and d["warmup"] == 2 and d["config"]["workload"] == "cube_1e5"
+    assert d["value"] == pytest.approx(d["config"]["n_particles"] / (d["ms_per_step"] * 1e-3), rel=1e-9)
+    return d
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_only_the_headline_and_full_the_rest():
+    """A plain run carries the headline and nothing measured after the timed steps; --full adds the per-kernel roofline
+    and the extra workloads (the CPU legs are skipped here to keep the test short)."""
+    plain = _bench_line()
+    assert not {"roofline", "extra_workloads", "cpu_baseline", "cpu_baseline_python_mp"} & set(plain)
+    full = _bench_line("--full", "--no-cpu-baseline")
+    r = full["roofline"]
+    assert r["bound"] == "hbm" and 0 < r["frac"] < 1 and r["per_kernel_avg_us"]
+    assert [e["workload"] for e in full["extra_workloads"]] == ["cube_1e6", "pore_1e6"]
+    assert "cpu_baseline" not in full
+
+
 def test_dump_outputs_keep_the_size_cap_and_a_fixed_sample():
     """--dump-outputs: float32 / float64 arrays only, at most 64 MB in all, and a state too large for that is reduced to
     the same seeded particle sample every time (no GPU: a stand-in for the engine's download / histograms)."""

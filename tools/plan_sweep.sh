@@ -6,6 +6,6 @@ print(sys.argv[1], d["config"]["workload"], d["config"]["n_particles"], d["confi
 for spec in "cube_1e5 200000" "cube_1e5 300000" "pore_5e5 750000" "pore_5e5 1000000" "pore_5e5 1400000"; do
     set -- $spec
     for t in 640 150; do
-        AMC_PLAN_SMALL=$t timeout -k 10 100 python bench.py --workload $1 --n $2 --steps 1000 --warmup 100 --no-cpu-baseline 2>> gpurun_out/pl.err | python -c "$show" $t
+        AMC_PLAN_SMALL=$t timeout -k 10 100 python bench.py --full --workload $1 --n $2 --steps 1000 --warmup 100 --no-cpu-baseline | python -c "$show" $t
     done
 done
