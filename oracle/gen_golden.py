@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """Generate the golden vectors under tests/golden/ from the REFERENCE ITSELF (build container only).
 
-    MPLBACKEND=Agg PYTHONDONTWRITEBYTECODE=1 python3 oracle/gen_golden.py [--only func|cube|pore|temp|consts|cube_natural|pore_natural]
+    MPLBACKEND=Agg PYTHONDONTWRITEBYTECODE=1 python3 oracle/gen_golden.py [--only func|edge|cube|pore|temp|consts|cube_natural|pore_natural]
 
 * function level: imports /root/reference/Open_Air_Pore_MC.py (its main loop is __main__-guarded) and calls
-  pairwise_particles_in_cell / hit_vertical_wall / hit_cylinder_side_wall / num_out_of_bounds on seeded inputs.
+  pairwise_particles_in_cell / hit_vertical_wall / hit_cylinder_side_wall / num_out_of_bounds on seeded inputs
+  (func) and on the crafted edge inputs of tests/edge_states.py (edge).
 * step level: writes a PATCHED TEMPORARY COPY of a reference script into a scratch directory under /tmp
   (single-line substitutions of num_molecules / sigma / slice count / loop bound, plus calls to a dump hook after
   every step), runs it there as a script and collects the dumps.  Nothing of the reference's text is stored in
@@ -221,6 +222,159 @@ def gen_func():
 
     np.savez_compressed(os.path.join(OUT, "func_pore.npz"), **out)
     print("func_pore.npz:", len(out), "arrays")
+
+
+# ------------------------------------------------------------------------------------------------ edge inputs
+EDGE_PLANES = ("zero", "H", "z_cold", "h_oa", "z_gap_bottom", "z_gap_top")
+
+
+def edge_side_cases():
+    """(case-name prefix, which collision radius) of the side-wall solves in tests/edge_states.pore_walls"""
+    return (("tangent_", "R_oa_c"), ("side_a0", "R_oa_c"), ("cur_r_R_oa", "R_oa_c"), ("graze_Rg", "R_g_c"),
+            ("cur_r_R_g", "R_g_c"), ("corner_Rg", "R_g_c"), ("graze_Rp", "R_p_c"), ("cur_r_R_p", "R_p_c"),
+            ("corner_Rp", "R_p_c"))
+
+
+def edge_inputs():
+    """The inputs of --only edge, built from tests/edge_states.py (also used by tests/test_oracle_edges.py to check that
+    the fixture still belongs to the builders)."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    from tests import edge_states as E
+    w = E.pore_walls(fp_cases=True)
+    p = w.p
+    dt = w.dt
+    # the positions and accumulators after the drift (ndarray arithmetic, Pore:427-437)
+    st = {}
+    for k, v in zip(STATE_KEYS[:3], (w.x, w.y, w.z)):
+        st[k] = v.copy()
+    sx, sy, sz = dt * w.vx, dt * w.vy, dt * w.vz
+    st["x_vals"], st["y_vals"], st["z_vals"] = w.x + sx, w.y + sy, w.z + sz
+    st["x_velocities"], st["y_velocities"], st["z_velocities"] = w.vx.copy(), w.vy.copy(), w.vz.copy()
+    st["dist_since_collision"] = w.d + np.abs(np.sqrt(sx * sx + sy * sy + sz * sz))
+    st["dist_x_since_collision"], st["dist_y_since_collision"] = w.dx + np.abs(sx), w.dy + np.abs(sy)
+    st["dist_z_since_collision"] = w.dz + np.abs(sz)
+    st["full_path_traveled"] = w.flag.astype(bool)
+    out = {"wall_in_" + k: v for k, v in st.items()}
+    planes = dict(zero=0.0, H=p.H, z_cold=p.z_cold, h_oa=p.h_oa, z_gap_bottom=p.z_gap_bottom, z_gap_top=p.z_gap_top)
+    for q, name in enumerate(EDGE_PLANES):
+        hits = np.zeros(w.n, dtype=bool)
+        for case in (f"cur_z_{name}", f"prior_z_{name}"):
+            hits[w.cases[case]] = True
+        # (not here: vz == 0 on the plane is 0 / 0, and the smallest |vz| underflows in vz**2 — the reference raises on
+        # both under np.seterr(all='raise'))
+        out[f"vedge{q}_hits"] = hits
+        out[f"vedge{q}_plane"] = np.float64(planes[name])
+    side = []
+    for pre, rc in edge_side_cases():
+        for case, idx in w.cases.items():
+            if case.startswith(pre):
+                side += [(i, getattr(p, rc)) for i in idx]
+    out["sedge_idx"] = np.array([i for i, _ in side], dtype=np.int64)
+    out["sedge_Rc"] = np.array([r for _, r in side], dtype=np.float64)
+    b = E.pore_bounds()
+    out["bedge_in_x"], out["bedge_in_y"], out["bedge_in_z"] = b.x, b.y, b.z
+    # pairs around collision_range (the detection-grid pairs, positions as built)
+    fields = ["cont", "cx", "cy", "cz", "flag", "x", "y", "z", "vx", "vy", "vz"]
+    pin = {f: [] for f in fields}
+    for kind in ("pore", "cube"):
+        g = E.grid_pairs(kind, for_timestep=False)
+        for i, j in g.extra["pairs"]:
+            s = [i, j]
+            for f, a in zip(fields, (g.d[s], g.dx[s], g.dy[s], g.dz[s], g.flag[s].astype(bool), g.x[s], g.y[s], g.z[s],
+                                     g.vx[s], g.vy[s], g.vz[s])):
+                pin[f].append(np.asarray(a, dtype=np.float64))
+    for f in fields:
+        out["pedge_in_" + f] = np.array(pin[f])
+    return out
+
+
+def gen_edge():
+    """The reference's own wall, bounds and pair functions on the crafted edge inputs (tests/edge_states.py)."""
+    out = edge_inputs()                 # (before the import: the reference turns every floating-point warning into an error)
+    os.environ.setdefault("MPLBACKEND", "Agg")
+    sys.path.insert(0, REF)
+    import multiprocessing
+    import Open_Air_Pore_MC as P  # noqa
+
+    wst = {k: out["wall_in_" + k] for k in STATE_KEYS}
+
+    def load(st):
+        for k, v in st.items():
+            setattr(P, k, v.copy())
+
+    def grab():
+        return {k: getattr(P, k).copy() for k in STATE_KEYS}
+
+    for q in range(len(EDGE_PLANES)):
+        load(wst)
+        counter = multiprocessing.Value('i', 0)
+        P.num_collisions_per_step = counter
+        lists = [[], [], [], []]
+        P.hit_vertical_wall(out[f"vedge{q}_hits"], float(out[f"vedge{q}_plane"]), *lists)
+        res = grab()
+        for k in STATE_KEYS:
+            out[f"vedge{q}_out_{k}"] = res[k]
+        out[f"vedge{q}_paths"] = np.array(list(zip(*lists)), dtype=np.float64).reshape(-1, 4)
+        out[f"vedge{q}_ncoll"] = np.int64(counter.value)
+    # side walls one particle at a time: a solve without a real root ends the reference's call (its except branch
+    # raises), so only the outcome is kept for those
+    ns = len(out["sedge_idx"])
+    outcome = np.zeros(ns, dtype=np.int64)
+    sout = {k: np.zeros(ns) for k in STATE_KEYS}
+    spaths = np.full((ns, 4), np.nan)
+    for m, (i, Rc) in enumerate(zip(out["sedge_idx"], out["sedge_Rc"])):
+        load({k: v[i:i + 1] for k, v in wst.items()})
+        counter = multiprocessing.Value('i', 0)
+        P.num_collisions_per_step = counter
+        lists = [[], [], [], []]
+        try:
+            P.hit_cylinder_side_wall(np.array([True]), float(Rc), *lists)
+        except Exception:          # (UnboundLocalError from the except branch's `total_errs += 1`)
+            outcome[m] = 1
+            for k in STATE_KEYS:
+                sout[k][m] = wst[k][i]
+            continue
+        res = grab()
+        for k in STATE_KEYS:
+            sout[k][m] = res[k][0]
+        if lists[0]:
+            spaths[m] = [lists[0][0], lists[1][0], lists[2][0], lists[3][0]]
+    out["sedge_outcome"] = outcome
+    out["sedge_paths"] = spaths
+    for k in STATE_KEYS:
+        out[f"sedge_out_{k}"] = sout[k]
+    # the mutating bounds check
+    n = len(out["bedge_in_x"])
+    load({"x_vals": out["bedge_in_x"], "y_vals": out["bedge_in_y"], "z_vals": out["bedge_in_z"]})
+    out["bedge_count"] = np.int64(P.num_out_of_bounds())
+    for k, f in (("x_vals", "x"), ("y_vals", "y"), ("z_vals", "z")):
+        out[f"bedge_out_{f}"] = getattr(P, k).copy()
+    assert len(out["bedge_out_x"]) == n
+    # pairs around collision_range
+    fields = ["cont", "cx", "cy", "cz", "flag", "x", "y", "z", "vx", "vy", "vz"]
+    npair = out["pedge_in_x"].shape[0]
+    pout = {f: np.zeros((npair, 2)) for f in fields}
+    ppaths = np.full((npair, 2, 4), np.nan)
+    pnc = np.zeros(npair, dtype=np.int64)
+    for k in range(npair):
+        counter = multiprocessing.Value('i', 0)
+        P.init_globals(counter)
+        args = [out["pedge_in_" + f][k].copy() for f in fields]
+        args[4] = args[4].astype(bool)
+        lists = [[], [], [], []]
+        res = P.pairwise_particles_in_cell(*lists, np.array([True, True]), *args)
+        for f, a in zip(fields, res[1:]):
+            pout[f][k] = a
+        for q in range(len(lists[0])):
+            ppaths[k, q] = [lists[0][q], lists[1][q], lists[2][q], lists[3][q]]
+        pnc[k] = counter.value
+    for f in fields:
+        out["pedge_out_" + f] = pout[f]
+    out["pedge_paths"] = ppaths
+    out["pedge_ncoll"] = pnc
+    np.savez_compressed(os.path.join(OUT, "func_edge.npz"), **out)
+    print("func_edge.npz:", len(out), "arrays,", int(outcome.sum()), "side-wall solves without a real root,",
+          int(pnc.sum()), "pair collisions")
 
 
 # ------------------------------------------------------------------------------------------------ constants
@@ -514,6 +668,8 @@ def main():
     # the reference's OWN parameters (minutes of run time: not part of "all")
     if a.only in ("all", "graph_hist"):
         gen_graph_hist()
+    if a.only == "edge":
+        gen_edge()
     if a.only == "cube_natural":
         gen_cube_natural()
     if a.only == "pore_natural":
