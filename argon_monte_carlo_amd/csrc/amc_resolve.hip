@@ -53,10 +53,15 @@
 //         only this kernel after it (A.force_mono, small sweeps) — the commit; else k_commit follows
 // MODE 2: no detection grid (single cells, small N): everything in one kernel incl. brute-force validation and commit
 template <int GEOM, int MODE>
-__global__ __launch_bounds__(RS_T) void k_resolve(rs_args A)
+__global__ __launch_bounds__(RS_T) void k_resolve(rs_args A_in_kernarg)
 {
-    long long t_last = (A.dbg && threadIdx.x == 0) ? wall_clock64() : 0;
-    if (A.dbg && MODE == 0 && A.wide_plan) {        // span of the wide kernel's launch: first working wave in -> last one out
+    // Until the hand-over below has decided, only the few fields it needs are read from the argument block (K); the body
+    // reads it behind the hand-over (A).  Read through the formal parameter everywhere, the block's fields were loaded at
+    // the kernel's entry and spilled (343 SGPRs), ahead of the idle path too.
+    const rs_args &K = A_in_kernarg;
+    long long t_last = (K.dbg && threadIdx.x == 0) ? wall_clock64() : 0;
+    if (K.dbg && MODE == 0 && K.wide_plan) {        // span of the wide kernel's launch: first working wave in -> last one out
+        const rs_args &A = K;
         __shared__ unsigned long long s_in, s_out;
         if (threadIdx.x == 0) { s_in = ~0ULL; s_out = 0ULL; }
         __syncthreads();
@@ -67,12 +72,14 @@ __global__ __launch_bounds__(RS_T) void k_resolve(rs_args A)
         __syncthreads();
         if (threadIdx.x == 0 && s_out > 0) { A.dbg[27] += (long long)(s_out - s_in); A.dbg[26] += t_last - (long long)s_out; A.dbg[25] += 1; }
         __syncthreads();
+        if (threadIdx.x == 0) t_last = wall_clock64();  // (the idle path's stamps start here)
     }
     __shared__ rs_shared sh;
     __shared__ int wide_ns;             // slots made by the wide cluster kernel in this sweep, -1 if it did not run
     __shared__ int wide_nh;             // history entries it made (published and validated there)
     __shared__ int wide_dirty;          // its validation found merge edges
     __shared__ int s_left;              // candidates it left to this kernel
+    __shared__ int s_idle;              // the hand-over was all there was to do: the workgroup ends after the first barrier
     __shared__ int s_heads[64], s_nheads;   // first member of every multi-particle cluster when all waves share them
     __shared__ unsigned long long lds_keys[RS_SORT_LDS];
     __shared__ double pool_d[10][RS_POOL];
@@ -81,47 +88,86 @@ __global__ __launch_bounds__(RS_T) void k_resolve(rs_args A)
     __shared__ int s_label[RS_NS], s_size[RS_NS];
     __shared__ unsigned char s_dirty[RS_NS];
     __shared__ int s_lay[RS_LAY];
-    const amc_resolve_ws &W = A.W;
     const int tid = threadIdx.x;
-    amc_dev_counters *cnt = A.O.cnt;
-    rs_shared *ctl = (rs_shared *)W.ctl;
-    int ncand = (int)cnt->cand_count;
-    if (ncand > W.max_cand) ncand = W.max_cand;
+    int sh_idle_ncand = 0;              // (thread 0, debug stamps only: the candidate count of an idle sweep)
     if (tid == 0) {
-        // what the wide cluster kernel did before this one (slots, history, events, merge edges); zero if it did not
-        // run.  Its control block is re-armed for the next sweep.
-        wide_ns = -1; wide_nh = 0; wide_dirty = 0; s_left = 0;
-        sh.nslots = 0; sh.nhist = 0; sh.nev = 0; sh.nfp = 0; sh.ovf = 0; sh.nedges = 0; sh.nclusters = 0;
-        if (MODE == 0 && A.wide_plan) {
+        const amc_resolve_ws &W = K.W;
+        amc_dev_counters *cnt = K.O.cnt;
+        // The hand-over, by one thread, in registers: what the wide cluster kernel did before this one (slots, history,
+        // events, merge edges; zero if it did not run), its control block re-armed for the next sweep, the candidate
+        // counter reset.  In 98 % of the sweeps at N = 1e5 that is all: no candidates, or the wide kernel emulated and
+        // validated every cluster and found no merge edge.  Then the counters go straight to W.ctl and the workgroup ends
+        // at the first barrier — before anything of the ordered body (LDS tables, the rest of the argument block) is
+        // touched.  Otherwise they go to LDS and the body below runs exactly as it always did.
+        int ncand = (int)cnt->cand_count;
+        if (ncand > W.max_cand) ncand = W.max_cand;
+        if (K.host_ncand) *K.host_ncand = ncand;        // (first: the host-mapped write is the slowest to complete)
+        cnt->cand_count = 0;
+        rs_shared t;
+        int w_ns = -1, w_nh = 0, w_dirty = 0, left = 0;
+        t.nslots = 0; t.nhist = 0; t.nev = 0; t.nfp = 0; t.ovf = 0; t.nedges = 0; t.nclusters = 0;
+        if (MODE == 0 && K.wide_plan) {
             // (candidate k owns slots 2k, 2k + 1 and the history pairs 4k, 4k + 2; what the wide kernel took from its
             // counters comes after those)
             rs_shared *wc = (rs_shared *)W.wctl;
             const int off = 2 * ncand;
-            sh.nslots = off + wc->nslots < W.max_slots ? off + wc->nslots : W.max_slots;
-            sh.nhist = 2 * off + wc->nhist; sh.nfp = wc->nfp; sh.ovf = wc->ovf; sh.nedges = wc->nedges;
-            sh.nclusters = 0;
-            for (int b = 0; b < 16; b++) { sh.nclusters += W.wctl[32 + b]; W.wctl[32 + b] = 0; }      // (banked by the wide kernel's waves)
-            wide_dirty = wc->dirty;
-            wide_ns = wc->active ? sh.nslots : -1;              // (>= 0: the wide kernel ran, W.cand_s[k].z is valid)
-            wide_nh = sh.nhist < W.max_hist ? sh.nhist : W.max_hist;
-            s_left = wc->changed ? -1 : 0;                      // it left components too large for it (how many candidates: counted below)
+            t.nslots = off + wc->nslots < W.max_slots ? off + wc->nslots : W.max_slots;
+            t.nhist = 2 * off + wc->nhist; t.nfp = wc->nfp; t.ovf = wc->ovf; t.nedges = wc->nedges;
+            for (int b = 0; b < 16; b++) t.nclusters += W.wctl[32 + b];        // (banked by the wide kernel's waves)
+            w_dirty = wc->dirty;
+            w_ns = wc->active ? t.nslots : -1;                  // (>= 0: the wide kernel ran, W.cand_s[k].z is valid)
+            w_nh = t.nhist < W.max_hist ? t.nhist : W.max_hist;
+            left = wc->changed ? -1 : 0;                        // it left components too large for it (how many candidates: counted below)
+            for (int b = 0; b < 16; b++) W.wctl[32 + b] = 0;
             wc->nslots = 0; wc->nhist = 0; wc->nedges = 0; wc->nfp = 0; wc->ovf = 0; wc->dirty = 0; wc->nclusters = 0;
             wc->changed = 0; wc->active = 0; wc->cur_round = 1;
-            if (wide_ns < 0) { sh.nslots = 0; sh.nhist = 0; s_left = ncand; }        // (it did not run)
+            if (w_ns < 0) { t.nslots = 0; t.nhist = 0; left = ncand; }        // (it did not run)
         } else {
-            s_left = ncand;
+            left = ncand;
         }
-        sh.nslots0 = 0;
-        sh.dirty = 0; sh.changed = 0; sh.nhits = 0;
-        sh.ncomplex = 0; sh.rounds = 0; sh.ncand = ncand;
-        sh.active = ncand > 0; sh.ok = 1; sh.edges_done = 0; sh.hist_begin = 0; sh.cur_round = 0;
-        sh.lazy_ns = 0;         // the streaming pass before this sweep consumed the previous sweep's deferred results
-        cnt->cand_count = 0;
-        if (A.host_ncand) *A.host_ncand = ncand;
-        if (ncand == 0) *ctl = sh;
+        t.nslots0 = 0;
+        t.dirty = 0; t.changed = 0; t.nhits = 0;
+        t.ncomplex = 0; t.rounds = 0; t.ncand = ncand;
+        t.active = ncand > 0; t.ok = 1; t.edges_done = 0; t.hist_begin = 0; t.cur_round = 0;
+        t.lazy_ns = 0;          // the streaming pass before this sweep consumed the previous sweep's deferred results
+        // nothing left and nothing found by the wide kernel's validation: the sweep is resolved, only the commit remains
+        // (the same test as `resolved` below; a sweep it does not catch takes the body, which then finds the same)
+        const bool resolved = !(MODE == 2) && w_ns >= 0 && left == 0 && !w_dirty;
+        const bool idle = ncand == 0 || resolved;
+        if (K.dbg && idle && ncand > 0) {       // (idle path, split: entry -> counts read; the wait is the stamp's own)
+            __builtin_amdgcn_s_waitcnt(0);
+            const long long now__ = wall_clock64();
+            K.dbg[16] += now__ - t_last;
+            t_last = now__;
+        }
+        if (resolved) { t.rounds = 1; t.ok = !t.ovf; }
+        if (idle) *(rs_shared *)W.ctl = t;
+        else { sh = t; wide_ns = w_ns; wide_nh = w_nh; wide_dirty = w_dirty; s_left = left; }
+        s_idle = idle;
+        sh_idle_ncand = idle ? ncand : 0;
+        if (K.dbg && idle && ncand > 0) {       // (-> hand-over written and acknowledged)
+            __builtin_amdgcn_s_waitcnt(0);
+            const long long now__ = wall_clock64();
+            K.dbg[17] += now__ - t_last;
+            t_last = now__;
+        }
     }
     __syncthreads();
-    if (ncand == 0) return;     // uniform: nothing to resolve this sweep
+    if (s_idle) {               // uniform: the hand-over was the whole sweep
+        if (K.dbg && tid == 0 && sh_idle_ncand > 0) {     // (-> through the barrier; a sweep without candidates is not counted)
+            K.dbg[18] += wall_clock64() - t_last;
+            K.dbg[8] += 1; K.dbg[9] += sh_idle_ncand; K.dbg[11] += 1; K.dbg[12] += 1;
+        }
+        return;
+    }
+    // the whole block, read from the kernarg segment again through a pointer the compiler cannot see before this point
+    const __attribute__((address_space(4))) rs_args *kp = (const __attribute__((address_space(4))) rs_args *)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(kp));
+    const rs_args &A = *(const rs_args *)kp;
+    const amc_resolve_ws &W = A.W;
+    amc_dev_counters *cnt = A.O.cnt;
+    rs_shared *ctl = (rs_shared *)W.ctl;
+    const int ncand = sh.ncand;
 
     const bool wide = wide_ns >= 0;
     const int gen_off = wide ? 16 : 0;          // (the wide kernel tags its own re-emulations of a cluster with rounds 1, 2, 3)
