@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <memory>
 #include <vector>
 #include <new>
 #include <type_traits>
@@ -32,8 +33,8 @@ void amc_prof_begin(amc_ctx *c, int kclass)
     if (!c->profiling) return;
     if (c->ev_used == c->ev_pool.size()) {
         hipEvent_t a, b;
-        hipEventCreate(&a);
-        hipEventCreate(&b);
+        (void)ctx_event(c, &a, hipEventDefault);
+        (void)ctx_event(c, &b, hipEventDefault);
         c->ev_pool.push_back({a, b});
     }
     c->ev_pending.push_back({kclass, (int)c->ev_used});
@@ -143,7 +144,7 @@ static int setup_grid(amc_ctx *c)
     }
     if (off > 0x7fff0000LL) return amc_fail(c, AMC_ERR_INVALID, "detection grid too large (%lld cells)", off);
     G.ncells = (int)off;
-    AMC_HIP(c, dalloc(&c->d_lay, (size_t)3 * G.gz));
+    AMC_HIP(c, dalloc(c, &c->d_lay, (size_t)3 * G.gz));
     AMC_HIP(c, hipMemcpy(c->d_lay, c->h_lay_lo.data(), sizeof(int) * G.gz, hipMemcpyHostToDevice));
     AMC_HIP(c, hipMemcpy(c->d_lay + G.gz, c->h_lay_n.data(), sizeof(int) * G.gz, hipMemcpyHostToDevice));
     AMC_HIP(c, hipMemcpy(c->d_lay + 2 * G.gz, c->h_lay_off.data(), sizeof(int) * G.gz, hipMemcpyHostToDevice));
@@ -171,31 +172,7 @@ void amc_destroy(amc_ctx *c)
     if (!c) return;
     hipSetDevice(c->device);
     hipStreamSynchronize(c->stream);
-    void *ptrs[] = {c->s_slab, c->s_slab2, c->d_lay, c->B_buf[0].rec, c->B_buf[0].head, c->B_buf[1].rec, c->B_buf[1].head,
-                    c->extra_buf[0], c->extra_count, c->wev_buf[0].rec, c->wev_buf[0].count, c->ovl_flags,
-                    c->W.ov_head, c->w_slab, c->d_rec, c->d_hist, c->d_edges, c->d_cnt, c->d_banks, c->d_dbg,
-                    c->B_buf[0].cell_of, c->B_buf[0].node_of, c->B_buf[0].wave_count, c->mg_wave_count, c->keep_K >= 2 ? (void *)c->B_buf[0].extra : nullptr};
-    for (void *p : ptrs)
-        if (p) hipFree(p);
-    if (c->h_host_ncand) hipHostFree((void *)c->h_host_ncand);
-    if (c->h_pin) hipHostFree(c->h_pin);
-    if (c->T.pin) hipHostFree(c->T.pin);
-    if (c->T.count) hipFree(c->T.count);
-    if (c->T.def_idx) hipFree(c->T.def_idx);
-    if (c->T.def_dir) hipFree(c->T.def_dir);
-    { void *td[] = {c->TD.idx, c->TD.count, c->TD.t, c->TD.contact, c->TD.normal, c->TD.dir, c->TD.Es, c->TD.dpz, c->TD.dE, c->TD.ok};
-      for (void *q : td) if (q) hipFree(q); }
-    amc_fields_free(c);
-    if (c->cand_send) hipFree(c->cand_send);
-    if (c->cand_recv) hipFree(c->cand_recv);
-    if (c->kin_send) hipFree(c->kin_send);
-    if (c->kin_recv) hipFree(c->kin_recv);
-    if (c->kin_vpub) hipFree(c->kin_vpub);
-    for (auto &pr : c->ev_pool) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
-    if (c->ev_detect) hipEventDestroy(c->ev_detect);
-    if (c->ev_stream) hipEventDestroy(c->ev_stream);
-    if (c->stream2) hipStreamDestroy(c->stream2);
-    if (c->own_stream) hipStreamDestroy(c->own_stream);
+    ctx_free_since(c, 0);
     delete c;
 }
 
@@ -221,58 +198,26 @@ int amc_create(amc_ctx **out, const amc_params *p)
     if (!c) { g_create_err = "out of host memory"; return AMC_ERR_INVALID; }
     c->P = *p;
     c->device = p->device;
-    c->n = p->n; c->lo = 0; c->hi = p->n;
-    c->uploaded = false;
+    c->n = p->n; c->hi = p->n;
     c->keep_prior = (p->reserved0 & 1) != 0;
-    c->profiling = false;
-    c->ev_used = 0;
-    c->prof_ev0 = c->prof_ev1 = nullptr;
-    memset(c->k_ms, 0, sizeof c->k_ms);
-    memset(c->k_launches, 0, sizeof c->k_launches);
-    memset(&c->S, 0, sizeof c->S); memset(&c->B, 0, sizeof c->B); memset(&c->W, 0, sizeof c->W);
-    memset(c->S_buf, 0, sizeof c->S_buf); memset(c->B_buf, 0, sizeof c->B_buf); memset(c->wev_buf, 0, sizeof c->wev_buf);
-    c->mg_wave_count = nullptr; c->mg_waves_pack = c->mg_waves_unpack = 0; c->mg_keep = false; c->kin_mode = 1; c->keep_pool = 0;
-    c->s_slab2 = nullptr; c->extra_buf[0] = c->extra_buf[1] = nullptr; c->extra_count = nullptr; c->max_extra = 0;
-    c->stream2 = nullptr; c->ev_detect = c->ev_stream = nullptr;
-    c->ovl_flags = nullptr; c->ovl_tick = 0;
+    // environment switches, read once per context
     c->ovl_sync_values = getenv("AMC_OVERLAP_SYNC") && !strcmp(getenv("AMC_OVERLAP_SYNC"), "value");
     // AMC_OVERLAP: 1 the streaming pass of step s + 1 runs beside the resolve of sweep s inside amc_run, on a second stream;
     // 2 the same kernels in order on one stream (debugging); 0 the plain sequence (the default: measured on MI355X the resolve
     // kernels take twice as long beside the pass's memory traffic, which with the fix-up kernel and the two cross-stream
     // dependencies of a step eats what the overlap hides — DESIGN 4.2 has the numbers)
     c->overlap_mode = getenv("AMC_OVERLAP") ? atoi(getenv("AMC_OVERLAP")) : 0;
-    c->ovl_steps = 0;
-    c->T.idx = nullptr; c->T.count = nullptr; c->T.t = c->T.contact = c->T.normal = c->T.dir = c->T.Es = c->T.dpz = c->T.dE = nullptr;
-    c->T.ok = nullptr; c->T.cap = 0; c->T.last_case = -1; c->T.last_n = 0; c->T.pre_case = -1; c->T.pin = nullptr;
-    c->T.def_idx = nullptr; c->T.def_dir = nullptr; c->T.def_case = -1; c->T.def_n = 0;
-    memset(&c->out, 0, sizeof c->out); memset(&c->h_prev, 0, sizeof c->h_prev);
-    memset(&c->F, 0, sizeof c->F);
-    c->d_lay = nullptr; c->d_banks = nullptr; c->d_rec = nullptr; c->d_hist = nullptr; c->d_edges = nullptr;
-    c->d_dbg = nullptr; c->w_slab = nullptr; c->s_slab = nullptr;
+    c->overlap_split = getenv("AMC_OVERLAP_SPLIT") && atoi(getenv("AMC_OVERLAP_SPLIT")) != 0;     // (experiment)
     c->cw_blocks_env = getenv("AMC_CW_BLOCKS") ? atoi(getenv("AMC_CW_BLOCKS")) : 0;
-    c->mg_count_pp = true;
-    c->lazy_pending = false; c->commit_pending = false; c->commit_defer = false;
-    c->h_host_ncand = nullptr; c->d_host_ncand = nullptr;
-    c->d_cnt = nullptr; c->own_stream = nullptr; c->h_pin = nullptr; c->h_pin_bytes = 0; c->plan_split = false;
-    c->plan_small = AMC_PLAN_SMALL;
     if (const char *e = getenv("AMC_PLAN_SMALL")) { const int v = atoi(e); if (v >= 0) c->plan_small = v; }
-    c->cand_send = c->cand_recv = nullptr; c->cand_cap = 0; c->cand_world = 0;
-    c->kin_send = c->kin_recv = c->kin_vpub = nullptr; c->kin_world = 0; c->kin_m = c->kin_cap = c->kin_block = 0; c->kin_lists = false; c->kin_counts_clear = false;
-    c->TD.idx = nullptr; c->TD.count = nullptr; c->TD.t = c->TD.contact = c->TD.normal = c->TD.dir = c->TD.Es = c->TD.dpz = c->TD.dE = nullptr;
-    c->TD.ok = nullptr; c->TD.cap = 0; c->TD.fetched = false;
-    c->stream = nullptr;
-    int rc = AMC_OK;
-#define CK(call)                                                                                       \
-    do {                                                                                               \
-        hipError_t e__ = (call);                                                                       \
-        if (e__ != hipSuccess) {                                                                       \
-            rc = amc_fail(c, AMC_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e__));             \
-            goto fail;                                                                                 \
-        }                                                                                              \
-    } while (0)
+    c->stream_bs = getenv("AMC_STREAM_BS") ? atoi(getenv("AMC_STREAM_BS")) : 256;      // (experiments: 64 / 128 / 256)
+    c->detect_bs = getenv("AMC_DETECT_BS") ? atoi(getenv("AMC_DETECT_BS")) : 256;      // (experiments: 64 / 128 / 256)
+    c->temp_unfused = getenv("AMC_TEMP_UNFUSED") != nullptr;  // cross-check path: one hits/sample/apply triple per case
+    // a failure below returns through amc_fail: the guard hands its message on and destroys what was built
+    std::unique_ptr<amc_ctx, void (*)(amc_ctx *)> guard(c, [](amc_ctx *x) { g_create_err = x->err; amc_destroy(x); });
     {
-        CK(hipSetDevice(c->device));
-        CK(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
+        AMC_HIP(c, hipSetDevice(c->device));
+        AMC_HIP(c, ctx_stream(c, &c->own_stream));
         c->stream = c->own_stream;
         const size_t n = (size_t)c->n;
         // detection mode: only single cells (AMC_GEOM_CELL: no geometry to lay a grid over) run without the detection grid —
@@ -287,8 +232,7 @@ int amc_create(amc_ctx **out, const amc_params *p)
         c->allpairs = (p->geometry == AMC_GEOM_CELL) || (p->detect_mode != 1 && c->n <= small_n);
         c->detect_ap = c->allpairs || p->detect_mode == 2;
         if (p->geometry == AMC_GEOM_CELL && p->detect_mode == 1) {
-            rc = amc_fail(c, AMC_ERR_INVALID, "AMC_GEOM_CELL has no cell grid: detect_mode must be 0 or 2");
-            goto fail;
+            return amc_fail(c, AMC_ERR_INVALID, "AMC_GEOM_CELL has no cell grid: detect_mode must be 0 or 2");
         }
         double **st[] = {&c->S.x, &c->S.y, &c->S.z, &c->S.vx, &c->S.vy, &c->S.vz, &c->S.d, &c->S.dx, &c->S.dy, &c->S.dz,
                          &c->S.px, &c->S.py, &c->S.pz};
@@ -297,57 +241,52 @@ int amc_create(amc_ctx **out, const amc_params *p)
             // arrays — in one slab they share address-translation entries instead of needing one each
             const size_t per = ((sizeof(double) * std::max<size_t>(n, 1)) + 255) & ~(size_t)255;
             const size_t total = 13 * per + ((std::max<size_t>(n, 1) + 255) & ~(size_t)255);
-            CK(hipMalloc((void **)&c->s_slab, total));
-            CK(hipMemsetAsync(c->s_slab, 0, total, c->stream));
+            AMC_HIP(c, dalloc(c, &c->s_slab, total));
+            AMC_HIP(c, hipMemsetAsync(c->s_slab, 0, total, c->stream));
             size_t off = 0;
             for (auto pp : st) { *pp = (double *)(c->s_slab + off); off += per; }
             c->S.flag = (uint8_t *)(c->s_slab + off);
             c->S_buf[0] = c->S;
         }
-        if ((rc = setup_grid(c)) != AMC_OK) goto fail;
+        if (int rc = setup_grid(c)) return rc;
         if (!c->allpairs) {
             const size_t nc = (size_t)c->G.ncells;
             c->max_extra = AMC_EXTRA_NODES(c->n);
             // kept lists (amc_lists): AMC_LIST_KEEP=K, a full build every K steps.  Off in an overlapped run (its fix-up kernel
             // files particles itself) and when the all-pairs detector is in front.  (The energised pore files its particles in
             // the bounds pass that follows the wall cases, amc_temp_end: the same pass, the same cycle.)
-            c->keep_K = 0; c->lists_age = -1; c->lists_owner = 0; c->keep_threads = 0;
             size_t pool = 0, keep_waves = 0;
             {
                 int K = (p->geometry == AMC_GEOM_PORE || p->geometry == AMC_GEOM_PORE_ENERGISED) ? AMC_LIST_KEEP_DEFAULT_PORE : 0;
                 if (const char *e = getenv("AMC_LIST_KEEP")) K = atoi(e);
                 if (c->overlap_mode || c->detect_ap || p->geometry == AMC_GEOM_CELL) K = 0;
-                const int threads = getenv("AMC_STREAM_BS") ? atoi(getenv("AMC_STREAM_BS")) : 256;
+                const int threads = c->stream_bs;
                 const long long nwaves = (((long long)n + threads - 1) / threads) * (threads / 64);
                 // (a wave's pool holds everything its 64 particles could hand out in K - 1 steps; shorter cycles rather than more
                 // than 2^30 nodes)
                 while (K >= 2 && (long long)n + nwaves * 64 * (K - 1) > 0x3fffffffLL) K--;
                 if (K >= 2 && n > 0 && threads % 64 == 0) {
-                    c->keep_K = K; c->keep_threads = threads;
+                    c->keep_K = K;
                     c->B.wave_cap = 64 * (K - 1);
                     pool = (size_t)c->B.wave_cap * (size_t)nwaves;
                     keep_waves = (size_t)nwaves;
                 }
             }
             c->keep_pool = pool;
-            CK(dalloc(&c->B.rec, n + std::max((size_t)c->max_extra, pool)));
-            CK(dalloc(&c->B.head, nc + 1));
-            CK(hipMemsetAsync(c->B.head, 0, sizeof(unsigned long long) * (nc + 1), c->stream));
-            c->B.epoch = 0;
-            c->B.n = (int)c->n; c->B.extra = nullptr;
-            c->B.cell_of = c->B.node_of = c->B.wave_count = nullptr;
+            AMC_HIP(c, dalloc(c, &c->B.rec, n + std::max((size_t)c->max_extra, pool)));
+            AMC_HIP(c, dalloc(c, &c->B.head, nc + 1));
+            AMC_HIP(c, hipMemsetAsync(c->B.head, 0, sizeof(unsigned long long) * (nc + 1), c->stream));
+            c->B.n = (int)c->n;
             if (c->keep_K >= 2) {
-                CK(dalloc(&c->B.extra, pool));
-                CK(dalloc(&c->B.cell_of, n));
-                CK(dalloc(&c->B.node_of, n));
-                CK(dalloc(&c->B.wave_count, keep_waves));
-                CK(hipMemsetAsync(c->B.wave_count, 0, sizeof(int) * keep_waves, c->stream));
-            } else {
-                c->B.wave_cap = 0;
+                AMC_HIP(c, dalloc(c, &c->B.extra, pool));
+                AMC_HIP(c, dalloc(c, &c->B.cell_of, n));
+                AMC_HIP(c, dalloc(c, &c->B.node_of, n));
+                AMC_HIP(c, dalloc(c, &c->B.wave_count, keep_waves));
+                AMC_HIP(c, hipMemsetAsync(c->B.wave_count, 0, sizeof(int) * keep_waves, c->stream));
             }
             c->B_buf[0] = c->B;
-            CK(dalloc(&c->W.ov_head, nc));
-            CK(hipMemsetAsync(c->W.ov_head, 0xff, sizeof(int) * std::max<size_t>(nc, 1), c->stream));
+            AMC_HIP(c, dalloc(c, &c->W.ov_head, nc));
+            AMC_HIP(c, hipMemsetAsync(c->W.ov_head, 0xff, sizeof(int) * std::max<size_t>(nc, 1), c->stream));
         }
         // resolve work space
         amc_resolve_ws &W = c->W;
@@ -385,64 +324,57 @@ int amc_create(amc_ctx **out, const amc_params *p)
                 return (off + 255) & ~(size_t)255;
             };
             const size_t total = carve(nullptr);
-            CK(hipMalloc((void **)&c->w_slab, total));
-            CK(hipMemsetAsync(c->w_slab, 0, total, c->stream));
+            AMC_HIP(c, dalloc(c, &c->w_slab, total));
+            AMC_HIP(c, hipMemsetAsync(c->w_slab, 0, total, c->stream));
             carve(c->w_slab);
         }
         // AMC_MAX_HIST (diagnostic): the history / overlay entries a sweep may USE (the allocation keeps its size): lets a test
         // drive the wide kernel's overlay protocol into its capacity limit at sizes the oracle handles in seconds
         if (const char *e = getenv("AMC_MAX_HIST")) { const int v = atoi(e); if (v > 0 && v < W.max_hist) W.max_hist = v; }
-        { amc_resolve_ctl z; memset(&z, 0, sizeof z); z.cur_round = 1; CK(hipMemcpyAsync(W.wctl, &z, sizeof z, hipMemcpyHostToDevice, c->stream)); CK(hipStreamSynchronize(c->stream)); }
-        c->sweep_epoch = 0;
-        CK(hipMemsetAsync(W.slot_of, 0xff, sizeof(int) * std::max<size_t>(n, 1), c->stream));
+        { amc_resolve_ctl z; memset(&z, 0, sizeof z); z.cur_round = 1; AMC_HIP(c, hipMemcpyAsync(W.wctl, &z, sizeof z, hipMemcpyHostToDevice, c->stream)); AMC_HIP(c, hipStreamSynchronize(c->stream)); }
+        AMC_HIP(c, hipMemsetAsync(W.slot_of, 0xff, sizeof(int) * std::max<size_t>(n, 1), c->stream));
         // outputs
         long long mp = p->max_paths > 0 ? p->max_paths : (p->max_paths < 0 ? 0 : (1LL << 20));   // < 0: histograms only
         if (mp > 0x7fffffff) mp = 0x7fffffff;
-        if (mp > 0) CK(dalloc(&c->d_rec, (size_t)mp));
-        CK(dalloc(&c->d_cnt, 1));
-        CK(hipMemsetAsync(c->d_cnt, 0, sizeof(amc_dev_counters), c->stream));
-        CK(dalloc(&c->d_banks, AMC_COUNTER_BANKS));
-        CK(hipMemsetAsync(c->d_banks, 0, sizeof(amc_counter_bank) * AMC_COUNTER_BANKS, c->stream));
+        if (mp > 0) AMC_HIP(c, dalloc(c, &c->d_rec, (size_t)mp));
+        AMC_HIP(c, dalloc(c, &c->d_cnt, 1));
+        AMC_HIP(c, hipMemsetAsync(c->d_cnt, 0, sizeof(amc_dev_counters), c->stream));
+        AMC_HIP(c, dalloc(c, &c->d_banks, AMC_COUNTER_BANKS));
+        AMC_HIP(c, hipMemsetAsync(c->d_banks, 0, sizeof(amc_counter_bank) * AMC_COUNTER_BANKS, c->stream));
         c->out.banks = c->d_banks;
-        c->out.rec = c->d_rec; c->out.cap = (unsigned)mp; c->out.cnt = c->d_cnt; c->out.step = 0;
-        c->out.nbins = 0; c->out.hist = nullptr; c->out.edges = nullptr; c->out.lo = p->hist_lo; c->out.hi = p->hist_hi;
+        c->out.rec = c->d_rec; c->out.cap = (unsigned)mp; c->out.cnt = c->d_cnt;
+        c->out.lo = p->hist_lo; c->out.hi = p->hist_hi;
         if (p->hist_bins > 0 && p->hist_hi > p->hist_lo) {
             const int nb = p->hist_bins;
-            CK(dalloc(&c->d_hist, (size_t)4 * nb * AMC_COUNTER_BANKS));
-            CK(hipMemsetAsync(c->d_hist, 0, sizeof(unsigned long long) * 4 * nb * AMC_COUNTER_BANKS, c->stream));
-            CK(dalloc(&c->d_edges, (size_t)nb + 1));
+            AMC_HIP(c, dalloc(c, &c->d_hist, (size_t)4 * nb * AMC_COUNTER_BANKS));
+            AMC_HIP(c, hipMemsetAsync(c->d_hist, 0, sizeof(unsigned long long) * 4 * nb * AMC_COUNTER_BANKS, c->stream));
+            AMC_HIP(c, dalloc(c, &c->d_edges, (size_t)nb + 1));
             // np.linspace(lo, hi, nb+1): start + k*step with step = (hi-lo)/nb, last element forced to hi
             std::vector<double> ed(nb + 1);
             const double step = (p->hist_hi - p->hist_lo) / (double)nb;
             for (int k = 0; k <= nb; k++) ed[k] = p->hist_lo + (double)k * step;
             ed[nb] = p->hist_hi;
-            CK(hipMemcpy(c->d_edges, ed.data(), sizeof(double) * (nb + 1), hipMemcpyHostToDevice));
+            AMC_HIP(c, hipMemcpy(c->d_edges, ed.data(), sizeof(double) * (nb + 1), hipMemcpyHostToDevice));
             c->out.nbins = nb; c->out.hist = c->d_hist; c->out.edges = c->d_edges; c->out.bin_step = step;
         }
         {
             void *hp = nullptr, *dp = nullptr;
-            if (hipHostMalloc(&hp, 64, hipHostMallocMapped) == hipSuccess && hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess) {
+            if (palloc(c, &hp, 64, hipHostMallocMapped) == hipSuccess && hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess) {
                 c->h_host_ncand = (volatile int *)hp;
                 *c->h_host_ncand = 0;
                 c->d_host_ncand = (int *)dp;
             }
         }
-        c->h_pin_bytes = (size_t)4 << 20;
-        if (hipHostMalloc((void **)&c->h_pin, c->h_pin_bytes, hipHostMallocDefault) != hipSuccess) { c->h_pin = nullptr; c->h_pin_bytes = 0; }
+        if (palloc(c, &c->h_pin, (size_t)4 << 20, hipHostMallocDefault) == hipSuccess) c->h_pin_bytes = (size_t)4 << 20;
         if (getenv("AMC_DEBUG_RESOLVE")) {
-            CK(dalloc(&c->d_dbg, 128 + 128 * 512));
-            CK(hipMemsetAsync(c->d_dbg, 0, sizeof(long long) * (128 + 128 * 512), c->stream));
-            { const long long big = 0x7fffffffffffffffLL; CK(hipMemcpyAsync(c->d_dbg + 28, &big, sizeof big, hipMemcpyHostToDevice, c->stream)); }
+            AMC_HIP(c, dalloc(c, &c->d_dbg, 128 + 128 * 512));
+            AMC_HIP(c, hipMemsetAsync(c->d_dbg, 0, sizeof(long long) * (128 + 128 * 512), c->stream));
+            { const long long big = 0x7fffffffffffffffLL; AMC_HIP(c, hipMemcpyAsync(c->d_dbg + 28, &big, sizeof big, hipMemcpyHostToDevice, c->stream)); }
         }
-        CK(hipStreamSynchronize(c->stream));
+        AMC_HIP(c, hipStreamSynchronize(c->stream));
     }
-#undef CK
-    *out = c;
+    *out = guard.release();
     return AMC_OK;
-fail:
-    g_create_err = c->err;
-    amc_destroy(c);
-    return rc;
 }
 
 int amc_set_stream(amc_ctx *c, void *hip_stream)
@@ -662,51 +594,54 @@ int amc_timestep(amc_ctx *c, double dt, amc_step_stats *out)
 static int ensure_overlap(amc_ctx *c)
 {
     if (c->s_slab2) return AMC_OK;
+    amc_alloc_group group(c);
     const size_t n = (size_t)std::max<int64_t>(c->n, 1);
-    {
-        const size_t per = ((sizeof(double) * n) + 255) & ~(size_t)255;
-        const size_t total = 10 * per + ((n + 255) & ~(size_t)255);
-        AMC_HIP(c, hipMalloc((void **)&c->s_slab2, total));
-        AMC_HIP(c, hipMemsetAsync(c->s_slab2, 0, total, c->stream));
-        amc_state &T = c->S_buf[1];
-        double **st[] = {&T.x, &T.y, &T.z, &T.vx, &T.vy, &T.vz, &T.d, &T.dx, &T.dy, &T.dz};
-        size_t off = 0;
-        for (auto pp : st) { *pp = (double *)(c->s_slab2 + off); off += per; }
-        T.flag = (uint8_t *)(c->s_slab2 + off);
-        T.px = c->S_buf[0].px; T.py = c->S_buf[0].py; T.pz = c->S_buf[0].pz;      // (prior_*_vals are not kept by these runs)
-    }
-    {
-        const size_t nc = (size_t)c->G.ncells;
-        amc_lists &T = c->B_buf[1];
-        AMC_HIP(c, dalloc(&T.rec, n + (size_t)c->max_extra));
-        AMC_HIP(c, dalloc(&T.head, nc + 1));
-        AMC_HIP(c, hipMemsetAsync(T.head, 0, sizeof(unsigned long long) * (nc + 1), c->stream));
-        T.epoch = 0; T.n = (int)c->n;
-        AMC_HIP(c, dalloc(&c->extra_buf[0], (size_t)2 * c->max_extra));
-        c->extra_buf[1] = c->extra_buf[0] + c->max_extra;
-        AMC_HIP(c, dalloc(&c->extra_count, 2));
-        AMC_HIP(c, hipMemsetAsync(c->extra_count, 0, 2 * sizeof(int), c->stream));
-    }
-    {
-        // deferred events of a pass: wall hits (~1e-3 per particle and step in the pore), by bank
-        const int cap = (int)std::max<long long>(1024, (long long)c->n / (4 * AMC_COUNTER_BANKS));
-        AMC_HIP(c, dalloc(&c->wev_buf[0].rec, (size_t)2 * AMC_COUNTER_BANKS * cap));
-        AMC_HIP(c, dalloc(&c->wev_buf[0].count, (size_t)2 * AMC_COUNTER_BANKS));
-        AMC_HIP(c, hipMemsetAsync(c->wev_buf[0].count, 0, sizeof(unsigned int) * 2 * AMC_COUNTER_BANKS, c->stream));
-        c->wev_buf[0].cap = c->wev_buf[1].cap = cap;
-        c->wev_buf[1].rec = c->wev_buf[0].rec + (size_t)AMC_COUNTER_BANKS * cap;
-        c->wev_buf[1].count = c->wev_buf[0].count + AMC_COUNTER_BANKS;
-    }
-    AMC_HIP(c, hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
-    {
-        int can = 0;
-        if (hipDeviceGetAttribute(&can, hipDeviceAttributeCanUseStreamWaitValue, c->device) != hipSuccess || !can) c->ovl_sync_values = 0;
-        AMC_HIP(c, dalloc(&c->ovl_flags, 64));
-        AMC_HIP(c, hipMemsetAsync(c->ovl_flags, 0, 64 * sizeof(unsigned int), c->stream));
-    }
-    AMC_HIP(c, hipEventCreateWithFlags(&c->ev_detect, hipEventDisableTiming));
-    AMC_HIP(c, hipEventCreateWithFlags(&c->ev_stream, hipEventDisableTiming));
+    const size_t per = ((sizeof(double) * n) + 255) & ~(size_t)255;
+    const size_t total = 10 * per + ((n + 255) & ~(size_t)255);
+    char *slab;
+    AMC_HIP(c, dalloc(c, &slab, total));
+    AMC_HIP(c, hipMemsetAsync(slab, 0, total, c->stream));
+    amc_state S;
+    double **st[] = {&S.x, &S.y, &S.z, &S.vx, &S.vy, &S.vz, &S.d, &S.dx, &S.dy, &S.dz};
+    size_t off = 0;
+    for (auto pp : st) { *pp = (double *)(slab + off); off += per; }
+    S.flag = (uint8_t *)(slab + off);
+    S.px = c->S_buf[0].px; S.py = c->S_buf[0].py; S.pz = c->S_buf[0].pz;      // (prior_*_vals are not kept by these runs)
+    const size_t nc = (size_t)c->G.ncells;
+    amc_lists B = c->B_buf[1];
+    AMC_HIP(c, dalloc(c, &B.rec, n + (size_t)c->max_extra));
+    AMC_HIP(c, dalloc(c, &B.head, nc + 1));
+    AMC_HIP(c, hipMemsetAsync(B.head, 0, sizeof(unsigned long long) * (nc + 1), c->stream));
+    B.epoch = 0; B.n = (int)c->n;
+    int *extra, *extra_count;
+    AMC_HIP(c, dalloc(c, &extra, (size_t)2 * c->max_extra));
+    AMC_HIP(c, dalloc(c, &extra_count, 2));
+    AMC_HIP(c, hipMemsetAsync(extra_count, 0, 2 * sizeof(int), c->stream));
+    // deferred events of a pass: wall hits (~1e-3 per particle and step in the pore), by bank
+    const int cap = (int)std::max<long long>(1024, (long long)c->n / (4 * AMC_COUNTER_BANKS));
+    amc_wev_rec *wev_rec;
+    unsigned int *wev_count, *flags;
+    AMC_HIP(c, dalloc(c, &wev_rec, (size_t)2 * AMC_COUNTER_BANKS * cap));
+    AMC_HIP(c, dalloc(c, &wev_count, (size_t)2 * AMC_COUNTER_BANKS));
+    AMC_HIP(c, hipMemsetAsync(wev_count, 0, sizeof(unsigned int) * 2 * AMC_COUNTER_BANKS, c->stream));
+    hipStream_t stream2;
+    hipEvent_t ev_detect, ev_stream;
+    AMC_HIP(c, ctx_stream(c, &stream2));
+    int can = 0, sync_values = c->ovl_sync_values;
+    if (hipDeviceGetAttribute(&can, hipDeviceAttributeCanUseStreamWaitValue, c->device) != hipSuccess || !can) sync_values = 0;
+    AMC_HIP(c, dalloc(c, &flags, 64));
+    AMC_HIP(c, hipMemsetAsync(flags, 0, 64 * sizeof(unsigned int), c->stream));
+    AMC_HIP(c, ctx_event(c, &ev_detect, hipEventDisableTiming));
+    AMC_HIP(c, ctx_event(c, &ev_stream, hipEventDisableTiming));
     AMC_HIP(c, hipStreamSynchronize(c->stream));
+    group.keep();
+    c->S_buf[1] = S; c->B_buf[1] = B;
+    c->extra_buf[0] = extra; c->extra_buf[1] = extra + c->max_extra; c->extra_count = extra_count;
+    c->wev_buf[0] = {wev_rec, wev_count, cap};
+    c->wev_buf[1] = {wev_rec + (size_t)AMC_COUNTER_BANKS * cap, wev_count + AMC_COUNTER_BANKS, cap};
+    c->stream2 = stream2; c->ev_detect = ev_detect; c->ev_stream = ev_stream;
+    c->ovl_sync_values = sync_values; c->ovl_flags = flags;
+    c->s_slab2 = slab;          // (the guard: last)
     return AMC_OK;
 }
 
@@ -741,9 +676,8 @@ static int run_overlapped(amc_ctx *c, double dt, int64_t nsteps)
             // (recorded above, BEHIND the detect kernel of step s - 1 and in front of its resolve kernels, which follow here)
             AMC_HIP(c, amc_launch_resolve(c, true));
         }
-        static const bool split = getenv("AMC_OVERLAP_SPLIT") && atoi(getenv("AMC_OVERLAP_SPLIT")) != 0;    // (experiment)
-        AMC_HIP(c, amc_launch_stream_ovl(c, dt, st, cur, prev_epoch, sp, !split));
-        if (split) AMC_HIP(c, amc_launch_bin_ovl(c, 1 - cur, prev_epoch, sp));
+        AMC_HIP(c, amc_launch_stream_ovl(c, dt, st, cur, prev_epoch, sp, !c->overlap_split));
+        if (c->overlap_split) AMC_HIP(c, amc_launch_bin_ovl(c, 1 - cur, prev_epoch, sp));
         if (two) {
             if (c->ovl_sync_values) {
                 AMC_HIP(c, hipStreamWriteValue32(c->stream2, c->ovl_flags + 16, c->ovl_tick, 0));

@@ -10,7 +10,7 @@ int amc_set_shard(amc_ctx *c, int64_t lo, int64_t hi)
     c->lo = lo; c->hi = hi;
     c->mg_count_pp = (lo == 0);     // the rank that owns particle 0 reports the sweep's collision count
     AMC_HIP(c, hipSetDevice(c->device));
-    if (!c->kin_vpub) AMC_HIP(c, hipMalloc((void **)&c->kin_vpub, sizeof(double) * 3 * (size_t)std::max<int64_t>(c->n, 1)));
+    if (!c->kin_vpub) AMC_HIP(c, dalloc(c, &c->kin_vpub, 3 * (size_t)std::max<int64_t>(c->n, 1)));
     if (c->uploaded) return amc_publish_velocities(c);
     return AMC_OK;
 }
@@ -32,45 +32,49 @@ int amc_mg_exchange_view(amc_ctx *c, int world, void **send, void **recv, int64_
     AMC_HIP(c, hipSetDevice(c->device));
     if (c->kin_world != world) {
         AMC_HIP(c, hipStreamSynchronize(c->stream));
-        if (c->kin_send) hipFree(c->kin_send);
-        if (c->kin_recv) hipFree(c->kin_recv);
-        c->kin_send = c->kin_recv = nullptr;
-        c->kin_world = 0;
-        c->kin_m = std::max<int64_t>((c->n + world - 1) / world, 1);
-        c->kin_cap = std::max<int64_t>(4096, c->kin_m / 8);
-        if (const char *e = getenv("AMC_MG_VELOCITY_LIST")) { const long long v = atoll(e); if (v > 0) c->kin_cap = v; }   // (tests)
+        const int64_t m = std::max<int64_t>((c->n + world - 1) / world, 1);
+        int64_t cap = std::max<int64_t>(4096, m / 8);
+        if (const char *e = getenv("AMC_MG_VELOCITY_LIST")) { const long long v = atoll(e); if (v > 0) cap = v; }   // (tests)
         const int64_t kb = amc_kin_banks();
-        c->kin_cap = (c->kin_cap + kb - 1) / kb * kb;                   // the same room in every bank
-        c->kin_block = 3 * c->kin_m + kb + 4 * c->kin_cap;
-        AMC_HIP(c, hipMalloc((void **)&c->kin_send, sizeof(double) * (size_t)c->kin_block));
-        AMC_HIP(c, hipMalloc((void **)&c->kin_recv, sizeof(double) * (size_t)c->kin_block * (size_t)world));
-        c->kin_world = world;
-        c->kin_counts_clear = false;
+        cap = (cap + kb - 1) / kb * kb;                                 // the same room in every bank
+        const int64_t blk = 3 * m + kb + 4 * cap;
         // kept lists (pore): a node pool per wave of the pack and of the unpack kernel, whose launch geometry is fixed by the
         // world size; the node records behind the particles' own grow if these pools need more than the single-GPU pass's
-        c->mg_keep = false;
-        c->lists_age = -1;
-        if (c->mg_wave_count) { hipFree(c->mg_wave_count); c->mg_wave_count = nullptr; }
-        if (c->keep_K >= 2 && c->B.cell_of && c->B_buf[0].rec == c->B.rec) {
-            const int64_t per = std::max<int64_t>(c->kin_m, c->kin_cap);
-            c->mg_waves_pack = (int)((c->kin_m + 255) / 256) * 4;
-            c->mg_waves_unpack = (int)(((int64_t)world * per + 255) / 256) * 4;
-            const size_t waves = (size_t)c->mg_waves_pack + (size_t)c->mg_waves_unpack;
-            const size_t pool = waves * (size_t)c->B.wave_cap;
-            if ((long long)c->n + (long long)pool <= 0x3fffffffLL) {
-                if (pool > c->keep_pool) {
-                    amc_rec *rec = nullptr; int *extra = nullptr;
-                    AMC_HIP(c, dalloc(&rec, (size_t)c->n + std::max((size_t)c->max_extra, pool)));
-                    AMC_HIP(c, dalloc(&extra, pool));
-                    hipFree(c->B.rec); hipFree(c->B.extra);
-                    c->B.rec = rec; c->B.extra = extra; c->keep_pool = pool;
-                    c->B_buf[0].rec = rec; c->B_buf[0].extra = extra;
-                }
-                AMC_HIP(c, dalloc(&c->mg_wave_count, waves));
-                AMC_HIP(c, hipMemsetAsync(c->mg_wave_count, 0, sizeof(int) * waves, c->stream));
-                c->mg_keep = true;
-            }
+        int waves_pack = 0, waves_unpack = 0;
+        size_t waves = 0, pool = 0;
+        const bool kept_lists = c->keep_K >= 2 && c->B.cell_of && c->B_buf[0].rec == c->B.rec;
+        if (kept_lists) {
+            const int64_t per = std::max<int64_t>(m, cap);
+            waves_pack = (int)((m + 255) / 256) * 4;
+            waves_unpack = (int)(((int64_t)world * per + 255) / 256) * 4;
+            waves = (size_t)waves_pack + (size_t)waves_unpack;
+            pool = waves * (size_t)c->B.wave_cap;
         }
+        const bool keep = kept_lists && (long long)c->n + (long long)pool <= 0x3fffffffLL, grow = keep && pool > c->keep_pool;
+        amc_alloc_group group(c);
+        double *ksend, *krecv;
+        amc_rec *rec = nullptr;
+        int *extra = nullptr, *wave_count = nullptr;
+        AMC_HIP(c, dalloc(c, &ksend, (size_t)blk));
+        AMC_HIP(c, dalloc(c, &krecv, (size_t)blk * (size_t)world));
+        if (grow) AMC_HIP(c, dalloc(c, &rec, (size_t)c->n + std::max((size_t)c->max_extra, pool)));
+        if (grow) AMC_HIP(c, dalloc(c, &extra, pool));
+        if (keep) AMC_HIP(c, dalloc(c, &wave_count, waves));
+        if (keep) AMC_HIP(c, hipMemsetAsync(wave_count, 0, sizeof(int) * waves, c->stream));
+        group.keep();
+        ctx_free(c, c->kin_send, c->kin_recv, c->mg_wave_count);
+        c->kin_send = ksend; c->kin_recv = krecv; c->mg_wave_count = wave_count;
+        c->kin_m = m; c->kin_cap = cap; c->kin_block = blk;
+        c->kin_counts_clear = false;
+        c->lists_age = -1;
+        if (grow) {
+            ctx_free(c, c->B.rec, c->B.extra);
+            c->B.rec = rec; c->B.extra = extra; c->keep_pool = pool;
+            c->B_buf[0].rec = rec; c->B_buf[0].extra = extra;
+        }
+        if (kept_lists) { c->mg_waves_pack = waves_pack; c->mg_waves_unpack = waves_unpack; }
+        c->mg_keep = keep;
+        c->kin_world = world;       // (the guard: last)
     }
     *send = c->kin_send; *recv = c->kin_recv; *block = c->kin_block;
     return AMC_OK;
@@ -124,22 +128,24 @@ int amc_mg_candidates_view(amc_ctx *c, int world, void **send, void **recv, int6
     AMC_HIP(c, hipSetDevice(c->device));
     if (c->cand_world != world) {
         AMC_HIP(c, hipStreamSynchronize(c->stream));
-        if (c->cand_send) hipFree(c->cand_send);
-        if (c->cand_recv) hipFree(c->cand_recv);
-        c->cand_send = c->cand_recv = nullptr;
         // a quarter of the context's candidate capacity (n / 32 pairs by default; amc_params.max_candidates scales it): ~60x the
         // pairs a rank of eight finds per step at the reference's density, and room for the first step of a synthetic start,
         // whose uniformly placed particles overlap by the ten thousand
         long long cap = std::max<long long>(4096, c->W.max_cand / 4);
         if (const char *e = getenv("AMC_MG_CANDIDATES")) { const long long v = atoll(e); if (v > 0) cap = v; }      // (tests)
-        c->cand_cap = (int)std::min<long long>(cap, c->W.max_cand);
-        const size_t blk = (size_t)2 + 2 * (size_t)c->cand_cap;
-        AMC_HIP(c, dalloc(&c->cand_send, blk));
-        AMC_HIP(c, dalloc(&c->cand_recv, blk * (size_t)world));
-        AMC_HIP(c, hipMemsetAsync(c->cand_send, 0, sizeof(int) * blk, c->stream));
-        AMC_HIP(c, hipMemsetAsync(c->cand_recv, 0, sizeof(int) * blk * (size_t)world, c->stream));
+        const int cand_cap = (int)std::min<long long>(cap, c->W.max_cand);
+        const size_t blk = (size_t)2 + 2 * (size_t)cand_cap;
+        amc_alloc_group group(c);
+        int *csend, *crecv;
+        AMC_HIP(c, dalloc(c, &csend, blk));
+        AMC_HIP(c, dalloc(c, &crecv, blk * (size_t)world));
+        AMC_HIP(c, hipMemsetAsync(csend, 0, sizeof(int) * blk, c->stream));
+        AMC_HIP(c, hipMemsetAsync(crecv, 0, sizeof(int) * blk * (size_t)world, c->stream));
         AMC_HIP(c, hipStreamSynchronize(c->stream));
-        c->cand_world = world;
+        group.keep();
+        ctx_free(c, c->cand_send, c->cand_recv);
+        c->cand_send = csend; c->cand_recv = crecv; c->cand_cap = cand_cap;
+        c->cand_world = world;      // (the guard: last)
     }
     *send = c->cand_send; *recv = c->cand_recv; *block_ints = 2 + 2 * (int64_t)c->cand_cap;
     return AMC_OK;

@@ -9,9 +9,9 @@ static int temp_ensure(amc_ctx *c)
 {
     if (c->P.geometry != AMC_GEOM_PORE_ENERGISED) return amc_fail(c, AMC_ERR_STATE, "energised-wall calls need AMC_GEOM_PORE_ENERGISED");
     if (c->T.idx) return AMC_OK;
-    amc_temp_ws &T = c->T;
-    T.cap = (int)std::min<int64_t>(std::max<int64_t>(4096, c->n / 8 + 1024), 0x3fffffff);
-    const size_t cap = (size_t)T.cap;
+    amc_alloc_group group(c);
+    const int icap = (int)std::min<int64_t>(std::max<int64_t>(4096, c->n / 8 + 1024), 0x3fffffff);
+    const size_t cap = (size_t)icap;
     // one pinned, device-mapped block: [count | idx | t | contact | normal | dir | Es | dpz | dE | ok]
     size_t off = 0;
     auto place = [&](size_t bytes) { const size_t at = off; off = (off + bytes + 255) & ~(size_t)255; return at; };
@@ -20,14 +20,20 @@ static int temp_ensure(amc_ctx *c)
                  o_dir = place(sizeof(double) * 3 * cap), o_Es = place(sizeof(double) * cap), o_dpz = place(sizeof(double) * cap),
                  o_dE = place(sizeof(double) * cap), o_ok = place(cap), o_dEs = place(sizeof(double) * cap),
                  o_ddpz = place(sizeof(double) * cap), o_ddE = place(sizeof(double) * cap);
-    void *hp = nullptr, *dp = nullptr;
-    AMC_HIP(c, hipHostMalloc(&hp, off, hipHostMallocMapped));
-    if (hipHostGetDevicePointer(&dp, hp, 0) != hipSuccess) { hipHostFree(hp); return amc_fail(c, AMC_ERR_HIP, "hipHostGetDevicePointer failed"); }
+    void *hp, *dp = nullptr;
+    int *count, *def_idx;
+    double *def_dir;
+    AMC_HIP(c, palloc(c, &hp, off, hipHostMallocMapped));
+    AMC_HIP(c, hipHostGetDevicePointer(&dp, hp, 0));
+    AMC_HIP(c, dalloc(c, &count, 16));      // (the hit counter stays in device memory: every hit increments it atomically)
+    AMC_HIP(c, dalloc(c, &def_idx, cap));
+    AMC_HIP(c, dalloc(c, &def_dir, 3 * cap));
+    group.keep();
     memset(hp, 0, off);
-    T.pin = hp;
+    amc_temp_ws &T = c->T;
     char *h = (char *)hp, *d = (char *)dp;
-    AMC_HIP(c, dalloc(&T.count, 16));       // (the hit counter stays in device memory: every hit increments it atomically)
-    T.idx = (int *)(d + o_idx); T.t = (double *)(d + o_t); T.contact = (double *)(d + o_contact);
+    T.cap = icap; T.pin = hp; T.count = count; T.def_idx = def_idx; T.def_dir = def_dir;
+    T.t = (double *)(d + o_t); T.contact = (double *)(d + o_contact);
     T.normal = (double *)(d + o_normal); T.dir = (double *)(d + o_dir); T.Es = (double *)(d + o_Es); T.dpz = (double *)(d + o_dpz);
     T.dE = (double *)(d + o_dE); T.ok = (unsigned char *)(d + o_ok);
     T.h_count = (int *)(h + o_count); T.h_idx = (int *)(h + o_idx); T.h_contact = (double *)(h + o_contact);
@@ -35,10 +41,7 @@ static int temp_ensure(amc_ctx *c)
     T.h_dpz = (double *)(h + o_dpz); T.h_dE = (double *)(h + o_dE);
     T.def_Es = (double *)(d + o_dEs); T.def_dpz = (double *)(d + o_ddpz); T.def_dE = (double *)(d + o_ddE);
     T.h_def_Es = (double *)(h + o_dEs); T.h_def_dpz = (double *)(h + o_ddpz); T.h_def_dE = (double *)(h + o_ddE);
-    AMC_HIP(c, dalloc(&T.def_idx, cap));
-    AMC_HIP(c, dalloc(&T.def_dir, 3 * cap));
-    T.def_case = -1; T.def_n = 0;
-    T.last_case = -1; T.last_n = 0; T.pre_case = -1;
+    T.idx = (int *)(d + o_idx);             // (the guard: last)
     return AMC_OK;
 }
 
@@ -196,11 +199,19 @@ static int temp_dev_ensure(amc_ctx *c)
     if (c->P.geometry != AMC_GEOM_PORE_ENERGISED) return amc_fail(c, AMC_ERR_STATE, "energised-wall calls need AMC_GEOM_PORE_ENERGISED");
     amc_temp_dev_ws &D = c->TD;
     if (D.idx) return AMC_OK;
-    D.cap = (int)std::min<int64_t>(std::max<int64_t>(4096, c->n / 64 + 1024), 0x0fffffff);
-    const size_t cap = (size_t)D.cap * 7;
-    AMC_HIP(c, dalloc(&D.idx, cap)); AMC_HIP(c, dalloc(&D.count, 8)); AMC_HIP(c, dalloc(&D.t, cap));
-    AMC_HIP(c, dalloc(&D.contact, 3 * cap)); AMC_HIP(c, dalloc(&D.normal, 3 * cap)); AMC_HIP(c, dalloc(&D.dir, 3 * cap));
-    AMC_HIP(c, dalloc(&D.Es, cap)); AMC_HIP(c, dalloc(&D.dpz, cap)); AMC_HIP(c, dalloc(&D.dE, cap)); AMC_HIP(c, dalloc(&D.ok, cap));
+    amc_alloc_group group(c);
+    const int icap = (int)std::min<int64_t>(std::max<int64_t>(4096, c->n / 64 + 1024), 0x0fffffff);
+    const size_t cap = (size_t)icap * 7;
+    int *idx, *count;
+    double *t, *contact, *normal, *dir, *Es, *dpz, *dE;
+    unsigned char *ok;
+    AMC_HIP(c, dalloc(c, &idx, cap)); AMC_HIP(c, dalloc(c, &count, 8)); AMC_HIP(c, dalloc(c, &t, cap));
+    AMC_HIP(c, dalloc(c, &contact, 3 * cap)); AMC_HIP(c, dalloc(c, &normal, 3 * cap)); AMC_HIP(c, dalloc(c, &dir, 3 * cap));
+    AMC_HIP(c, dalloc(c, &Es, cap)); AMC_HIP(c, dalloc(c, &dpz, cap)); AMC_HIP(c, dalloc(c, &dE, cap)); AMC_HIP(c, dalloc(c, &ok, cap));
+    group.keep();
+    D.cap = icap;
+    D.count = count; D.t = t; D.contact = contact; D.normal = normal; D.dir = dir; D.Es = Es; D.dpz = dpz; D.dE = dE; D.ok = ok;
+    D.idx = idx;                // (the guard: last)
     return AMC_OK;
 }
 

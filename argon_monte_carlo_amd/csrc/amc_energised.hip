@@ -324,9 +324,7 @@ hipError_t amc_launch_temp_cases_device(amc_ctx *c, const amc_temp_rng *cfg)
     amc_temp_dev_ws &D = c->TD;
     hipError_t e = hipMemsetAsync(D.count, 0, sizeof(int) * 7, c->stream);
     if (e != hipSuccess || cnt <= 0) return e;
-    static int unfused = -1;
-    if (unfused < 0) unfused = getenv("AMC_TEMP_UNFUSED") ? 1 : 0;      // cross-check path: one hits/sample/apply triple per case
-    if (!unfused) {
+    if (!c->temp_unfused) {
         temp_dev_segments G;
         G.idx = D.idx; G.count = D.count; G.t = D.t; G.contact = D.contact; G.normal = D.normal; G.dir = D.dir;
         G.Es = D.Es; G.dpz = D.dpz; G.dE = D.dE; G.ok = D.ok; G.cap = D.cap;

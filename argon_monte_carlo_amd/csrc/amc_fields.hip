@@ -181,13 +181,10 @@ static int fields_enqueue(amc_ctx *c)
     return AMC_OK;
 }
 
-void amc_fields_free(amc_ctx *c)
+static void fields_free(amc_ctx *c)
 {
-    amc_fields_ws &F = c->F;
-    if (F.slab) hipFree(F.slab);
-    if (F.tot) hipFree(F.tot);
-    if (F.meta) hipFree(F.meta);
-    memset(&F, 0, sizeof F);
+    ctx_free(c, c->F.slab, c->F.tot, c->F.meta);
+    c->F = amc_fields_ws();
 }
 
 static int fields_clear(amc_ctx *c)
@@ -214,7 +211,7 @@ int amc_fields_config(amc_ctx *c, const amc_field_grid *g)
     AMC_HIP(c, hipSetDevice(c->device));
     AMC_HIP(c, hipStreamSynchronize(c->stream));        // (a sample in flight may still use the old buffers)
     if (!g) {
-        amc_fields_free(c);
+        fields_free(c);
         return AMC_OK;
     }
     if (g->struct_size != (int32_t)sizeof(amc_field_grid)) return amc_fail(c, AMC_ERR_INVALID, "amc_field_grid.struct_size mismatch (ABI)");
@@ -231,7 +228,7 @@ int amc_fields_config(amc_ctx *c, const amc_field_grid *g)
     for (int k = 0; k < axes; k++)
         if (!(isfinite(g->lo[k]) && isfinite(g->hi[k]) && g->lo[k] < g->hi[k]))
             return amc_fail(c, AMC_ERR_INVALID, "amc_field_grid: axis %d needs finite bounds lo < hi", k + 1);
-    amc_fields_free(c);
+    fields_free(c);
     amc_fields_ws &F = c->F;
     F.g = *g;
     F.bins = g->n1 * g->n2 * g->n3;
@@ -244,13 +241,13 @@ int amc_fields_config(amc_ctx *c, const amc_field_grid *g)
     F.max_blocks = F.blocks_env > 0 ? F.blocks_env : cus;
     const size_t M = (size_t)F.bins * AMC_FIELDS_Q;
     int rc = AMC_OK;
-    if (dalloc(&F.slab, (size_t)F.max_blocks * (M + 1)) != hipSuccess || dalloc(&F.tot, 2 * M) != hipSuccess ||
-        dalloc(&F.meta, 3) != hipSuccess) {
-        amc_fields_free(c);
+    if (dalloc(c, &F.slab, (size_t)F.max_blocks * (M + 1)) != hipSuccess || dalloc(c, &F.tot, 2 * M) != hipSuccess ||
+        dalloc(c, &F.meta, 3) != hipSuccess) {
+        fields_free(c);
         return amc_fail(c, AMC_ERR_HIP, "amc_fields_config: device allocation failed");
     }
     F.on = true;
-    if ((rc = fields_clear(c))) { amc_fields_free(c); return rc; }
+    if ((rc = fields_clear(c))) { fields_free(c); return rc; }
     return AMC_OK;
 }
 

@@ -448,7 +448,7 @@ hipError_t amc_launch_detect(amc_ctx *c)
         // (an overlapped run: four more blocks for the particles the fix-up kernel filed again under extra nodes)
         const bool extras = c->B.extra != nullptr && c->keep_K < 2;
         const int slot = (c->B.extra == c->extra_buf[1]) ? 1 : 0;
-        static const int bs = getenv("AMC_DETECT_BS") ? atoi(getenv("AMC_DETECT_BS")) : 256;      // (experiments: 64 / 128 / 256)
+        const int bs = c->detect_bs;
         // (occupancy is not what bounds this kernel: capped at 4 waves per SIMD instead of 5 it takes the same 36.7 us at
         // N = 1e6, at 2 it takes 59 — it runs at the rate of its random requests; two or four particles per thread,
         // one after the other, change nothing at N = 1e6 and cost 5 / 15 us at N = 1e5)

@@ -12,13 +12,55 @@
 
 #include "amc_internal.h"
 
-template <class T>
-static hipError_t dalloc(T **p, size_t count)
+// ---- what a context owns ------------------------------------------------------------------------------------------------
+// Every device and pinned allocation, stream and event of a context is made by dalloc / palloc / ctx_stream / ctx_event and
+// recorded in amc_ctx::owned: ctx_free releases recorded objects (a buffer that is replaced), amc_destroy whatever is left.
+static hipError_t ctx_record(amc_ctx *c, hipError_t e, void **p, amc_res_kind kind)
 {
-    *p = nullptr;
-    if (count == 0) count = 1;
-    return hipMalloc((void **)p, sizeof(T) * count);
+    if (e == hipSuccess) c->owned.push_back({*p, kind});
+    else *p = nullptr;
+    return e;
 }
+template <class T>
+static hipError_t dalloc(amc_ctx *c, T **p, size_t count)       // device memory for count (at least one) elements
+{ return ctx_record(c, hipMalloc((void **)p, sizeof(T) * std::max<size_t>(count, 1)), (void **)p, AMC_RES_DEVICE); }
+template <class T>
+static hipError_t palloc(amc_ctx *c, T **p, size_t bytes, unsigned int flags)     // pinned host memory
+{ return ctx_record(c, hipHostMalloc((void **)p, bytes, flags), (void **)p, AMC_RES_PINNED); }
+static hipError_t ctx_stream(amc_ctx *c, hipStream_t *s)
+{ return ctx_record(c, hipStreamCreateWithFlags(s, hipStreamNonBlocking), (void **)s, AMC_RES_STREAM); }
+static hipError_t ctx_event(amc_ctx *c, hipEvent_t *ev, unsigned int flags)
+{ return ctx_record(c, hipEventCreateWithFlags(ev, flags), (void **)ev, AMC_RES_EVENT); }
+
+static void ctx_release(const amc_res &r)
+{
+    if (r.kind == AMC_RES_DEVICE) (void)hipFree(r.p);
+    else if (r.kind == AMC_RES_PINNED) (void)hipHostFree(r.p);
+    else if (r.kind == AMC_RES_STREAM) (void)hipStreamDestroy((hipStream_t)r.p);
+    else (void)hipEventDestroy((hipEvent_t)r.p);
+}
+template <class... P>
+static void ctx_free(amc_ctx *c, P... ps)                       // (nullptr: nothing)
+{
+    for (const void *q : {(const void *)ps...})
+        for (size_t k = c->owned.size(); q && k-- > 0;)
+            if (c->owned[k].p == q) { ctx_release(c->owned[k]); c->owned.erase(c->owned.begin() + k); break; }
+}
+static void ctx_free_since(amc_ctx *c, size_t mark)             // all but the first `mark` objects, newest first
+{
+    for (; c->owned.size() > mark; c->owned.pop_back()) ctx_release(c->owned.back());
+}
+
+// All-or-nothing set-up of a lazily built work space: what is allocated while the group is open is released again when it
+// goes out of scope (an early return on a failed call), unless keep() was called.  The caller builds into locals, calls
+// keep() once everything succeeded, then publishes the pointers, its guard last.  Nothing older is freed while it is open.
+struct amc_alloc_group {
+    amc_ctx *c;
+    size_t mark;
+    explicit amc_alloc_group(amc_ctx *ctx) : c(ctx), mark(ctx->owned.size()) {}
+    ~amc_alloc_group() { if (c) ctx_free_since(c, mark); }
+    void keep() { c = nullptr; }
+};
 
 // Small device -> host read-backs go through the pinned staging buffer: queue any number of pieces, synchronise once,
 // then copy out.  (Falls back to direct copies when a piece does not fit.)
@@ -56,7 +98,6 @@ AMC_INTERNAL int amc_publish_velocities(amc_ctx *c);                    // multi
 AMC_INTERNAL int amc_flush(amc_ctx *c);                                 // write deferred sweep results to the particle arrays
 AMC_INTERNAL int amc_enqueue_sweep(amc_ctx *c, bool counted = false, bool defer_commit = false);   // bin (unless counted) + detect + resolve
 AMC_INTERNAL int amc_fields_step(amc_ctx *c);                         // the cadence hook after a completed step (amc_fields.hip)
-AMC_INTERNAL void amc_fields_free(amc_ctx *c);
 
 // a sample is due after the step that leaves the step counter at `step`
 static inline bool amc_fields_due(const amc_ctx *c, int64_t step)

@@ -154,8 +154,8 @@ struct amc_temp_ws {
     double *h_contact, *h_normal, *h_dir, *h_Es, *h_dpz, *h_dE;
     void *pin;
     int cap;
-    int last_case, last_n;       // the pending amc_wall_hits
-    int pre_case;                // >= 0: the hits of this case are already in the records (launched behind the previous
+    int last_case = -1, last_n = 0;  // the pending amc_wall_hits
+    int pre_case = -1;           // >= 0: the hits of this case are already in the records (launched behind the previous
                                  // case's apply kernel: one synchronisation serves both)
     std::vector<int> perm;       // sorted position -> record slot of the pending hits
     // a PARKED case (amc_wall_park / amc_wall_finish: the gap case while its surface energies are still being integrated):
@@ -163,7 +163,7 @@ struct amc_temp_ws {
     int *def_idx;
     double *def_dir, *def_Es, *def_dpz, *def_dE;    // (the last three: device views of pinned memory, host views below)
     double *h_def_Es, *h_def_dpz, *h_def_dE;
-    int def_case, def_n;
+    int def_case = -1, def_n = 0;
     std::vector<int> def_perm;
 };
 
@@ -193,6 +193,14 @@ struct amc_fields_ws {
     unsigned long long *meta;   // [0] samples, [1] particles outside, [2] lowest particle index out of range (~0: none)
 };
 
+// what amc_ctx::owned records (amc_host.h): the context's device / pinned allocations, streams and events
+enum amc_res_kind { AMC_RES_DEVICE, AMC_RES_PINNED, AMC_RES_STREAM, AMC_RES_EVENT };
+struct amc_res { void *p; amc_res_kind kind; };
+
+#define AMC_PLAN_SMALL 430      // default of amc_ctx::plan_small: measured crossover of the two launch plans (tools/plan_sweep.sh;
+                                // experiments: environment variable AMC_PLAN_SMALL)
+
+// Created by amc_create with value-initialisation: every member without an initialiser below starts at zero.
 struct amc_ctx {
     amc_params P;
     int device;
@@ -220,10 +228,9 @@ struct amc_ctx {
     int ovl_sync_values;      // ~2 us per dependency instead of ~8, tools/ubench_xstream.hip, but the resolve suffers more: DESIGN 4.2)
     int64_t ovl_steps;        // steps run overlapped so far
     int keep_K;               // kept lists: a full build every keep_K steps (< 2: every step, the lists are not kept)
-    int lists_age;            // steps since the last full build of a kept cycle (-1: the lists are not a kept cycle's)
+    int lists_age = -1;       // steps since the last full build of a kept cycle (-1: the lists are not a kept cycle's)
     int lists_owner;          // who runs the cycle: 1 the streaming pass, 2 the multi-GPU exchange kernels (their node pools differ)
-    int keep_threads;         // block size of the streaming pass the pools were sized for
-    int overlap_mode;         // AMC_OVERLAP: 1 (default) two streams, 2 the same kernels in order on one stream (debug), 0 off
+    int overlap_mode;         // AMC_OVERLAP: 0 off (default), 1 two streams, 2 the same kernels in order on one stream (debug)
     amc_resolve_ws W;
     char *w_slab;             // the one allocation W's arrays are carved from
     char *s_slab;             // the one allocation the particle state arrays are carved from
@@ -242,6 +249,10 @@ struct amc_ctx {
     amc_dev_counters h_prev;  // snapshot used to report per-step deltas
     long long *d_dbg;         // resolve phase timers (diagnostic, enabled by AMC_DEBUG_RESOLVE=1)
     int cw_blocks_env;        // AMC_CW_BLOCKS at creation (0 = default number of wide-kernel waves)
+    int stream_bs;            // AMC_STREAM_BS at creation: block size of the streaming pass (the kept-list pools are sized for it)
+    int detect_bs;            // AMC_DETECT_BS at creation: block size of the list-based detect kernel
+    bool temp_unfused;        // AMC_TEMP_UNFUSED set at creation: the device-RNG energised mode runs one kernel triple per case
+    bool overlap_split;       // AMC_OVERLAP_SPLIT != 0 at creation: an overlapped run builds its lists in a kernel of its own
     // profiling
     bool profiling;
     double k_ms[AMC_K_COUNT];
@@ -252,7 +263,7 @@ struct amc_ctx {
     hipEvent_t prof_ev0, prof_ev1;  // the open bracket's events (nullptr outside a bracket / when not profiling): AMC_LAUNCH
                                     // attaches them to the dispatch itself
     // multi-GPU
-    bool mg_count_pp;              // this rank adds the p-p collision count to its counters
+    bool mg_count_pp = true;       // this rank adds the p-p collision count to its counters
     volatile int *h_host_ncand;    // host-mapped word written by k_resolve (candidate count of the last sweep)
     int *d_host_ncand;             // its device address
     bool lazy_pending;             // sweep results wait in the slot arrays for the next streaming pass (or amc_flush)
@@ -260,7 +271,7 @@ struct amc_ctx {
     bool commit_defer;             // ... and that sweep's results stay in the slot arrays
     unsigned int sweep_epoch;      // tag of the degree counts of the current sweep (advanced by every detect launch)
     bool plan_split;               // launch plan of the current sweep, fixed when its detect kernel is launched
-    int plan_small;                // candidate pairs up to which the single resolve kernel does the whole sweep
+    int plan_small = AMC_PLAN_SMALL;   // candidate pairs up to which the single resolve kernel does the whole sweep
     // pinned host staging for the small per-step read-backs (a copy into pageable memory costs ~100 us on this stack)
     char *h_pin;
     size_t h_pin_bytes;
@@ -275,10 +286,11 @@ struct amc_ctx {
     int *mg_wave_count;            // [mg_waves_pack + mg_waves_unpack]
     int mg_waves_pack, mg_waves_unpack;
     bool mg_keep;                  // the pools exist for the current world size
-    int kin_mode;                  // this step's list build: 1 anew, 2 full build of a kept cycle, 3 a step in between
+    int kin_mode = 1;              // this step's list build: 1 anew, 2 full build of a kept cycle, 3 a step in between
     size_t keep_pool;              // nodes behind the particles' own in B.rec / entries of B.extra
     bool kin_lists;                // amc_mg_pack started this step's per-cell lists (the unpack completes them)
     bool kin_counts_clear;         // the bank counters in kin_send are zero (cleared by the last unpack kernel)
+    std::vector<amc_res> owned;    // everything allocated for the context, in order (amc_host.h); amc_destroy frees it
 };
 
 int amc_fail(amc_ctx *c, int code, const char *fmt, ...);
@@ -307,9 +319,6 @@ void amc_prof_cancel(amc_ctx *c);
 void amc_prof_collect(amc_ctx *c);
 
 // stage bits of the streaming kernel
-#define AMC_PLAN_SMALL 430      // default of amc_ctx::plan_small: measured crossover of the two launch plans (tools/plan_sweep.sh;
-                                // experiments: environment variable AMC_PLAN_SMALL)
-#define AMC_OVERLAP_MIN_N 300000 // default of the overlapped run (amc_api.hip): particles from which amc_run overlaps
 #define AMC_ST_DRIFT 1
 #define AMC_ST_WALLS 2
 #define AMC_ST_BOUNDS 4

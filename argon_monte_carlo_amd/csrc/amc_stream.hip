@@ -326,10 +326,10 @@ amc_commit_args amc_make_commit_args(amc_ctx *c)
 
 hipError_t amc_launch_stream(amc_ctx *c, double dt, int stages, int bounds_slot, bool fuse_bin)
 {
-    static const int threads = getenv("AMC_STREAM_BS") ? atoi(getenv("AMC_STREAM_BS")) : 256;      // (experiments: 64 / 128 / 256)
+    const int threads = c->stream_bs;
     int build = 0;
     if (fuse_bin && !c->allpairs && c->lo == 0 && c->hi == c->n) {
-        if (c->keep_K >= 2 && threads == c->keep_threads && c->B.cell_of) {
+        if (c->keep_K >= 2 && c->B.cell_of) {
             // kept lists: a full build when the lists are not this pass's own or the cycle is over, else a step in between
             if (c->lists_owner != 1) c->lists_age = -1;
             c->lists_owner = 1;

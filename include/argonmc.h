@@ -359,9 +359,9 @@ int amc_mg_finish(amc_ctx *ctx, amc_step_stats *out);      /* out == NULL: no ho
 int amc_profile(amc_ctx *ctx, int enable);
 int amc_kernel_times(amc_ctx *ctx, double *total_ms /*[AMC_K_COUNT]*/, int64_t *launches /*[AMC_K_COUNT]*/);
 const char *amc_kernel_name(int k);
-/* amc_run overlaps the streaming pass of step s + 1 with the resolve of sweep s (whole range in one context, cube /
- * specular pore, binned detector, at least two steps; environment AMC_OVERLAP=0 turns it off, =2 runs the same kernels in
- * order on one stream).  Results are those of the plain sequence bit for bit — the loop body of Pore:416-557 / Cube:175-338
+/* With environment AMC_OVERLAP=1 (opt-in: off by default), amc_run overlaps the streaming pass of step s + 1 with the
+ * resolve of sweep s (whole range in one context, cube / specular pore, binned detector, at least two steps); =2 runs the
+ * same kernels in order on one stream.  Results are those of the plain sequence bit for bit — the loop body of Pore:416-557 / Cube:175-338
  * once per step.  out[0] = steps run that way so far, out[1] = particles a sweep pulled into a cluster after the next pass
  * had already advanced them (advanced again from the sweep's result and filed under an extra list node), out[2] = mode,
  * out[3] = extra list nodes available per step. */
