@@ -7,12 +7,14 @@
 #include <string.h>
 
 #include <algorithm>
+#include <chrono>
 #include <memory>
 #include <vector>
 #include <new>
 #include <type_traits>
 
 #include "amc_host.h"
+#include "amc_resolve_dev.h"
 
 int amc_fail(amc_ctx *c, int code, const char *fmt, ...)
 {
@@ -209,6 +211,9 @@ int amc_create(amc_ctx **out, const amc_params *p)
     c->overlap_mode = getenv("AMC_OVERLAP") ? atoi(getenv("AMC_OVERLAP")) : 0;
     c->overlap_split = getenv("AMC_OVERLAP_SPLIT") && atoi(getenv("AMC_OVERLAP_SPLIT")) != 0;     // (experiment)
     c->cw_blocks_env = getenv("AMC_CW_BLOCKS") ? atoi(getenv("AMC_CW_BLOCKS")) : 0;
+    c->ordered_always = getenv("AMC_ORDERED_ALWAYS") && atoi(getenv("AMC_ORDERED_ALWAYS")) != 0;
+    if (const char *e = getenv("AMC_OD_MAX_N")) c->od_max_n = atoll(e);                                  // (tests, experiments)
+    if (const char *e = getenv("AMC_OD_AHEAD")) c->od_ahead = std::min(std::max(atoi(e), 1), 32);     // (experiments)
     if (const char *e = getenv("AMC_PLAN_SMALL")) { const int v = atoi(e); if (v >= 0) c->plan_small = v; }
     c->stream_bs = getenv("AMC_STREAM_BS") ? atoi(getenv("AMC_STREAM_BS")) : 256;      // (experiments: 64 / 128 / 256)
     c->detect_bs = getenv("AMC_DETECT_BS") ? atoi(getenv("AMC_DETECT_BS")) : 256;      // (experiments: 64 / 128 / 256)
@@ -359,11 +364,16 @@ int amc_create(amc_ctx **out, const amc_params *p)
         }
         {
             void *hp = nullptr, *dp = nullptr;
-            if (palloc(c, &hp, 64, hipHostMallocMapped) == hipSuccess && hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess) {
+            // (three words, a cache line apart: candidate count; mirror of stalled_at; last step whose wide kernel ran)
+            if (palloc(c, &hp, 256, hipHostMallocMapped) == hipSuccess && hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess) {
+                memset(hp, 0, 256);
                 c->h_host_ncand = (volatile int *)hp;
-                *c->h_host_ncand = 0;
                 c->d_host_ncand = (int *)dp;
+                c->h_od_stall = (volatile int *)hp + 16; c->d_od_stall_host = (int *)dp + 16;
+                c->h_od_done = (volatile int *)hp + 32; c->d_od_done_host = (int *)dp + 32;
             }
+            AMC_HIP(c, dalloc(c, &c->d_od, 16));
+            AMC_HIP(c, hipMemsetAsync(c->d_od, 0, 16 * sizeof(int), c->stream));
         }
         if (palloc(c, &c->h_pin, (size_t)4 << 20, hipHostMallocDefault) == hipSuccess) c->h_pin_bytes = (size_t)4 << 20;
         if (getenv("AMC_DEBUG_RESOLVE")) {
@@ -709,6 +719,95 @@ static int run_overlapped(amc_ctx *c, double dt, int64_t nsteps)
     return AMC_OK;
 }
 
+// ---- the ordered workgroup on demand -------------------------------------------------------------------------
+// host state after a step has been enqueued: what a rewind to that step restores, and the arguments its wide kernel had
+struct amc_od_snap {
+    amc_lists B;
+    int lists_age, lists_owner;
+    unsigned int sweep_epoch;
+    bool plan_split;
+    unsigned int out_step;
+    rs_args used;
+};
+
+static int run_on_demand(amc_ctx *c, double dt, int64_t nsteps)
+{
+    const int g = c->P.geometry;
+    const int st0 = (g == AMC_GEOM_CUBE) ? (AMC_ST_DRIFT | AMC_ST_WALLS) : (AMC_ST_DRIFT | AMC_ST_WALLS | AMC_ST_BOUNDS);
+    std::vector<amc_od_snap> ring(AMC_OD_RING);
+    const int tick0 = c->od_tick;                       // step s of this run has index tick0 + s
+    int rc = AMC_OK;
+    // the answer to a stall: the ordered workgroup for the sweep that raised the word (it clears it), the host's epochs back
+    // to the state after that step; the steps after it did nothing and are enqueued again
+    auto answer = [&](int at, int64_t *s, bool stalled) -> int {
+        const amc_od_snap &R = ring[at % AMC_OD_RING];
+        c->B = R.B; c->lists_age = R.lists_age; c->lists_owner = R.lists_owner; c->sweep_epoch = R.sweep_epoch;
+        c->plan_split = R.plan_split; c->out.step = R.out_step;
+        c->commit_pending = true; c->lazy_pending = true; c->commit_defer = true;
+        AMC_HIP(c, amc_launch_ordered(c, R.used));
+        c->od_handled = at;
+        if (stalled) { c->od_stalls++; if (at == tick0 + (int)nsteps - 1) c->od_stalls_last++; }
+        *s = (int64_t)(at - tick0) + 1;
+        return AMC_OK;
+    };
+    auto stall_seen = [&]() -> int { const int v = *c->h_od_stall; return v > c->od_handled ? v : 0; };
+    c->od_active = true;
+    for (int64_t s = 0;;) {
+        if (s == nsteps) {
+            // the end of the run: only now is it known whether a sweep before the last one still waits
+            if (hipStreamSynchronize(c->stream) != hipSuccess) { rc = amc_fail(c, AMC_ERR_HIP, "hipStreamSynchronize failed in amc_run"); break; }
+            int at = stall_seen();
+            const bool stalled = at != 0;
+            // (the last sweep gets its ordered pass in any case: the run ends in the state every other entry point expects)
+            if (!at) at = tick0 + (int)nsteps - 1;
+            if ((rc = answer(at, &s, stalled))) break;
+            if (s == nsteps) break;
+            continue;
+        }
+        // not more than od_ahead steps in front of the last wide kernel that ran: a stall costs the empty launches in between
+        const int tick = tick0 + (int)s;
+        if (tick - *c->h_od_done > c->od_ahead && !stall_seen()) {
+            // (a plain read of host memory; the clock is read every 1,024 reads, and after 2 ms without a step finishing the
+            // stream is asked where it is — the wait ends with the stream's completion at the latest)
+            int last = *c->h_od_done;
+            unsigned spins = 0;
+            auto t_last = std::chrono::steady_clock::now();
+            for (;;) {
+                const int done = *c->h_od_done;
+                if (tick - done <= c->od_ahead || stall_seen()) break;
+                if (done != last) { last = done; t_last = std::chrono::steady_clock::now(); }
+                else if ((++spins & 1023u) == 0 && std::chrono::steady_clock::now() - t_last > std::chrono::milliseconds(2)) {
+                    if (hipStreamSynchronize(c->stream) != hipSuccess) rc = amc_fail(c, AMC_ERR_HIP, "hipStreamSynchronize failed in amc_run");
+                    break;
+                }
+            }
+            if (rc) break;
+        }
+        if (const int at = stall_seen()) {
+            if ((rc = answer(at, &s, true))) break;
+            continue;
+        }
+        c->od_tick = tick;
+        int st = st0;
+        if (s > 0 && g == AMC_GEOM_PORE) st |= AMC_ST_BOUNDS_PRE;       // (the previous step's post-sweep bounds check rides along)
+        hipError_t e = amc_launch_stream(c, dt, st, 0, true);
+        if (e == hipSuccess) e = amc_launch_detect(c);
+        amc_od_snap &R = ring[tick % AMC_OD_RING];
+        if (e == hipSuccess) e = amc_launch_wide_only(c, &R.used);
+        if (e != hipSuccess) { rc = amc_fail(c, AMC_ERR_HIP, "launch failed in amc_run: %s", hipGetErrorString(e)); break; }
+        c->lazy_pending = true;
+        c->out.step++;
+        R.B = c->B; R.lists_age = c->lists_age; R.lists_owner = c->lists_owner; R.sweep_epoch = c->sweep_epoch;
+        R.plan_split = c->plan_split; R.out_step = c->out.step;
+        s++;
+    }
+    c->od_active = false;
+    c->od_tick = tick0 + (int)nsteps;
+    if (rc) return rc;
+    if (g == AMC_GEOM_PORE) AMC_HIP(c, amc_launch_stream(c, dt, AMC_ST_BOUNDS, 1));     // Pore:550 of the last step
+    return AMC_OK;
+}
+
 int amc_run(amc_ctx *c, double dt, int64_t nsteps, amc_step_stats *sum)
 {
     if (!c) return AMC_ERR_INVALID;
@@ -725,6 +824,13 @@ int amc_run(amc_ctx *c, double dt, int64_t nsteps, amc_step_stats *sum)
     }
     // inside the run only the last step needs its own post-sweep bounds pass (needs the whole range in one context) — and
     // every step that is sampled: the sample sees the step's final state
+    if (!c->ordered_always && whole && nsteps >= AMC_OD_MIN_STEPS && nsteps < (1 << 30) && !c->F.on && !c->keep_prior && !c->detect_ap &&
+        !c->d_dbg && c->n > 0 && c->n <= c->od_max_n && c->h_od_stall && c->od_tick < (1 << 30) &&
+        (c->P.geometry == AMC_GEOM_CUBE || c->P.geometry == AMC_GEOM_PORE)) {
+        int rc = run_on_demand(c, dt, nsteps);
+        if (rc) return rc;
+        return amc_finish_stats(c, sum);
+    }
     const bool fold = c->P.geometry == AMC_GEOM_PORE && whole;
     bool deferred = false;
     for (int64_t s = 0; s < nsteps; s++) {
@@ -914,6 +1020,7 @@ int amc_overlap_stats(amc_ctx *c, int64_t *out)
     int rc = amc_read_counters(c, &now);
     if (rc) return rc;
     out[0] = c->ovl_steps; out[1] = now.n_refiled; out[2] = c->overlap_mode; out[3] = c->max_extra;
+    out[4] = c->od_ordered_launches; out[5] = c->od_steps; out[6] = c->od_stalls; out[7] = c->od_stalls_last;
     return AMC_OK;
 }
 

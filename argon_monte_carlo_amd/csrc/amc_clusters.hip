@@ -141,7 +141,7 @@ AMC_DEV void cw_probe_grid(const rs_args &A, rs_shared *wc, cw_lds &L, const cw_
                     L.redo[own] = 1;
                     continue;
                 }
-                if (s >= W.max_slots) wc->ovf = 1;
+                if (s >= W.max_slots) { wc->ovf = 1; rs_raise(W); }
                 else { W.sl_meta[s] = make_int4(idx, s, 0, 0); W.sl_moved[s] = 0; atomicAnd(&W.sl_hits[s], 0); }
                 W.slot_of[idx] = s < W.max_slots ? s : -1;      // too many at once: a plain merge edge instead
             }
@@ -175,7 +175,7 @@ AMC_DEV void cw_probe_overlay(const rs_args &A, rs_shared *wc, cw_lds &L, const 
     int h2 = skip_own(__hip_atomic_load(&W.ov_head[cell], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
     int guard = 0;
     while (h2 >= 0) {
-        if (++guard > W.max_hist) { wc->ovf = 1; break; }      // (a list cannot be longer than there are entries: reported, not spun on)
+        if (++guard > W.max_hist) { wc->ovf = 1; rs_raise(W); break; }      // (a list cannot be longer than there are entries: reported, not spun on)
         const double4 o = cw_load_hist(W, h2);
         const int nx = __hip_atomic_load(&W.ov_next[h2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         h2 = skip_own(nx);
@@ -258,8 +258,14 @@ __global__ __launch_bounds__(64 * CW_WPB) void k_clusters_wide(rs_args A_in_kern
     unsigned long long mark_first = 0;
     if (lane < per && k_first < W.max_cand) { c4_first = W.cand4[k_first]; mark_first = W.cand_mark[k_first]; }
     int ncand = (int)A.O.cnt->cand_count;
+    // (on demand: a sweep before this one waits for the ordered workgroup — this step does nothing, the host enqueues it again)
+    const int stalled = A.od_stall ? *A.od_stall : 0;
+    if (stalled && A.od_tick > stalled) return;
     if (ncand > W.max_cand) ncand = W.max_cand;
-    if (wave_id == 0 && lane == 0) { wc->active = 1; wc->ncand = ncand; }
+    if (wave_id == 0 && lane == 0) {
+        wc->active = 1; wc->ncand = ncand;
+        if (A.od_done) *A.od_done = A.od_tick;          // (host-mapped: how far the host may run ahead)
+    }
     if (ncand == 0) return;
     const int s_off = 2 * ncand;        // first counter-allocated slot of this sweep (candidate k owns slots 2k, 2k + 1)
     const int h_off = 4 * ncand;        // first counter-allocated history entry (candidate k owns the pairs 4k and 4k + 2)
@@ -353,13 +359,13 @@ __global__ __launch_bounds__(64 * CW_WPB) void k_clusters_wide(rs_args A_in_kern
                     bool seen = false;
                     for (int e = 0; e < nc; e++) seen |= cnd[e] == c;
                     if (!seen) {
-                        if (nc == CW_MAXC) { owner = false; wc->changed = 1; break; }       // too large for this kernel: left to the ordered workgroup
+                        if (nc == CW_MAXC) { owner = false; wc->changed = 1; rs_raise(W); break; }       // too large for this kernel: left to the ordered workgroup
                         cnd[nc++] = c;
                     }
                     seen = false;
                     for (int e = 0; e < nm; e++) seen |= mem[e] == q;
                     if (!seen) {
-                        if (nm == CW_MAXM) { owner = false; wc->changed = 1; break; }
+                        if (nm == CW_MAXM) { owner = false; wc->changed = 1; rs_raise(W); break; }
                         mem[nm++] = q;
                     }
                     c = nx;

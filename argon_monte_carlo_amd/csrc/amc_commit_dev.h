@@ -26,17 +26,46 @@ struct amc_commit_args {
     int defer;                      // results stay in the slot arrays (the streaming pass picks them up through slot_of[])
     int nogrid;
     int enabled;
+    // the ordered workgroup on demand (amc_internal.h).  od_stall: the sticky word — the commit (and the pass it rides along
+    // with) of a step later than it does nothing.  from_wide: no ordered pass ran for this sweep, so nobody has handed its
+    // counts over: they are taken from the wide kernel's own words, and this commit does what the idle ordered workgroup
+    // did besides — the candidate counter cleared, the candidate count told to the host.  (The wide kernel's words are
+    // re-armed by the next detect kernel: every block here reads them.)
+    const int *od_stall;
+    int od_tick;
+    int from_wide;
+    const int *wctl;
+    int *host_ncand;
 };
 
 AMC_DEV void amc_commit_part(const amc_commit_args &C, const amc_out &O, const amc_grid &G, const amc_state &S, int gtid,
                              int gstride)
 {
     amc_resolve_ctl *ctl = C.ctl;
-    if (!ctl->active) return;
-    const bool ok = ctl->ok && !ctl->ovf;
+    int c_active, c_ok, c_nslots, c_nhist, c_ncand, c_nclusters = 0, c_rounds;
+    if (C.from_wide) {
+        // (candidate k owns slots 2k, 2k + 1 and the history pairs 4k, 4k + 2; what the wide kernel took from its counters
+        // comes after those — the sums the idle ordered workgroup handed over)
+        const amc_resolve_ctl *wc = (const amc_resolve_ctl *)C.wctl;
+        c_ncand = wc->ncand;
+        c_active = c_ncand > 0;
+        c_nslots = 2 * c_ncand + wc->nslots; c_nhist = 4 * c_ncand + wc->nhist;
+        c_ok = !wc->ovf; c_rounds = 1;
+        if (gtid == 0) {
+            for (int b = 0; b < 16; b++) c_nclusters += C.wctl[32 + b];
+            if (C.host_ncand) *C.host_ncand = c_ncand;
+            O.cnt->cand_count = 0;
+        }
+    } else {
+        c_active = ctl->active; c_ok = ctl->ok && !ctl->ovf; c_nslots = ctl->nslots; c_nhist = ctl->nhist;
+        c_ncand = ctl->ncand; c_rounds = ctl->rounds;
+        if (gtid == 0) c_nclusters = ctl->nclusters;
+    }
+    if (!c_active) return;
+    const bool ok = c_ok != 0;
     const bool defer = ok && C.defer;
-    const int ns = ctl->nslots < C.max_slots ? ctl->nslots : C.max_slots;
-    const int nh = ctl->nhist < C.max_hist ? ctl->nhist : C.max_hist;
+    const int ns = c_nslots < C.max_slots ? c_nslots : C.max_slots;
+    const int nh = c_nhist < C.max_hist ? c_nhist : C.max_hist;
     int my_hits = 0, my_fp = 0;
     for (int s = gtid; s < ns; s += gstride) {
         const int p = C.sl_meta[s].x;
@@ -72,9 +101,9 @@ AMC_DEV void amc_commit_part(const amc_commit_args &C, const amc_out &O, const a
         }
     if (gtid == 0) {
         amc_dev_counters *cnt = O.cnt;
-        cnt->n_candidates += (unsigned long long)ctl->ncand;
-        cnt->n_clusters += (unsigned long long)ctl->nclusters;
-        cnt->n_rounds += (unsigned long long)ctl->rounds;
+        cnt->n_candidates += (unsigned long long)c_ncand;
+        cnt->n_clusters += (unsigned long long)c_nclusters;
+        cnt->n_rounds += (unsigned long long)c_rounds;
         if (!ok) cnt->flags |= 4ULL;
         ctl->lazy_ns = defer ? ns : 0;
     }

@@ -104,12 +104,15 @@ AMC_DEV int amc_push_candidate(int a, int b, int max_cand, amc_dev_counters *cnt
 // (heads + list elements, ~1.3 per particle at 0.25 particles per cell), not its bytes.
 // One list NODE: its own cell's list (the part inserted before it) and the lists of the lower-numbered cells its box overlaps.
 AMC_DEV void amc_detect_node(const amc_grid &G, const amc_lists &B, int node, double cr2i, double cr_probe, int max_cand,
-                             amc_dev_counters *cnt, const amc_adj &D)
+                             amc_dev_counters *cnt, const amc_adj &D, const int *od_stall = nullptr, int od_tick = 0)
 {
+    // (the ordered workgroup on demand: the sticky word is asked for with the record and tested before anything is stored)
+    const int stalled = od_stall ? *od_stall : 0;
     amc_rec me_r = B.rec[node];
     // (kept lists: where the particle's live node is — asked for together with the record, so that a moved particle costs its
     // wave one more round trip, not two; at 6 % movers nearly every wave has one)
     const int live = (B.node_of && node < B.n) ? B.node_of[node] : node;
+    if (stalled && od_tick > stalled) return;       // a sweep before this step waits for the ordered workgroup
     if (me_r.x != me_r.x) {
         // a particle's own node after the particle was filed again under another one.  Kept lists: THIS thread walks for the
         // live node (one node per thread whatever moved; blocks of their own for the extra nodes cost what blocks of
@@ -183,12 +186,20 @@ AMC_DEV void amc_detect_node(const amc_grid &G, const amc_lists &B, int node, do
 #endif
 __global__ __launch_bounds__(256, AMC_DETECT_MINW) void k_detect_lists(amc_grid G, amc_lists B, long long n, double cr2i, double cr_probe,
                                                       int max_cand, amc_dev_counters *cnt, amc_adj D, const int *extra_count,
-                                                      int max_extra)
+                                                      int max_extra, const int *od_stall, int od_tick, int *wctl_rearm)
 {
     const long long nb = (n + blockDim.x - 1) / blockDim.x;
     if ((long long)blockIdx.x < nb) {
         const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-        if (p < n) amc_detect_node(G, B, (int)p, cr2i, cr_probe, max_cand, cnt, D);
+        if (p < n) amc_detect_node(G, B, (int)p, cr2i, cr_probe, max_cand, cnt, D, od_stall, od_tick);
+        // The last sweep had no ordered pass: the wide kernel's words, which that workgroup re-arms, were read by every block
+        // of the commit in the streaming pass before this kernel and are touched next by the wide kernel after it.
+        if (wctl_rearm && p == 0 && !(*od_stall && od_tick > *od_stall)) {
+            amc_resolve_ctl *wc = (amc_resolve_ctl *)wctl_rearm;
+            for (int b = 0; b < 16; b++) wctl_rearm[32 + b] = 0;
+            wc->nslots = 0; wc->nhist = 0; wc->nedges = 0; wc->nfp = 0; wc->ovf = 0; wc->dirty = 0; wc->nclusters = 0;
+            wc->changed = 0; wc->active = 0; wc->cur_round = 1;
+        }
         return;
     }
     if (!extra_count) return;
@@ -197,7 +208,7 @@ __global__ __launch_bounds__(256, AMC_DETECT_MINW) void k_detect_lists(amc_grid 
     if (ne > max_extra) ne = max_extra;
     const int stride = (int)((gridDim.x - nb) * blockDim.x);
     for (int e = (int)((blockIdx.x - nb) * blockDim.x + threadIdx.x); e < ne; e += stride)
-        amc_detect_node(G, B, (int)n + e, cr2i, cr_probe, max_cand, cnt, D);
+        amc_detect_node(G, B, (int)n + e, cr2i, cr_probe, max_cand, cnt, D, od_stall, od_tick);
 }
 
 // ---- detection sharded by index (multi-GPU) ------------------------------------------------------------------
@@ -454,7 +465,8 @@ hipError_t amc_launch_detect(amc_ctx *c)
         // one after the other, change nothing at N = 1e6 and cost 5 / 15 us at N = 1e5)
         AMC_LAUNCH(c, k_detect_lists, dim3((unsigned)((n + bs - 1) / bs) + (extras ? 4u : 0u)), dim3(bs), c->G, c->B, n, cr2i,
                    c->G.cr_probe, c->W.max_cand, c->d_cnt, D, (const int *)(extras ? c->extra_count + slot : nullptr),
-                   c->max_extra);
+                   c->max_extra, (const int *)(c->od_active ? c->d_od : nullptr), c->od_tick,
+                   (c->od_active && !c->od_prev_ordered) ? c->W.wctl : nullptr);
     }
     amc_prof_end(c);
     return hipGetLastError();

@@ -93,6 +93,8 @@ struct amc_lazy {
 // So what one thread handles at a time is ONE record (array of structures); only what the ordered workgroup scans in
 // bulk stays a plain array.
 // the resolve kernels' hand-over block (mirror of rs_shared in amc_resolve_dev.h)
+// (Inside amc_run's on-demand loop W.ctl is STALE: it holds what the last ordered pass left — lazy_ns included — until the
+// next one, and the run always ends with one.  The commit of a sweep without an ordered pass reads the wide kernel's words.)
 struct amc_resolve_ctl {
     int nslots, nedges, nhist, nev, dirty, changed, nhits, nfp, ovf, nclusters, ncomplex;
     int rounds, ncand, active, ok, edges_done;
@@ -132,6 +134,10 @@ struct amc_resolve_ws {
     rs_event *ev;             // [max_hist]
     int *ctl;                 // rs_shared in global memory: hand-over between the resolve kernels
     int *wctl;                // rs_shared of the wide cluster kernel (counters it advanced before the ordered workgroup starts)
+    // the ordered workgroup on demand (amc_run): where a wave of the wide kernel that leaves work for the
+    // ordered workgroup says so — the sticky device word, its host-mapped mirror, the step index to write (null: nobody listens)
+    int *raise_dev, *raise_host;
+    int raise_tick;
     // (what only the ordered workgroup's large-sweep fallbacks touch comes last: the argument block is read line by line)
     int *sl_label, *sl_tmp;   // labels / sizes of the ordered workgroup when they do not fit its LDS
     uint8_t *sl_dirty;
@@ -197,6 +203,10 @@ struct amc_fields_ws {
 enum amc_res_kind { AMC_RES_DEVICE, AMC_RES_PINNED, AMC_RES_STREAM, AMC_RES_EVENT };
 struct amc_res { void *p; amc_res_kind kind; };
 
+#define AMC_OD_AHEAD 2          // default of amc_ctx::od_ahead (experiments: environment variable AMC_OD_AHEAD)
+#define AMC_OD_MAX_N 100000     // default of amc_ctx::od_max_n: measured faster at N = 1e5, slower at N = 1e6 (AMC_OD_MAX_N)
+#define AMC_OD_RING 64          // snapshots kept (od_ahead is capped at 32)
+#define AMC_OD_MIN_STEPS 8      // shorter runs keep the ordered workgroup in every sweep (the run ends with a synchronisation of its own)
 #define AMC_PLAN_SMALL 430      // default of amc_ctx::plan_small: measured crossover of the two launch plans (tools/plan_sweep.sh;
                                 // experiments: environment variable AMC_PLAN_SMALL)
 
@@ -290,6 +300,23 @@ struct amc_ctx {
     size_t keep_pool;              // nodes behind the particles' own in B.rec / entries of B.extra
     bool kin_lists;                // amc_mg_pack started this step's per-cell lists (the unpack completes them)
     bool kin_counts_clear;         // the bank counters in kin_send are zero (cleared by the last unpack kernel)
+    // The ordered workgroup on demand (amc_run's plain loop): steps are enqueued without k_resolve<GEOM,0>; a
+    // sweep that needs it sets the sticky device word `stalled_at` to its step index, every kernel of a later step then leaves
+    // without a side effect, and the host — which watches the host-mapped mirror — launches the workgroup for that sweep and
+    // enqueues the later steps again.
+    bool ordered_always;           // AMC_ORDERED_ALWAYS=1 at creation: k_resolve<GEOM,0> in every sweep, as amc_timestep does
+    int64_t od_max_n = AMC_OD_MAX_N;   // particle counts above this keep the ordered workgroup in every sweep
+    int od_ahead = AMC_OD_AHEAD;   // steps amc_run may be ahead of the last step the GPU has started to resolve
+    int *d_od;                     // [0] stalled_at (0: none)
+    volatile int *h_od_stall, *h_od_done;   // host-mapped: mirror of stalled_at, step index of the last wide kernel that ran
+    int *d_od_stall_host, *d_od_done_host;  // their device addresses
+    bool od_active;                // the launchers pass the word and the step index (inside amc_run's on-demand loop only)
+    bool od_prev_ordered = true;   // the last sweep had its ordered pass: W.ctl holds its counts (else the wide kernel's words do)
+    int od_tick = 1;               // step index of the step being enqueued (never 0, grows across runs)
+    int od_handled;                // the last stall the host has answered
+    int64_t od_ordered_launches;   // launches of k_resolve<GEOM,0> so far
+    int64_t od_steps;              // steps enqueued without it
+    int64_t od_stalls, od_stalls_last;   // stalls the host has answered; those raised by the last step of their run
     std::vector<amc_res> owned;    // everything allocated for the context, in order (amc_host.h); amc_destroy frees it
 };
 
@@ -337,6 +364,9 @@ hipError_t amc_launch_detect(amc_ctx *c);              // binned or all-pairs, f
 hipError_t amc_launch_detect_own(amc_ctx *c);          // multi-GPU: own index range against everybody, into the candidate block
 hipError_t amc_launch_ingest(amc_ctx *c, int world);   // ... and the candidate graph from the gathered blocks of all ranks
 hipError_t amc_launch_resolve(amc_ctx *c, bool defer_commit = false);   // resolve_A -> validate -> resolve_B -> commit
+struct rs_args;
+hipError_t amc_launch_wide_only(amc_ctx *c, rs_args *used);     // on demand: k_clusters_wide alone (results deferred); the arguments it used
+hipError_t amc_launch_ordered(amc_ctx *c, const rs_args &used);  // ... and k_resolve<GEOM,0> for that sweep, later
 hipError_t amc_launch_apply(amc_ctx *c);                // write deferred sweep results to the particle arrays now
 hipError_t amc_launch_commit(amc_ctx *c);               // the pending commit as a kernel of its own
 struct amc_commit_args;

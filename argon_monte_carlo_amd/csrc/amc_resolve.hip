@@ -101,6 +101,8 @@ __global__ __launch_bounds__(RS_T) void k_resolve(rs_args A_in_kernarg)
         // touched.  Otherwise they go to LDS and the body below runs exactly as it always did.
         int ncand = (int)cnt->cand_count;
         if (ncand > W.max_cand) ncand = W.max_cand;
+        // (on demand: this launch answers the sweep that raised the sticky word — the later steps may run again)
+        if (K.od_stall) { *K.od_stall = 0; *K.od_stall_host = 0; }
         if (K.host_ncand) *K.host_ncand = ncand;        // (first: the host-mapped write is the slowest to complete)
         cnt->cand_count = 0;
         rs_shared t;
@@ -567,6 +569,7 @@ __global__ __launch_bounds__(256) void k_commit(rs_args A)
     C.sl_meta = W.sl_meta; C.sl_hits = W.sl_hits; C.sl_moved = W.sl_moved; C.sl_state = W.sl_state; C.slot_of = W.slot_of;
     C.max_slots = W.max_slots; C.max_hist = W.max_hist; C.lo = A.lo; C.hi = A.hi; C.count_pp = A.count_pp;
     C.defer = A.defer_commit; C.nogrid = A.allpairs; C.enabled = 1;
+    C.od_stall = nullptr; C.od_tick = 0; C.from_wide = 0; C.wctl = nullptr; C.host_ncand = nullptr;
     amc_commit_part(C, A.O, A.G, A.S, gtid, gstride);
 }
 
@@ -597,6 +600,8 @@ static void rs_launch_all(amc_ctx *c, const rs_args &A)
     amc_prof_end(c);
     amc_prof_begin(c, AMC_K_RESOLVE);
     AMC_LAUNCH(c, (k_resolve<GEOM, 0>), dim3(1), dim3(RS_T), Aw);
+    c->od_ordered_launches++;
+    c->od_prev_ordered = true;
     // the commit: deferred results -> it waits for the next streaming pass (or amc_flush); else a kernel of its own, now
     c->commit_defer = A.defer_commit != 0;
     if (A.defer_commit) { c->commit_pending = true; return; }
@@ -623,7 +628,50 @@ static rs_args rs_make_args(amc_ctx *c)
     A.count_pp = c->mg_count_pp ? 1 : 0;
     A.lo = c->lo; A.hi = c->hi;
     A.inv_dx = c->P.dx > 0 ? 1.0 / c->P.dx : 0.0; A.inv_dy = c->P.dy > 0 ? 1.0 / c->P.dy : 0.0; A.inv_dz = c->P.dz > 0 ? 1.0 / c->P.dz : 0.0;
+    A.W.raise_dev = nullptr; A.W.raise_host = nullptr; A.W.raise_tick = 0;
+    A.od_stall = nullptr; A.od_stall_host = nullptr; A.od_done = nullptr; A.od_tick = 0;
     return A;
+}
+
+// ---- the ordered workgroup on demand (amc_run's plain loop, grid mode, results deferred) --------------------------------------
+// The wide kernel alone: its waves raise the sticky word when they leave work for the ordered workgroup.  `used` gets the
+// arguments, for amc_launch_ordered should the sweep turn out to need it.
+hipError_t amc_launch_wide_only(amc_ctx *c, rs_args *used)
+{
+    rs_args Aw = rs_make_args(c);
+    Aw.defer_commit = 1;
+    Aw.wide_plan = 1;
+    {
+        const long long lag = c->h_host_ncand ? *c->h_host_ncand : 0;
+        const long long nb = amc_clusters_wide_blocks(c);
+        long long per = (lag + lag / 4 + nb - 1) / nb;
+        Aw.wide_per = (int)std::min<long long>(std::max<long long>(per, 1), 64);
+    }
+    Aw.W.raise_dev = c->d_od; Aw.W.raise_host = c->d_od_stall_host; Aw.W.raise_tick = c->od_tick;
+    Aw.od_stall = c->d_od; Aw.od_stall_host = c->d_od_stall_host; Aw.od_done = c->d_od_done_host; Aw.od_tick = c->od_tick;
+    amc_prof_begin(c, AMC_K_CLUSTERS_WIDE);
+    amc_launch_clusters_wide(c, Aw);
+    amc_prof_end(c);
+    c->commit_defer = true;
+    c->commit_pending = true;
+    c->od_prev_ordered = false;
+    c->od_steps++;
+    *used = Aw;
+    return hipGetLastError();
+}
+
+hipError_t amc_launch_ordered(amc_ctx *c, const rs_args &used)
+{
+    rs_args Aw = used;
+    Aw.W.raise_dev = nullptr; Aw.W.raise_host = nullptr;        // (the workgroup's own edges are its own business)
+    Aw.od_done = nullptr;
+    amc_prof_begin(c, AMC_K_RESOLVE);
+    if (c->P.geometry == AMC_GEOM_CUBE) AMC_LAUNCH(c, (k_resolve<AMC_GEOM_CUBE, 0>), dim3(1), dim3(RS_T), Aw);
+    else AMC_LAUNCH(c, (k_resolve<AMC_GEOM_PORE, 0>), dim3(1), dim3(RS_T), Aw);
+    amc_prof_end(c);
+    c->od_ordered_launches++;
+    c->od_prev_ordered = true;
+    return hipGetLastError();
 }
 
 hipError_t amc_launch_commit(amc_ctx *c)

@@ -38,6 +38,10 @@ struct rs_args {
     unsigned int sweep_epoch; // tag of the W.adj_head entries that belong to this sweep
     int wide_plan;            // k_clusters_wide ran before this kernel: start from the counters it left in W.wctl
     int wide_per;             // candidates per wave of k_clusters_wide (from the lagging candidate count)
+    // the ordered workgroup on demand (amc_internal.h): k_clusters_wide of a step later than *od_stall leaves at once and tells
+    // the host through od_done that it has run; k_resolve, launched for the sweep that raised the word, clears it
+    int *od_stall, *od_stall_host, *od_done;
+    int od_tick;
 };
 
 // The argument block of the resolve kernels is 1.3 KB.  Read field by field from the kernarg segment it costs every wave a
@@ -59,6 +63,7 @@ hipError_t amc_launch_clusters_wide(amc_ctx *c, const rs_args &A);      // amc_c
 int amc_clusters_wide_blocks(amc_ctx *c);
 
 // counters of one sweep; lives in LDS while a resolve kernel runs and in W.ctl (global) between the kernels
+// (W.ctl is written by the ordered workgroup only: while amc_run launches it on demand it is stale between two such passes)
 struct rs_shared {
     int nslots, nedges, nhist, nev, dirty, changed, nhits, nfp, ovf, nclusters, ncomplex;
     int rounds, ncand, active, ok, edges_done;
@@ -67,6 +72,14 @@ struct rs_shared {
     int hist_begin;           // first history entry of the current round (older ones were validated already)
     int cur_round;
 };
+
+// the wide kernel leaves work for the ordered workgroup (a merge or self edge, a component it did not take, an overflow): the
+// sweep's step index goes into the sticky word the later steps' kernels test, and into its host-mapped mirror.  Plain
+// stores of the same value by the few waves that have something to report.
+AMC_DEV void rs_raise(const amc_resolve_ws &W)
+{
+    if (W.raise_dev) { *W.raise_dev = W.raise_tick; *W.raise_host = W.raise_tick; }
+}
 
 // working set of the multi-particle clusters (LDS pool or global fallback), indexed by sorted rank
 struct rs_work {
@@ -207,7 +220,7 @@ AMC_DEV bool rs_hit(const rs_args &A, rs_shared *sh, amc_particle &p1, amc_parti
         h = rs_count_add(&sh->nhist, 2);
     }
     const bool room = h + 1 < W.max_hist;
-    if (!room) sh->ovf = 1;
+    if (!room) { sh->ovf = 1; rs_raise(W); }
     const int gen = wide ? wd.gen : sh->cur_round;
     if (room) { W.ev_gen[h] = 0; W.ev_gen[h + 1] = 0; }
     auto emit = [&](int which, double tot, double px, double py, double pz) {
@@ -713,6 +726,7 @@ AMC_DEV void rs_add_edge(const amc_resolve_ws &W, rs_shared *sh, int pa, int pb)
     const int k = atomicAdd(&sh->nedges, 1);
     if (k < W.max_edges) { W.edge_a[k] = pa; W.edge_b[k] = pb; } else sh->ovf = 1;
     sh->dirty = 1;
+    rs_raise(W);                // (null in the ordered workgroup's own launches)
 }
 
 

@@ -119,9 +119,12 @@ __global__ __launch_bounds__(256) void k_stream(amc_state S, amc_state S_out, am
 {
     // the previous sweep's commit rides along on EXTRA blocks behind the streaming ones (amc_commit_dev.h): order-free work
     // that nothing in this pass depends on (results reach the particles through slot_of[] below), done while the others stream
+    // (the ordered workgroup on demand: the sticky word is asked for with the first loads and tested in front of the first store)
+    const int stalled = C.od_stall ? *C.od_stall : 0;
     if (C.enabled) {
         const unsigned nstream = gridDim.x - (unsigned)C.enabled;       // (enabled = number of commit blocks)
         if (blockIdx.x >= nstream) {
+            if (stalled && C.od_tick > stalled) return;
             amc_commit_part(C, O, G, S, (int)((blockIdx.x - nstream) * blockDim.x + threadIdx.x), (int)(C.enabled * blockDim.x));
             return;
         }
@@ -149,6 +152,8 @@ __global__ __launch_bounds__(256) void k_stream(amc_state S, amc_state S_out, am
         q.flag = S.flag[p] != 0;
         flag_in = q.flag; d_in = q.d; dx_in = q.dx; dy_in = q.dy; dz_in = q.dz;
     }
+    // a sweep before this step waits for the ordered workgroup: the step does nothing (the host enqueues it again)
+    if (stalled && C.od_tick > stalled) return;
     // deferred commit of the previous sweep: a particle that collided has its new state in the slot arrays
     bool force = S_out.x != S.x;        // (another buffer: every field is written)
     if (L.enabled) {
@@ -321,6 +326,7 @@ amc_commit_args amc_make_commit_args(amc_ctx *c)
     C.sl_meta = W.sl_meta; C.sl_hits = W.sl_hits; C.sl_moved = W.sl_moved; C.sl_state = W.sl_state; C.slot_of = W.slot_of;
     C.max_slots = W.max_slots; C.max_hist = W.max_hist; C.lo = c->lo; C.hi = c->hi; C.count_pp = c->mg_count_pp ? 1 : 0;
     C.defer = c->commit_defer ? 1 : 0; C.nogrid = c->allpairs ? 1 : 0; C.enabled = 0;
+    C.od_stall = nullptr; C.od_tick = 0; C.from_wide = 0; C.wctl = nullptr; C.host_ncand = nullptr;
     return C;
 }
 
@@ -350,13 +356,16 @@ hipError_t amc_launch_stream(amc_ctx *c, double dt, int stages, int bounds_slot,
     const long long cnt = c->hi - c->lo;
     if (cnt <= 0) return hipSuccess;
     amc_commit_args C = amc_make_commit_args(c);
+    const amc_resolve_ws &W_ = c->W;
     unsigned extra = 0;
     if (c->commit_pending) {            // this launch does the last sweep's commit as well, on blocks of its own
         const long long lag = c->h_host_ncand ? *c->h_host_ncand : 0;      // (entries to commit ~ 2 per candidate)
         extra = (unsigned)std::min<long long>(std::max<long long>((2 * lag + 255) / 256, 4), AMC_COMMIT_BLOCKS);
         C.enabled = (int)extra;
         c->commit_pending = false;
+        if (c->od_active && !c->od_prev_ordered) { C.from_wide = 1; C.wctl = W_.wctl; C.host_ncand = c->d_host_ncand; }
     }
+    if (c->od_active) { C.od_stall = c->d_od; C.od_tick = c->od_tick; }
     const unsigned blocks = (unsigned)((cnt + threads - 1) / threads) + extra;
     const int kp = c->keep_prior ? 1 : 0;
     amc_ovl V;

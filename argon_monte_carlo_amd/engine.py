@@ -189,10 +189,14 @@ class Engine:
         self._ck(self.lib.amc_synchronize(self._ctx))
 
     def overlap_stats(self):
-        """(steps amc_run has overlapped, particles advanced again after a sweep pulled them in, mode, extra list nodes)."""
-        out = np.zeros(4, dtype=np.int64)
+        """(steps amc_run has overlapped, particles advanced again after a sweep pulled them in, mode, extra list nodes,
+        launches of the ordered workgroup so far, steps amc_run has enqueued without it, stalls answered, those raised by
+        the last step of their run)."""
+        out = np.zeros(8, dtype=np.int64)
         self._ck(self.lib.amc_overlap_stats(self._ctx, out.ctypes.data_as(C.POINTER(C.c_int64))))
-        return dict(steps=int(out[0]), refiled=int(out[1]), mode=int(out[2]), extra_nodes=int(out[3]))
+        return dict(steps=int(out[0]), refiled=int(out[1]), mode=int(out[2]), extra_nodes=int(out[3]),
+                    ordered_launches=int(out[4]), on_demand_steps=int(out[5]),
+                    stalls=int(out[6]), stalls_at_last_step=int(out[7]))
 
     def profile(self, on=True):
         self._ck(self.lib.amc_profile(self._ctx, int(on)))

@@ -364,8 +364,12 @@ const char *amc_kernel_name(int k);
  * same kernels in order on one stream.  Results are those of the plain sequence bit for bit — the loop body of Pore:416-557 / Cube:175-338
  * once per step.  out[0] = steps run that way so far, out[1] = particles a sweep pulled into a cluster after the next pass
  * had already advanced them (advanced again from the sweep's result and filed under an extra list node), out[2] = mode,
- * out[3] = extra list nodes available per step. */
-int amc_overlap_stats(amc_ctx *ctx, int64_t *out /*[4]*/);
+ * out[3] = extra list nodes available per step, out[4] = launches of the ordered workgroup (k_resolve<GEOM,0>) so far,
+ * out[5] = steps amc_run has enqueued without it (environment AMC_ORDERED_ALWAYS=1: it is launched in every sweep),
+ * out[6] = sweeps that asked for it and were answered, out[7] = those among them that were the last step of their run.
+ * NOTE: `out` must hold EIGHT values.  Up to the release that launched the ordered workgroup in every sweep the call wrote
+ * four: a caller built against that header has to enlarge its buffer (nothing else of the ABI changed). */
+int amc_overlap_stats(amc_ctx *ctx, int64_t *out /*[8]*/);
 
 /* ---- sampled fields: number density, flow velocity, temperature per spatial bin (opt-in) -----------
  * The reference has no such output.  A sample bins every particle of the context's range [lo, hi) and adds, per bin,
