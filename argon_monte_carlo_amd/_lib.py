@@ -46,6 +46,9 @@ SIGNATURES = {
     "amc_temp_device_results": (C.c_int, [_ctx, C.c_int, _i32p, _dp, _dp, C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t)]),
     "amc_temp_device_sums": (C.c_int, [_ctx, _dp, C.POINTER(C.c_int32)]),
     "amc_temp_device_draws": (C.c_int, [_ctx, C.c_int, _i32p, _dp, _dp, _dp, _dp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "amc_temp_run_device": (C.c_int, [_ctx, C.c_double, C.c_int64, C.POINTER(AmcTempRng), C.POINTER(AmcStepStats)]),
+    "amc_temp_series_read": (C.c_int, [_ctx, C.c_int64, C.c_int64, _dp, _u8p, _i64p]),
+    "amc_set_step": (C.c_int, [_ctx, C.c_int64]),
     "amc_host_directions": (C.c_int, [C.POINTER(C.c_uint32), _i32p, C.POINTER(C.c_uint32), _i32p, _dp, _u8p, C.c_int64, C.c_double,
                                       C.c_double, C.c_int, C.c_void_p, _dp]),
     "amc_wall_hits": (C.c_int, [_ctx, C.c_int, _i32p, _dp, _dp, C.c_size_t, C.POINTER(C.c_size_t)]),

@@ -218,6 +218,11 @@ int amc_create(amc_ctx **out, const amc_params *p)
     c->stream_bs = getenv("AMC_STREAM_BS") ? atoi(getenv("AMC_STREAM_BS")) : 256;      // (experiments: 64 / 128 / 256)
     c->detect_bs = getenv("AMC_DETECT_BS") ? atoi(getenv("AMC_DETECT_BS")) : 256;      // (experiments: 64 / 128 / 256)
     c->temp_unfused = getenv("AMC_TEMP_UNFUSED") != nullptr;  // cross-check path: one hits/sample/apply triple per case
+    // amc_temp_run_device: AMC_TEMP_RUN_UNFUSED=1 enqueues the single step's three streaming passes (the cross-check form),
+    // AMC_TEMP_RUN_FUSED=1 the one fused pass; without either, what AMC_TEMP_RUN_FUSED_DEFAULT says
+    c->temp_run_unfused = !AMC_TEMP_RUN_FUSED_DEFAULT;
+    if (const char *e = getenv("AMC_TEMP_RUN_FUSED")) { if (atoi(e) != 0) c->temp_run_unfused = false; }
+    if (const char *e = getenv("AMC_TEMP_RUN_UNFUSED")) { if (atoi(e) != 0) c->temp_run_unfused = true; }
     // a failure below returns through amc_fail: the guard hands its message on and destroys what was built
     std::unique_ptr<amc_ctx, void (*)(amc_ctx *)> guard(c, [](amc_ctx *x) { g_create_err = x->err; amc_destroy(x); });
     {
@@ -577,7 +582,7 @@ static int enqueue_step(amc_ctx *c, double dt, bool fold_prev_bounds = false, bo
         if ((rc = amc_enqueue_sweep(c, fuse, c->lo == 0 && c->hi == c->n))) return rc;
         if (g == AMC_GEOM_PORE && !defer_bounds) AMC_HIP(c, amc_launch_stream(c, dt, AMC_ST_BOUNDS, 1));
     } else {
-        return amc_fail(c, AMC_ERR_INVALID, "energised walls need the host handshake: use the Python driver (amc_wall_hits/apply)");
+        return amc_fail(c, AMC_ERR_INVALID, "energised walls need the host handshake: use the Python driver (amc_wall_hits/apply), or amc_temp_run_device for the device-RNG mode");
     }
     c->out.step++;
     // (a step that leaves its post-sweep bounds check to the next pass is never sampled: amc_run does not defer it)

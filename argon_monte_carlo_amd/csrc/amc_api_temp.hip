@@ -200,7 +200,9 @@ static int temp_dev_ensure(amc_ctx *c)
     amc_temp_dev_ws &D = c->TD;
     if (D.idx) return AMC_OK;
     amc_alloc_group group(c);
-    const int icap = (int)std::min<int64_t>(std::max<int64_t>(4096, c->n / 64 + 1024), 0x0fffffff);
+    int icap = (int)std::min<int64_t>(std::max<int64_t>(4096, c->n / 64 + 1024), 0x0fffffff);
+    // AMC_TEMP_DEV_CAP (diagnostic): fewer records per case, so that a test reaches the overflow path with a handful of hits
+    if (const char *e = getenv("AMC_TEMP_DEV_CAP")) { const int v = atoi(e); if (v > 0 && v < icap) icap = v; }
     const size_t cap = (size_t)icap * 7;
     int *idx, *count;
     double *t, *contact, *normal, *dir, *Es, *dpz, *dE;
@@ -356,6 +358,123 @@ int amc_temp_device_draws(amc_ctx *c, int case_id, int32_t *idx, double *normal_
         if (contact_z) contact_z[u] = hc[3 * r + 2];
         if (surface_energy) surface_energy[u] = he[r];
     }
+    return AMC_OK;
+}
+
+// ---- the host-free run of the device-RNG mode ------------------------------------------------------------------------------
+// the series buffer for `rows` steps, the ordering scratch and the overflow words of the sums kernel, the pass's constants
+static int temp_run_ensure(amc_ctx *c, int64_t rows)
+{
+    amc_temp_dev_ws &D = c->TD;
+    if (!D.ovf) {
+        amc_alloc_group group(c);
+        int *perm, *ovf;
+        amc_temp_pass *pass;
+        AMC_HIP(c, dalloc(c, &perm, (size_t)7 * (size_t)D.cap));
+        AMC_HIP(c, dalloc(c, &pass, 1));
+        AMC_HIP(c, dalloc(c, &ovf, 4));
+        group.keep();
+        D.perm = perm; D.pass = pass;
+        D.ovf = ovf;            // (the guard: last)
+    }
+    if (rows > D.series_cap) {
+        amc_temp_row *series;
+        AMC_HIP(c, dalloc(c, &series, (size_t)rows));
+        AMC_HIP(c, hipStreamSynchronize(c->stream));        // (nothing in flight writes the old rows)
+        ctx_free(c, D.series);
+        D.series = series; D.series_cap = rows;
+    }
+    return AMC_OK;
+}
+
+int amc_temp_run_device(amc_ctx *c, double dt, int64_t nsteps, const amc_temp_rng *cfg, amc_step_stats *sum)
+{
+    if (!c) return AMC_ERR_INVALID;
+    if (c->P.geometry != AMC_GEOM_PORE_ENERGISED) return amc_fail(c, AMC_ERR_STATE, "amc_temp_run_device needs AMC_GEOM_PORE_ENERGISED");
+    if (!cfg || cfg->struct_size != (int32_t)sizeof(amc_temp_rng) || cfg->n_gl < 2 || cfg->n_gl > 32)
+        return amc_fail(c, AMC_ERR_INVALID, "amc_temp_rng: bad struct_size / n_gl");
+    if (nsteps < 0 || nsteps > 0x3fffffffLL) return amc_fail(c, AMC_ERR_INVALID, "amc_temp_run_device: nsteps %lld out of range", (long long)nsteps);
+    if (!c->uploaded) return amc_fail(c, AMC_ERR_STATE, "amc_temp_run_device before amc_upload");
+    if (c->lo != 0 || c->hi != c->n) return amc_fail(c, AMC_ERR_STATE, "amc_temp_run_device needs the whole index range in one context");
+    AMC_HIP(c, hipSetDevice(c->device));
+    int rc = temp_dev_ensure(c);
+    if (rc) return rc;
+    if ((rc = temp_run_ensure(c, std::max<int64_t>(nsteps, 1)))) return rc;
+    amc_temp_dev_ws &D = c->TD;
+    if ((rc = amc_flush(c))) return rc;
+    D.series_n = 0;
+    D.fetched = false;
+    c->T.pre_case = -1;
+    c->keep_prior = true;               // (as after amc_temp_begin)
+    AMC_HIP(c, hipMemsetAsync(D.ovf, 0, 4 * sizeof(int), c->stream));
+    const bool fuse = !c->allpairs;     // the detection grid's lists are filed by the last pass in front of the sweep
+    const bool fused = !c->temp_run_unfused;
+    if (fused && nsteps > 0) {
+        amc_temp_pass h;
+        memset(&h, 0, sizeof h);
+        h.g = *cfg; h.D = amc_temp_segments(c);
+        AMC_HIP(c, hipMemcpyAsync(D.pass, &h, sizeof h, hipMemcpyHostToDevice, c->stream));
+        AMC_HIP(c, hipStreamSynchronize(c->stream));        // (the source is this frame's)
+    }
+    bool deferred = false;              // the previous step left its post-sweep recapture (Temp:844) to this step's pass
+    for (int64_t s = 0; s < nsteps; s++) {
+        if (fused) {
+            // ONE pass in front of the sweep: drift, cases 1-2, cases 3-9 with the device draws, recapture (Temp:804), filing
+            AMC_HIP(c, hipMemsetAsync(D.count, 0, sizeof(int) * 7, c->stream));
+            AMC_HIP(c, amc_launch_stream(c, dt, AMC_ST_DRIFT | AMC_ST_WALLS | AMC_ST_TEMP_CASES | AMC_ST_BOUNDS | (deferred ? AMC_ST_BOUNDS_PRE : 0),
+                                         0, fuse));
+        } else {
+            // what amc_temp_begin, amc_temp_cases_device and amc_temp_end enqueue
+            AMC_HIP(c, amc_launch_stream(c, dt, AMC_ST_DRIFT | AMC_ST_WALLS, 0));
+            AMC_HIP(c, amc_launch_temp_cases_device(c, cfg));
+            AMC_HIP(c, amc_launch_stream(c, 0.0, AMC_ST_BOUNDS, 0, fuse));
+        }
+        AMC_HIP(c, amc_launch_temp_sums(c, s));
+        if ((rc = amc_enqueue_sweep(c, fuse))) return rc;                               // Temp:813-842
+        // a sampled step and the last one end with the state everybody reads: their recapture is a pass of its own
+        deferred = fused && s + 1 < nsteps && !amc_fields_due(c, (int64_t)c->out.step + 1);
+        if (!deferred) AMC_HIP(c, amc_launch_stream(c, 0.0, AMC_ST_BOUNDS, 1));       // Temp:844
+        c->out.step++;
+        if ((rc = amc_fields_step(c))) return rc;
+    }
+    D.series_n = nsteps;
+    rc = amc_finish_stats(c, sum);      // the one synchronisation; overflow flags and counters of the whole run
+    int ovf[4] = {0, 0, 0, 0};
+    AMC_HIP(c, hipMemcpy(ovf, D.ovf, sizeof ovf, hipMemcpyDeviceToHost));
+    if (ovf[0]) {
+        D.series_n = 0;
+        return amc_fail(c, AMC_ERR_CAPACITY, "%d wall hits in case %d exceed the record capacity %d (step %d of the run)", ovf[2], ovf[0], D.cap, ovf[1]);
+    }
+    if (rc) D.series_n = 0;
+    return rc;
+}
+
+int amc_temp_series_read(amc_ctx *c, int64_t first, int64_t count, double *sums, uint8_t *had, int64_t *n_steps)
+{
+    if (!c) return AMC_ERR_INVALID;
+    const amc_temp_dev_ws &D = c->TD;
+    if (n_steps) *n_steps = D.series_n;
+    if (first < 0 || count < 0 || first + count > D.series_n)
+        return amc_fail(c, AMC_ERR_INVALID, "amc_temp_series_read: rows %lld .. %lld of a run of %lld steps", (long long)first,
+                        (long long)(first + count) - 1, (long long)D.series_n);
+    if (!count) return AMC_OK;
+    AMC_HIP(c, hipSetDevice(c->device));
+    std::vector<amc_temp_row> rows((size_t)count);
+    AMC_HIP(c, hipMemcpyAsync(rows.data(), D.series + first, sizeof(amc_temp_row) * (size_t)count, hipMemcpyDeviceToHost, c->stream));
+    AMC_HIP(c, hipStreamSynchronize(c->stream));
+    for (int64_t k = 0; k < count; k++)
+        for (int e = 0; e < 3; e++) {
+            if (sums) sums[3 * k + e] = rows[(size_t)k].sums[e];
+            if (had) had[3 * k + e] = (rows[(size_t)k].had >> e) & 1u;
+        }
+    return AMC_OK;
+}
+
+int amc_set_step(amc_ctx *c, int64_t step)
+{
+    if (!c) return AMC_ERR_INVALID;
+    if (step < 0 || step > 0x3fffffffLL) return amc_fail(c, AMC_ERR_INVALID, "amc_set_step: step %lld out of range", (long long)step);
+    c->out.step = (int)step;
     return AMC_OK;
 }
 

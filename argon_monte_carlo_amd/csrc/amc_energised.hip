@@ -10,8 +10,7 @@
 //
 // The cases are sequential in the reference (each mask is evaluated after the previous handler ran), hence one
 // hits/apply pair per case.  Both kernels are O(N) streaming passes over positions (+prior); hits are ~1e-3 of N.
-#include "amc_internal.h"
-#include "amc_philox.h"
+#include "amc_energised_dev.h"
 
 struct temp_records {
     int *idx;
@@ -21,75 +20,6 @@ struct temp_records {
     int cap;
 };
 
-__device__ inline bool temp_mask(const amc_params &P, int case_id, double x, double y, double z, double px, double py,
-                                 double pz)
-{
-    const double r2 = x * x + y * y, r02 = px * px + py * py;
-    switch (case_id) {
-    case 3: return (pz >= P.t_z3_cold) && (z < P.t_z3_cold) && (r2 > P.R_p_sq);                              // Temp:708
-    case 4: return (pz <= P.t_z3_hot) && (z > P.t_z3_hot) && (r2 > P.R_p_sq);                                // Temp:713
-    case 5: return (pz < P.t_zgap_hi) && (pz > P.t_zgap_lo) && (r02 <= P.R_g_c_sq) && (r2 > P.R_g_c_sq);     // Temp:720
-    case 6: return (r02 >= P.R_p_c_sq) && (z < P.t_zgap_lo) && (pz <= P.t_zgap_hi) && (pz >= P.t_zgap_lo);   // Temp:728
-    case 7: return (r02 >= P.R_p_c_sq) && (z > P.t_zgap_hi) && (pz <= P.t_zgap_hi) && (pz >= P.t_zgap_lo);   // Temp:734
-    case 8: return (r02 <= P.R_p_c_sq) && (r2 > P.R_p_c_sq) && (z <= P.t_zgap_lo) && (z >= P.t_z3_hot);      // Temp:743
-    case 9: return (r02 <= P.R_p_c_sq) && (r2 > P.R_p_c_sq) && (z < P.t_z3_cold) && (z > P.t_zgap_hi);       // Temp:749
-    default: return false;
-    }
-}
-
-// contact of a hit of case `case_id`: flight time since contact, contact point, inward unit normal (Temp:349-375 for the
-// planes, Temp:430-474 for the cylinders); ok = 0 when the cylinder solve has no real root (Temp:472-474)
-struct temp_contact {
-    double t, cx, cy, cz, n0, n1, n2;
-    unsigned char ok;
-};
-__device__ inline temp_contact temp_solve(const amc_params &P, int case_id, double x, double y, double z, double vx,
-                                          double vy, double vz)
-{
-    temp_contact c;
-    c.ok = 1; c.t = 0; c.cx = 0; c.cy = 0; c.cz = 0; c.n0 = 0; c.n1 = 0; c.n2 = 0;
-    if (case_id == 3 || case_id == 4 || case_id == 6 || case_id == 7) {
-        const double zp = case_id == 3 ? P.t_z3_cold : case_id == 4 ? P.t_z3_hot : case_id == 6 ? P.t_zgap_lo : P.t_zgap_hi;
-        c.t = (z - zp) / vz;                                                                 // Temp:353
-        c.cx = x - vx * c.t; c.cy = y - vy * c.t; c.cz = zp;                                 // Temp:372
-        c.n2 = (case_id == 3 || case_id == 6) ? 1.0 : -1.0;                                  // Temp:709,714,730,736
-    } else {
-        const double Rc = case_id == 5 ? P.R_g_c : P.R_p_c;
-        const double a = (-vx) * (-vx) + (-vy) * (-vy);                                      // Temp:436
-        const double b = 2 * (x * (-vx) + y * (-vy));
-        const double cc = x * x + y * y - Rc * Rc;
-        const double disc2 = b * b - 4 * a * cc;
-        if (a == 0.0 || disc2 < 0.0 || disc2 != disc2) {
-            c.ok = 0;                                                                        // Temp:472-474
-        } else {
-            const double sq = sqrt(disc2);
-            const double t1 = (-b + sq) / (2 * a), t2 = (-b - sq) / (2 * a);
-            c.t = (t1 < t2) ? t1 : t2;                                                       // Temp:439
-            c.cx = x - vx * c.t; c.cy = y - vy * c.t; c.cz = z - vz * c.t;                   // Temp:440
-            c.n0 = -(c.cx / Rc); c.n1 = -(c.cy / Rc); c.n2 = -(0.0 / Rc);                    // Temp:442-444 (negated)
-        }
-    }
-    return c;
-}
-
-// energy accommodation and new velocity of a hit (Temp:377-388); returns the particle's speed before the hit
-__device__ inline double temp_accommodate(const amc_params &P, int case_id, double vx, double vy, double vz, double Es,
-                                          double d0, double d1, double d2, double &wvx, double &wvy, double &wvz,
-                                          double &dpz, double &dE)
-{
-    const double m = P.argon_mass;
-    const double alpha = (case_id == 5) ? P.alpha_gap : P.alpha_coated;
-    const double v_magnitude = sqrt(vx * vx + vy * vy + vz * vz);                            // Temp:377
-    const double old_pz = m * vz;                                                            // Temp:378
-    const double E = 0.5 * m * (v_magnitude * v_magnitude);                                  // Temp:128-129,379
-    const double diff = Es - E;                                                              // Temp:380
-    const double Enew = E + diff * alpha;                                                    // Temp:381
-    const double mag = sqrt(Enew * 2 / m);                                                   // Temp:383
-    dE = Enew - E;                                                                           // Temp:384
-    wvx = d0 * mag; wvy = d1 * mag; wvz = d2 * mag;                                          // Temp:386
-    dpz = m * wvz - old_pz;                                                                  // Temp:387-388
-    return v_magnitude;
-}
 
 __global__ __launch_bounds__(256) void k_temp_hits(amc_state S, amc_params P, int case_id, long long lo, long long hi,
                                                    temp_records R, amc_dev_counters *cnt)
@@ -193,51 +123,6 @@ hipError_t amc_launch_temp_velocity(amc_ctx *c, int case_id, int n)
 
 
 // ---- opt-in non-parity mode: directions and energies drawn on the device (include/argonmc.h, amc_temp_rng) -----------
-// surface_energy_gap (Temp:143-152): 9 T n k (T/theta)^3 * integral_0^{theta/T} x^3/(e^x - 1) dx, Gauss-Legendre
-__device__ inline double temp_gap_energy(const amc_temp_rng &g, double z)
-{
-    const double m = (g.t_cold - g.t_hot) / g.gap_height;                            // Temp:144
-    const double t_gap = m * (z - g.gap_bottom_height) + g.t_hot;                    // Temp:145
-    const double X = g.t_debye_alumina / t_gap, half = 0.5 * X;
-    double q = 0.0;
-    for (int i = 0; i < g.n_gl; i++) {
-        const double x = half * (g.gl_x[i] + 1.0);
-        q += g.gl_w[i] * (x * x * x / expm1(x));
-    }
-    q *= half;
-    const double r = t_gap / g.t_debye_alumina;
-    return 9 * t_gap * g.n_alumina * g.boltzman * (r * r * r) * q;                   // Temp:152
-}
-
-// re-emission direction (Temp:119-141 recipe on Philox numbers) and surface energy of one hit
-__device__ inline void temp_draw(const amc_params &P, const amc_temp_rng &g, int case_id, unsigned int step, int particle,
-                                 double n0, double n1, double n2, double contact_z, double &fx, double &fy, double &fz,
-                                 double &Es)
-{
-    const double cos85 = 0.087155742747658166;      // cos(85 deg), Temp:136
-    const double pi = 3.14159265358979323846;
-    fx = fy = fz = 0;
-    for (unsigned int attempt = 0; attempt < 4096u; attempt++) {                     // Temp:133-141 (acceptance ~91 %)
-        unsigned int c[4] = {(unsigned int)particle, step, ((unsigned int)case_id << 16) | attempt, 0x414d4331u};
-        philox4x32_10(c, g.seed);
-        const double u1 = (double)((((unsigned long long)c[0] << 32) | c[1]) >> 11) * (1.0 / 9007199254740992.0);
-        const double u2 = (double)((((unsigned long long)c[2] << 32) | c[3]) >> 12) * (1.0 / 4503599627370496.0);
-        const double costheta = -1.0 + 2.0 * u1;                                     // Temp:120  U(-1, 1)
-        const double phi = pi * u2;                                                  // Temp:121  U(0, pi)
-        const double sgn = (c[3] & 1u) ? 1.0 : -1.0;                                 // Temp:124  choice([-1, 1])
-        const double theta = acos(costheta);
-        fx = cos(phi) * sin(theta);
-        fy = sin(phi) * sin(theta) * sgn;
-        fz = cos(theta);
-        const double d = fma(fz, n2, fma(fy, n1, fx * n0));
-        if (fabs(d) < cos85) continue;                                               // Temp:135-136
-        if (d < cos85) { fx = -fx; fy = -fy; fz = -fz; }                             // Temp:138-139
-        break;
-    }
-    Es = (case_id == 5) ? temp_gap_energy(g, contact_z)
-                        : ((case_id == 3 || case_id == 7 || case_id == 9) ? P.E_cold : P.E_hot);
-}
-
 __global__ __launch_bounds__(256) void k_temp_sample(amc_params P, amc_temp_rng g, int case_id, unsigned int step,
                                                      temp_records R, double *__restrict__ dir, double *__restrict__ Es)
 {
@@ -255,67 +140,35 @@ __global__ __launch_bounds__(256) void k_temp_sample(amc_params P, amc_temp_rng 
 
 // All seven energised cases of a step in ONE pass (device-RNG mode): every case reads and writes only the particle
 // itself and the masks are evaluated in case order, each after the previous handler ran (Temp:705-758) — which per
-// particle is a sequential evaluation, so with the random numbers available on the device the 7 x (hits, sample,
-// apply) kernels collapse into this one.  The per-hit records (one segment per case) are still written: the host
-// sums their z-momentum / energy changes in the reference's order, tests read the draws.
-struct temp_dev_segments {
-    int *idx, *count;
-    double *t, *contact, *normal, *dir, *Es, *dpz, *dE;
-    unsigned char *ok;
-    int cap;
-};
+// particle is a sequential evaluation (temp_cases_particle, amc_energised_dev.h), so with the random numbers available on
+// the device the 7 x (hits, sample, apply) kernels collapse into this one.  The per-hit records (one segment per case) are
+// still written: their z-momentum / energy changes are summed in the reference's order, tests read the draws.
 __global__ __launch_bounds__(256) void k_temp_all(amc_state S, amc_params P, amc_out O, amc_temp_rng g, unsigned int step,
                                                   long long lo, long long hi, temp_dev_segments D, amc_dev_counters *cnt)
 {
     const long long p = lo + (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= hi) return;
-    double x = S.x[p], y = S.y[p], z = S.z[p];
+    temp_particle q;
+    q.x = S.x[p]; q.y = S.y[p]; q.z = S.z[p];
     const double px = S.px[p], py = S.py[p], pz = S.pz[p];
-    bool any = false;
-    for (int case_id = 3; case_id <= 9; case_id++)
-        any |= temp_mask(P, case_id, x, y, z, px, py, pz);
-    if (!any) return;                                   // (a hit moves the particle: the masks are re-evaluated below)
-    double vx = S.vx[p], vy = S.vy[p], vz = S.vz[p];
-    double d = S.d[p], dx = S.dx[p], dy = S.dy[p], dz = S.dz[p];
-    bool flag = S.flag[p] != 0;
-    int nwall = 0, nerr = 0;
-    for (int case_id = 3; case_id <= 9; case_id++) {
-        if (!temp_mask(P, case_id, x, y, z, px, py, pz)) continue;
-        const int s = case_id - 3;
-        const int k = atomicAdd(&D.count[s], 1);
-        const bool rec = k < D.cap;
-        if (!rec) atomicOr(&cnt->flags, 4ULL);
-        const size_t o = (size_t)s * (size_t)D.cap + (size_t)(rec ? k : 0);
-        const temp_contact c = temp_solve(P, case_id, x, y, z, vx, vy, vz);
-        double fx = 0, fy = 0, fz = 0, es = 0, dpz = 0, dE = 0;
-        nwall++;                                                                             // Temp:411,482,552
-        if (!c.ok) {
-            nerr++;                                                                          // Temp:472-474
-        } else {
-            temp_draw(P, g, case_id, step, (int)p, c.n0, c.n1, c.n2, c.cz, fx, fy, fz, es);
-            double wvx, wvy, wvz;
-            const double v_magnitude = temp_accommodate(P, case_id, vx, vy, vz, es, fx, fy, fz, wvx, wvy, wvz, dpz, dE);
-            if (flag)                                                                        // Temp:391-395
-                amc_emit(O, case_id + 1, 0, (int)p, -1, 0, fabs(d - fabs(v_magnitude * c.t)), fabs(dx - fabs(vx * c.t)),
-                         fabs(dy - fabs(vy * c.t)), fabs(dz - fabs(vz * c.t)));
-            else
-                flag = true;
-            d = 0; dx = 0; dy = 0; dz = 0;                                                   // Temp:398-401
-            x = c.cx; y = c.cy; z = c.cz;                                                    // Temp:402
-            vx = wvx; vy = wvy; vz = wvz;                                                    // Temp:403
-        }
-        if (rec) {
-            D.idx[o] = (int)p; D.t[o] = c.t; D.ok[o] = c.ok;
-            D.contact[3 * o] = c.cx; D.contact[3 * o + 1] = c.cy; D.contact[3 * o + 2] = c.cz;
-            D.normal[3 * o] = c.n0; D.normal[3 * o + 1] = c.n1; D.normal[3 * o + 2] = c.n2;
-            D.dir[3 * o] = fx; D.dir[3 * o + 1] = fy; D.dir[3 * o + 2] = fz;
-            D.Es[o] = es; D.dpz[o] = dpz; D.dE[o] = dE;
-        }
-    }
-    S.x[p] = x; S.y[p] = y; S.z[p] = z; S.vx[p] = vx; S.vy[p] = vy; S.vz[p] = vz;
-    S.d[p] = d; S.dx[p] = dx; S.dy[p] = dy; S.dz[p] = dz; S.flag[p] = flag ? 1 : 0;
-    if (nwall) atomicAdd(&O.banks[amc_bank_id()].n_wall, (unsigned long long)nwall);
-    if (nerr) atomicAdd(&O.banks[amc_bank_id()].n_fp_errors, (unsigned long long)nerr);
+    if (!temp_any_mask(P, q.x, q.y, q.z, px, py, pz)) return;   // (a hit moves the particle: the masks are re-evaluated case by case)
+    q.vx = S.vx[p]; q.vy = S.vy[p]; q.vz = S.vz[p];
+    q.d = S.d[p]; q.dx = S.dx[p]; q.dy = S.dy[p]; q.dz = S.dz[p];
+    q.flag = S.flag[p] != 0;
+    temp_cases_particle<false>(P, O, g, step, D, (int)p, px, py, pz, q);
+    S.x[p] = q.x; S.y[p] = q.y; S.z[p] = q.z; S.vx[p] = q.vx; S.vy[p] = q.vy; S.vz[p] = q.vz;
+    S.d[p] = q.d; S.dx[p] = q.dx; S.dy[p] = q.dy; S.dz[p] = q.dz; S.flag[p] = q.flag ? 1 : 0;
+    if (q.nwall) atomicAdd(&O.banks[amc_bank_id()].n_wall, (unsigned long long)q.nwall);
+    if (q.nerr) atomicAdd(&O.banks[amc_bank_id()].n_fp_errors, (unsigned long long)q.nerr);
+}
+
+temp_dev_segments amc_temp_segments(amc_ctx *c)
+{
+    const amc_temp_dev_ws &D = c->TD;
+    temp_dev_segments G;
+    G.idx = D.idx; G.count = D.count; G.t = D.t; G.contact = D.contact; G.normal = D.normal; G.dir = D.dir;
+    G.Es = D.Es; G.dpz = D.dpz; G.dE = D.dE; G.ok = D.ok; G.cap = D.cap;
+    return G;
 }
 
 hipError_t amc_launch_temp_cases_device(amc_ctx *c, const amc_temp_rng *cfg)
@@ -325,9 +178,7 @@ hipError_t amc_launch_temp_cases_device(amc_ctx *c, const amc_temp_rng *cfg)
     hipError_t e = hipMemsetAsync(D.count, 0, sizeof(int) * 7, c->stream);
     if (e != hipSuccess || cnt <= 0) return e;
     if (!c->temp_unfused) {
-        temp_dev_segments G;
-        G.idx = D.idx; G.count = D.count; G.t = D.t; G.contact = D.contact; G.normal = D.normal; G.dir = D.dir;
-        G.Es = D.Es; G.dpz = D.dpz; G.dE = D.dE; G.ok = D.ok; G.cap = D.cap;
+        const temp_dev_segments G = amc_temp_segments(c);
         AMC_LAUNCH(c, k_temp_all, dim3((unsigned)((cnt + 255) / 256)), dim3(256), c->S, c->P, c->out, *cfg,
                            (unsigned int)c->out.step, c->lo, c->hi, G, c->d_cnt);
         return hipGetLastError();
@@ -346,5 +197,113 @@ hipError_t amc_launch_temp_cases_device(amc_ctx *c, const amc_temp_rng *cfg)
         AMC_LAUNCH(c, k_temp_apply, dim3(rec_blocks), dim3(256), c->S, c->P, c->out, case_id, -1, R,
                            D.dir + 3 * o, D.Es + o, D.dpz + o, D.dE + o, 0, (int *)nullptr, (double *)nullptr);
     }
+    return hipGetLastError();
+}
+
+// ---- the step's sums on the device (a host-free run, amc_temp_run_device) ------------------------------------------------
+// What amc_temp_device_sums does on the host, addition for addition: per case the hits in ASCENDING PARTICLE INDEX, failed
+// contact solves skipped, m_case = m_case + dpz and e_case = e_case + dE left to right from 0.0; then the cases folded in
+// order 3..9.  The records of a segment stand in the order their atomics happened to run, so the kernel orders them first:
+// a particle hits a case at most once per step, hence the RANK of a record — the records of its case with a smaller
+// particle index — is its place.  Counting ranks is quadratic in a case's hits but needs no exchange between threads: with
+// ~90 hits per case (N = 1e6) it is a few hundred LDS reads per thread.  One workgroup; lanes 0..6 then add one case each.
+// A step with more hits than the tile takes the same steps through global memory (perm): slow, and as exact.
+#define AMC_TEMP_SUMS_TILE 2048
+#define AMC_TEMP_SUMS_THREADS 256
+__global__ __launch_bounds__(AMC_TEMP_SUMS_THREADS) void k_temp_sums(temp_dev_segments D, int *__restrict__ perm, amc_temp_row *__restrict__ row,
+                                                                     int row_index, int *__restrict__ ovf)
+{
+    __shared__ int s_idx[AMC_TEMP_SUMS_TILE];
+    __shared__ double s_dpz[AMC_TEMP_SUMS_TILE], s_dE[AMC_TEMP_SUMS_TILE];
+    __shared__ unsigned char s_ok[AMC_TEMP_SUMS_TILE];
+    __shared__ int s_n[7], s_off[8];
+    __shared__ double s_m[7], s_e[7];
+    __shared__ int s_any[7];
+    const int tid = threadIdx.x;
+    if (tid == 0) {
+        int off = 0;
+        for (int s = 0; s < 7; s++) {
+            const int cnt = D.count[s];
+            if (cnt > D.cap && ovf[0] == 0) { ovf[1] = row_index; ovf[2] = cnt; ovf[0] = 3 + s; }   // (the run fails: AMC_ERR_CAPACITY)
+            const int k = cnt < 0 ? 0 : (cnt < D.cap ? cnt : D.cap);
+            s_n[s] = k; s_off[s] = off;
+            off += k;
+        }
+        s_off[7] = off;
+    }
+    __syncthreads();
+    const int total = s_off[7];
+    const bool tiled = total <= AMC_TEMP_SUMS_TILE;
+    if (tiled) {
+        for (int i = tid; i < total; i += AMC_TEMP_SUMS_THREADS) {
+            int s = 0;
+            while (i >= s_off[s + 1]) s++;
+            s_idx[i] = D.idx[(size_t)s * (size_t)D.cap + (size_t)(i - s_off[s])];
+        }
+        __syncthreads();
+    }
+    for (int i = tid; i < total; i += AMC_TEMP_SUMS_THREADS) {
+        int s = 0;
+        while (i >= s_off[s + 1]) s++;
+        const size_t seg = (size_t)s * (size_t)D.cap;
+        const int k = i - s_off[s], n = s_n[s];
+        int rank = 0;
+        if (tiled) {
+            const int mine = s_idx[i];
+            const int *v = s_idx + s_off[s];
+            for (int j = 0; j < n; j++) rank += v[j] < mine ? 1 : 0;
+            const int at = s_off[s] + rank;
+            s_dpz[at] = D.dpz[seg + k]; s_dE[at] = D.dE[seg + k]; s_ok[at] = D.ok[seg + k];
+        } else {
+            const int mine = D.idx[seg + k];
+            const int *v = D.idx + seg;
+            for (int j = 0; j < n; j++) rank += v[j] < mine ? 1 : 0;
+            perm[seg + rank] = k;
+        }
+    }
+    __syncthreads();
+    if (tid < 7) {
+        const int s = tid, n = s_n[s];
+        const size_t seg = (size_t)s * (size_t)D.cap;
+        double m_case = 0.0, e_case = 0.0;
+        int any = 0;
+        for (int u = 0; u < n; u++) {
+            double a, b;
+            unsigned char ok;
+            if (tiled) {
+                a = s_dpz[s_off[s] + u]; b = s_dE[s_off[s] + u]; ok = s_ok[s_off[s] + u];
+            } else {
+                const int r = perm[seg + u];
+                a = D.dpz[seg + r]; b = D.dE[seg + r]; ok = D.ok[seg + r];
+            }
+            if (!ok) continue;
+            m_case = m_case + a;
+            e_case = e_case + b;
+            any = 1;
+        }
+        s_m[s] = m_case; s_e[s] = e_case; s_any[s] = any;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double sums[3] = {0.0, 0.0, 0.0};
+        unsigned int had = 0;
+        for (int s = 0; s < 7; s++) {
+            if (!s_n[s]) continue;
+            const int case_id = 3 + s;
+            sums[0] = sums[0] + s_m[s];
+            if (s_any[s]) had |= 1u;
+            const bool cold = (case_id == 3 || case_id == 7 || case_id == 9), hot = (case_id == 4 || case_id == 6 || case_id == 8);
+            if (cold) { sums[1] = sums[1] + s_e[s]; if (s_any[s]) had |= 2u; }
+            if (hot) { sums[2] = sums[2] + s_e[s]; if (s_any[s]) had |= 4u; }
+        }
+        amc_temp_row r;
+        r.sums[0] = sums[0]; r.sums[1] = sums[1]; r.sums[2] = sums[2]; r.had = had; r.pad = 0;
+        row[row_index] = r;
+    }
+}
+
+hipError_t amc_launch_temp_sums(amc_ctx *c, int64_t row)
+{
+    AMC_LAUNCH(c, k_temp_sums, dim3(1), dim3(AMC_TEMP_SUMS_THREADS), amc_temp_segments(c), c->TD.perm, c->TD.series, (int)row, c->TD.ovf);
     return hipGetLastError();
 }

@@ -174,11 +174,36 @@ struct amc_temp_ws {
 };
 
 // device-RNG mode (amc_temp_cases_device): one record segment per energised case, kept until the next step
+struct temp_dev_segments {       // the segments as the kernels see them (amc_energised.hip)
+    int *idx, *count;
+    double *t, *contact, *normal, *dir, *Es, *dpz, *dE;
+    unsigned char *ok;
+    int cap;
+};
+// what the streaming pass's energised stage (AMC_ST_TEMP_CASES) reads besides its own arguments: in device memory, written
+// once per amc_temp_run_device
+struct amc_temp_pass {
+    amc_temp_rng g;
+    temp_dev_segments D;
+};
+// one row of the per-step series of a host-free run (amc_temp_run_device): what amc_temp_device_sums returns for that step
+struct amc_temp_row {
+    double sums[3];              // z-momentum, energy to the cold walls, energy to the hot walls
+    unsigned int had;            // bit k: a hit contributed to sums[k]
+    unsigned int pad;
+};
 struct amc_temp_dev_ws {
     int *idx, *count;            // [7 * cap], [7]
     double *t, *contact, *normal, *dir, *Es, *dpz, *dE;
     unsigned char *ok;
     int cap;                     // records per case
+    // the host-free run: its series (grown when a run needs more rows), the ordering scratch of a step with more hits than
+    // the sums kernel's LDS tile, the first hit-record overflow (case, row, count; case 0: none) and the pass's constants
+    amc_temp_row *series;
+    int64_t series_cap, series_n;
+    int *perm;                   // [7 * cap]
+    int *ovf;                    // [4]
+    amc_temp_pass *pass;
     bool fetched;                // host copies below are valid for the last step
     int h_count[7];
     std::vector<int> h_idx[7];
@@ -262,6 +287,7 @@ struct amc_ctx {
     int stream_bs;            // AMC_STREAM_BS at creation: block size of the streaming pass (the kept-list pools are sized for it)
     int detect_bs;            // AMC_DETECT_BS at creation: block size of the list-based detect kernel
     bool temp_unfused;        // AMC_TEMP_UNFUSED set at creation: the device-RNG energised mode runs one kernel triple per case
+    bool temp_run_unfused;    // amc_temp_run_device enqueues the three streaming passes of a single step (AMC_TEMP_RUN_UNFUSED / _FUSED)
     bool overlap_split;       // AMC_OVERLAP_SPLIT != 0 at creation: an overlapped run builds its lists in a kernel of its own
     // profiling
     bool profiling;
@@ -350,9 +376,12 @@ void amc_prof_collect(amc_ctx *c);
 #define AMC_ST_WALLS 2
 #define AMC_ST_BOUNDS 4
 #define AMC_ST_BOUNDS_PRE 8     // the PREVIOUS step's bounds check after its sweep (Pore:550), folded into this pass
+#define AMC_TEMP_RUN_FUSED_DEFAULT 1   // amc_temp_run_device: one fused streaming pass per step unless AMC_TEMP_RUN_UNFUSED=1
+#define AMC_ST_TEMP_CASES 16    // energised pore, device-RNG mode: cases 3-9 (Temp:705-758) between the walls and the bounds check
 
 // launchers (each enqueues on c->stream; returns hipError_t of the launch)
 hipError_t amc_launch_stream(amc_ctx *c, double dt, int stages, int bounds_slot, bool fuse_bin = false);
+// (stages with AMC_ST_TEMP_CASES: the caller has written c->TD.pass and cleared the segments' counters)
 // the overlapped run (amc_stream.hip): the streaming pass of the next step while the sweep is being resolved,
 // and the fix-up kernel that joins the two
 hipError_t amc_launch_stream_ovl(amc_ctx *c, double dt, int stages, int from, unsigned int skip_epoch, hipStream_t stream,
@@ -375,5 +404,7 @@ hipError_t amc_launch_temp_hits(amc_ctx *c, int case_id);
 hipError_t amc_launch_temp_apply(amc_ctx *c, int case_id, int n, bool park = false);
 hipError_t amc_launch_temp_velocity(amc_ctx *c, int case_id, int n);
 hipError_t amc_launch_temp_cases_device(amc_ctx *c, const amc_temp_rng *cfg);
+hipError_t amc_launch_temp_sums(amc_ctx *c, int64_t row);     // the step's sums -> row `row` of the series (one workgroup)
+temp_dev_segments amc_temp_segments(amc_ctx *c);
 hipError_t amc_launch_kin_pack(amc_ctx *c, int world, int rank, int unpack);
 int amc_kin_banks(void);         // banks of the velocity-change list in an exchange block

@@ -14,6 +14,7 @@
 #include <algorithm>
 
 #include "amc_commit_dev.h"
+#include "amc_energised_dev.h"
 
 // One particle through the stages of a streaming pass, in registers: the previous step's post-sweep bounds check (if it
 // was left to this pass), drift, the wall cases in reference order, this step's bounds check.  px, py, pz: prior_*_vals —
@@ -111,11 +112,11 @@ AMC_DEV void amc_stream_count(const amc_out &O, const amc_stream_counts &cn, int
 #define AMC_LD(p) __builtin_nontemporal_load(&(p))
 #define AMC_ST(p, v) __builtin_nontemporal_store((v), &(p))
 
-template <int GEOM>
+template <int GEOM, int TEMP = 0>
 __global__ __launch_bounds__(256) void k_stream(amc_state S, amc_state S_out, amc_params P, amc_out O, double dt, int stages,
                                                 long long lo, long long hi, int keep_prior, int bounds_slot,
                                                 amc_grid G, amc_lists B, int build_lists, amc_lazy L, amc_commit_args C,
-                                                amc_ovl V)
+                                                amc_ovl V, const amc_temp_pass *TP)
 {
     // the previous sweep's commit rides along on EXTRA blocks behind the streaming ones (amc_commit_dev.h): order-free work
     // that nothing in this pass depends on (results reach the particles through slot_of[] below), done while the others stream
@@ -172,8 +173,24 @@ __global__ __launch_bounds__(256) void k_stream(amc_state S, amc_state S_out, am
     double px = q.x, py = q.y, pz = q.z;
     if (!(stages & AMC_ST_DRIFT) && GEOM != AMC_GEOM_CUBE && (stages & AMC_ST_WALLS)) { px = S.px[p]; py = S.py[p]; pz = S.pz[p]; }
     amc_stream_counts cn = {0, 0, 0, 0};
-    amc_stream_particle<GEOM>(q, P, O, dt, stages, (int)p, px, py, pz, cn);
+    // (energised pore, a host-free device-RNG run: cases 3-9 stand between the wall cases and the bounds check)
+    const bool temp_cases = GEOM == AMC_GEOM_PORE_ENERGISED && TEMP != 0;
+    amc_stream_particle<GEOM>(q, P, O, dt, temp_cases ? (stages & ~AMC_ST_BOUNDS) : stages, (int)p, px, py, pz, cn);
     if ((stages & AMC_ST_DRIFT) && keep_prior && GEOM != AMC_GEOM_CUBE) { S.px[p] = px; S.py[p] = py; S.pz[p] = pz; }
+    if (GEOM == AMC_GEOM_PORE_ENERGISED && TEMP != 0) {
+        // Temp:705-758 on the particle in registers, the prior position with it: what k_temp_all reads back from memory.  A
+        // wave without a hit (nearly all) skips the branch
+        if (temp_any_mask(P, q.x, q.y, q.z, px, py, pz)) {
+            temp_particle t;
+            t.x = q.x; t.y = q.y; t.z = q.z; t.vx = q.vx; t.vy = q.vy; t.vz = q.vz;
+            t.d = q.d; t.dx = q.dx; t.dy = q.dy; t.dz = q.dz; t.flag = q.flag ? 1 : 0; t.nwall = 0; t.nerr = 0;
+            temp_cases_particle<true>(P, O, TP->g, (unsigned int)O.step, TP->D, (int)p, px, py, pz, t);
+            q.x = t.x; q.y = t.y; q.z = t.z; q.vx = t.vx; q.vy = t.vy; q.vz = t.vz;
+            q.d = t.d; q.dx = t.dx; q.dy = t.dy; q.dz = t.dz; q.flag = t.flag != 0;
+            cn.nwall += t.nwall; cn.nerr += t.nerr;
+        }
+        if (stages & AMC_ST_BOUNDS) cn.noob = amc_bounds(P, q.x, q.y, q.z, true);                 // Temp:804
+    }
 
     // write back only what changed (positions and accumulators always change in a drift step)
     if (force || q.x != x_in) AMC_ST(S_out.x[p], q.x);
@@ -367,22 +384,28 @@ hipError_t amc_launch_stream(amc_ctx *c, double dt, int stages, int bounds_slot,
     }
     if (c->od_active) { C.od_stall = c->d_od; C.od_tick = c->od_tick; }
     const unsigned blocks = (unsigned)((cnt + threads - 1) / threads) + extra;
-    const int kp = c->keep_prior ? 1 : 0;
+    // (the energised stage has the prior position in registers: it is stored only for amc_download_prior)
+    const int kp = (stages & AMC_ST_TEMP_CASES) ? (int)(c->P.reserved0 & 1) : (c->keep_prior ? 1 : 0);
     amc_ovl V;
     V.adj_head = nullptr; V.skip_epoch = 0;
+    if ((stages & AMC_ST_TEMP_CASES) && (c->P.geometry != AMC_GEOM_PORE_ENERGISED || !c->TD.pass)) return hipErrorInvalidValue;
     amc_prof_begin(c, (stages == AMC_ST_BOUNDS) ? AMC_K_BOUNDS : AMC_K_DRIFT_WALLS);
     switch (c->P.geometry) {
     case AMC_GEOM_CUBE:
         AMC_LAUNCH(c, k_stream<AMC_GEOM_CUBE>, dim3(blocks), dim3(threads), c->S, c->S, c->P, c->out, dt,
-                           stages, c->lo, c->hi, kp, bounds_slot, c->G, c->B, build, L, C, V);
+                           stages, c->lo, c->hi, kp, bounds_slot, c->G, c->B, build, L, C, V, (const amc_temp_pass *)nullptr);
         break;
     case AMC_GEOM_PORE:
         AMC_LAUNCH(c, k_stream<AMC_GEOM_PORE>, dim3(blocks), dim3(threads), c->S, c->S, c->P, c->out, dt,
-                           stages, c->lo, c->hi, kp, bounds_slot, c->G, c->B, build, L, C, V);
+                           stages, c->lo, c->hi, kp, bounds_slot, c->G, c->B, build, L, C, V, (const amc_temp_pass *)nullptr);
         break;
     case AMC_GEOM_PORE_ENERGISED:
-        AMC_LAUNCH(c, k_stream<AMC_GEOM_PORE_ENERGISED>, dim3(blocks), dim3(threads), c->S, c->S, c->P,
-                           c->out, dt, stages, c->lo, c->hi, kp, bounds_slot, c->G, c->B, build, L, C, V);
+        if (stages & AMC_ST_TEMP_CASES)
+            AMC_LAUNCH(c, (k_stream<AMC_GEOM_PORE_ENERGISED, 1>), dim3(blocks), dim3(threads), c->S, c->S, c->P,
+                               c->out, dt, stages, c->lo, c->hi, kp, bounds_slot, c->G, c->B, build, L, C, V, (const amc_temp_pass *)c->TD.pass);
+        else
+            AMC_LAUNCH(c, k_stream<AMC_GEOM_PORE_ENERGISED>, dim3(blocks), dim3(threads), c->S, c->S, c->P,
+                               c->out, dt, stages, c->lo, c->hi, kp, bounds_slot, c->G, c->B, build, L, C, V, (const amc_temp_pass *)nullptr);
         break;
     default:
         break;
@@ -411,10 +434,10 @@ hipError_t amc_launch_stream_ovl(amc_ctx *c, double dt, int stages, int from, un
     amc_prof_begin(c, AMC_K_DRIFT_WALLS);
     if (c->P.geometry == AMC_GEOM_CUBE)
         AMC_LAUNCH_ON(c, stream, k_stream<AMC_GEOM_CUBE>, dim3(blocks), dim3(256), c->S_buf[from], c->S_buf[to], c->P, O, dt, stages,
-                      0LL, (long long)c->n, 0, 0, c->G, Bn, build_lists ? 1 : 0, L, C, V);
+                      0LL, (long long)c->n, 0, 0, c->G, Bn, build_lists ? 1 : 0, L, C, V, (const amc_temp_pass *)nullptr);
     else
         AMC_LAUNCH_ON(c, stream, k_stream<AMC_GEOM_PORE>, dim3(blocks), dim3(256), c->S_buf[from], c->S_buf[to], c->P, O, dt, stages,
-                      0LL, (long long)c->n, 0, 0, c->G, Bn, build_lists ? 1 : 0, L, C, V);
+                      0LL, (long long)c->n, 0, 0, c->G, Bn, build_lists ? 1 : 0, L, C, V, (const amc_temp_pass *)nullptr);
     amc_prof_end(c);
     return hipGetLastError();
 }

@@ -360,6 +360,23 @@ class EnergisedEngine(Engine):
         self._ck(self.lib.amc_temp_device_sums(self._ctx, sums, had))
         return (st, sums[0], sums[1], sums[2], bool(had[0]), bool(had[1]), bool(had[2]))
 
+    def temp_run_device(self, dt, nsteps, cfg):
+        """``nsteps`` device-RNG steps enqueued back to back, one synchronisation at the end.  Returns (summed counters,
+        float64[nsteps, 3] per-step sums: z-momentum, energy to the cold walls, energy to the hot walls — the values
+        ``temp_timestep_device`` returns step by step —, bool[nsteps, 3]: a hit contributed)."""
+        nsteps = int(nsteps)
+        st = AmcStepStats()
+        self._ck(self.lib.amc_temp_run_device(self._ctx, float(dt), nsteps, C.byref(cfg), C.byref(st)))
+        sums = np.zeros((max(nsteps, 1), 3))
+        had = np.zeros((max(nsteps, 1), 3), dtype=np.uint8)
+        left = C.c_int64(0)
+        self._ck(self.lib.amc_temp_series_read(self._ctx, 0, nsteps, _d(sums), had.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(left)))
+        return st.as_dict(), sums[:nsteps], had[:nsteps].astype(bool)
+
+    def set_step(self, step):
+        """Index of the next step: the step word of the device draws (a resumed run continues the interrupted one's)."""
+        self._ck(self.lib.amc_set_step(self._ctx, int(step)))
+
     def temp_timestep(self, dt, sampler, energies):
         """One iteration of Temperature_Pore_MC.py's loop (Temp:662-853)."""
         from .energised import drive_energised_cases

@@ -287,8 +287,24 @@ class TemperatureSimulation(Simulation):
         return st
 
     def run(self, nsteps, dt=None):
-        for _ in range(int(nsteps)):
-            self.timestep(dt, collect_paths=False)
+        """``nsteps`` iterations.  With ``device_rng_seed`` nothing in a step waits for the host: the whole run is enqueued at
+        once and the per-step sums come back as a series (``EnergisedEngine.temp_run_device``); otherwise a loop of steps."""
+        if self._device_rng is None:
+            for _ in range(int(nsteps)):
+                self.timestep(dt, collect_paths=False)
+            return None
+        nsteps = int(nsteps)
+        st, sums, had = self.engine.temp_run_device(self.dt if dt is None else dt, nsteps, self._device_rng)
+        self._cache = None
+        self.momentum_z_change_per_step.extend(sums[:, 0].tolist())
+        self.energy_transfer_cold_per_step.extend(sums[:, 1].tolist())
+        self.energy_transfer_hot_per_step.extend(sums[:, 2].tolist())
+        self._zero_flags.extend((not m, not c, not h) for m, c, h in had.tolist())
+        self.num_collisions_per_step = None
+        self.total_cols += st["n_pp"] + st["n_wall"]
+        self.total_errs += st["n_fp_errors"]
+        self.steps_done += nsteps
+        return st
 
     def _checkpoint_extra(self):
         np_state = self.sampler.np_rng.get_state()
@@ -307,6 +323,11 @@ class TemperatureSimulation(Simulation):
         self.energy_transfer_hot_per_step = z["energy_hot"].tolist()
         self._zero_flags = [tuple(bool(b) for b in row) for row in z["zero_flags"]]
         self.total_errs = int(z["total_errs"])
+        if self._device_rng is not None:
+            # the device draws are keyed by the step index: the resumed run counts on from the checkpoint's (the cadence of the
+            # sampled fields then needs no offset of its own)
+            self.engine.set_step(self.steps_done)
+            self._step_base = 0
         self.sampler.np_rng.set_state(("MT19937", z["np_rng_keys"], int(z["np_rng_rest"][0]), int(z["np_rng_rest"][1]),
                                        float(z["np_rng_gauss"])))
         self.sampler.py_rng.setstate((int(z["py_rng_version"]), tuple(int(v) for v in z["py_rng_state"]), None))

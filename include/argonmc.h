@@ -175,7 +175,8 @@ int amc_download_prior(amc_ctx *ctx, double *px, double *py, double *pz);
  * Blocks until the step is done and returns its counters. */
 int amc_timestep(amc_ctx *ctx, double dt, amc_step_stats *out);
 /* nsteps iterations enqueued back-to-back with no host synchronisation in between; *sum receives the counters
- * summed over the steps (may be NULL).  Not available for AMC_GEOM_PORE_ENERGISED (host RNG handshake per step). */
+ * summed over the steps (may be NULL).  Not available for AMC_GEOM_PORE_ENERGISED (host RNG handshake per step; its
+ * device-RNG mode has amc_temp_run_device). */
 int amc_run(amc_ctx *ctx, double dt, int64_t nsteps, amc_step_stats *sum);
 
 /* individual stages, for function-level parity tests against the reference's handlers */
@@ -271,6 +272,24 @@ int amc_temp_device_results(amc_ctx *ctx, int case_id, int32_t *idx, double *dpz
 int amc_temp_device_sums(amc_ctx *ctx, double *sums /*[3]*/, int32_t *had /*[3]*/);
 int amc_temp_device_draws(amc_ctx *ctx, int case_id, int32_t *idx, double *normal_xyz, double *contact_z, double *dir_xyz,
                           double *surface_energy, size_t cap, size_t *n);
+/* nsteps iterations of Temp:662-853 with the draws of amc_temp_cases_device, enqueued back to back with ONE synchronisation
+ * at the end: per step what amc_temp_begin -> amc_temp_cases_device -> amc_temp_end enqueue (step counter and the cadence of
+ * the sampled fields included), and a kernel that forms the step's sums on the device exactly as amc_temp_device_sums
+ * does.  *sum = counters summed over the steps (may be NULL).  Needs the whole index range in one context.  Overflow flags
+ * are examined once, at the end: a case with more hits than its record segment holds in any step makes the run fail with
+ * AMC_ERR_CAPACITY (the message names the case).  Afterwards amc_temp_device_results / _draws / _sums describe the LAST
+ * step.  Same bits as nsteps single steps.  (By default the three streaming passes in front of a step's sweep — drift and
+ * cases 1-2, cases 3-9, recapture and list filing — are one pass, and the recapture behind the sweep rides with the next
+ * step's; AMC_TEMP_RUN_UNFUSED=1 enqueues the single step's kernels instead.) */
+int amc_temp_run_device(amc_ctx *ctx, double dt, int64_t nsteps, const amc_temp_rng *cfg, amc_step_stats *sum);
+/* the per-step sums of the LAST amc_temp_run_device: rows first .. first + count - 1 of sums[.][3] = (z-momentum, energy to
+ * the cold walls, energy to the hot walls) and had[.][3] (non-zero: a hit contributed), as amc_temp_device_sums defines
+ * them; *n_steps = rows the run left (any of the three may be NULL) */
+int amc_temp_series_read(amc_ctx *ctx, int64_t first, int64_t count, double *sums, uint8_t *had, int64_t *n_steps);
+/* The index of the next step (0 after amc_create and amc_reset_outputs): the `step` key of the path records, the step word
+ * of the device draws' Philox counter and what the cadence of the sampled fields counts.  A run resumed from a checkpoint
+ * sets it to the steps already done, so that its device draws continue where the interrupted run's would have. */
+int amc_set_step(amc_ctx *ctx, int64_t step);
 
 /* ---- synthetic initial conditions on the device (opt-in) ------------------------------------------
  * The recipe of the reference's generators (Cube:144-172, Pore:106-158): positions uniform per region — the cube, or
