@@ -1,20 +1,9 @@
-// amc_api.hip — the C ABI of libargonmc.so (include/argonmc.h): context, HBM allocation, upload/download, the
-// timestep driver and measurement helpers.  No CPU compute path exists here: without a HIP device amc_create fails.
-#include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <algorithm>
-#include <chrono>
+// amc_api.hip — the C ABI of libargonmc.so (include/argonmc.h): context, HBM allocation, upload/download, outputs and
+// measurement helpers (the step driver: amc_run.hip).  No CPU compute path exists here: without a HIP device amc_create fails.
 #include <memory>
-#include <vector>
-#include <new>
 #include <type_traits>
 
 #include "amc_host.h"
-#include "amc_resolve_dev.h"
 
 int amc_fail(amc_ctx *c, int code, const char *fmt, ...)
 {
@@ -154,6 +143,205 @@ static int setup_grid(amc_ctx *c)
     return AMC_OK;
 }
 
+// ---- amc_create in steps ---------------------------------------------------------------------------------------------------
+// The environment switches, read once per context.  Three spellings, each switch keeps its own: set at all, set to a
+// non-zero number, a number with a default.
+static bool env_set(const char *name) { return getenv(name) != nullptr; }
+static bool env_nonzero(const char *name) { const char *e = getenv(name); return e && atoi(e) != 0; }
+static int env_int(const char *name, int unset) { const char *e = getenv(name); return e ? atoi(e) : unset; }
+static long long env_ll(const char *name, long long unset) { const char *e = getenv(name); return e ? atoll(e) : unset; }
+
+static void read_env(amc_ctx *c)
+{
+    const char *sync = getenv("AMC_OVERLAP_SYNC");
+    c->ovl_sync_values = sync && !strcmp(sync, "value");
+    // AMC_OVERLAP: 1 the streaming pass of step s + 1 runs beside the resolve of sweep s inside amc_run, on a second stream;
+    // 2 the same kernels in order on one stream (debugging); 0 the plain sequence (the default: measured on MI355X the resolve
+    // kernels take twice as long beside the pass's memory traffic, which with the fix-up kernel and the two cross-stream
+    // dependencies of a step eats what the overlap hides — DESIGN 4.2 has the numbers)
+    c->overlap_mode = env_int("AMC_OVERLAP", 0);
+    c->overlap_split = env_nonzero("AMC_OVERLAP_SPLIT");                                 // (experiment)
+    c->cw_blocks_env = env_int("AMC_CW_BLOCKS", 0);
+    c->ordered_always = env_nonzero("AMC_ORDERED_ALWAYS");
+    c->od_max_n = env_ll("AMC_OD_MAX_N", c->od_max_n);                                   // (tests, experiments)
+    c->od_ahead = std::min(std::max(env_int("AMC_OD_AHEAD", c->od_ahead), 1), 32);       // (experiments)
+    if (const int v = env_int("AMC_PLAN_SMALL", -1); v >= 0) c->plan_small = v;
+    c->stream_bs = env_int("AMC_STREAM_BS", 256);      // (experiments: 64 / 128 / 256)
+    c->detect_bs = env_int("AMC_DETECT_BS", 256);      // (experiments: 64 / 128 / 256)
+    c->temp_unfused = env_set("AMC_TEMP_UNFUSED");     // cross-check path: one hits/sample/apply triple per case
+    // amc_temp_run_device: AMC_TEMP_RUN_UNFUSED=1 enqueues the single step's three streaming passes (the cross-check form),
+    // AMC_TEMP_RUN_FUSED=1 the one fused pass; without either, what AMC_TEMP_RUN_FUSED_DEFAULT says (DESIGN.md 8)
+    c->temp_run_unfused = !AMC_TEMP_RUN_FUSED_DEFAULT;
+    if (env_nonzero("AMC_TEMP_RUN_FUSED")) c->temp_run_unfused = false;
+    if (env_nonzero("AMC_TEMP_RUN_UNFUSED")) c->temp_run_unfused = true;
+    // AMC_ALLPAIRS_MAX_N restores a size threshold below which cube / pore contexts run without the grid (experiments)
+    c->allpairs_max_n = env_ll("AMC_ALLPAIRS_MAX_N", 0);
+    // kept lists (amc_lists): AMC_LIST_KEEP=K, a full build every K steps
+    const int g = c->P.geometry;
+    c->list_keep = env_int("AMC_LIST_KEEP", (g == AMC_GEOM_PORE || g == AMC_GEOM_PORE_ENERGISED) ? AMC_LIST_KEEP_DEFAULT_PORE : 0);
+    // AMC_MAX_HIST (diagnostic): the history / overlay entries a sweep may USE (the allocation keeps its size): lets a test
+    // drive the wide kernel's overlay protocol into its capacity limit at sizes the oracle handles in seconds
+    c->max_hist_env = env_int("AMC_MAX_HIST", 0);
+    c->debug_resolve = env_set("AMC_DEBUG_RESOLVE");
+}
+
+// the particle state in ONE allocation: the resolve kernels gather the eleven fields of a particle from eleven arrays — in
+// one slab they share address-translation entries instead of needing one each
+static int alloc_state(amc_ctx *c)
+{
+    const size_t n = std::max<size_t>((size_t)c->n, 1);
+    double **st[] = {&c->S.x, &c->S.y, &c->S.z, &c->S.vx, &c->S.vy, &c->S.vz, &c->S.d, &c->S.dx, &c->S.dy, &c->S.dz,
+                     &c->S.px, &c->S.py, &c->S.pz};
+    const size_t per = ((sizeof(double) * n) + 255) & ~(size_t)255;
+    const size_t total = 13 * per + ((n + 255) & ~(size_t)255);
+    AMC_HIP(c, dalloc(c, &c->s_slab, total));
+    AMC_HIP(c, hipMemsetAsync(c->s_slab, 0, total, c->stream));
+    size_t off = 0;
+    for (auto pp : st) { *pp = (double *)(c->s_slab + off); off += per; }
+    c->S.flag = (uint8_t *)(c->s_slab + off);
+    c->S_buf[0] = c->S;
+    return AMC_OK;
+}
+
+// the detection grid and the per-cell lists over it (nothing without a grid)
+static int alloc_grid_lists(amc_ctx *c)
+{
+    if (int rc = setup_grid(c)) return rc;
+    if (c->allpairs) return AMC_OK;
+    const size_t n = (size_t)c->n, nc = (size_t)c->G.ncells;
+    c->max_extra = AMC_EXTRA_NODES(c->n);
+    // kept lists: off in an overlapped run (its fix-up kernel files particles itself) and when the all-pairs detector is in
+    // front.  (The energised pore files its particles in the bounds pass that follows the wall cases, amc_temp_end: the same
+    // pass, the same cycle.)
+    size_t pool = 0, keep_waves = 0;
+    int K = c->list_keep;
+    if (c->overlap_mode || c->detect_ap || c->P.geometry == AMC_GEOM_CELL) K = 0;
+    const int threads = c->stream_bs;
+    const long long nwaves = (((long long)n + threads - 1) / threads) * (threads / 64);
+    // (a wave's pool holds everything its 64 particles could hand out in K - 1 steps; shorter cycles rather than more
+    // than 2^30 nodes)
+    while (K >= 2 && (long long)n + nwaves * 64 * (K - 1) > 0x3fffffffLL) K--;
+    if (K >= 2 && n > 0 && threads % 64 == 0) {
+        c->keep_K = K;
+        c->B.wave_cap = 64 * (K - 1);
+        pool = (size_t)c->B.wave_cap * (size_t)nwaves;
+        keep_waves = (size_t)nwaves;
+    }
+    c->keep_pool = pool;
+    AMC_HIP(c, dalloc(c, &c->B.rec, n + std::max((size_t)c->max_extra, pool)));
+    AMC_HIP(c, dalloc(c, &c->B.head, nc + 1));
+    AMC_HIP(c, hipMemsetAsync(c->B.head, 0, sizeof(unsigned long long) * (nc + 1), c->stream));
+    c->B.n = (int)c->n;
+    if (c->keep_K >= 2) {
+        AMC_HIP(c, dalloc(c, &c->B.extra, pool));
+        AMC_HIP(c, dalloc(c, &c->B.cell_of, n));
+        AMC_HIP(c, dalloc(c, &c->B.node_of, n));
+        AMC_HIP(c, dalloc(c, &c->B.wave_count, keep_waves));
+        AMC_HIP(c, hipMemsetAsync(c->B.wave_count, 0, sizeof(int) * keep_waves, c->stream));
+    }
+    c->B_buf[0] = c->B;
+    AMC_HIP(c, dalloc(c, &c->W.ov_head, nc));
+    AMC_HIP(c, hipMemsetAsync(c->W.ov_head, 0xff, sizeof(int) * std::max<size_t>(nc, 1), c->stream));
+    return AMC_OK;
+}
+
+// ONE allocation for the whole sweep work space: the resolve kernels are chains of dependent, scattered accesses to some
+// sixty small arrays — carved from one slab they share a handful of translation entries instead of one each
+static int alloc_resolve_ws(amc_ctx *c)
+{
+    amc_resolve_ws &W = c->W;
+    const size_t n = (size_t)c->n;
+    long long mc = c->P.max_candidates > 0 ? c->P.max_candidates : std::max<long long>(4096, c->n / 8 + 1024);
+    if (mc > 0x3fffffff) mc = 0x3fffffff;
+    W.max_cand = (int)mc;
+    // every candidate brings two slots of its own (2k, 2k + 1); particles that join a cluster later take theirs from a counter
+    W.max_slots = (int)std::min<long long>(2 * mc + std::max<long long>(1024, mc / 2), 0x7ffffff0LL);
+    W.max_edges = 4 * W.max_slots + 1024;
+    W.max_hist = 8 * W.max_slots + 1024;
+    const size_t ms = (size_t)W.max_slots;
+    auto carve = [&](char *base) -> size_t {
+        size_t off = 0;
+        auto take = [&](auto **pp, size_t count) {
+            using T = std::remove_pointer_t<std::remove_pointer_t<decltype(pp)>>;
+            off = (off + 255) & ~(size_t)255;
+            *pp = base ? (T *)(base + off) : nullptr;
+            off += sizeof(T) * std::max<size_t>(count, 1);
+        };
+        take(&W.ctl, 64); take(&W.wctl, 64);
+        take(&W.cand4, (size_t)W.max_cand); take(&W.cand_s, (size_t)W.max_cand); take(&W.cand_mark, (size_t)W.max_cand);
+        take(&W.sl_meta, ms); take(&W.sl_hits, ms); take(&W.sl_moved, ms);
+        take(&W.sl_state, (size_t)RS_SLOT_DOUBLES * ms);
+        take(&W.sl_label, ms); take(&W.sl_tmp, ms); take(&W.sl_dirty, ms); take(&W.order, ms);
+        take(&W.sl_key, (size_t)next_pow2(W.max_slots));
+        for (int k = 0; k < 10; k++) take(&W.cw_d[k], ms);
+        take(&W.cw_tmp, ms); take(&W.cw_pidx, ms); take(&W.cw_slot, ms); take(&W.cw_flag, ms); take(&W.cw_moved, ms);
+        take(&W.edge_a, (size_t)W.max_edges); take(&W.edge_b, (size_t)W.max_edges);
+        take(&W.hist, (size_t)W.max_hist); take(&W.ov_next, (size_t)W.max_hist);
+        take(&W.ev_gen, (size_t)W.max_hist); take(&W.ev, (size_t)W.max_hist);
+        take(&W.adj_head, n); take(&W.slot_of, n); take(&W.victim, n);
+        return (off + 255) & ~(size_t)255;
+    };
+    const size_t total = carve(nullptr);
+    AMC_HIP(c, dalloc(c, &c->w_slab, total));
+    AMC_HIP(c, hipMemsetAsync(c->w_slab, 0, total, c->stream));
+    carve(c->w_slab);
+    if (c->max_hist_env > 0 && c->max_hist_env < W.max_hist) W.max_hist = c->max_hist_env;
+    amc_resolve_ctl z;
+    memset(&z, 0, sizeof z);
+    z.cur_round = 1;
+    AMC_HIP(c, hipMemcpyAsync(W.wctl, &z, sizeof z, hipMemcpyHostToDevice, c->stream));
+    AMC_HIP(c, hipStreamSynchronize(c->stream));
+    AMC_HIP(c, hipMemsetAsync(W.slot_of, 0xff, sizeof(int) * std::max<size_t>(n, 1), c->stream));
+    return AMC_OK;
+}
+
+// path records, counters and their banks, histograms
+static int alloc_outputs(amc_ctx *c)
+{
+    const amc_params *p = &c->P;
+    long long mp = p->max_paths > 0 ? p->max_paths : (p->max_paths < 0 ? 0 : (1LL << 20));   // < 0: histograms only
+    if (mp > 0x7fffffff) mp = 0x7fffffff;
+    if (mp > 0) AMC_HIP(c, dalloc(c, &c->d_rec, (size_t)mp));
+    AMC_HIP(c, dalloc(c, &c->d_cnt, 1));
+    AMC_HIP(c, hipMemsetAsync(c->d_cnt, 0, sizeof(amc_dev_counters), c->stream));
+    AMC_HIP(c, dalloc(c, &c->d_banks, AMC_COUNTER_BANKS));
+    AMC_HIP(c, hipMemsetAsync(c->d_banks, 0, sizeof(amc_counter_bank) * AMC_COUNTER_BANKS, c->stream));
+    c->out.banks = c->d_banks;
+    c->out.rec = c->d_rec; c->out.cap = (unsigned)mp; c->out.cnt = c->d_cnt;
+    c->out.lo = p->hist_lo; c->out.hi = p->hist_hi;
+    if (p->hist_bins > 0 && p->hist_hi > p->hist_lo) {
+        const int nb = p->hist_bins;
+        AMC_HIP(c, dalloc(c, &c->d_hist, (size_t)4 * nb * AMC_COUNTER_BANKS));
+        AMC_HIP(c, hipMemsetAsync(c->d_hist, 0, sizeof(unsigned long long) * 4 * nb * AMC_COUNTER_BANKS, c->stream));
+        AMC_HIP(c, dalloc(c, &c->d_edges, (size_t)nb + 1));
+        // np.linspace(lo, hi, nb+1): start + k*step with step = (hi-lo)/nb, last element forced to hi
+        std::vector<double> ed(nb + 1);
+        const double step = (p->hist_hi - p->hist_lo) / (double)nb;
+        for (int k = 0; k <= nb; k++) ed[k] = p->hist_lo + (double)k * step;
+        ed[nb] = p->hist_hi;
+        AMC_HIP(c, hipMemcpy(c->d_edges, ed.data(), sizeof(double) * (nb + 1), hipMemcpyHostToDevice));
+        c->out.nbins = nb; c->out.hist = c->d_hist; c->out.edges = c->d_edges; c->out.bin_step = step;
+    }
+    return AMC_OK;
+}
+
+// the host-mapped words of the launch plans, the on-demand run's device words, the pinned staging buffer
+static int alloc_host_words(amc_ctx *c)
+{
+    void *hp = nullptr, *dp = nullptr;
+    // (three words, a cache line apart: candidate count; mirror of stalled_at; last step whose wide kernel ran)
+    if (palloc(c, &hp, 256, hipHostMallocMapped) == hipSuccess && hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess) {
+        memset(hp, 0, 256);
+        c->h_host_ncand = (volatile int *)hp;
+        c->d_host_ncand = (int *)dp;
+        c->h_od_stall = (volatile int *)hp + 16; c->d_od_stall_host = (int *)dp + 16;
+        c->h_od_done = (volatile int *)hp + 32; c->d_od_done_host = (int *)dp + 32;
+    }
+    AMC_HIP(c, dalloc(c, &c->d_od, 16));
+    AMC_HIP(c, hipMemsetAsync(c->d_od, 0, 16 * sizeof(int), c->stream));
+    if (palloc(c, &c->h_pin, (size_t)4 << 20, hipHostMallocDefault) == hipSuccess) c->h_pin_bytes = (size_t)4 << 20;
+    return AMC_OK;
+}
 
 extern "C" {
 
@@ -202,192 +390,33 @@ int amc_create(amc_ctx **out, const amc_params *p)
     c->device = p->device;
     c->n = p->n; c->hi = p->n;
     c->keep_prior = (p->reserved0 & 1) != 0;
-    // environment switches, read once per context
-    c->ovl_sync_values = getenv("AMC_OVERLAP_SYNC") && !strcmp(getenv("AMC_OVERLAP_SYNC"), "value");
-    // AMC_OVERLAP: 1 the streaming pass of step s + 1 runs beside the resolve of sweep s inside amc_run, on a second stream;
-    // 2 the same kernels in order on one stream (debugging); 0 the plain sequence (the default: measured on MI355X the resolve
-    // kernels take twice as long beside the pass's memory traffic, which with the fix-up kernel and the two cross-stream
-    // dependencies of a step eats what the overlap hides — DESIGN 4.2 has the numbers)
-    c->overlap_mode = getenv("AMC_OVERLAP") ? atoi(getenv("AMC_OVERLAP")) : 0;
-    c->overlap_split = getenv("AMC_OVERLAP_SPLIT") && atoi(getenv("AMC_OVERLAP_SPLIT")) != 0;     // (experiment)
-    c->cw_blocks_env = getenv("AMC_CW_BLOCKS") ? atoi(getenv("AMC_CW_BLOCKS")) : 0;
-    c->ordered_always = getenv("AMC_ORDERED_ALWAYS") && atoi(getenv("AMC_ORDERED_ALWAYS")) != 0;
-    if (const char *e = getenv("AMC_OD_MAX_N")) c->od_max_n = atoll(e);                                  // (tests, experiments)
-    if (const char *e = getenv("AMC_OD_AHEAD")) c->od_ahead = std::min(std::max(atoi(e), 1), 32);     // (experiments)
-    if (const char *e = getenv("AMC_PLAN_SMALL")) { const int v = atoi(e); if (v >= 0) c->plan_small = v; }
-    c->stream_bs = getenv("AMC_STREAM_BS") ? atoi(getenv("AMC_STREAM_BS")) : 256;      // (experiments: 64 / 128 / 256)
-    c->detect_bs = getenv("AMC_DETECT_BS") ? atoi(getenv("AMC_DETECT_BS")) : 256;      // (experiments: 64 / 128 / 256)
-    c->temp_unfused = getenv("AMC_TEMP_UNFUSED") != nullptr;  // cross-check path: one hits/sample/apply triple per case
-    // amc_temp_run_device: AMC_TEMP_RUN_UNFUSED=1 enqueues the single step's three streaming passes (the cross-check form),
-    // AMC_TEMP_RUN_FUSED=1 the one fused pass; without either, what AMC_TEMP_RUN_FUSED_DEFAULT says (DESIGN.md 8)
-    c->temp_run_unfused = !AMC_TEMP_RUN_FUSED_DEFAULT;
-    if (const char *e = getenv("AMC_TEMP_RUN_FUSED")) { if (atoi(e) != 0) c->temp_run_unfused = false; }
-    if (const char *e = getenv("AMC_TEMP_RUN_UNFUSED")) { if (atoi(e) != 0) c->temp_run_unfused = true; }
+    read_env(c);
     // a failure below returns through amc_fail: the guard hands its message on and destroys what was built
     std::unique_ptr<amc_ctx, void (*)(amc_ctx *)> guard(c, [](amc_ctx *x) { g_create_err = x->err; amc_destroy(x); });
-    {
-        AMC_HIP(c, hipSetDevice(c->device));
-        AMC_HIP(c, ctx_stream(c, &c->own_stream));
-        c->stream = c->own_stream;
-        const size_t n = (size_t)c->n;
-        // detection mode: only single cells (AMC_GEOM_CELL: no geometry to lay a grid over) run without the detection grid —
-        // all-pairs detector, brute-force validation, everything in the one ordered workgroup.  Cube and pore contexts use
-        // the grid and the wide cluster kernel at ANY size: measured at N = 4,096 the grid path takes 32 us per step, the
-        // gridless one 132 (N = 1,000: 28 against 45; round 2 sent N <= 4,096 down the gridless path).  AMC_ALLPAIRS_MAX_N
-        // restores a threshold for experiments.
-        // (detect_mode 2: the all-pairs DETECTOR in front of the same grid-based resolve — the kernel the reference's
-        // pairwise loop maps to directly, measurable at full size against the fp64 vector peak)
-        long long small_n = 0;
-        if (const char *e = getenv("AMC_ALLPAIRS_MAX_N")) small_n = atoll(e);
-        c->allpairs = (p->geometry == AMC_GEOM_CELL) || (p->detect_mode != 1 && c->n <= small_n);
-        c->detect_ap = c->allpairs || p->detect_mode == 2;
-        if (p->geometry == AMC_GEOM_CELL && p->detect_mode == 1) {
-            return amc_fail(c, AMC_ERR_INVALID, "AMC_GEOM_CELL has no cell grid: detect_mode must be 0 or 2");
-        }
-        double **st[] = {&c->S.x, &c->S.y, &c->S.z, &c->S.vx, &c->S.vy, &c->S.vz, &c->S.d, &c->S.dx, &c->S.dy, &c->S.dz,
-                         &c->S.px, &c->S.py, &c->S.pz};
-        {
-            // the particle state in ONE allocation: the resolve kernels gather the eleven fields of a particle from eleven
-            // arrays — in one slab they share address-translation entries instead of needing one each
-            const size_t per = ((sizeof(double) * std::max<size_t>(n, 1)) + 255) & ~(size_t)255;
-            const size_t total = 13 * per + ((std::max<size_t>(n, 1) + 255) & ~(size_t)255);
-            AMC_HIP(c, dalloc(c, &c->s_slab, total));
-            AMC_HIP(c, hipMemsetAsync(c->s_slab, 0, total, c->stream));
-            size_t off = 0;
-            for (auto pp : st) { *pp = (double *)(c->s_slab + off); off += per; }
-            c->S.flag = (uint8_t *)(c->s_slab + off);
-            c->S_buf[0] = c->S;
-        }
-        if (int rc = setup_grid(c)) return rc;
-        if (!c->allpairs) {
-            const size_t nc = (size_t)c->G.ncells;
-            c->max_extra = AMC_EXTRA_NODES(c->n);
-            // kept lists (amc_lists): AMC_LIST_KEEP=K, a full build every K steps.  Off in an overlapped run (its fix-up kernel
-            // files particles itself) and when the all-pairs detector is in front.  (The energised pore files its particles in
-            // the bounds pass that follows the wall cases, amc_temp_end: the same pass, the same cycle.)
-            size_t pool = 0, keep_waves = 0;
-            {
-                int K = (p->geometry == AMC_GEOM_PORE || p->geometry == AMC_GEOM_PORE_ENERGISED) ? AMC_LIST_KEEP_DEFAULT_PORE : 0;
-                if (const char *e = getenv("AMC_LIST_KEEP")) K = atoi(e);
-                if (c->overlap_mode || c->detect_ap || p->geometry == AMC_GEOM_CELL) K = 0;
-                const int threads = c->stream_bs;
-                const long long nwaves = (((long long)n + threads - 1) / threads) * (threads / 64);
-                // (a wave's pool holds everything its 64 particles could hand out in K - 1 steps; shorter cycles rather than more
-                // than 2^30 nodes)
-                while (K >= 2 && (long long)n + nwaves * 64 * (K - 1) > 0x3fffffffLL) K--;
-                if (K >= 2 && n > 0 && threads % 64 == 0) {
-                    c->keep_K = K;
-                    c->B.wave_cap = 64 * (K - 1);
-                    pool = (size_t)c->B.wave_cap * (size_t)nwaves;
-                    keep_waves = (size_t)nwaves;
-                }
-            }
-            c->keep_pool = pool;
-            AMC_HIP(c, dalloc(c, &c->B.rec, n + std::max((size_t)c->max_extra, pool)));
-            AMC_HIP(c, dalloc(c, &c->B.head, nc + 1));
-            AMC_HIP(c, hipMemsetAsync(c->B.head, 0, sizeof(unsigned long long) * (nc + 1), c->stream));
-            c->B.n = (int)c->n;
-            if (c->keep_K >= 2) {
-                AMC_HIP(c, dalloc(c, &c->B.extra, pool));
-                AMC_HIP(c, dalloc(c, &c->B.cell_of, n));
-                AMC_HIP(c, dalloc(c, &c->B.node_of, n));
-                AMC_HIP(c, dalloc(c, &c->B.wave_count, keep_waves));
-                AMC_HIP(c, hipMemsetAsync(c->B.wave_count, 0, sizeof(int) * keep_waves, c->stream));
-            }
-            c->B_buf[0] = c->B;
-            AMC_HIP(c, dalloc(c, &c->W.ov_head, nc));
-            AMC_HIP(c, hipMemsetAsync(c->W.ov_head, 0xff, sizeof(int) * std::max<size_t>(nc, 1), c->stream));
-        }
-        // resolve work space
-        amc_resolve_ws &W = c->W;
-        long long mc = p->max_candidates > 0 ? p->max_candidates : std::max<long long>(4096, c->n / 8 + 1024);
-        if (mc > 0x3fffffff) mc = 0x3fffffff;
-        W.max_cand = (int)mc;
-        // every candidate brings two slots of its own (2k, 2k + 1); particles that join a cluster later take theirs from a counter
-        W.max_slots = (int)std::min<long long>(2 * mc + std::max<long long>(1024, mc / 2), 0x7ffffff0LL);
-        W.max_edges = 4 * W.max_slots + 1024;
-        W.max_hist = 8 * W.max_slots + 1024;
-        // ONE allocation for the whole sweep work space: the resolve kernels are chains of dependent, scattered accesses to
-        // some sixty small arrays — carved from one slab they share a handful of translation entries instead of one each
-        {
-            const size_t ms = (size_t)W.max_slots;
-            auto carve = [&](char *base) -> size_t {
-                size_t off = 0;
-                auto take = [&](auto **pp, size_t count) {
-                    using T = std::remove_pointer_t<std::remove_pointer_t<decltype(pp)>>;
-                    off = (off + 255) & ~(size_t)255;
-                    *pp = base ? (T *)(base + off) : nullptr;
-                    off += sizeof(T) * std::max<size_t>(count, 1);
-                };
-                take(&W.ctl, 64); take(&W.wctl, 64);
-                take(&W.cand4, (size_t)W.max_cand); take(&W.cand_s, (size_t)W.max_cand); take(&W.cand_mark, (size_t)W.max_cand);
-                take(&W.sl_meta, ms); take(&W.sl_hits, ms); take(&W.sl_moved, ms);
-                take(&W.sl_state, (size_t)RS_SLOT_DOUBLES * ms);
-                take(&W.sl_label, ms); take(&W.sl_tmp, ms); take(&W.sl_dirty, ms); take(&W.order, ms);
-                take(&W.sl_key, (size_t)next_pow2(W.max_slots));
-                for (int k = 0; k < 10; k++) take(&W.cw_d[k], ms);
-                take(&W.cw_tmp, ms); take(&W.cw_pidx, ms); take(&W.cw_slot, ms); take(&W.cw_flag, ms); take(&W.cw_moved, ms);
-                take(&W.edge_a, (size_t)W.max_edges); take(&W.edge_b, (size_t)W.max_edges);
-                take(&W.hist, (size_t)W.max_hist); take(&W.ov_next, (size_t)W.max_hist);
-                take(&W.ev_gen, (size_t)W.max_hist); take(&W.ev, (size_t)W.max_hist);
-                take(&W.adj_head, n); take(&W.slot_of, n); take(&W.victim, n);
-                return (off + 255) & ~(size_t)255;
-            };
-            const size_t total = carve(nullptr);
-            AMC_HIP(c, dalloc(c, &c->w_slab, total));
-            AMC_HIP(c, hipMemsetAsync(c->w_slab, 0, total, c->stream));
-            carve(c->w_slab);
-        }
-        // AMC_MAX_HIST (diagnostic): the history / overlay entries a sweep may USE (the allocation keeps its size): lets a test
-        // drive the wide kernel's overlay protocol into its capacity limit at sizes the oracle handles in seconds
-        if (const char *e = getenv("AMC_MAX_HIST")) { const int v = atoi(e); if (v > 0 && v < W.max_hist) W.max_hist = v; }
-        { amc_resolve_ctl z; memset(&z, 0, sizeof z); z.cur_round = 1; AMC_HIP(c, hipMemcpyAsync(W.wctl, &z, sizeof z, hipMemcpyHostToDevice, c->stream)); AMC_HIP(c, hipStreamSynchronize(c->stream)); }
-        AMC_HIP(c, hipMemsetAsync(W.slot_of, 0xff, sizeof(int) * std::max<size_t>(n, 1), c->stream));
-        // outputs
-        long long mp = p->max_paths > 0 ? p->max_paths : (p->max_paths < 0 ? 0 : (1LL << 20));   // < 0: histograms only
-        if (mp > 0x7fffffff) mp = 0x7fffffff;
-        if (mp > 0) AMC_HIP(c, dalloc(c, &c->d_rec, (size_t)mp));
-        AMC_HIP(c, dalloc(c, &c->d_cnt, 1));
-        AMC_HIP(c, hipMemsetAsync(c->d_cnt, 0, sizeof(amc_dev_counters), c->stream));
-        AMC_HIP(c, dalloc(c, &c->d_banks, AMC_COUNTER_BANKS));
-        AMC_HIP(c, hipMemsetAsync(c->d_banks, 0, sizeof(amc_counter_bank) * AMC_COUNTER_BANKS, c->stream));
-        c->out.banks = c->d_banks;
-        c->out.rec = c->d_rec; c->out.cap = (unsigned)mp; c->out.cnt = c->d_cnt;
-        c->out.lo = p->hist_lo; c->out.hi = p->hist_hi;
-        if (p->hist_bins > 0 && p->hist_hi > p->hist_lo) {
-            const int nb = p->hist_bins;
-            AMC_HIP(c, dalloc(c, &c->d_hist, (size_t)4 * nb * AMC_COUNTER_BANKS));
-            AMC_HIP(c, hipMemsetAsync(c->d_hist, 0, sizeof(unsigned long long) * 4 * nb * AMC_COUNTER_BANKS, c->stream));
-            AMC_HIP(c, dalloc(c, &c->d_edges, (size_t)nb + 1));
-            // np.linspace(lo, hi, nb+1): start + k*step with step = (hi-lo)/nb, last element forced to hi
-            std::vector<double> ed(nb + 1);
-            const double step = (p->hist_hi - p->hist_lo) / (double)nb;
-            for (int k = 0; k <= nb; k++) ed[k] = p->hist_lo + (double)k * step;
-            ed[nb] = p->hist_hi;
-            AMC_HIP(c, hipMemcpy(c->d_edges, ed.data(), sizeof(double) * (nb + 1), hipMemcpyHostToDevice));
-            c->out.nbins = nb; c->out.hist = c->d_hist; c->out.edges = c->d_edges; c->out.bin_step = step;
-        }
-        {
-            void *hp = nullptr, *dp = nullptr;
-            // (three words, a cache line apart: candidate count; mirror of stalled_at; last step whose wide kernel ran)
-            if (palloc(c, &hp, 256, hipHostMallocMapped) == hipSuccess && hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess) {
-                memset(hp, 0, 256);
-                c->h_host_ncand = (volatile int *)hp;
-                c->d_host_ncand = (int *)dp;
-                c->h_od_stall = (volatile int *)hp + 16; c->d_od_stall_host = (int *)dp + 16;
-                c->h_od_done = (volatile int *)hp + 32; c->d_od_done_host = (int *)dp + 32;
-            }
-            AMC_HIP(c, dalloc(c, &c->d_od, 16));
-            AMC_HIP(c, hipMemsetAsync(c->d_od, 0, 16 * sizeof(int), c->stream));
-        }
-        if (palloc(c, &c->h_pin, (size_t)4 << 20, hipHostMallocDefault) == hipSuccess) c->h_pin_bytes = (size_t)4 << 20;
-        if (getenv("AMC_DEBUG_RESOLVE")) {
-            AMC_HIP(c, dalloc(c, &c->d_dbg, 128 + 128 * 512));
-            AMC_HIP(c, hipMemsetAsync(c->d_dbg, 0, sizeof(long long) * (128 + 128 * 512), c->stream));
-            { const long long big = 0x7fffffffffffffffLL; AMC_HIP(c, hipMemcpyAsync(c->d_dbg + 28, &big, sizeof big, hipMemcpyHostToDevice, c->stream)); }
-        }
-        AMC_HIP(c, hipStreamSynchronize(c->stream));
+    AMC_HIP(c, hipSetDevice(c->device));
+    AMC_HIP(c, ctx_stream(c, &c->own_stream));
+    c->stream = c->own_stream;
+    // detection mode: only single cells (AMC_GEOM_CELL: no geometry to lay a grid over) run without the detection grid —
+    // all-pairs detector, brute-force validation, everything in the one ordered workgroup.  Cube and pore contexts use
+    // the grid and the wide cluster kernel at ANY size: measured at N = 4,096 the grid path takes 32 us per step, the
+    // gridless one 132 (N = 1,000: 28 against 45; round 2 sent N <= 4,096 down the gridless path).
+    // (detect_mode 2: the all-pairs DETECTOR in front of the same grid-based resolve — the kernel the reference's
+    // pairwise loop maps to directly, measurable at full size against the fp64 vector peak)
+    c->allpairs = (p->geometry == AMC_GEOM_CELL) || (p->detect_mode != 1 && c->n <= c->allpairs_max_n);
+    c->detect_ap = c->allpairs || p->detect_mode == 2;
+    if (p->geometry == AMC_GEOM_CELL && p->detect_mode == 1) {
+        return amc_fail(c, AMC_ERR_INVALID, "AMC_GEOM_CELL has no cell grid: detect_mode must be 0 or 2");
     }
+    int rc;
+    if ((rc = alloc_state(c)) || (rc = alloc_grid_lists(c)) || (rc = alloc_resolve_ws(c)) || (rc = alloc_outputs(c)) ||
+        (rc = alloc_host_words(c)))
+        return rc;
+    if (c->debug_resolve) {
+        AMC_HIP(c, dalloc(c, &c->d_dbg, 128 + 128 * 512));
+        AMC_HIP(c, hipMemsetAsync(c->d_dbg, 0, sizeof(long long) * (128 + 128 * 512), c->stream));
+        { const long long big = 0x7fffffffffffffffLL; AMC_HIP(c, hipMemcpyAsync(c->d_dbg + 28, &big, sizeof big, hipMemcpyHostToDevice, c->stream)); }
+    }
+    AMC_HIP(c, hipStreamSynchronize(c->stream));
     *out = guard.release();
     return AMC_OK;
 }
@@ -427,7 +456,7 @@ int amc_upload(amc_ctx *c, const double *x, const double *y, const double *z, co
     if (!c) return AMC_ERR_INVALID;
     AMC_HIP(c, hipSetDevice(c->device));
     { int rc_ = amc_flush(c); if (rc_) return rc_; }
-    c->lists_age = -1;          // (kept lists: a new state starts with a full build)
+    c->step.lists_age = -1;          // (kept lists: a new state starts with a full build)
     const size_t nb = sizeof(double) * (size_t)c->n;
     const double *src[] = {x, y, z, vx, vy, vz, dist, dist_x, dist_y, dist_z};
     double *dst[] = {c->S.x, c->S.y, c->S.z, c->S.vx, c->S.vy, c->S.vz, c->S.d, c->S.dx, c->S.dy, c->S.dz};
@@ -477,419 +506,6 @@ int amc_download_prior(amc_ctx *c, double *px, double *py, double *pz)
     if (pz && nb) AMC_HIP(c, hipMemcpyAsync(pz, c->S.pz, nb, hipMemcpyDeviceToHost, c->stream));
     AMC_HIP(c, hipStreamSynchronize(c->stream));
     return AMC_OK;
-}
-
-// ---- the step ----------------------------------------------------------------------------------------------------------
-static void fold_banks(amc_dev_counters *h, const amc_counter_bank *b)
-{
-    for (int k = 0; k < AMC_COUNTER_BANKS; k++) {
-        h->n_wall += b[k].n_wall; h->n_paths += b[k].n_paths; h->n_paths_total += b[k].n_paths_total;
-        h->n_fp_errors += b[k].n_fp_errors; h->n_pp += b[k].n_pp;
-    }
-}
-
-int amc_read_counters(amc_ctx *c, amc_dev_counters *h)
-{
-    if (c->commit_pending) {            // the last sweep's paths / counters are not in yet: commit it now (its results stay deferred)
-        AMC_HIP(c, amc_launch_commit(c));
-        c->commit_pending = false;
-    }
-    amc_counter_bank banks[AMC_COUNTER_BANKS];
-    amc_stage st(c);
-    AMC_HIP(c, st.get(h, c->d_cnt, sizeof *h));
-    AMC_HIP(c, st.get(banks, c->d_banks, sizeof banks));
-    AMC_HIP(c, st.finish());
-    fold_banks(h, banks);
-    return AMC_OK;
-}
-
-static void delta_stats(const amc_dev_counters &now, const amc_dev_counters &prev, amc_step_stats *o)
-{
-    o->n_pp = (int64_t)(now.n_pp - prev.n_pp);
-    o->n_wall = (int64_t)(now.n_wall - prev.n_wall);
-    o->n_oob_walls = (int64_t)(now.n_oob_walls - prev.n_oob_walls);
-    o->n_oob_pp = (int64_t)(now.n_oob_pp - prev.n_oob_pp);
-    o->n_paths = (int64_t)(now.n_paths - prev.n_paths);
-    o->n_candidates = (int64_t)(now.n_candidates - prev.n_candidates);
-    o->n_clusters = (int64_t)(now.n_clusters - prev.n_clusters);
-    o->n_rounds = (int64_t)(now.n_rounds - prev.n_rounds);
-    o->n_fp_errors = (int64_t)(now.n_fp_errors - prev.n_fp_errors);
-    o->flags = (int64_t)now.flags;
-}
-
-int amc_finish_stats(amc_ctx *c, amc_step_stats *out)
-{
-    amc_dev_counters now;
-    int rc = amc_read_counters(c, &now);
-    if (rc) return rc;
-    amc_step_stats st;
-    delta_stats(now, c->h_prev, &st);
-    c->h_prev = now;
-    if (out) *out = st;
-    if (now.flags & 21ULL) {    // candidate / resolve work-space / velocity-change list overflow; a full path-record buffer (bit1) only stops recording
-        const unsigned long long f = now.flags;
-        // clear the sticky flags on the device so that a later call can succeed after the caller drained / resized
-        unsigned long long zero = 0;
-        hipMemcpyAsync(&c->d_cnt->flags, &zero, sizeof zero, hipMemcpyHostToDevice, c->stream);
-        hipStreamSynchronize(c->stream);
-        c->h_prev.flags = 0;
-        return amc_fail(c, AMC_ERR_CAPACITY, "device work buffer overflow (flags=%llu: 1 candidates, 4 resolve work space, 16 velocity changes of one step in the multi-GPU exchange)", f);
-    }
-    if (st.n_fp_errors > 0 && c->P.geometry != AMC_GEOM_PORE_ENERGISED && !(c->P.reserved1 & 1))
-        return amc_fail(c, AMC_ERR_FP, "%lld event(s) where the reference raises FloatingPointError", (long long)st.n_fp_errors);
-    return AMC_OK;
-}
-
-// sweep results deferred to the next streaming pass: write them now (before anything else reads the particle arrays)
-int amc_flush(amc_ctx *c)
-{
-    if (c->commit_pending) {            // (before the results are applied: the commit leaves the number of deferred slots)
-        AMC_HIP(c, amc_launch_commit(c));
-        c->commit_pending = false;
-    }
-    if (!c->lazy_pending) return AMC_OK;
-    AMC_HIP(c, amc_launch_apply(c));
-    c->lazy_pending = false;
-    return AMC_OK;
-}
-
-int amc_enqueue_sweep(amc_ctx *c, bool counted, bool defer_commit)
-{
-    if (!counted) AMC_HIP(c, amc_launch_bin(c));
-    AMC_HIP(c, amc_launch_detect(c));
-    AMC_HIP(c, amc_launch_resolve(c, defer_commit));
-    if (defer_commit) c->lazy_pending = true;
-    return AMC_OK;
-}
-
-
-// fold_prev_bounds: the previous step of the same amc_run left its post-sweep bounds check to this step's streaming
-// pass; defer_bounds: leave this step's to the next one (the caller runs it separately after the last step)
-static int enqueue_step(amc_ctx *c, double dt, bool fold_prev_bounds = false, bool defer_bounds = false)
-{
-    const int g = c->P.geometry;
-    int rc;
-    if (g == AMC_GEOM_CELL) {
-        if ((rc = amc_enqueue_sweep(c))) return rc;
-    } else if (g == AMC_GEOM_CUBE || g == AMC_GEOM_PORE) {
-        // the streaming pass also counts the particles into the detection grid when it covers all of them
-        const bool fuse = !c->allpairs && c->lo == 0 && c->hi == c->n;
-        int st = (g == AMC_GEOM_CUBE) ? (AMC_ST_DRIFT | AMC_ST_WALLS) : (AMC_ST_DRIFT | AMC_ST_WALLS | AMC_ST_BOUNDS);
-        if (fold_prev_bounds && g == AMC_GEOM_PORE) st |= AMC_ST_BOUNDS_PRE;
-        AMC_HIP(c, amc_launch_stream(c, dt, st, 0, fuse));
-        // the scattered commit is deferred: the next streaming pass over all particles (the bounds check for the pore,
-        // the next step's drift for the cube) picks the results up through slot_of[]
-        if ((rc = amc_enqueue_sweep(c, fuse, c->lo == 0 && c->hi == c->n))) return rc;
-        if (g == AMC_GEOM_PORE && !defer_bounds) AMC_HIP(c, amc_launch_stream(c, dt, AMC_ST_BOUNDS, 1));
-    } else {
-        return amc_fail(c, AMC_ERR_INVALID, "energised walls need the host handshake: use the Python driver (amc_wall_hits/apply), or amc_temp_run_device for the device-RNG mode");
-    }
-    c->out.step++;
-    // (a step that leaves its post-sweep bounds check to the next pass is never sampled: amc_run does not defer it)
-    return amc_fields_step(c);
-}
-
-int amc_timestep(amc_ctx *c, double dt, amc_step_stats *out)
-{
-    if (!c) return AMC_ERR_INVALID;
-    if (!c->uploaded) return amc_fail(c, AMC_ERR_STATE, "amc_timestep before amc_upload");
-    AMC_HIP(c, hipSetDevice(c->device));
-    int rc = enqueue_step(c, dt);
-    if (rc) return rc;
-    return amc_finish_stats(c, out);
-}
-
-// ---- the overlapped run -----------------------------------------------------------------------------------
-// Resolving a sweep is latency-bound work for a few hundred waves (k_clusters_wide, the ordered workgroup) and needs the
-// PRE-sweep state; the next step's streaming pass is bandwidth- and atomic-bound work for the whole chip and needs the sweep's
-// results only for the few thousand particles it touches.  Inside amc_run the two therefore run side by side: the pass reads
-// the state buffer the resolve reads and writes the other one, leaves out the particles of the sweep's candidates, and a
-// fix-up kernel advances those from the sweep's results afterwards (amc_stream.hip).  What is needed for it — a second set of
-// state arrays and per-cell lists, the deferred-event buffers, a second stream — is allocated by the first such run.
-static int ensure_overlap(amc_ctx *c)
-{
-    if (c->s_slab2) return AMC_OK;
-    amc_alloc_group group(c);
-    const size_t n = (size_t)std::max<int64_t>(c->n, 1);
-    const size_t per = ((sizeof(double) * n) + 255) & ~(size_t)255;
-    const size_t total = 10 * per + ((n + 255) & ~(size_t)255);
-    char *slab;
-    AMC_HIP(c, dalloc(c, &slab, total));
-    AMC_HIP(c, hipMemsetAsync(slab, 0, total, c->stream));
-    amc_state S;
-    double **st[] = {&S.x, &S.y, &S.z, &S.vx, &S.vy, &S.vz, &S.d, &S.dx, &S.dy, &S.dz};
-    size_t off = 0;
-    for (auto pp : st) { *pp = (double *)(slab + off); off += per; }
-    S.flag = (uint8_t *)(slab + off);
-    S.px = c->S_buf[0].px; S.py = c->S_buf[0].py; S.pz = c->S_buf[0].pz;      // (prior_*_vals are not kept by these runs)
-    const size_t nc = (size_t)c->G.ncells;
-    amc_lists B = c->B_buf[1];
-    AMC_HIP(c, dalloc(c, &B.rec, n + (size_t)c->max_extra));
-    AMC_HIP(c, dalloc(c, &B.head, nc + 1));
-    AMC_HIP(c, hipMemsetAsync(B.head, 0, sizeof(unsigned long long) * (nc + 1), c->stream));
-    B.epoch = 0; B.n = (int)c->n;
-    int *extra, *extra_count;
-    AMC_HIP(c, dalloc(c, &extra, (size_t)2 * c->max_extra));
-    AMC_HIP(c, dalloc(c, &extra_count, 2));
-    AMC_HIP(c, hipMemsetAsync(extra_count, 0, 2 * sizeof(int), c->stream));
-    // deferred events of a pass: wall hits (~1e-3 per particle and step in the pore), by bank
-    const int cap = (int)std::max<long long>(1024, (long long)c->n / (4 * AMC_COUNTER_BANKS));
-    amc_wev_rec *wev_rec;
-    unsigned int *wev_count, *flags;
-    AMC_HIP(c, dalloc(c, &wev_rec, (size_t)2 * AMC_COUNTER_BANKS * cap));
-    AMC_HIP(c, dalloc(c, &wev_count, (size_t)2 * AMC_COUNTER_BANKS));
-    AMC_HIP(c, hipMemsetAsync(wev_count, 0, sizeof(unsigned int) * 2 * AMC_COUNTER_BANKS, c->stream));
-    hipStream_t stream2;
-    hipEvent_t ev_detect, ev_stream;
-    AMC_HIP(c, ctx_stream(c, &stream2));
-    int can = 0, sync_values = c->ovl_sync_values;
-    if (hipDeviceGetAttribute(&can, hipDeviceAttributeCanUseStreamWaitValue, c->device) != hipSuccess || !can) sync_values = 0;
-    AMC_HIP(c, dalloc(c, &flags, 64));
-    AMC_HIP(c, hipMemsetAsync(flags, 0, 64 * sizeof(unsigned int), c->stream));
-    AMC_HIP(c, ctx_event(c, &ev_detect, hipEventDisableTiming));
-    AMC_HIP(c, ctx_event(c, &ev_stream, hipEventDisableTiming));
-    AMC_HIP(c, hipStreamSynchronize(c->stream));
-    group.keep();
-    c->S_buf[1] = S; c->B_buf[1] = B;
-    c->extra_buf[0] = extra; c->extra_buf[1] = extra + c->max_extra; c->extra_count = extra_count;
-    c->wev_buf[0] = {wev_rec, wev_count, cap};
-    c->wev_buf[1] = {wev_rec + (size_t)AMC_COUNTER_BANKS * cap, wev_count + AMC_COUNTER_BANKS, cap};
-    c->stream2 = stream2; c->ev_detect = ev_detect; c->ev_stream = ev_stream;
-    c->ovl_sync_values = sync_values; c->ovl_flags = flags;
-    c->s_slab2 = slab;          // (the guard: last)
-    return AMC_OK;
-}
-
-static int run_overlapped(amc_ctx *c, double dt, int64_t nsteps)
-{
-    int rc = ensure_overlap(c);
-    if (rc) return rc;
-    if ((rc = amc_flush(c))) return rc;                 // the state is complete in the current arrays
-    const int g = c->P.geometry;
-    const bool two = c->overlap_mode == 1;
-    int cur = (c->S.x == c->S_buf[1].x) ? 1 : 0;
-    c->B_buf[cur] = c->B;                               // (the list epoch lives in the current copy)
-    c->B_buf[0].extra = c->extra_buf[0]; c->B_buf[1].extra = c->extra_buf[1];
-    unsigned int prev_epoch = 0;                        // the sweep in flight (none before the first step)
-    for (int64_t s = 0; s < nsteps; s++) {
-        int st = (g == AMC_GEOM_CUBE) ? (AMC_ST_DRIFT | AMC_ST_WALLS) : (AMC_ST_DRIFT | AMC_ST_WALLS | AMC_ST_BOUNDS);
-        if (g == AMC_GEOM_PORE && s > 0) st |= AMC_ST_BOUNDS_PRE;       // Pore:550 of the previous step
-        hipStream_t sp = two ? c->stream2 : c->stream;
-        if (two) {
-            // the pass may start once the previous sweep's detect kernel has marked its candidates' particles (and, at the
-            // first step, once everything queued before the run has finished)
-            c->ovl_tick++;
-            if (c->ovl_sync_values) {
-                AMC_HIP(c, hipStreamWriteValue32(c->stream, c->ovl_flags, c->ovl_tick, 0));
-                AMC_HIP(c, hipStreamWaitValue32(c->stream2, c->ovl_flags, c->ovl_tick, hipStreamWaitValueGte, 0xffffffffu));
-            } else {
-                AMC_HIP(c, hipEventRecord(c->ev_detect, c->stream));
-                AMC_HIP(c, hipStreamWaitEvent(c->stream2, c->ev_detect, 0));
-            }
-        }
-        if (s > 0) {
-            // (recorded above, BEHIND the detect kernel of step s - 1 and in front of its resolve kernels, which follow here)
-            AMC_HIP(c, amc_launch_resolve(c, true));
-        }
-        AMC_HIP(c, amc_launch_stream_ovl(c, dt, st, cur, prev_epoch, sp, !c->overlap_split));
-        if (c->overlap_split) AMC_HIP(c, amc_launch_bin_ovl(c, 1 - cur, prev_epoch, sp));
-        if (two) {
-            if (c->ovl_sync_values) {
-                AMC_HIP(c, hipStreamWriteValue32(c->stream2, c->ovl_flags + 16, c->ovl_tick, 0));
-                AMC_HIP(c, hipStreamWaitValue32(c->stream, c->ovl_flags + 16, c->ovl_tick, hipStreamWaitValueGte, 0xffffffffu));
-            } else {
-                AMC_HIP(c, hipEventRecord(c->ev_stream, c->stream2));
-                AMC_HIP(c, hipStreamWaitEvent(c->stream, c->ev_stream, 0));
-            }
-        }
-        AMC_HIP(c, amc_launch_fixup(c, dt, st, cur, prev_epoch));
-        c->commit_pending = false; c->lazy_pending = false;             // (consumed by the fix-up kernel)
-        cur = 1 - cur;
-        c->S = c->S_buf[cur];
-        c->B = c->B_buf[cur];
-        AMC_HIP(c, amc_launch_detect(c));
-        prev_epoch = c->sweep_epoch;
-        c->out.step++;
-        c->ovl_steps++;
-    }
-    // the last sweep: resolved, and left to the plain machinery (its commit and its results wait for the next streaming pass,
-    // a flush or a read of the counters, as after any step)
-    AMC_HIP(c, amc_launch_resolve(c, true));
-    c->lazy_pending = true;
-    c->B_buf[cur] = c->B;
-    // the current lists' extra nodes die with them (the next build starts from the particles' own nodes)
-    AMC_HIP(c, hipMemsetAsync(c->extra_count, 0, 2 * sizeof(int), c->stream));
-    AMC_HIP(c, hipMemsetAsync(c->wev_buf[0].count, 0, sizeof(unsigned int) * 2 * AMC_COUNTER_BANKS, c->stream));
-    if (g == AMC_GEOM_PORE) AMC_HIP(c, amc_launch_stream(c, dt, AMC_ST_BOUNDS, 1));     // Pore:550 of the last step
-    return AMC_OK;
-}
-
-// ---- the ordered workgroup on demand -------------------------------------------------------------------------
-// host state after a step has been enqueued: what a rewind to that step restores, and the arguments its wide kernel had
-struct amc_od_snap {
-    amc_lists B;
-    int lists_age, lists_owner;
-    unsigned int sweep_epoch;
-    bool plan_split;
-    unsigned int out_step;
-    rs_args used;
-};
-
-static int run_on_demand(amc_ctx *c, double dt, int64_t nsteps)
-{
-    const int g = c->P.geometry;
-    const int st0 = (g == AMC_GEOM_CUBE) ? (AMC_ST_DRIFT | AMC_ST_WALLS) : (AMC_ST_DRIFT | AMC_ST_WALLS | AMC_ST_BOUNDS);
-    std::vector<amc_od_snap> ring(AMC_OD_RING);
-    const int tick0 = c->od_tick;                       // step s of this run has index tick0 + s
-    int rc = AMC_OK;
-    // the answer to a stall: the ordered workgroup for the sweep that raised the word (it clears it), the host's epochs back
-    // to the state after that step; the steps after it did nothing and are enqueued again
-    auto answer = [&](int at, int64_t *s, bool stalled) -> int {
-        const amc_od_snap &R = ring[at % AMC_OD_RING];
-        c->B = R.B; c->lists_age = R.lists_age; c->lists_owner = R.lists_owner; c->sweep_epoch = R.sweep_epoch;
-        c->plan_split = R.plan_split; c->out.step = R.out_step;
-        c->commit_pending = true; c->lazy_pending = true; c->commit_defer = true;
-        AMC_HIP(c, amc_launch_ordered(c, R.used));
-        c->od_handled = at;
-        if (stalled) { c->od_stalls++; if (at == tick0 + (int)nsteps - 1) c->od_stalls_last++; }
-        *s = (int64_t)(at - tick0) + 1;
-        return AMC_OK;
-    };
-    auto stall_seen = [&]() -> int { const int v = *c->h_od_stall; return v > c->od_handled ? v : 0; };
-    c->od_active = true;
-    for (int64_t s = 0;;) {
-        if (s == nsteps) {
-            // the end of the run: only now is it known whether a sweep before the last one still waits
-            if (hipStreamSynchronize(c->stream) != hipSuccess) { rc = amc_fail(c, AMC_ERR_HIP, "hipStreamSynchronize failed in amc_run"); break; }
-            int at = stall_seen();
-            const bool stalled = at != 0;
-            // (the last sweep gets its ordered pass in any case: the run ends in the state every other entry point expects)
-            if (!at) at = tick0 + (int)nsteps - 1;
-            if ((rc = answer(at, &s, stalled))) break;
-            if (s == nsteps) break;
-            continue;
-        }
-        // not more than od_ahead steps in front of the last wide kernel that ran: a stall costs the empty launches in between
-        const int tick = tick0 + (int)s;
-        if (tick - *c->h_od_done > c->od_ahead && !stall_seen()) {
-            // (a plain read of host memory; the clock is read every 1,024 reads, and after 2 ms without a step finishing the
-            // stream is asked where it is — the wait ends with the stream's completion at the latest)
-            int last = *c->h_od_done;
-            unsigned spins = 0;
-            auto t_last = std::chrono::steady_clock::now();
-            for (;;) {
-                const int done = *c->h_od_done;
-                if (tick - done <= c->od_ahead || stall_seen()) break;
-                if (done != last) { last = done; t_last = std::chrono::steady_clock::now(); }
-                else if ((++spins & 1023u) == 0 && std::chrono::steady_clock::now() - t_last > std::chrono::milliseconds(2)) {
-                    if (hipStreamSynchronize(c->stream) != hipSuccess) rc = amc_fail(c, AMC_ERR_HIP, "hipStreamSynchronize failed in amc_run");
-                    break;
-                }
-            }
-            if (rc) break;
-        }
-        if (const int at = stall_seen()) {
-            if ((rc = answer(at, &s, true))) break;
-            continue;
-        }
-        c->od_tick = tick;
-        int st = st0;
-        if (s > 0 && g == AMC_GEOM_PORE) st |= AMC_ST_BOUNDS_PRE;       // (the previous step's post-sweep bounds check rides along)
-        hipError_t e = amc_launch_stream(c, dt, st, 0, true);
-        if (e == hipSuccess) e = amc_launch_detect(c);
-        amc_od_snap &R = ring[tick % AMC_OD_RING];
-        if (e == hipSuccess) e = amc_launch_wide_only(c, &R.used);
-        if (e != hipSuccess) { rc = amc_fail(c, AMC_ERR_HIP, "launch failed in amc_run: %s", hipGetErrorString(e)); break; }
-        c->lazy_pending = true;
-        c->out.step++;
-        R.B = c->B; R.lists_age = c->lists_age; R.lists_owner = c->lists_owner; R.sweep_epoch = c->sweep_epoch;
-        R.plan_split = c->plan_split; R.out_step = c->out.step;
-        s++;
-    }
-    c->od_active = false;
-    c->od_tick = tick0 + (int)nsteps;
-    if (rc) return rc;
-    if (g == AMC_GEOM_PORE) AMC_HIP(c, amc_launch_stream(c, dt, AMC_ST_BOUNDS, 1));     // Pore:550 of the last step
-    return AMC_OK;
-}
-
-int amc_run(amc_ctx *c, double dt, int64_t nsteps, amc_step_stats *sum)
-{
-    if (!c) return AMC_ERR_INVALID;
-    if (!c->uploaded) return amc_fail(c, AMC_ERR_STATE, "amc_run before amc_upload");
-    AMC_HIP(c, hipSetDevice(c->device));
-    const bool whole = c->lo == 0 && c->hi == c->n && !c->allpairs;
-    // (sampled fields with a cadence: the plain loop, whose steps end with the state a sample reads)
-    const bool sampling = c->F.on && c->F.g.every > 0;
-    if (c->overlap_mode && whole && nsteps >= 2 && !c->keep_prior && !c->detect_ap && c->n > 0 && !sampling &&
-        (c->P.geometry == AMC_GEOM_CUBE || c->P.geometry == AMC_GEOM_PORE)) {
-        int rc = run_overlapped(c, dt, nsteps);
-        if (rc) return rc;
-        return amc_finish_stats(c, sum);
-    }
-    // inside the run only the last step needs its own post-sweep bounds pass (needs the whole range in one context) — and
-    // every step that is sampled: the sample sees the step's final state
-    if (!c->ordered_always && whole && nsteps >= AMC_OD_MIN_STEPS && nsteps < (1 << 30) && !c->F.on && !c->keep_prior && !c->detect_ap &&
-        !c->d_dbg && c->n > 0 && c->n <= c->od_max_n && c->h_od_stall && c->od_tick < (1 << 30) &&
-        (c->P.geometry == AMC_GEOM_CUBE || c->P.geometry == AMC_GEOM_PORE)) {
-        int rc = run_on_demand(c, dt, nsteps);
-        if (rc) return rc;
-        return amc_finish_stats(c, sum);
-    }
-    const bool fold = c->P.geometry == AMC_GEOM_PORE && whole;
-    bool deferred = false;
-    for (int64_t s = 0; s < nsteps; s++) {
-        const bool defer = fold && s + 1 < nsteps && !amc_fields_due(c, (int64_t)c->out.step + 1);
-        int rc = enqueue_step(c, dt, deferred, defer);
-        if (rc) return rc;
-        deferred = defer;
-    }
-    return amc_finish_stats(c, sum);
-}
-
-int amc_stage_drift(amc_ctx *c, double dt)
-{
-    if (!c || !c->uploaded) return AMC_ERR_STATE;
-    AMC_HIP(c, hipSetDevice(c->device));
-    { int rc_ = amc_flush(c); if (rc_) return rc_; }
-    const bool kp = c->keep_prior;
-    c->keep_prior = true;       // a following amc_stage_walls needs prior_*_vals
-    hipError_t e = amc_launch_stream(c, dt, AMC_ST_DRIFT, 0);
-    c->keep_prior = kp;
-    AMC_HIP(c, e);
-    AMC_HIP(c, hipStreamSynchronize(c->stream));
-    return AMC_OK;
-}
-
-int amc_stage_walls(amc_ctx *c, amc_step_stats *out)
-{
-    if (!c || !c->uploaded) return AMC_ERR_STATE;
-    AMC_HIP(c, hipSetDevice(c->device));
-    { int rc_ = amc_flush(c); if (rc_) return rc_; }
-    AMC_HIP(c, amc_launch_stream(c, 0.0, AMC_ST_WALLS, 0));
-    return amc_finish_stats(c, out);
-}
-
-int amc_stage_bounds(amc_ctx *c, int64_t *n_moved)
-{
-    if (!c || !c->uploaded) return AMC_ERR_STATE;
-    AMC_HIP(c, hipSetDevice(c->device));
-    { int rc_ = amc_flush(c); if (rc_) return rc_; }
-    AMC_HIP(c, amc_launch_stream(c, 0.0, AMC_ST_BOUNDS, 0));
-    amc_step_stats st;
-    int rc = amc_finish_stats(c, &st);
-    if (n_moved) *n_moved = st.n_oob_walls;
-    return rc;
-}
-
-int amc_stage_sweep(amc_ctx *c, amc_step_stats *out)
-{
-    if (!c || !c->uploaded) return AMC_ERR_STATE;
-    AMC_HIP(c, hipSetDevice(c->device));
-    { int rc_ = amc_flush(c); if (rc_) return rc_; }
-    int rc = amc_enqueue_sweep(c);
-    if (rc) return rc;
-    return amc_finish_stats(c, out);
 }
 
 // ---- outputs ----------------------------------------------------------------------------------------------------------

@@ -21,8 +21,7 @@ int amc_mg_local(amc_ctx *c, double dt)
     if (c->allpairs || c->P.geometry == AMC_GEOM_CELL || c->P.geometry == AMC_GEOM_PORE_ENERGISED)
         return amc_fail(c, AMC_ERR_INVALID, "amc_mg_local needs the binned detector and the cube / specular pore geometry (energised walls: amc_temp_begin)");
     AMC_HIP(c, hipSetDevice(c->device));
-    const int st = (c->P.geometry == AMC_GEOM_CUBE) ? (AMC_ST_DRIFT | AMC_ST_WALLS) : (AMC_ST_DRIFT | AMC_ST_WALLS | AMC_ST_BOUNDS);
-    AMC_HIP(c, amc_launch_stream(c, dt, st, 0));
+    AMC_HIP(c, amc_launch_stream(c, dt, amc_step_stages(c->P.geometry), 0));
     return AMC_OK;
 }
 
@@ -66,7 +65,7 @@ int amc_mg_exchange_view(amc_ctx *c, int world, void **send, void **recv, int64_
         c->kin_send = ksend; c->kin_recv = krecv; c->mg_wave_count = wave_count;
         c->kin_m = m; c->kin_cap = cap; c->kin_block = blk;
         c->kin_counts_clear = false;
-        c->lists_age = -1;
+        c->step.lists_age = -1;
         if (grow) {
             ctx_free(c, c->B.rec, c->B.extra);
             c->B.rec = rec; c->B.extra = extra; c->keep_pool = pool;
@@ -174,7 +173,7 @@ int amc_mg_resolve(amc_ctx *c, int world)
     AMC_HIP(c, hipSetDevice(c->device));
     AMC_HIP(c, amc_launch_ingest(c, world));
     AMC_HIP(c, amc_launch_resolve(c, true));
-    c->lazy_pending = true;
+    c->step.lazy_pending = true;
     return AMC_OK;
 }
 

@@ -148,14 +148,7 @@ hipError_t amc_launch_kin_pack(amc_ctx *c, int world, int rank, int unpack)
     Bm.wave_count = c->mg_wave_count;       // (kept lists: the exchange kernels' own pools)
     if (!unpack) {
         // a new set of lists — this shard now, the other shards at the unpack — or, with kept lists (pore), a step of a cycle
-        if (c->mg_keep) {
-            if (c->lists_owner != 2) c->lists_age = -1;
-            c->lists_owner = 2;
-            if (c->lists_age < 0 || c->lists_age + 1 >= c->keep_K) { c->kin_mode = 2; c->B.epoch++; c->lists_age = 0; }
-            else { c->kin_mode = 3; c->lists_age++; }
-        } else {
-            c->kin_mode = 1; c->lists_age = -1; c->B.epoch++;
-        }
+        c->kin_mode = amc_list_build_mode(c, 2, c->mg_keep);
         Bm = c->B;
         Bm.wave_count = c->mg_wave_count;
         c->kin_lists = true;

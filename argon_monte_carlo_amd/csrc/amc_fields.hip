@@ -164,7 +164,7 @@ static int fields_enqueue(amc_ctx *c)
     blocks = std::min(blocks, F.max_blocks);
     amc_lazy L;
     memset(&L, 0, sizeof L);
-    if (c->lazy_pending) { L.slot_of = c->W.slot_of; L.state = c->W.sl_state; L.moved = c->W.sl_moved; L.enabled = 1; }
+    if (c->step.lazy_pending) { L.slot_of = c->W.slot_of; L.state = c->W.sl_state; L.moved = c->W.sl_moved; L.enabled = 1; }
     amc_fields_grid_dev G;
     G.kind = F.g.kind; G.n1 = F.g.n1; G.n2 = F.g.n2; G.n3 = F.g.n3; G.bins = F.bins;
     for (int k = 0; k < 3; k++) { G.lo[k] = F.g.lo[k]; G.hi[k] = F.g.hi[k]; G.w[k] = F.w[k]; }

@@ -336,7 +336,7 @@ hipError_t amc_launch_bin(amc_ctx *c)
     if (c->allpairs || c->n <= 0) return hipSuccess;
     const long long n = c->n;
     c->B.epoch++;
-    c->lists_age = -1;          // (kept lists: these are not the streaming pass's own)
+    c->step.lists_age = -1;          // (kept lists: these are not the streaming pass's own)
     amc_prof_begin(c, AMC_K_BIN_COUNT);
     amc_ovl V;
     V.adj_head = nullptr; V.skip_epoch = 0;
@@ -424,19 +424,25 @@ __global__ __launch_bounds__(AP2_THREADS) void k_detect_allpairs_tiled(const dou
     }
 }
 
+// a new sweep: its tag in the candidate graph's heads (0 is the value of the zero-initialised table)
+static unsigned int next_sweep_epoch(unsigned int epoch)
+{
+    epoch = (epoch + 1u) & 0x3fffffffu;
+    return epoch ? epoch : 1u;
+}
+
 hipError_t amc_launch_detect(amc_ctx *c)
 {
     const long long n = c->n;
     if (n <= 0) return hipSuccess;
     const double cr2i = c->allpairs || c->detect_ap ? c->P.collision_range * c->P.collision_range * AMC_CR2_INFLATE : c->G.cr2_probe;
     amc_adj D;
-    c->sweep_epoch = (c->sweep_epoch + 1u) & 0x3fffffffu;
-    if (c->sweep_epoch == 0u) c->sweep_epoch = 1u;      // (0 is the value of the zero-initialised table)
+    c->step.sweep_epoch = next_sweep_epoch(c->step.sweep_epoch);
     // launch plan of this sweep from the candidate count of the most recent sweep the host has seen (a word the resolve
     // kernel writes into host-mapped memory; it may lag by a step): a small sweep is committed by the ordered
     // workgroup itself, a large one by the wide commit kernel
-    c->plan_split = !c->allpairs && !(c->h_host_ncand && *c->h_host_ncand <= c->plan_small);
-    D.head = c->allpairs ? nullptr : c->W.adj_head; D.rec = c->W.cand4; D.sd = c->W.cand_s; D.epoch = c->sweep_epoch;
+    c->step.plan_split = !c->allpairs && !(c->h_host_ncand && *c->h_host_ncand <= c->plan_small);
+    D.head = c->allpairs ? nullptr : c->W.adj_head; D.rec = c->W.cand4; D.sd = c->W.cand_s; D.epoch = c->step.sweep_epoch;
     D.sl_meta = c->W.sl_meta; D.sl_hits = c->W.sl_hits; D.ev_gen = c->W.ev_gen; D.mark = c->W.cand_mark;
     amc_prof_begin(c, AMC_K_DETECT);
     if (c->detect_ap) {
@@ -466,7 +472,7 @@ hipError_t amc_launch_detect(amc_ctx *c)
         AMC_LAUNCH(c, k_detect_lists, dim3((unsigned)((n + bs - 1) / bs) + (extras ? 4u : 0u)), dim3(bs), c->G, c->B, n, cr2i,
                    c->G.cr_probe, c->W.max_cand, c->d_cnt, D, (const int *)(extras ? c->extra_count + slot : nullptr),
                    c->max_extra, (const int *)(c->od_active ? c->d_od : nullptr), c->od_tick,
-                   (c->od_active && !c->od_prev_ordered) ? c->W.wctl : nullptr);
+                   (c->od_active && !c->step.od_prev_ordered) ? c->W.wctl : nullptr);
     }
     amc_prof_end(c);
     return hipGetLastError();
@@ -487,10 +493,9 @@ hipError_t amc_launch_detect_own(amc_ctx *c)
 hipError_t amc_launch_ingest(amc_ctx *c, int world)
 {
     amc_adj D;
-    c->sweep_epoch = (c->sweep_epoch + 1u) & 0x3fffffffu;
-    if (c->sweep_epoch == 0u) c->sweep_epoch = 1u;
-    c->plan_split = !(c->h_host_ncand && *c->h_host_ncand <= c->plan_small);
-    D.head = c->W.adj_head; D.rec = c->W.cand4; D.sd = c->W.cand_s; D.epoch = c->sweep_epoch;
+    c->step.sweep_epoch = next_sweep_epoch(c->step.sweep_epoch);
+    c->step.plan_split = !(c->h_host_ncand && *c->h_host_ncand <= c->plan_small);
+    D.head = c->W.adj_head; D.rec = c->W.cand4; D.sd = c->W.cand_s; D.epoch = c->step.sweep_epoch;
     D.sl_meta = c->W.sl_meta; D.sl_hits = c->W.sl_hits; D.ev_gen = c->W.ev_gen; D.mark = c->W.cand_mark;
     amc_prof_begin(c, AMC_K_DETECT);
     AMC_LAUNCH(c, k_ingest_candidates, dim3(16), dim3(256), (const int *)c->cand_recv, world, 2 + 2 * c->cand_cap, c->cand_cap,

@@ -1,5 +1,5 @@
-// amc_host.h — host-side helpers shared by the C ABI translation units (amc_api*.hip): device allocation, the pinned
-// staging of small read-backs, counters / per-step statistics, the deferred commit and the sweep driver.
+// amc_host.h — host-side helpers shared by the C ABI translation units (amc_api*.hip, amc_run.hip): device allocation, the
+// pinned staging of small read-backs, counters / per-step statistics, the deferred commit and the sweep driver.
 #pragma once
 #include <math.h>
 #include <stdarg.h>
@@ -90,7 +90,7 @@ struct amc_stage {
     }
 };
 
-// (defined in amc_api.hip inside its extern "C" block; internal to the library, not part of the ABI)
+// (defined inside the extern "C" block of amc_run.hip — amc_publish_velocities: amc_api.hip; internal to the library, not part of the ABI)
 #define AMC_INTERNAL extern "C" __attribute__((visibility("hidden")))
 AMC_INTERNAL int amc_read_counters(amc_ctx *c, amc_dev_counters *h);    // device counters with the banks folded in (synchronises)
 AMC_INTERNAL int amc_finish_stats(amc_ctx *c, amc_step_stats *out);     // per-step deltas + error flags

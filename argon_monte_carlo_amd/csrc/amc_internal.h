@@ -235,6 +235,19 @@ struct amc_res { void *p; amc_res_kind kind; };
 #define AMC_PLAN_SMALL 430      // default of amc_ctx::plan_small: measured crossover of the two launch plans (tools/plan_sweep.sh;
                                 // experiments: environment variable AMC_PLAN_SMALL)
 
+// What the launchers change as they enqueue a step: everything a rewind of amc_run's on-demand loop has to put back (it keeps
+// a copy per step, together with c->B and c->out.step).  A new per-step member of the host's goes HERE.
+struct amc_step_state {
+    bool lazy_pending;             // sweep results wait in the slot arrays for the next streaming pass (or amc_flush)
+    bool commit_pending;           // the last sweep's commit (paths -> histograms, counters, overlay) waits for the next streaming pass (or amc_flush)
+    bool commit_defer;             // ... and that sweep's results stay in the slot arrays
+    unsigned int sweep_epoch;      // tag of the degree counts of the current sweep (advanced by every detect launch)
+    bool plan_split;               // launch plan of the current sweep, fixed when its detect kernel is launched
+    int lists_age = -1;            // steps since the last full build of a kept cycle (-1: the lists are not a kept cycle's)
+    int lists_owner;               // who runs the cycle: 1 the streaming pass, 2 the multi-GPU exchange kernels (their node pools differ)
+    bool od_prev_ordered = true;   // the last sweep had its ordered pass: W.ctl holds its counts (else the wide kernel's words do)
+};
+
 // Created by amc_create with value-initialisation: every member without an initialiser below starts at zero.
 struct amc_ctx {
     amc_params P;
@@ -244,36 +257,28 @@ struct amc_ctx {
     int64_t n, lo, hi;
     bool uploaded;
     bool keep_prior;
+    std::vector<amc_res> owned;    // everything allocated for the context, in order (amc_host.h); amc_destroy frees it
+    amc_step_state step;
+    // particle state, detection grid, per-cell lists
     amc_state S;              // the CURRENT state arrays (one of S_buf's two sets)
-    amc_state S_buf[2];       // [1] is allocated by the first overlapped run: its streaming pass writes the buffer the sweep in
-    char *s_slab2;            // flight does not read
+    char *s_slab;             // the one allocation the particle state arrays are carved from
     amc_grid G;
     std::vector<int> h_lay_lo, h_lay_n, h_lay_off;
     int *d_lay;               // device copy of the three layer tables, contiguous
     amc_lists B;              // the CURRENT per-cell lists (one of B_buf's two)
-    amc_lists B_buf[2];
-    int *extra_buf[2];        // node -> particle of the extra nodes of each list buffer, and how many were handed out
-    int *extra_count;         // [2]
-    int max_extra;
-    amc_wev wev_buf[2];       // deferred events of the overlapped streaming pass, by step parity
-    hipStream_t stream2;      // the overlapped streaming pass runs here
-    hipEvent_t ev_detect, ev_stream;
-    unsigned int *ovl_flags;  // two words (64 bytes apart) the streams of an overlapped run signal each other through
-    unsigned int ovl_tick;    // (AMC_OVERLAP_SYNC=value: hipStreamWriteValue32 / hipStreamWaitValue32 instead of event record + wait —
-    int ovl_sync_values;      // ~2 us per dependency instead of ~8, tools/ubench_xstream.hip, but the resolve suffers more: DESIGN 4.2)
-    int64_t ovl_steps;        // steps run overlapped so far
+    int max_extra;            // list nodes behind the particles' own that an overlapped run's fix-up kernel may hand out
     int keep_K;               // kept lists: a full build every keep_K steps (< 2: every step, the lists are not kept)
-    int lists_age = -1;       // steps since the last full build of a kept cycle (-1: the lists are not a kept cycle's)
-    int lists_owner;          // who runs the cycle: 1 the streaming pass, 2 the multi-GPU exchange kernels (their node pools differ)
-    int overlap_mode;         // AMC_OVERLAP: 0 off (default), 1 two streams, 2 the same kernels in order on one stream (debug)
+    size_t keep_pool;         // nodes behind the particles' own in B.rec / entries of B.extra
+    bool allpairs;            // no detection grid at all (single cells, N <= 4096): all-pairs detector, brute-force validation
+    bool detect_ap;           // candidates come from the LDS-tiled all-pairs kernel (always without a grid; with one when detect_mode == 2)
+    // the sweep
     amc_resolve_ws W;
     char *w_slab;             // the one allocation W's arrays are carved from
-    char *s_slab;             // the one allocation the particle state arrays are carved from
+    volatile int *h_host_ncand;    // host-mapped word written by k_resolve (candidate count of the last sweep)
+    int *d_host_ncand;             // its device address
     amc_temp_ws T;
     amc_temp_dev_ws TD;
     amc_fields_ws F;
-    bool allpairs;            // no detection grid at all (single cells, N <= 4096): all-pairs detector, brute-force validation
-    bool detect_ap;           // candidates come from the LDS-tiled all-pairs kernel (always without a grid; with one when detect_mode == 2)
     // outputs
     amc_out out;
     amc_path_record *d_rec;
@@ -283,12 +288,25 @@ struct amc_ctx {
     amc_counter_bank *d_banks;   // banked per-event counters, folded into the copy read_counters() returns
     amc_dev_counters h_prev;  // snapshot used to report per-step deltas
     long long *d_dbg;         // resolve phase timers (diagnostic, enabled by AMC_DEBUG_RESOLVE=1)
-    int cw_blocks_env;        // AMC_CW_BLOCKS at creation (0 = default number of wide-kernel waves)
-    int stream_bs;            // AMC_STREAM_BS at creation: block size of the streaming pass (the kept-list pools are sized for it)
-    int detect_bs;            // AMC_DETECT_BS at creation: block size of the list-based detect kernel
-    bool temp_unfused;        // AMC_TEMP_UNFUSED set at creation: the device-RNG energised mode runs one kernel triple per case
+    // pinned host staging for the small per-step read-backs (a copy into pageable memory costs ~100 us on this stack)
+    char *h_pin;
+    size_t h_pin_bytes;
+    // environment switches, read once by amc_create (amc_api.hip)
+    int overlap_mode;         // AMC_OVERLAP: 0 off (default), 1 two streams, 2 the same kernels in order on one stream (debug)
+    bool overlap_split;       // AMC_OVERLAP_SPLIT != 0: an overlapped run builds its lists in a kernel of its own
+    int cw_blocks_env;        // AMC_CW_BLOCKS (0 = default number of wide-kernel waves)
+    int stream_bs;            // AMC_STREAM_BS: block size of the streaming pass (the kept-list pools are sized for it)
+    int detect_bs;            // AMC_DETECT_BS: block size of the list-based detect kernel
+    bool temp_unfused;        // AMC_TEMP_UNFUSED set: the device-RNG energised mode runs one kernel triple per case
     bool temp_run_unfused;    // amc_temp_run_device enqueues the three streaming passes of a single step (AMC_TEMP_RUN_UNFUSED / _FUSED)
-    bool overlap_split;       // AMC_OVERLAP_SPLIT != 0 at creation: an overlapped run builds its lists in a kernel of its own
+    bool ordered_always;      // AMC_ORDERED_ALWAYS != 0: k_resolve<GEOM,0> in every sweep, as amc_timestep does
+    int64_t od_max_n = AMC_OD_MAX_N;   // AMC_OD_MAX_N: particle counts above this keep the ordered workgroup in every sweep
+    int od_ahead = AMC_OD_AHEAD;   // AMC_OD_AHEAD: steps amc_run may be ahead of the last step the GPU has started to resolve
+    int plan_small = AMC_PLAN_SMALL;   // AMC_PLAN_SMALL: candidate pairs up to which the single resolve kernel does the whole sweep
+    long long allpairs_max_n; // AMC_ALLPAIRS_MAX_N: cube / pore contexts up to this size run without the detection grid (0: none)
+    int list_keep;            // AMC_LIST_KEEP, else the geometry's default: the kept-list cycle asked for (amc_create caps it: keep_K)
+    int max_hist_env;         // AMC_MAX_HIST (diagnostic): history entries a sweep may use (0: all that are allocated)
+    bool debug_resolve;       // AMC_DEBUG_RESOLVE set: d_dbg is allocated
     // profiling
     bool profiling;
     double k_ms[AMC_K_COUNT];
@@ -298,52 +316,48 @@ struct amc_ctx {
     size_t ev_used;
     hipEvent_t prof_ev0, prof_ev1;  // the open bracket's events (nullptr outside a bracket / when not profiling): AMC_LAUNCH
                                     // attaches them to the dispatch itself
-    // multi-GPU
+    // the overlapped run (amc_run.hip)
+    amc_state S_buf[2];       // [1] is allocated by the first overlapped run: its streaming pass writes the buffer the sweep in
+    char *s_slab2;            // flight does not read
+    amc_lists B_buf[2];
+    int *extra_buf[2];        // node -> particle of the extra nodes of each list buffer, and how many were handed out
+    int *extra_count;         // [2]
+    amc_wev wev_buf[2];       // deferred events of the overlapped streaming pass, by step parity
+    hipStream_t stream2;      // the overlapped streaming pass runs here
+    hipEvent_t ev_detect, ev_stream;
+    unsigned int *ovl_flags;  // two words (64 bytes apart) the streams of an overlapped run signal each other through
+    unsigned int ovl_tick;    // (AMC_OVERLAP_SYNC=value: hipStreamWriteValue32 / hipStreamWaitValue32 instead of event record + wait —
+    int ovl_sync_values;      // ~2 us per dependency instead of ~8, tools/ubench_xstream.hip, but the resolve suffers more: DESIGN 4.2)
+    int64_t ovl_steps;        // steps run overlapped so far
+    // The ordered workgroup on demand (amc_run.hip): steps are enqueued without k_resolve<GEOM,0>; a
+    // sweep that needs it sets the sticky device word `stalled_at` to its step index, every kernel of a later step then leaves
+    // without a side effect, and the host — which watches the host-mapped mirror — launches the workgroup for that sweep and
+    // enqueues the later steps again.
+    int *d_od;                     // [0] stalled_at (0: none)
+    volatile int *h_od_stall, *h_od_done;   // host-mapped: mirror of stalled_at, step index of the last wide kernel that ran
+    int *d_od_stall_host, *d_od_done_host;  // their device addresses
+    bool od_active;                // the launchers pass the word and the step index (inside amc_run's on-demand loop only)
+    int od_tick = 1;               // step index of the step being enqueued (never 0, grows across runs)
+    int od_handled;                // the last stall the host has answered
+    int64_t od_ordered_launches;   // launches of k_resolve<GEOM,0> so far
+    int64_t od_steps;              // steps enqueued without it
+    int64_t od_stalls, od_stalls_last;   // stalls the host has answered; those raised by the last step of their run
+    // multi-GPU (amc_api_mg.hip, amc_exchange.hip)
     bool mg_count_pp = true;       // this rank adds the p-p collision count to its counters
-    volatile int *h_host_ncand;    // host-mapped word written by k_resolve (candidate count of the last sweep)
-    int *d_host_ncand;             // its device address
-    bool lazy_pending;             // sweep results wait in the slot arrays for the next streaming pass (or amc_flush)
-    bool commit_pending;           // the last sweep's commit (paths -> histograms, counters, overlay) waits for the next streaming pass (or amc_flush)
-    bool commit_defer;             // ... and that sweep's results stay in the slot arrays
-    unsigned int sweep_epoch;      // tag of the degree counts of the current sweep (advanced by every detect launch)
-    bool plan_split;               // launch plan of the current sweep, fixed when its detect kernel is launched
-    int plan_small = AMC_PLAN_SMALL;   // candidate pairs up to which the single resolve kernel does the whole sweep
-    // pinned host staging for the small per-step read-backs (a copy into pageable memory costs ~100 us on this stack)
-    char *h_pin;
-    size_t h_pin_bytes;
     double *kin_send, *kin_recv;   // per-step exchange (amc_exchange.hip): one block of kin_block doubles, and world of them
     double *kin_vpub;              // [3][n] velocities as last published to the other ranks (allocated by amc_set_shard;
                                    // every upload publishes: all ranks upload the same full state)
     int kin_world;
     int64_t kin_m, kin_cap, kin_block;   // shard length (padded), capacity of the velocity-change list (all banks), 3m + banks + 4cap
-    int *cand_send, *cand_recv;    // multi-GPU, detection sharded by index: this rank's candidate block ([0] count, [2 + 2k] pairs)
+    int *cand_send, *cand_recv;    // detection sharded by index: this rank's candidate block ([0] count, [2 + 2k] pairs)
     int cand_cap, cand_world;      // and the blocks of all ranks (the second all-gather of a step); pairs per block
     // kept lists in the exchange kernels (pore, amc_lists): pools per wave of the pack and of the unpack kernel
     int *mg_wave_count;            // [mg_waves_pack + mg_waves_unpack]
     int mg_waves_pack, mg_waves_unpack;
     bool mg_keep;                  // the pools exist for the current world size
     int kin_mode = 1;              // this step's list build: 1 anew, 2 full build of a kept cycle, 3 a step in between
-    size_t keep_pool;              // nodes behind the particles' own in B.rec / entries of B.extra
     bool kin_lists;                // amc_mg_pack started this step's per-cell lists (the unpack completes them)
     bool kin_counts_clear;         // the bank counters in kin_send are zero (cleared by the last unpack kernel)
-    // The ordered workgroup on demand (amc_run's plain loop): steps are enqueued without k_resolve<GEOM,0>; a
-    // sweep that needs it sets the sticky device word `stalled_at` to its step index, every kernel of a later step then leaves
-    // without a side effect, and the host — which watches the host-mapped mirror — launches the workgroup for that sweep and
-    // enqueues the later steps again.
-    bool ordered_always;           // AMC_ORDERED_ALWAYS=1 at creation: k_resolve<GEOM,0> in every sweep, as amc_timestep does
-    int64_t od_max_n = AMC_OD_MAX_N;   // particle counts above this keep the ordered workgroup in every sweep
-    int od_ahead = AMC_OD_AHEAD;   // steps amc_run may be ahead of the last step the GPU has started to resolve
-    int *d_od;                     // [0] stalled_at (0: none)
-    volatile int *h_od_stall, *h_od_done;   // host-mapped: mirror of stalled_at, step index of the last wide kernel that ran
-    int *d_od_stall_host, *d_od_done_host;  // their device addresses
-    bool od_active;                // the launchers pass the word and the step index (inside amc_run's on-demand loop only)
-    bool od_prev_ordered = true;   // the last sweep had its ordered pass: W.ctl holds its counts (else the wide kernel's words do)
-    int od_tick = 1;               // step index of the step being enqueued (never 0, grows across runs)
-    int od_handled;                // the last stall the host has answered
-    int64_t od_ordered_launches;   // launches of k_resolve<GEOM,0> so far
-    int64_t od_steps;              // steps enqueued without it
-    int64_t od_stalls, od_stalls_last;   // stalls the host has answered; those raised by the last step of their run
-    std::vector<amc_res> owned;    // everything allocated for the context, in order (amc_host.h); amc_destroy frees it
 };
 
 int amc_fail(amc_ctx *c, int code, const char *fmt, ...);
@@ -378,6 +392,12 @@ void amc_prof_collect(amc_ctx *c);
 #define AMC_ST_BOUNDS_PRE 8     // the PREVIOUS step's bounds check after its sweep (Pore:550), folded into this pass
 #define AMC_TEMP_RUN_FUSED_DEFAULT 1   // amc_temp_run_device: one fused streaming pass per step unless AMC_TEMP_RUN_UNFUSED=1
 #define AMC_ST_TEMP_CASES 16    // energised pore, device-RNG mode: cases 3-9 (Temp:705-758) between the walls and the bounds check
+// the stages of a cube / specular-pore step's streaming pass; prev_bounds: the previous step's post-sweep bounds check rides along
+static inline int amc_step_stages(int geometry, bool prev_bounds = false)
+{
+    if (geometry == AMC_GEOM_CUBE) return AMC_ST_DRIFT | AMC_ST_WALLS;
+    return AMC_ST_DRIFT | AMC_ST_WALLS | AMC_ST_BOUNDS | (prev_bounds && geometry == AMC_GEOM_PORE ? AMC_ST_BOUNDS_PRE : 0);
+}
 
 // launchers (each enqueues on c->stream; returns hipError_t of the launch)
 hipError_t amc_launch_stream(amc_ctx *c, double dt, int stages, int bounds_slot, bool fuse_bin = false);
@@ -388,6 +408,7 @@ hipError_t amc_launch_stream_ovl(amc_ctx *c, double dt, int stages, int from, un
                                  bool build_lists = true);
 hipError_t amc_launch_fixup(amc_ctx *c, double dt, int stages, int from, unsigned int sweep_epoch);
 hipError_t amc_launch_bin_ovl(amc_ctx *c, int to, unsigned int skip_epoch, hipStream_t stream);
+int amc_list_build_mode(amc_ctx *c, int owner, bool kept);     // this step's list build for `owner`: 1 anew, 2 / 3 kept cycle (amc_stream.hip)
 hipError_t amc_launch_bin(amc_ctx *c);                 // stand-alone list build over all n particles (stages, multi-GPU)
 hipError_t amc_launch_detect(amc_ctx *c);              // binned or all-pairs, fills W.cand_* / counters.cand_count
 hipError_t amc_launch_detect_own(amc_ctx *c);          // multi-GPU: own index range against everybody, into the candidate block

@@ -573,6 +573,15 @@ __global__ __launch_bounds__(256) void k_commit(rs_args A)
     amc_commit_part(C, A.O, A.G, A.S, gtid, gstride);
 }
 
+// candidates per wave of the wide kernel from the lagging host count (with head room; more candidates = more passes)
+static int rs_wide_per(amc_ctx *c)
+{
+    const long long lag = c->h_host_ncand ? *c->h_host_ncand : 0;
+    const long long nb = amc_clusters_wide_blocks(c);
+    const long long per = (lag + lag / 4 + nb - 1) / nb;
+    return (int)std::min<long long>(std::max<long long>(per, 1), 64);
+}
+
 template <int GEOM>
 static void rs_launch_all(amc_ctx *c, const rs_args &A)
 {
@@ -587,13 +596,7 @@ static void rs_launch_all(amc_ctx *c, const rs_args &A)
     rs_args Aw = A;
     Aw.wide_plan = 1;
     Aw.force_mono = 0;
-    {
-        // candidates per wave of the wide kernel from the lagging count (with head room; more candidates = more passes)
-        const long long lag = c->h_host_ncand ? *c->h_host_ncand : 0;
-        const long long nb = amc_clusters_wide_blocks(c);
-        long long per = (lag + lag / 4 + nb - 1) / nb;
-        Aw.wide_per = (int)std::min<long long>(std::max<long long>(per, 1), 64);
-    }
+    Aw.wide_per = rs_wide_per(c);
     amc_prof_cancel(c);                 // (the caller's bracket is re-opened below, around the kernel it is named after)
     amc_prof_begin(c, AMC_K_CLUSTERS_WIDE);
     amc_launch_clusters_wide(c, Aw);
@@ -601,10 +604,10 @@ static void rs_launch_all(amc_ctx *c, const rs_args &A)
     amc_prof_begin(c, AMC_K_RESOLVE);
     AMC_LAUNCH(c, (k_resolve<GEOM, 0>), dim3(1), dim3(RS_T), Aw);
     c->od_ordered_launches++;
-    c->od_prev_ordered = true;
+    c->step.od_prev_ordered = true;
     // the commit: deferred results -> it waits for the next streaming pass (or amc_flush); else a kernel of its own, now
-    c->commit_defer = A.defer_commit != 0;
-    if (A.defer_commit) { c->commit_pending = true; return; }
+    c->step.commit_defer = A.defer_commit != 0;
+    if (A.defer_commit) { c->step.commit_pending = true; return; }
     amc_prof_end(c);
     amc_prof_begin(c, AMC_K_COMMIT);
     AMC_LAUNCH(c, k_commit, dim3(AMC_COMMIT_BLOCKS), dim3(256), Aw);
@@ -623,7 +626,7 @@ static rs_args rs_make_args(amc_ctx *c)
     A.plan_small = c->plan_small;
     A.defer_commit = 0;
     A.apply_only = 0;
-    A.sweep_epoch = c->sweep_epoch;
+    A.sweep_epoch = c->step.sweep_epoch;
     A.wide_plan = 0;
     A.count_pp = c->mg_count_pp ? 1 : 0;
     A.lo = c->lo; A.hi = c->hi;
@@ -641,20 +644,15 @@ hipError_t amc_launch_wide_only(amc_ctx *c, rs_args *used)
     rs_args Aw = rs_make_args(c);
     Aw.defer_commit = 1;
     Aw.wide_plan = 1;
-    {
-        const long long lag = c->h_host_ncand ? *c->h_host_ncand : 0;
-        const long long nb = amc_clusters_wide_blocks(c);
-        long long per = (lag + lag / 4 + nb - 1) / nb;
-        Aw.wide_per = (int)std::min<long long>(std::max<long long>(per, 1), 64);
-    }
+    Aw.wide_per = rs_wide_per(c);
     Aw.W.raise_dev = c->d_od; Aw.W.raise_host = c->d_od_stall_host; Aw.W.raise_tick = c->od_tick;
     Aw.od_stall = c->d_od; Aw.od_stall_host = c->d_od_stall_host; Aw.od_done = c->d_od_done_host; Aw.od_tick = c->od_tick;
     amc_prof_begin(c, AMC_K_CLUSTERS_WIDE);
     amc_launch_clusters_wide(c, Aw);
     amc_prof_end(c);
-    c->commit_defer = true;
-    c->commit_pending = true;
-    c->od_prev_ordered = false;
+    c->step.commit_defer = true;
+    c->step.commit_pending = true;
+    c->step.od_prev_ordered = false;
     c->od_steps++;
     *used = Aw;
     return hipGetLastError();
@@ -670,14 +668,14 @@ hipError_t amc_launch_ordered(amc_ctx *c, const rs_args &used)
     else AMC_LAUNCH(c, (k_resolve<AMC_GEOM_PORE, 0>), dim3(1), dim3(RS_T), Aw);
     amc_prof_end(c);
     c->od_ordered_launches++;
-    c->od_prev_ordered = true;
+    c->step.od_prev_ordered = true;
     return hipGetLastError();
 }
 
 hipError_t amc_launch_commit(amc_ctx *c)
 {
     rs_args A = rs_make_args(c);
-    A.defer_commit = c->commit_defer ? 1 : 0;
+    A.defer_commit = c->step.commit_defer ? 1 : 0;
     amc_prof_begin(c, AMC_K_COMMIT);
     AMC_LAUNCH(c, k_commit, dim3(AMC_COMMIT_BLOCKS), dim3(256), A);
     amc_prof_end(c);

@@ -342,45 +342,67 @@ amc_commit_args amc_make_commit_args(amc_ctx *c)
     C.ctl = (amc_resolve_ctl *)W.ctl; C.hist = W.hist; C.ov_head = W.ov_head; C.ev_gen = W.ev_gen; C.ev = W.ev;
     C.sl_meta = W.sl_meta; C.sl_hits = W.sl_hits; C.sl_moved = W.sl_moved; C.sl_state = W.sl_state; C.slot_of = W.slot_of;
     C.max_slots = W.max_slots; C.max_hist = W.max_hist; C.lo = c->lo; C.hi = c->hi; C.count_pp = c->mg_count_pp ? 1 : 0;
-    C.defer = c->commit_defer ? 1 : 0; C.nogrid = c->allpairs ? 1 : 0; C.enabled = 0;
+    C.defer = c->step.commit_defer ? 1 : 0; C.nogrid = c->allpairs ? 1 : 0; C.enabled = 0;
     C.od_stall = nullptr; C.od_tick = 0; C.from_wide = 0; C.wctl = nullptr; C.host_ncand = nullptr;
     return C;
+}
+
+// How `owner` (1 the streaming pass, 2 the exchange kernels) builds this step's lists: 1 anew; with kept lists (`kept`: the owner
+// has its node pools) 2 the full build of a cycle, 3 a step in between.  Advances step.lists_owner, step.lists_age and B.epoch.
+int amc_list_build_mode(amc_ctx *c, int owner, bool kept)
+{
+    amc_step_state &T = c->step;
+    if (!kept) { c->B.epoch++; T.lists_age = -1; return 1; }
+    // kept lists: a full build when the lists are not this owner's or the cycle is over, else a step in between
+    if (T.lists_owner != owner) T.lists_age = -1;
+    T.lists_owner = owner;
+    if (T.lists_age < 0 || T.lists_age + 1 >= c->keep_K) { c->B.epoch++; T.lists_age = 0; return 2; }
+    T.lists_age++;
+    return 3;
+}
+
+// The one launch of k_stream: the kernel of the context's geometry (the energised pore's fused form when the stages hold its
+// cases) on `blocks` blocks of `threads` in `stream`.  Parameters, grid and the energised pass's constants come from the context.
+static void launch_k_stream(amc_ctx *c, hipStream_t stream, unsigned blocks, int threads, const amc_state &S, const amc_state &S_out,
+                            const amc_out &O, double dt, int stages, long long lo, long long hi, int keep_prior, int bounds_slot,
+                            const amc_lists &B, int build, const amc_lazy &L, const amc_commit_args &C, const amc_ovl &V)
+{
+    const bool cases = (stages & AMC_ST_TEMP_CASES) != 0;
+    auto *k = k_stream<AMC_GEOM_CUBE>;
+    switch (c->P.geometry) {
+    case AMC_GEOM_CUBE: break;
+    case AMC_GEOM_PORE: k = k_stream<AMC_GEOM_PORE>; break;
+    case AMC_GEOM_PORE_ENERGISED: k = cases ? k_stream<AMC_GEOM_PORE_ENERGISED, 1> : k_stream<AMC_GEOM_PORE_ENERGISED>; break;
+    default: return;
+    }
+    AMC_LAUNCH_ON(c, stream, k, dim3(blocks), dim3(threads), S, S_out, c->P, O, dt, stages, lo, hi, keep_prior, bounds_slot, c->G, B,
+                  build, L, C, V, (const amc_temp_pass *)(cases ? c->TD.pass : nullptr));
 }
 
 hipError_t amc_launch_stream(amc_ctx *c, double dt, int stages, int bounds_slot, bool fuse_bin)
 {
     const int threads = c->stream_bs;
     int build = 0;
-    if (fuse_bin && !c->allpairs && c->lo == 0 && c->hi == c->n) {
-        if (c->keep_K >= 2 && c->B.cell_of) {
-            // kept lists: a full build when the lists are not this pass's own or the cycle is over, else a step in between
-            if (c->lists_owner != 1) c->lists_age = -1;
-            c->lists_owner = 1;
-            if (c->lists_age < 0 || c->lists_age + 1 >= c->keep_K) { build = 2; c->B.epoch++; c->lists_age = 0; }
-            else { build = 3; c->lists_age++; }
-        } else {
-            build = 1; c->B.epoch++; c->lists_age = -1;
-        }
-    }
+    if (fuse_bin && !c->allpairs && c->lo == 0 && c->hi == c->n) build = amc_list_build_mode(c, 1, c->keep_K >= 2 && c->B.cell_of);
     amc_lazy L;
     memset(&L, 0, sizeof L);
-    if (c->lazy_pending) {              // (a shard: its own particles here, the slots of the others are cleared by the unpack)
+    if (c->step.lazy_pending) {              // (a shard: its own particles here, the slots of the others are cleared by the unpack)
         const amc_resolve_ws &W = c->W;
         L.slot_of = W.slot_of; L.state = W.sl_state; L.moved = W.sl_moved;
         L.enabled = 1;
-        c->lazy_pending = false;        // this pass consumes them
+        c->step.lazy_pending = false;        // this pass consumes them
     }
     const long long cnt = c->hi - c->lo;
     if (cnt <= 0) return hipSuccess;
     amc_commit_args C = amc_make_commit_args(c);
     const amc_resolve_ws &W_ = c->W;
     unsigned extra = 0;
-    if (c->commit_pending) {            // this launch does the last sweep's commit as well, on blocks of its own
+    if (c->step.commit_pending) {            // this launch does the last sweep's commit as well, on blocks of its own
         const long long lag = c->h_host_ncand ? *c->h_host_ncand : 0;      // (entries to commit ~ 2 per candidate)
         extra = (unsigned)std::min<long long>(std::max<long long>((2 * lag + 255) / 256, 4), AMC_COMMIT_BLOCKS);
         C.enabled = (int)extra;
-        c->commit_pending = false;
-        if (c->od_active && !c->od_prev_ordered) { C.from_wide = 1; C.wctl = W_.wctl; C.host_ncand = c->d_host_ncand; }
+        c->step.commit_pending = false;
+        if (c->od_active && !c->step.od_prev_ordered) { C.from_wide = 1; C.wctl = W_.wctl; C.host_ncand = c->d_host_ncand; }
     }
     if (c->od_active) { C.od_stall = c->d_od; C.od_tick = c->od_tick; }
     const unsigned blocks = (unsigned)((cnt + threads - 1) / threads) + extra;
@@ -390,26 +412,7 @@ hipError_t amc_launch_stream(amc_ctx *c, double dt, int stages, int bounds_slot,
     V.adj_head = nullptr; V.skip_epoch = 0;
     if ((stages & AMC_ST_TEMP_CASES) && (c->P.geometry != AMC_GEOM_PORE_ENERGISED || !c->TD.pass)) return hipErrorInvalidValue;
     amc_prof_begin(c, (stages == AMC_ST_BOUNDS) ? AMC_K_BOUNDS : AMC_K_DRIFT_WALLS);
-    switch (c->P.geometry) {
-    case AMC_GEOM_CUBE:
-        AMC_LAUNCH(c, k_stream<AMC_GEOM_CUBE>, dim3(blocks), dim3(threads), c->S, c->S, c->P, c->out, dt,
-                           stages, c->lo, c->hi, kp, bounds_slot, c->G, c->B, build, L, C, V, (const amc_temp_pass *)nullptr);
-        break;
-    case AMC_GEOM_PORE:
-        AMC_LAUNCH(c, k_stream<AMC_GEOM_PORE>, dim3(blocks), dim3(threads), c->S, c->S, c->P, c->out, dt,
-                           stages, c->lo, c->hi, kp, bounds_slot, c->G, c->B, build, L, C, V, (const amc_temp_pass *)nullptr);
-        break;
-    case AMC_GEOM_PORE_ENERGISED:
-        if (stages & AMC_ST_TEMP_CASES)
-            AMC_LAUNCH(c, (k_stream<AMC_GEOM_PORE_ENERGISED, 1>), dim3(blocks), dim3(threads), c->S, c->S, c->P,
-                               c->out, dt, stages, c->lo, c->hi, kp, bounds_slot, c->G, c->B, build, L, C, V, (const amc_temp_pass *)c->TD.pass);
-        else
-            AMC_LAUNCH(c, k_stream<AMC_GEOM_PORE_ENERGISED>, dim3(blocks), dim3(threads), c->S, c->S, c->P,
-                               c->out, dt, stages, c->lo, c->hi, kp, bounds_slot, c->G, c->B, build, L, C, V, (const amc_temp_pass *)nullptr);
-        break;
-    default:
-        break;
-    }
+    launch_k_stream(c, c->stream, blocks, threads, c->S, c->S, c->out, dt, stages, c->lo, c->hi, kp, bounds_slot, c->B, build, L, C, V);
     amc_prof_end(c);
     return hipGetLastError();
 }
@@ -422,7 +425,7 @@ hipError_t amc_launch_stream_ovl(amc_ctx *c, double dt, int stages, int from, un
     const int to = 1 - from;
     amc_lists &Bn = c->B_buf[to];
     Bn.epoch++;
-    c->lists_age = -1;
+    c->step.lists_age = -1;
     amc_lazy L;
     memset(&L, 0, sizeof L);
     amc_commit_args C = amc_make_commit_args(c);
@@ -432,12 +435,7 @@ hipError_t amc_launch_stream_ovl(amc_ctx *c, double dt, int stages, int from, un
     O.wev = c->wev_buf[c->out.step & 1];
     const unsigned blocks = (unsigned)((c->n + 255) / 256);
     amc_prof_begin(c, AMC_K_DRIFT_WALLS);
-    if (c->P.geometry == AMC_GEOM_CUBE)
-        AMC_LAUNCH_ON(c, stream, k_stream<AMC_GEOM_CUBE>, dim3(blocks), dim3(256), c->S_buf[from], c->S_buf[to], c->P, O, dt, stages,
-                      0LL, (long long)c->n, 0, 0, c->G, Bn, build_lists ? 1 : 0, L, C, V, (const amc_temp_pass *)nullptr);
-    else
-        AMC_LAUNCH_ON(c, stream, k_stream<AMC_GEOM_PORE>, dim3(blocks), dim3(256), c->S_buf[from], c->S_buf[to], c->P, O, dt, stages,
-                      0LL, (long long)c->n, 0, 0, c->G, Bn, build_lists ? 1 : 0, L, C, V, (const amc_temp_pass *)nullptr);
+    launch_k_stream(c, stream, blocks, 256, c->S_buf[from], c->S_buf[to], O, dt, stages, 0, c->n, 0, 0, Bn, build_lists ? 1 : 0, L, C, V);
     amc_prof_end(c);
     return hipGetLastError();
 }
