@@ -542,6 +542,8 @@ int amc_histograms(amc_ctx *c, uint64_t *counts, uint64_t *n_paths_total)
     if (counts) {
         if (!c->d_hist) return amc_fail(c, AMC_ERR_STATE, "histograms disabled (hist_bins == 0)");
     }
+    // the pending commit first: the bins copied below and the total read after them describe the same sweeps
+    { int rc_ = amc_settle_commit(c); if (rc_) return rc_; }
     std::vector<uint64_t> banks;
     if (counts) {
         banks.resize((size_t)4 * c->out.nbins * AMC_COUNTER_BANKS);
@@ -564,6 +566,10 @@ int amc_reset_outputs(amc_ctx *c)
 {
     if (!c) return AMC_ERR_INVALID;
     AMC_HIP(c, hipSetDevice(c->device));
+    // a commit still pending runs now, so that what it emits is discarded with the rest instead of landing in the zeroed
+    // outputs with the next streaming pass; the sweep's deferred results stay in the slot arrays (step.lazy_pending) and
+    // reach the particle arrays as they would have
+    { int rc_ = amc_settle_commit(c); if (rc_) return rc_; }
     if (c->d_hist) AMC_HIP(c, hipMemsetAsync(c->d_hist, 0, sizeof(uint64_t) * 4 * c->out.nbins * AMC_COUNTER_BANKS, c->stream));
     AMC_HIP(c, hipMemsetAsync(c->d_cnt, 0, sizeof(amc_dev_counters), c->stream));
     AMC_HIP(c, hipMemsetAsync(c->d_banks, 0, sizeof(amc_counter_bank) * AMC_COUNTER_BANKS, c->stream));

@@ -26,6 +26,7 @@ struct amc_commit_args {
     int defer;                      // results stay in the slot arrays (the streaming pass picks them up through slot_of[])
     int nogrid;
     int enabled;
+    int step;                       // the `step` key of the paths this commit emits: the index of the sweep's own step
     // the ordered workgroup on demand (amc_internal.h).  od_stall: the sticky word — the commit (and the pass it rides along
     // with) of a step later than it does nothing.  from_wide: no ordered pass ran for this sweep, so nobody has handed its
     // counts over: they are taken from the wide kernel's own words, and this commit does what the idle ordered workgroup

@@ -92,6 +92,7 @@ struct amc_stage {
 
 // (defined inside the extern "C" block of amc_run.hip — amc_publish_velocities: amc_api.hip; internal to the library, not part of the ABI)
 #define AMC_INTERNAL extern "C" __attribute__((visibility("hidden")))
+AMC_INTERNAL int amc_settle_commit(amc_ctx *c);                         // run the last sweep's commit if it is still pending (no synchronisation)
 AMC_INTERNAL int amc_read_counters(amc_ctx *c, amc_dev_counters *h);    // device counters with the banks folded in (synchronises)
 AMC_INTERNAL int amc_finish_stats(amc_ctx *c, amc_step_stats *out);     // per-step deltas + error flags
 AMC_INTERNAL int amc_publish_velocities(amc_ctx *c);                    // multi-GPU: vpub = current velocities (after an upload)

@@ -237,10 +237,14 @@ struct amc_res { void *p; amc_res_kind kind; };
 
 // What the launchers change as they enqueue a step: everything a rewind of amc_run's on-demand loop has to put back (it keeps
 // a copy per step, together with c->B and c->out.step).  A new per-step member of the host's goes HERE.
+// The rule for what a step leaves pending: an entry point that reads outputs runs the pending commit before its first copy
+// (amc_settle_commit, or amc_read_counters which starts with it); one that reads or replaces particle arrays calls amc_flush
+// first; amc_reset_outputs runs the pending commit and then zeroes, and leaves lazy_pending alone.
 struct amc_step_state {
     bool lazy_pending;             // sweep results wait in the slot arrays for the next streaming pass (or amc_flush)
     bool commit_pending;           // the last sweep's commit (paths -> histograms, counters, overlay) waits for the next streaming pass (or amc_flush)
     bool commit_defer;             // ... and that sweep's results stay in the slot arrays
+    int commit_step = 0;           // ... and the `step` key its path records carry: the index of the sweep's own step, whoever commits it
     unsigned int sweep_epoch;      // tag of the degree counts of the current sweep (advanced by every detect launch)
     bool plan_split;               // launch plan of the current sweep, fixed when its detect kernel is launched
     int lists_age = -1;            // steps since the last full build of a kept cycle (-1: the lists are not a kept cycle's)

@@ -568,7 +568,7 @@ __global__ __launch_bounds__(256) void k_commit(rs_args A)
     C.ctl = (amc_resolve_ctl *)W.ctl; C.hist = W.hist; C.ov_head = W.ov_head; C.ev_gen = W.ev_gen; C.ev = W.ev;
     C.sl_meta = W.sl_meta; C.sl_hits = W.sl_hits; C.sl_moved = W.sl_moved; C.sl_state = W.sl_state; C.slot_of = W.slot_of;
     C.max_slots = W.max_slots; C.max_hist = W.max_hist; C.lo = A.lo; C.hi = A.hi; C.count_pp = A.count_pp;
-    C.defer = A.defer_commit; C.nogrid = A.allpairs; C.enabled = 1;
+    C.defer = A.defer_commit; C.nogrid = A.allpairs; C.enabled = 1; C.step = A.O.step;
     C.od_stall = nullptr; C.od_tick = 0; C.from_wide = 0; C.wctl = nullptr; C.host_ncand = nullptr;
     amc_commit_part(C, A.O, A.G, A.S, gtid, gstride);
 }
@@ -607,7 +607,7 @@ static void rs_launch_all(amc_ctx *c, const rs_args &A)
     c->step.od_prev_ordered = true;
     // the commit: deferred results -> it waits for the next streaming pass (or amc_flush); else a kernel of its own, now
     c->step.commit_defer = A.defer_commit != 0;
-    if (A.defer_commit) { c->step.commit_pending = true; return; }
+    if (A.defer_commit) { c->step.commit_pending = true; c->step.commit_step = c->out.step; return; }
     amc_prof_end(c);
     amc_prof_begin(c, AMC_K_COMMIT);
     AMC_LAUNCH(c, k_commit, dim3(AMC_COMMIT_BLOCKS), dim3(256), Aw);
@@ -652,6 +652,7 @@ hipError_t amc_launch_wide_only(amc_ctx *c, rs_args *used)
     amc_prof_end(c);
     c->step.commit_defer = true;
     c->step.commit_pending = true;
+    c->step.commit_step = c->out.step;
     c->step.od_prev_ordered = false;
     c->od_steps++;
     *used = Aw;
@@ -676,6 +677,7 @@ hipError_t amc_launch_commit(amc_ctx *c)
 {
     rs_args A = rs_make_args(c);
     A.defer_commit = c->step.commit_defer ? 1 : 0;
+    A.O.step = c->step.commit_step;         // (c->out.step may have moved on to the next step)
     amc_prof_begin(c, AMC_K_COMMIT);
     AMC_LAUNCH(c, k_commit, dim3(AMC_COMMIT_BLOCKS), dim3(256), A);
     amc_prof_end(c);

@@ -19,12 +19,19 @@ static void fold_banks(amc_dev_counters *h, const amc_counter_bank *b)
     }
 }
 
+// the last sweep's paths / counters are not in yet: commit it now (its results stay deferred).  An entry point that reads or
+// replaces outputs calls this BEFORE its first copy or memset (amc_step_state, amc_internal.h)
+int amc_settle_commit(amc_ctx *c)
+{
+    if (!c->step.commit_pending) return AMC_OK;
+    AMC_HIP(c, amc_launch_commit(c));
+    c->step.commit_pending = false;
+    return AMC_OK;
+}
+
 int amc_read_counters(amc_ctx *c, amc_dev_counters *h)
 {
-    if (c->step.commit_pending) {            // the last sweep's paths / counters are not in yet: commit it now (its results stay deferred)
-        AMC_HIP(c, amc_launch_commit(c));
-        c->step.commit_pending = false;
-    }
+    if (int rc = amc_settle_commit(c)) return rc;
     amc_counter_bank banks[AMC_COUNTER_BANKS];
     amc_stage st(c);
     AMC_HIP(c, st.get(h, c->d_cnt, sizeof *h));
@@ -74,10 +81,7 @@ int amc_finish_stats(amc_ctx *c, amc_step_stats *out)
 // sweep results deferred to the next streaming pass: write them now (before anything else reads the particle arrays)
 int amc_flush(amc_ctx *c)
 {
-    if (c->step.commit_pending) {            // (before the results are applied: the commit leaves the number of deferred slots)
-        AMC_HIP(c, amc_launch_commit(c));
-        c->step.commit_pending = false;
-    }
+    if (int rc = amc_settle_commit(c)) return rc;       // (before the results are applied: the commit leaves the number of deferred slots)
     if (!c->step.lazy_pending) return AMC_OK;
     AMC_HIP(c, amc_launch_apply(c));
     c->step.lazy_pending = false;
@@ -243,6 +247,7 @@ static int run_overlapped(amc_ctx *c, double dt, int64_t nsteps)
     // a flush or a read of the counters, as after any step)
     AMC_HIP(c, amc_launch_resolve(c, true));
     c->step.lazy_pending = true;
+    c->step.commit_step = (int)c->out.step - 1;         // (the step index has moved on: the sweep belongs to the last step)
     c->B_buf[cur] = c->B;
     // the current lists' extra nodes die with them (the next build starts from the particles' own nodes)
     AMC_HIP(c, hipMemsetAsync(c->extra_count, 0, 2 * sizeof(int), c->stream));

@@ -126,7 +126,9 @@ __global__ __launch_bounds__(256) void k_stream(amc_state S, amc_state S_out, am
         const unsigned nstream = gridDim.x - (unsigned)C.enabled;       // (enabled = number of commit blocks)
         if (blockIdx.x >= nstream) {
             if (stalled && C.od_tick > stalled) return;
-            amc_commit_part(C, O, G, S, (int)((blockIdx.x - nstream) * blockDim.x + threadIdx.x), (int)(C.enabled * blockDim.x));
+            amc_out Oc = O;
+            Oc.step = C.step;               // (the sweep's step, not this pass's)
+            amc_commit_part(C, Oc, G, S, (int)((blockIdx.x - nstream) * blockDim.x + threadIdx.x), (int)(C.enabled * blockDim.x));
             return;
         }
     }
@@ -343,6 +345,7 @@ amc_commit_args amc_make_commit_args(amc_ctx *c)
     C.sl_meta = W.sl_meta; C.sl_hits = W.sl_hits; C.sl_moved = W.sl_moved; C.sl_state = W.sl_state; C.slot_of = W.slot_of;
     C.max_slots = W.max_slots; C.max_hist = W.max_hist; C.lo = c->lo; C.hi = c->hi; C.count_pp = c->mg_count_pp ? 1 : 0;
     C.defer = c->step.commit_defer ? 1 : 0; C.nogrid = c->allpairs ? 1 : 0; C.enabled = 0;
+    C.step = c->step.commit_step;
     C.od_stall = nullptr; C.od_tick = 0; C.from_wide = 0; C.wctl = nullptr; C.host_ncand = nullptr;
     return C;
 }

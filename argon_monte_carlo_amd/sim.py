@@ -25,7 +25,8 @@ class Simulation:
     """``kind``: "cube" (Open_Air_Cube_MC.py), "pore" (Open_Air_Pore_MC.py) — see params.py for the constants."""
 
     def __init__(self, kind="pore", n=None, sigma=PR.SIGMA, device=0, keep_prior=False, tolerate_fp_errors=False,
-                 params=None, consts=None):
+                 params=None, consts=None, engine=None):
+        """``engine``: drive this context (an ``Engine`` created with the same ``params``) instead of creating one."""
         if params is None:
             if kind == "cube":
                 params, consts = PR.cube_params(n=n, sigma=sigma, device=device) if n is None else \
@@ -41,7 +42,7 @@ class Simulation:
         self.kind = kind
         self.params, self.consts = params, consts
         self.dt = consts["dt"]
-        self.engine = Engine(params)
+        self.engine = engine if engine is not None else Engine(params)
         self.completed_paths, self.completed_x_paths = [], []
         self.completed_y_paths, self.completed_z_paths = [], []
         self.num_collisions_per_step = 0          # Pore:424 (value of the last step)

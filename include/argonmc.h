@@ -230,6 +230,10 @@ int amc_paths_pending(amc_ctx *ctx, size_t *n);
 /* free-path histograms accumulated on the device with np.histogram(range=(lo,hi), bins) semantics
  * (Pore:575-596): counts[4][hist_bins] (total, x, y, z) and the number of paths seen (incl. out of range). */
 int amc_histograms(amc_ctx *ctx, uint64_t *counts, uint64_t *n_paths_total);
+/* Zero histograms, counters, the pending path records and the step index.  Whatever was enqueued before the call is
+ * discarded from the outputs — the paths and collisions of a step that has returned without its statistics
+ * (amc_mg_finish(ctx, NULL)) included — and its results still reach the particle arrays: the state is the one the steps so
+ * far produce, and the next step's outputs and statistics hold that step alone.  Sampled fields are left alone. */
 int amc_reset_outputs(amc_ctx *ctx);
 
 /* Host-only helper of the hand-over above (no GPU, no context): the re-emission directions of one case's hits —
