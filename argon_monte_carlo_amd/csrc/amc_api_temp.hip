@@ -53,8 +53,31 @@ int amc_temp_begin(amc_ctx *c, double dt)
     if (rc) return rc;
     if ((rc = amc_flush(c))) return rc;
     c->keep_prior = true;       // the energised masks read prior_*_vals (Temp:708-750)
-    c->T.pre_case = -1;
+    c->T.h.fresh();
     AMC_HIP(c, amc_launch_stream(c, dt, AMC_ST_DRIFT | AMC_ST_WALLS, 0));
+    return AMC_OK;
+}
+
+// sorted position -> record, ascending particle index (unique: a particle hits a case at most once per step)
+static void temp_order(const int *idx, size_t n, std::vector<int> &perm)
+{
+    perm.resize(n);
+    for (size_t k = 0; k < n; k++) perm[k] = (int)k;
+    std::sort(perm.begin(), perm.end(), [idx](int a, int b) { return idx[a] < idx[b]; });
+}
+
+// The hits of `case_id` (none past the last case) behind whatever is enqueued, their count, ONE synchronisation.  A case's
+// mask is evaluated on the state the previous apply leaves (Temp:708-751) and needs nothing from the host: behind that kernel,
+// one synchronisation returns its results and this case's hits (the hand-over is synchronisation latency: 12 -> 7 per step).
+// The hit records are separate from what the apply kernel wrote back (dpz / dE) and from the host's copy of the permutation.
+static int temp_hits_sync(amc_ctx *c, int case_id)
+{
+    amc_temp_ws &T = c->T;
+    if (case_id <= 9) {
+        AMC_HIP(c, amc_launch_temp_hits(c, case_id));
+        AMC_HIP(c, hipMemcpyAsync(T.h_count, T.count, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    }
+    AMC_HIP(c, hipStreamSynchronize(c->stream));    // the records are in host memory now (the kernel wrote them there)
     return AMC_OK;
 }
 
@@ -65,32 +88,50 @@ int amc_wall_hits(amc_ctx *c, int case_id, int32_t *idx, double *normal_xyz, dou
     int rc = temp_ensure(c);
     if (rc) return rc;
     amc_temp_ws &T = c->T;
-    if (T.pre_case == case_id) {
-        T.pre_case = -1;        // launched behind the previous case's apply kernel and already synchronised with it
-    } else {
-        T.pre_case = -1;
-        AMC_HIP(c, amc_launch_temp_hits(c, case_id));
-        AMC_HIP(c, hipMemcpyAsync(T.h_count, T.count, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        AMC_HIP(c, hipStreamSynchronize(c->stream));    // the records are in host memory now (the kernel wrote them there)
-    }
+    amc_temp_handover &H = T.h;
+    const bool ahead = H.ahead_case == case_id;     // launched behind the previous case's apply kernel, synchronised with it
+    H.ahead_case = -1;
+    if (!ahead && (rc = temp_hits_sync(c, case_id))) return rc;
     const int cnt = *T.h_count;
     if (cnt > T.cap) return amc_fail(c, AMC_ERR_CAPACITY, "%d wall hits exceed the record capacity %d", cnt, T.cap);
     if ((size_t)cnt > cap) return amc_fail(c, AMC_ERR_CAPACITY, "%d wall hits, caller buffer holds %zu", cnt, cap);
-    T.last_case = case_id; T.last_n = cnt;
-    T.perm.resize((size_t)cnt);
+    H.hits_case = case_id; H.hits_n = cnt;
+    temp_order(T.h_idx, (size_t)cnt, H.perm);
     *n = (size_t)cnt;
-    if (cnt == 0) return AMC_OK;
-    const int *hidx = T.h_idx;
-    const double *hnorm = T.h_normal, *hcontact = T.h_contact;
-    for (int k = 0; k < cnt; k++) T.perm[k] = k;
-    std::sort(T.perm.begin(), T.perm.end(), [&](int a, int b) { return hidx[a] < hidx[b]; });   // ascending particle index
     for (int s = 0; s < cnt; s++) {
-        const int k = T.perm[s];
-        if (idx) idx[s] = hidx[k];
-        if (normal_xyz) { normal_xyz[3 * s] = hnorm[3 * k]; normal_xyz[3 * s + 1] = hnorm[3 * k + 1]; normal_xyz[3 * s + 2] = hnorm[3 * k + 2]; }
-        if (contact_z) contact_z[s] = hcontact[3 * k + 2];
+        const int k = H.perm[s];
+        if (idx) idx[s] = T.h_idx[k];
+        for (int e = 0; e < 3 && normal_xyz; e++) normal_xyz[3 * s + e] = T.h_normal[3 * k + e];
+        if (contact_z) contact_z[s] = T.h_contact[3 * k + 2];
     }
     return AMC_OK;
+}
+
+// amc_wall_apply / amc_wall_park: the call matches the pending amc_wall_hits, else AMC_ERR_STATE
+static int temp_match_hits(amc_ctx *c, const char *who, int case_id, size_t n)
+{
+    const amc_temp_handover &H = c->T.h;
+    if (c->T.idx && H.hits_case == case_id && (size_t)H.hits_n == n) return AMC_OK;
+    return amc_fail(c, AMC_ERR_STATE, "%s(case %d, n=%zu) does not match the pending amc_wall_hits(case %d, n=%d)", who, case_id, n, H.hits_case, H.hits_n);
+}
+
+// caller order (ascending particle index) -> record order, written where the kernel reads it (no energies yet: zeros)
+static void temp_scatter(amc_temp_ws &T, const double *dir_xyz, const double *surface_energy, size_t n)
+{
+    for (size_t s = 0; s < n; s++) {
+        const int k = T.h.perm[s];
+        for (int e = 0; e < 3; e++) T.h_dir[3 * k + e] = dir_xyz[3 * s + e];
+        T.h_Es[k] = surface_energy ? surface_energy[s] : 0.0;
+    }
+}
+
+// record order -> caller order: what a kernel wrote back for the n hits behind `perm`
+static void temp_gather(const std::vector<int> &perm, size_t n, const double *h_dpz, const double *h_dE, double *dpz, double *dE)
+{
+    for (size_t s = 0; s < n; s++) {
+        if (dpz) dpz[s] = h_dpz[perm[s]];
+        if (dE) dE[s] = h_dE[perm[s]];
+    }
 }
 
 int amc_wall_apply(amc_ctx *c, int case_id, const double *dir_xyz, const double *surface_energy, size_t n, double *dpz, double *dE)
@@ -98,34 +139,16 @@ int amc_wall_apply(amc_ctx *c, int case_id, const double *dir_xyz, const double 
     if (!c) return AMC_ERR_INVALID;
     AMC_HIP(c, hipSetDevice(c->device));
     amc_temp_ws &T = c->T;
-    if (!T.idx || T.last_case != case_id || (size_t)T.last_n != n)
-        return amc_fail(c, AMC_ERR_STATE, "amc_wall_apply(case %d, n=%zu) does not match the pending amc_wall_hits(case %d, n=%d)", case_id, n, T.last_case, T.last_n);
-    T.last_case = -1;
+    int rc = temp_match_hits(c, "amc_wall_apply", case_id, n);
+    if (rc) return rc;
+    T.h.hits_case = -1;
     if (n == 0) return AMC_OK;
     if (!dir_xyz || !surface_energy) return AMC_ERR_INVALID;
-    // caller order (ascending particle index) -> record order, written where the kernel reads it
-    for (size_t s = 0; s < n; s++) {
-        const int k = T.perm[s];
-        T.h_dir[3 * k] = dir_xyz[3 * s]; T.h_dir[3 * k + 1] = dir_xyz[3 * s + 1]; T.h_dir[3 * k + 2] = dir_xyz[3 * s + 2];
-        T.h_Es[k] = surface_energy[s];
-    }
+    temp_scatter(T, dir_xyz, surface_energy, n);
     AMC_HIP(c, amc_launch_temp_apply(c, case_id, (int)n));
-    // The next case's mask is evaluated on the state this apply leaves (Temp:708-751: each mask after the previous handler)
-    // and needs nothing from the host: its hits kernel goes right behind, so that ONE synchronisation returns this case's
-    // results and the next case's hits (the hand-over of a step is synchronisation latency: 12 -> 7 of them).  The hit
-    // records are separate from what the apply kernel wrote back (dpz / dE) and from the host's copy of the permutation.
-    int pre = -1;
-    if (case_id < 9) {
-        AMC_HIP(c, amc_launch_temp_hits(c, case_id + 1));
-        AMC_HIP(c, hipMemcpyAsync(T.h_count, T.count, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        pre = case_id + 1;
-    }
-    AMC_HIP(c, hipStreamSynchronize(c->stream));
-    T.pre_case = pre;
-    for (size_t s = 0; s < n; s++) {
-        if (dpz) dpz[s] = T.h_dpz[T.perm[s]];
-        if (dE) dE[s] = T.h_dE[T.perm[s]];
-    }
+    if ((rc = temp_hits_sync(c, case_id + 1))) return rc;
+    T.h.ahead_case = case_id < 9 ? case_id + 1 : -1;
+    temp_gather(T.h.perm, n, T.h_dpz, T.h_dE, dpz, dE);
     return AMC_OK;
 }
 
@@ -140,28 +163,19 @@ int amc_wall_park(amc_ctx *c, int case_id, const double *dir_xyz, size_t n)
     if (!c) return AMC_ERR_INVALID;
     AMC_HIP(c, hipSetDevice(c->device));
     amc_temp_ws &T = c->T;
-    if (!T.idx || T.last_case != case_id || (size_t)T.last_n != n)
-        return amc_fail(c, AMC_ERR_STATE, "amc_wall_park(case %d, n=%zu) does not match the pending amc_wall_hits(case %d, n=%d)", case_id, n, T.last_case, T.last_n);
-    if (T.def_case >= 0) return amc_fail(c, AMC_ERR_STATE, "amc_wall_park: case %d is still parked", T.def_case);
-    T.last_case = -1;
-    T.def_case = case_id; T.def_n = 0;          // (a shard without a hit of its own parks nothing and finishes nothing)
+    amc_temp_handover &H = T.h;
+    int rc = temp_match_hits(c, "amc_wall_park", case_id, n);
+    if (rc) return rc;
+    if (H.parked_case >= 0) return amc_fail(c, AMC_ERR_STATE, "amc_wall_park: case %d is still parked", H.parked_case);
+    H.hits_case = -1;
+    H.parked_case = case_id; H.parked_n = 0;    // (a shard without a hit of its own parks nothing and finishes nothing)
     if (n == 0) return AMC_OK;
     if (!dir_xyz) return AMC_ERR_INVALID;
-    for (size_t s = 0; s < n; s++) {
-        const int k = T.perm[s];
-        T.h_dir[3 * k] = dir_xyz[3 * s]; T.h_dir[3 * k + 1] = dir_xyz[3 * s + 1]; T.h_dir[3 * k + 2] = dir_xyz[3 * s + 2];
-        T.h_Es[k] = 0.0;
-    }
+    temp_scatter(T, dir_xyz, nullptr, n);
     AMC_HIP(c, amc_launch_temp_apply(c, case_id, (int)n, true));
-    T.def_case = case_id; T.def_n = (int)n; T.def_perm = T.perm;
-    int pre = -1;
-    if (case_id < 9) {                          // (the next case's hits behind it, as in amc_wall_apply)
-        AMC_HIP(c, amc_launch_temp_hits(c, case_id + 1));
-        AMC_HIP(c, hipMemcpyAsync(T.h_count, T.count, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        pre = case_id + 1;
-    }
-    AMC_HIP(c, hipStreamSynchronize(c->stream));
-    T.pre_case = pre;
+    H.parked_n = (int)n; H.parked_perm = H.perm;
+    if ((rc = temp_hits_sync(c, case_id + 1))) return rc;
+    H.ahead_case = case_id < 9 ? case_id + 1 : -1;
     return AMC_OK;
 }
 
@@ -170,26 +184,24 @@ int amc_wall_finish(amc_ctx *c, int case_id, const double *surface_energy, size_
     if (!c) return AMC_ERR_INVALID;
     AMC_HIP(c, hipSetDevice(c->device));
     amc_temp_ws &T = c->T;
-    if (T.def_case != case_id || (size_t)T.def_n != n)
-        return amc_fail(c, AMC_ERR_STATE, "amc_wall_finish(case %d, n=%zu) does not match the parked case %d (n=%d)", case_id, n, T.def_case, T.def_n);
-    T.def_case = -1;
+    amc_temp_handover &H = T.h;
+    if (H.parked_case != case_id || (size_t)H.parked_n != n)
+        return amc_fail(c, AMC_ERR_STATE, "amc_wall_finish(case %d, n=%zu) does not match the parked case %d (n=%d)", case_id, n, H.parked_case, H.parked_n);
+    H.parked_case = -1;
     if (n == 0) return AMC_OK;
     if (!surface_energy) return AMC_ERR_INVALID;
-    for (size_t s = 0; s < n; s++) T.h_def_Es[T.def_perm[s]] = surface_energy[s];
+    for (size_t s = 0; s < n; s++) T.h_def_Es[H.parked_perm[s]] = surface_energy[s];
     AMC_HIP(c, amc_launch_temp_velocity(c, case_id, (int)n));
     AMC_HIP(c, hipStreamSynchronize(c->stream));
-    for (size_t s = 0; s < n; s++) {
-        if (dpz) dpz[s] = T.h_def_dpz[T.def_perm[s]];
-        if (dE) dE[s] = T.h_def_dE[T.def_perm[s]];
-    }
+    temp_gather(H.parked_perm, n, T.h_def_dpz, T.h_def_dE, dpz, dE);
     return AMC_OK;
 }
 
 int amc_wall_hits_again(amc_ctx *c)
 {
     if (!c) return AMC_ERR_INVALID;
-    c->T.pre_case = -1;             // the hits launched behind the last apply are not used: the next amc_wall_hits evaluates its case anew
-    c->T.last_case = -1;
+    c->T.h.ahead_case = -1;         // the hits launched behind the last apply are not used: the next amc_wall_hits evaluates its case anew
+    c->T.h.hits_case = -1;
     return AMC_OK;
 }
 
@@ -197,37 +209,51 @@ int amc_wall_hits_again(amc_ctx *c)
 static int temp_dev_ensure(amc_ctx *c)
 {
     if (c->P.geometry != AMC_GEOM_PORE_ENERGISED) return amc_fail(c, AMC_ERR_STATE, "energised-wall calls need AMC_GEOM_PORE_ENERGISED");
-    amc_temp_dev_ws &D = c->TD;
-    if (D.idx) return AMC_OK;
+    if (c->TD.seg.idx) return AMC_OK;
     amc_alloc_group group(c);
     int icap = (int)std::min<int64_t>(std::max<int64_t>(4096, c->n / 64 + 1024), 0x0fffffff);
     // AMC_TEMP_DEV_CAP (diagnostic): fewer records per case, so that a test reaches the overflow path with a handful of hits
     if (const char *e = getenv("AMC_TEMP_DEV_CAP")) { const int v = atoi(e); if (v > 0 && v < icap) icap = v; }
     const size_t cap = (size_t)icap * 7;
-    int *idx, *count;
-    double *t, *contact, *normal, *dir, *Es, *dpz, *dE;
-    unsigned char *ok;
-    AMC_HIP(c, dalloc(c, &idx, cap)); AMC_HIP(c, dalloc(c, &count, 8)); AMC_HIP(c, dalloc(c, &t, cap));
-    AMC_HIP(c, dalloc(c, &contact, 3 * cap)); AMC_HIP(c, dalloc(c, &normal, 3 * cap)); AMC_HIP(c, dalloc(c, &dir, 3 * cap));
-    AMC_HIP(c, dalloc(c, &Es, cap)); AMC_HIP(c, dalloc(c, &dpz, cap)); AMC_HIP(c, dalloc(c, &dE, cap)); AMC_HIP(c, dalloc(c, &ok, cap));
-    group.keep();
+    temp_dev_segments D;
     D.cap = icap;
-    D.count = count; D.t = t; D.contact = contact; D.normal = normal; D.dir = dir; D.Es = Es; D.dpz = dpz; D.dE = dE; D.ok = ok;
-    D.idx = idx;                // (the guard: last)
+    AMC_HIP(c, dalloc(c, &D.idx, cap)); AMC_HIP(c, dalloc(c, &D.count, 8)); AMC_HIP(c, dalloc(c, &D.t, cap));
+    AMC_HIP(c, dalloc(c, &D.contact, 3 * cap)); AMC_HIP(c, dalloc(c, &D.normal, 3 * cap)); AMC_HIP(c, dalloc(c, &D.dir, 3 * cap));
+    AMC_HIP(c, dalloc(c, &D.Es, cap)); AMC_HIP(c, dalloc(c, &D.dpz, cap)); AMC_HIP(c, dalloc(c, &D.dE, cap)); AMC_HIP(c, dalloc(c, &D.ok, cap));
+    group.keep();
+    c->TD.seg = D;              // (published whole: seg.idx is the guard)
     return AMC_OK;
+}
+
+static int temp_rng_check(amc_ctx *c, const amc_temp_rng *cfg)
+{
+    if (cfg && cfg->struct_size == (int32_t)sizeof(amc_temp_rng) && cfg->n_gl >= 2 && cfg->n_gl <= 32) return AMC_OK;
+    return amc_fail(c, AMC_ERR_INVALID, "amc_temp_rng: bad struct_size / n_gl");
 }
 
 int amc_temp_cases_device(amc_ctx *c, const amc_temp_rng *cfg)
 {
     if (!c || !c->uploaded) return AMC_ERR_STATE;
-    if (!cfg || cfg->struct_size != (int32_t)sizeof(amc_temp_rng) || cfg->n_gl < 2 || cfg->n_gl > 32)
-        return amc_fail(c, AMC_ERR_INVALID, "amc_temp_rng: bad struct_size / n_gl");
-    AMC_HIP(c, hipSetDevice(c->device));
-    int rc = temp_dev_ensure(c);
+    int rc = temp_rng_check(c, cfg);
     if (rc) return rc;
+    AMC_HIP(c, hipSetDevice(c->device));
+    if ((rc = temp_dev_ensure(c))) return rc;
     if (!c->keep_prior) return amc_fail(c, AMC_ERR_STATE, "amc_temp_cases_device follows amc_temp_begin");
     c->TD.fetched = false;
     AMC_HIP(c, amc_launch_temp_cases_device(c, cfg));
+    return AMC_OK;
+}
+
+// the first k records' particle and results of segment s -> the host copies, queued on `st`
+static int temp_dev_get(amc_ctx *c, amc_stage &st, int s, size_t k)
+{
+    amc_temp_dev_ws &D = c->TD;
+    const size_t o = (size_t)s * (size_t)D.seg.cap;
+    D.h_idx[s].resize(k); D.h_dpz[s].resize(k); D.h_dE[s].resize(k); D.h_ok[s].resize(k);
+    AMC_HIP(c, st.get(D.h_idx[s].data(), D.seg.idx + o, sizeof(int) * k));
+    AMC_HIP(c, st.get(D.h_dpz[s].data(), D.seg.dpz + o, sizeof(double) * k));
+    AMC_HIP(c, st.get(D.h_dE[s].data(), D.seg.dE + o, sizeof(double) * k));
+    AMC_HIP(c, st.get(D.h_ok[s].data(), D.seg.ok + o, k));
     return AMC_OK;
 }
 
@@ -236,31 +262,18 @@ static int temp_dev_fetch(amc_ctx *c)
 {
     amc_temp_dev_ws &D = c->TD;
     if (D.fetched) return AMC_OK;
-    const int pre = std::min(D.cap, 2048);
-    {
-        amc_stage st(c);
-        AMC_HIP(c, st.get(D.h_count, D.count, sizeof(int) * 7));
-        for (int s = 0; s < 7; s++) {
-            const size_t o = (size_t)s * (size_t)D.cap;
-            D.h_idx[s].resize((size_t)pre); D.h_dpz[s].resize((size_t)pre); D.h_dE[s].resize((size_t)pre); D.h_ok[s].resize((size_t)pre);
-            AMC_HIP(c, st.get(D.h_idx[s].data(), D.idx + o, sizeof(int) * (size_t)pre));
-            AMC_HIP(c, st.get(D.h_dpz[s].data(), D.dpz + o, sizeof(double) * (size_t)pre));
-            AMC_HIP(c, st.get(D.h_dE[s].data(), D.dE + o, sizeof(double) * (size_t)pre));
-            AMC_HIP(c, st.get(D.h_ok[s].data(), D.ok + o, (size_t)pre));
-        }
-        AMC_HIP(c, st.finish());
-    }
+    const int cap = D.seg.cap, pre = std::min(cap, 2048);
+    int rc;
+    amc_stage st(c);
+    AMC_HIP(c, st.get(D.h_count, D.seg.count, sizeof(int) * 7));
+    for (int s = 0; s < 7; s++)
+        if ((rc = temp_dev_get(c, st, s, (size_t)pre))) return rc;
+    AMC_HIP(c, st.finish());
     for (int s = 0; s < 7; s++) {
-        if (D.h_count[s] > D.cap) return amc_fail(c, AMC_ERR_CAPACITY, "%d wall hits in case %d exceed the record capacity %d", D.h_count[s], 3 + s, D.cap);
+        if (D.h_count[s] > cap) return amc_fail(c, AMC_ERR_CAPACITY, "%d wall hits in case %d exceed the record capacity %d", D.h_count[s], 3 + s, cap);
         const size_t k = (size_t)std::max(D.h_count[s], 0);
         if ((int)k > pre) {
-            const size_t o = (size_t)s * (size_t)D.cap;
-            D.h_idx[s].resize(k); D.h_dpz[s].resize(k); D.h_dE[s].resize(k); D.h_ok[s].resize(k);
-            amc_stage st(c);
-            AMC_HIP(c, st.get(D.h_idx[s].data(), D.idx + o, sizeof(int) * k));
-            AMC_HIP(c, st.get(D.h_dpz[s].data(), D.dpz + o, sizeof(double) * k));
-            AMC_HIP(c, st.get(D.h_dE[s].data(), D.dE + o, sizeof(double) * k));
-            AMC_HIP(c, st.get(D.h_ok[s].data(), D.ok + o, k));
+            if ((rc = temp_dev_get(c, st, s, k))) return rc;
             AMC_HIP(c, st.finish());
         }
     }
@@ -270,7 +283,7 @@ static int temp_dev_fetch(amc_ctx *c)
 
 int amc_temp_device_results(amc_ctx *c, int case_id, int32_t *idx, double *dpz, double *dE, uint8_t *ok, size_t cap, size_t *n)
 {
-    if (!c || !n || case_id < 3 || case_id > 9 || !c->TD.idx) return AMC_ERR_INVALID;
+    if (!c || !n || case_id < 3 || case_id > 9 || !c->TD.seg.idx) return AMC_ERR_INVALID;
     AMC_HIP(c, hipSetDevice(c->device));
     int rc = temp_dev_fetch(c);
     if (rc) return rc;
@@ -278,9 +291,8 @@ int amc_temp_device_results(amc_ctx *c, int case_id, int32_t *idx, double *dpz, 
     const int s = case_id - 3;
     const size_t k = (size_t)std::max(D.h_count[s], 0);
     if (k > cap) return amc_fail(c, AMC_ERR_CAPACITY, "%zu wall hits, caller buffer holds %zu", k, cap);
-    std::vector<int> perm(k);
-    for (size_t u = 0; u < k; u++) perm[u] = (int)u;
-    std::sort(perm.begin(), perm.end(), [&](int a, int b) { return D.h_idx[s][a] < D.h_idx[s][b]; });   // ascending particle index
+    std::vector<int> perm;
+    temp_order(D.h_idx[s].data(), k, perm);
     for (size_t u = 0; u < k; u++) {
         const int r = perm[u];
         if (idx) idx[u] = D.h_idx[s][r];
@@ -294,7 +306,7 @@ int amc_temp_device_results(amc_ctx *c, int case_id, int32_t *idx, double *dpz, 
 
 int amc_temp_device_sums(amc_ctx *c, double *sums, int32_t *had)
 {
-    if (!c || !sums || !had || !c->TD.idx) return AMC_ERR_INVALID;
+    if (!c || !sums || !had || !c->TD.seg.idx) return AMC_ERR_INVALID;
     AMC_HIP(c, hipSetDevice(c->device));
     int rc = temp_dev_fetch(c);
     if (rc) return rc;
@@ -306,9 +318,7 @@ int amc_temp_device_sums(amc_ctx *c, double *sums, int32_t *had)
         const int case_id = 3 + s;
         const size_t k = (size_t)std::max(D.h_count[s], 0);
         if (!k) continue;
-        perm.resize(k);
-        for (size_t u = 0; u < k; u++) perm[u] = (int)u;
-        std::sort(perm.begin(), perm.end(), [&](int a, int b) { return D.h_idx[s][a] < D.h_idx[s][b]; });
+        temp_order(D.h_idx[s].data(), k, perm);
         double m_case = 0.0, e_case = 0.0;
         bool any = false;
         for (size_t u = 0; u < k; u++) {
@@ -330,24 +340,23 @@ int amc_temp_device_sums(amc_ctx *c, double *sums, int32_t *had)
 int amc_temp_device_draws(amc_ctx *c, int case_id, int32_t *idx, double *normal_xyz, double *contact_z, double *dir_xyz,
                           double *surface_energy, size_t cap, size_t *n)
 {
-    if (!c || !n || case_id < 3 || case_id > 9 || !c->TD.idx) return AMC_ERR_INVALID;
+    if (!c || !n || case_id < 3 || case_id > 9 || !c->TD.seg.idx) return AMC_ERR_INVALID;
     AMC_HIP(c, hipSetDevice(c->device));
     int rc = temp_dev_fetch(c);
     if (rc) return rc;
     amc_temp_dev_ws &D = c->TD;
     const int s = case_id - 3;
-    const size_t k = (size_t)std::max(D.h_count[s], 0), o = (size_t)s * (size_t)D.cap;
+    const size_t k = (size_t)std::max(D.h_count[s], 0), o = (size_t)s * (size_t)D.seg.cap;
     if (k > cap) return amc_fail(c, AMC_ERR_CAPACITY, "%zu wall hits, caller buffer holds %zu", k, cap);
     *n = k;
     if (!k) return AMC_OK;
     std::vector<double> hn(3 * k), hc(3 * k), hd(3 * k), he(k);
-    AMC_HIP(c, hipMemcpy(hn.data(), D.normal + 3 * o, sizeof(double) * 3 * k, hipMemcpyDeviceToHost));
-    AMC_HIP(c, hipMemcpy(hc.data(), D.contact + 3 * o, sizeof(double) * 3 * k, hipMemcpyDeviceToHost));
-    AMC_HIP(c, hipMemcpy(hd.data(), D.dir + 3 * o, sizeof(double) * 3 * k, hipMemcpyDeviceToHost));
-    AMC_HIP(c, hipMemcpy(he.data(), D.Es + o, sizeof(double) * k, hipMemcpyDeviceToHost));
-    std::vector<int> perm(k);
-    for (size_t u = 0; u < k; u++) perm[u] = (int)u;
-    std::sort(perm.begin(), perm.end(), [&](int a, int b) { return D.h_idx[s][a] < D.h_idx[s][b]; });
+    AMC_HIP(c, hipMemcpy(hn.data(), D.seg.normal + 3 * o, sizeof(double) * 3 * k, hipMemcpyDeviceToHost));
+    AMC_HIP(c, hipMemcpy(hc.data(), D.seg.contact + 3 * o, sizeof(double) * 3 * k, hipMemcpyDeviceToHost));
+    AMC_HIP(c, hipMemcpy(hd.data(), D.seg.dir + 3 * o, sizeof(double) * 3 * k, hipMemcpyDeviceToHost));
+    AMC_HIP(c, hipMemcpy(he.data(), D.seg.Es + o, sizeof(double) * k, hipMemcpyDeviceToHost));
+    std::vector<int> perm;
+    temp_order(D.h_idx[s].data(), k, perm);
     for (size_t u = 0; u < k; u++) {
         const int r = perm[u];
         if (idx) idx[u] = D.h_idx[s][r];
@@ -370,7 +379,7 @@ static int temp_run_ensure(amc_ctx *c, int64_t rows)
         amc_alloc_group group(c);
         int *perm, *ovf;
         amc_temp_pass *pass;
-        AMC_HIP(c, dalloc(c, &perm, (size_t)7 * (size_t)D.cap));
+        AMC_HIP(c, dalloc(c, &perm, (size_t)7 * (size_t)D.seg.cap));
         AMC_HIP(c, dalloc(c, &pass, 1));
         AMC_HIP(c, dalloc(c, &ovf, 4));
         group.keep();
@@ -391,20 +400,19 @@ int amc_temp_run_device(amc_ctx *c, double dt, int64_t nsteps, const amc_temp_rn
 {
     if (!c) return AMC_ERR_INVALID;
     if (c->P.geometry != AMC_GEOM_PORE_ENERGISED) return amc_fail(c, AMC_ERR_STATE, "amc_temp_run_device needs AMC_GEOM_PORE_ENERGISED");
-    if (!cfg || cfg->struct_size != (int32_t)sizeof(amc_temp_rng) || cfg->n_gl < 2 || cfg->n_gl > 32)
-        return amc_fail(c, AMC_ERR_INVALID, "amc_temp_rng: bad struct_size / n_gl");
+    int rc = temp_rng_check(c, cfg);
+    if (rc) return rc;
     if (nsteps < 0 || nsteps > 0x3fffffffLL) return amc_fail(c, AMC_ERR_INVALID, "amc_temp_run_device: nsteps %lld out of range", (long long)nsteps);
     if (!c->uploaded) return amc_fail(c, AMC_ERR_STATE, "amc_temp_run_device before amc_upload");
     if (c->lo != 0 || c->hi != c->n) return amc_fail(c, AMC_ERR_STATE, "amc_temp_run_device needs the whole index range in one context");
     AMC_HIP(c, hipSetDevice(c->device));
-    int rc = temp_dev_ensure(c);
-    if (rc) return rc;
+    if ((rc = temp_dev_ensure(c))) return rc;
     if ((rc = temp_run_ensure(c, std::max<int64_t>(nsteps, 1)))) return rc;
     amc_temp_dev_ws &D = c->TD;
     if ((rc = amc_flush(c))) return rc;
     D.series_n = 0;
     D.fetched = false;
-    c->T.pre_case = -1;
+    c->T.h.fresh();
     c->keep_prior = true;               // (as after amc_temp_begin)
     AMC_HIP(c, hipMemsetAsync(D.ovf, 0, 4 * sizeof(int), c->stream));
     const bool fuse = !c->allpairs;     // the detection grid's lists are filed by the last pass in front of the sweep
@@ -412,7 +420,7 @@ int amc_temp_run_device(amc_ctx *c, double dt, int64_t nsteps, const amc_temp_rn
     if (fused && nsteps > 0) {
         amc_temp_pass h;
         memset(&h, 0, sizeof h);
-        h.g = *cfg; h.D = amc_temp_segments(c);
+        h.g = *cfg; h.D = D.seg;
         AMC_HIP(c, hipMemcpyAsync(D.pass, &h, sizeof h, hipMemcpyHostToDevice, c->stream));
         AMC_HIP(c, hipStreamSynchronize(c->stream));        // (the source is this frame's)
     }
@@ -420,7 +428,7 @@ int amc_temp_run_device(amc_ctx *c, double dt, int64_t nsteps, const amc_temp_rn
     for (int64_t s = 0; s < nsteps; s++) {
         if (fused) {
             // ONE pass in front of the sweep: drift, cases 1-2, cases 3-9 with the device draws, recapture (Temp:804), filing
-            AMC_HIP(c, hipMemsetAsync(D.count, 0, sizeof(int) * 7, c->stream));
+            AMC_HIP(c, hipMemsetAsync(D.seg.count, 0, sizeof(int) * 7, c->stream));
             AMC_HIP(c, amc_launch_stream(c, dt, AMC_ST_DRIFT | AMC_ST_WALLS | AMC_ST_TEMP_CASES | AMC_ST_BOUNDS | (deferred ? AMC_ST_BOUNDS_PRE : 0),
                                          0, fuse));
         } else {
@@ -443,7 +451,7 @@ int amc_temp_run_device(amc_ctx *c, double dt, int64_t nsteps, const amc_temp_rn
     AMC_HIP(c, hipMemcpy(ovf, D.ovf, sizeof ovf, hipMemcpyDeviceToHost));
     if (ovf[0]) {
         D.series_n = 0;
-        return amc_fail(c, AMC_ERR_CAPACITY, "%d wall hits in case %d exceed the record capacity %d (step %d of the run)", ovf[2], ovf[0], D.cap, ovf[1]);
+        return amc_fail(c, AMC_ERR_CAPACITY, "%d wall hits in case %d exceed the record capacity %d (step %d of the run)", ovf[2], ovf[0], D.seg.cap, ovf[1]);
     }
     if (rc) D.series_n = 0;
     return rc;
@@ -483,7 +491,8 @@ int amc_temp_end(amc_ctx *c, amc_step_stats *out)
     if (!c || !c->uploaded) return AMC_ERR_STATE;
     AMC_HIP(c, hipSetDevice(c->device));
     if (c->P.geometry != AMC_GEOM_PORE_ENERGISED) return amc_fail(c, AMC_ERR_STATE, "amc_temp_end needs AMC_GEOM_PORE_ENERGISED");
-    c->T.pre_case = -1;
+    if (c->T.h.parked_case >= 0) return amc_fail(c, AMC_ERR_STATE, "amc_temp_end: case %d is still parked", c->T.h.parked_case);
+    c->T.h.ahead_case = -1;
     // the bounds pass before the sweep sees every particle at its final pre-sweep position: it builds the detection
     // grid's lists as well (like the fused streaming pass of the specular geometries)
     const bool fuse = !c->allpairs && c->lo == 0 && c->hi == c->n;

@@ -162,25 +162,15 @@ __global__ __launch_bounds__(256) void k_temp_all(amc_state S, amc_params P, amc
     if (q.nerr) atomicAdd(&O.banks[amc_bank_id()].n_fp_errors, (unsigned long long)q.nerr);
 }
 
-temp_dev_segments amc_temp_segments(amc_ctx *c)
-{
-    const amc_temp_dev_ws &D = c->TD;
-    temp_dev_segments G;
-    G.idx = D.idx; G.count = D.count; G.t = D.t; G.contact = D.contact; G.normal = D.normal; G.dir = D.dir;
-    G.Es = D.Es; G.dpz = D.dpz; G.dE = D.dE; G.ok = D.ok; G.cap = D.cap;
-    return G;
-}
-
 hipError_t amc_launch_temp_cases_device(amc_ctx *c, const amc_temp_rng *cfg)
 {
     const long long cnt = c->hi - c->lo;
-    amc_temp_dev_ws &D = c->TD;
+    const temp_dev_segments &D = c->TD.seg;
     hipError_t e = hipMemsetAsync(D.count, 0, sizeof(int) * 7, c->stream);
     if (e != hipSuccess || cnt <= 0) return e;
     if (!c->temp_unfused) {
-        const temp_dev_segments G = amc_temp_segments(c);
         AMC_LAUNCH(c, k_temp_all, dim3((unsigned)((cnt + 255) / 256)), dim3(256), c->S, c->P, c->out, *cfg,
-                           (unsigned int)c->out.step, c->lo, c->hi, G, c->d_cnt);
+                           (unsigned int)c->out.step, c->lo, c->hi, D, c->d_cnt);
         return hipGetLastError();
     }
     const unsigned rec_blocks = (unsigned)((D.cap + 255) / 256);
@@ -304,6 +294,6 @@ __global__ __launch_bounds__(AMC_TEMP_SUMS_THREADS) void k_temp_sums(temp_dev_se
 
 hipError_t amc_launch_temp_sums(amc_ctx *c, int64_t row)
 {
-    AMC_LAUNCH(c, k_temp_sums, dim3(1), dim3(AMC_TEMP_SUMS_THREADS), amc_temp_segments(c), c->TD.perm, c->TD.series, (int)row, c->TD.ovf);
+    AMC_LAUNCH(c, k_temp_sums, dim3(1), dim3(AMC_TEMP_SUMS_THREADS), c->TD.seg, c->TD.perm, c->TD.series, (int)row, c->TD.ovf);
     return hipGetLastError();
 }

@@ -148,6 +148,26 @@ struct amc_resolve_ws {
     uint8_t *cw_flag, *cw_moved;
 };
 
+// What the energised hand-over leaves pending between two of its calls (amc_api_temp.hip).  The rule:
+//   amc_wall_hits(case)       leaves the pending hits (hits_case, hits_n, perm); it uses up ahead_case when that is `case`.
+//   amc_wall_apply / _park    require hits_case == case and hits_n == n (else AMC_ERR_STATE) and clear hits_case; with n > 0 they
+//                             leave ahead_case = case + 1 (-1 after case 9).  amc_wall_park also requires that nothing is parked
+//                             and leaves the parked case (parked_case, parked_n, parked_perm).
+//   amc_wall_finish(case, n)  requires parked_case == case and parked_n == n (else AMC_ERR_STATE) and clears parked_case.
+//   amc_wall_hits_again       clears hits_case and ahead_case.
+// amc_temp_begin and amc_temp_run_device start from a fresh record (fresh(): the vectors keep their capacity): a step that
+// ended in an error leaves nothing behind.
+// amc_temp_end returns AMC_ERR_STATE, before it enqueues anything, while a case is still parked.
+struct amc_temp_handover {
+    int hits_case = -1, hits_n = 0;     // the pending amc_wall_hits
+    int ahead_case = -1;                // >= 0: the hits of this case are already in the records (launched behind the previous
+                                        // case's apply kernel: one synchronisation serves both)
+    std::vector<int> perm;              // sorted position -> record slot of the pending hits
+    int parked_case = -1, parked_n = 0; // the case between amc_wall_park and amc_wall_finish
+    std::vector<int> parked_perm;
+    void fresh() { hits_case = ahead_case = parked_case = -1; hits_n = parked_n = 0; perm.clear(); parked_perm.clear(); }
+};
+
 // energised-wall hand-over buffers (amc_energised.hip)
 struct amc_temp_ws {
     // The records live in ONE block of pinned host memory mapped into the device: the kernels write the (few hundred) hits of
@@ -160,17 +180,12 @@ struct amc_temp_ws {
     double *h_contact, *h_normal, *h_dir, *h_Es, *h_dpz, *h_dE;
     void *pin;
     int cap;
-    int last_case = -1, last_n = 0;  // the pending amc_wall_hits
-    int pre_case = -1;           // >= 0: the hits of this case are already in the records (launched behind the previous
-                                 // case's apply kernel: one synchronisation serves both)
-    std::vector<int> perm;       // sorted position -> record slot of the pending hits
     // a PARKED case (amc_wall_park / amc_wall_finish: the gap case while its surface energies are still being integrated):
     // particle (-1: failed solve) and direction of every hit in record order, the energies / results of the finishing kernel
     int *def_idx;
     double *def_dir, *def_Es, *def_dpz, *def_dE;    // (the last three: device views of pinned memory, host views below)
     double *h_def_Es, *h_def_dpz, *h_def_dE;
-    int def_case = -1, def_n = 0;
-    std::vector<int> def_perm;
+    amc_temp_handover h;
 };
 
 // device-RNG mode (amc_temp_cases_device): one record segment per energised case, kept until the next step
@@ -193,10 +208,7 @@ struct amc_temp_row {
     unsigned int pad;
 };
 struct amc_temp_dev_ws {
-    int *idx, *count;            // [7 * cap], [7]
-    double *t, *contact, *normal, *dir, *Es, *dpz, *dE;
-    unsigned char *ok;
-    int cap;                     // records per case
+    temp_dev_segments seg;       // idx ... ok: [7 * cap] ([7] count), cap records per case; idx is the guard of the allocation
     // the host-free run: its series (grown when a run needs more rows), the ordering scratch of a step with more hits than
     // the sums kernel's LDS tile, the first hit-record overflow (case, row, count; case 0: none) and the pass's constants
     amc_temp_row *series;
@@ -430,6 +442,5 @@ hipError_t amc_launch_temp_apply(amc_ctx *c, int case_id, int n, bool park = fal
 hipError_t amc_launch_temp_velocity(amc_ctx *c, int case_id, int n);
 hipError_t amc_launch_temp_cases_device(amc_ctx *c, const amc_temp_rng *cfg);
 hipError_t amc_launch_temp_sums(amc_ctx *c, int64_t row);     // the step's sums -> row `row` of the series (one workgroup)
-temp_dev_segments amc_temp_segments(amc_ctx *c);
 hipError_t amc_launch_kin_pack(amc_ctx *c, int world, int rank, int unpack);
 int amc_kin_banks(void);         // banks of the velocity-change list in an exchange block

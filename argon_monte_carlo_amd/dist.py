@@ -280,38 +280,33 @@ class _GlobalWallHooks:
 
     def __init__(self, engine, comm, rank):
         self.e, self.comm, self.rank = engine, comm, rank
-        # the gap case parked at its turn and finished after the last case (energised.drive_energised_cases), when the engine can
-        if hasattr(engine, "wall_park"):
-            self.early_gap = True
-            self.wall_park, self.wall_finish, self.wall_hits_again = self._wall_park, self._wall_finish, engine.wall_hits_again
-
-    def _wall_park(self, case, dirs):
-        self._parked = (self._off, self._cnt)
-        a, b = self._off, self._off + self._cnt
-        self.e.wall_park(case, np.asarray(dirs)[a:b])
-
-    def _wall_finish(self, case, Es):
-        a, b = self._parked[0], self._parked[0] + self._parked[1]
-        dpz, dE = self.e.wall_finish(case, np.asarray(Es)[a:b])
-        parts = self.comm.allgather_var(np.column_stack([dpz, dE]).reshape(-1, 2))
-        allr = np.concatenate(parts)
-        return allr[:, 0].copy(), allr[:, 1].copy()
+        if hasattr(engine, "wall_park"):        # (not the NumPy stand-in of tests/test_dist_gloo.py: it applies every case at its turn)
+            self.early_gap, self.wall_park, self.wall_finish = True, self._wall_park, self._wall_finish
+            self.wall_hits_again = engine.wall_hits_again
 
     def wall_hits(self, case):
         idx, normals, contact_z, ok = self.e.wall_hits(case)
         mine = np.column_stack([idx.astype(np.float64), normals.reshape(-1, 3), contact_z, ok.astype(np.float64)])
         parts = self.comm.allgather_var(mine.reshape(-1, 6))
-        self._off = sum(len(p) for p in parts[:self.rank])
-        self._cnt = len(parts[self.rank])
+        a = sum(len(p) for p in parts[:self.rank])
+        self._mine = slice(a, a + len(parts[self.rank]))        # this rank's hits among all
         allr = np.concatenate(parts) if parts else mine
         return allr[:, 0].astype(np.int32), allr[:, 1:4].copy(), allr[:, 4].copy(), allr[:, 5] != 0.0
 
-    def wall_apply(self, case, dirs, Es):
-        a, b = self._off, self._off + self._cnt
-        dpz, dE = self.e.wall_apply(case, np.asarray(dirs)[a:b], np.asarray(Es)[a:b])
-        parts = self.comm.allgather_var(np.column_stack([dpz, dE]).reshape(-1, 2))
-        allr = np.concatenate(parts)
+    def _gathered(self, dpz, dE):
+        allr = np.concatenate(self.comm.allgather_var(np.column_stack([dpz, dE]).reshape(-1, 2)))
         return allr[:, 0].copy(), allr[:, 1].copy()
+
+    def wall_apply(self, case, dirs, Es):
+        return self._gathered(*self.e.wall_apply(case, np.asarray(dirs)[self._mine], np.asarray(Es)[self._mine]))
+
+    # the gap case parked at its turn and finished after the last case (energised.drive_energised_cases)
+    def _wall_park(self, case, dirs):
+        self._parked = self._mine
+        self.e.wall_park(case, np.asarray(dirs)[self._mine])
+
+    def _wall_finish(self, case, Es):
+        return self._gathered(*self.e.wall_finish(case, np.asarray(Es)[self._parked]))
 
 
 class ShardedTemperatureSimulation(ShardedSimulation):

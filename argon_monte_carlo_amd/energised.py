@@ -322,33 +322,36 @@ class SurfaceEnergies:
             cls._pool = None
             cls._pool_owner = None
 
+    def _without_workers(self, zs):
+        """A dead worker: shut the pool down; this process does the integrals, now and from now on."""
+        import os
+        SurfaceEnergies._shutdown_pool()
+        os.environ["AMC_GAP_WORKERS"] = "0"
+        return [self.gap(z) for z in zs]
+
     def gap_many(self, z_values):
         """surface_energy_gap for every contact height of a case, in order (Temp:143-152 per hit)."""
         zs = [float(z) for z in z_values]
-        if len(zs) >= 2:
-            pool = self._get_pool()
-            if pool is not None:
-                try:
-                    return pool.map(zs)
-                except Exception:
-                    SurfaceEnergies._shutdown_pool()            # (a dead worker: this process does it, now and from now on)
-                    import os
-                    os.environ["AMC_GAP_WORKERS"] = "0"
-        return [self.gap(z) for z in zs]
+        pool = self._get_pool() if len(zs) >= 2 else None
+        if pool is None:
+            return [self.gap(z) for z in zs]
+        try:
+            return pool.map(zs)
+        except Exception:
+            return self._without_workers(zs)
 
     def gap_start(self, z_values):
         """Hand the contact heights of a case to the worker processes and return at once; ``gap_finish`` collects the
-        energies.  None when there are no workers (or nothing to do): the caller evaluates them when it needs them."""
+        energies (``gap_discard`` drops them).  None when there are no workers (or nothing to do): the caller evaluates
+        them when it needs them."""
         zs = [float(z) for z in z_values]
-        if not zs:
-            return None
-        pool = self._get_pool()
+        pool = self._get_pool() if zs else None
         if pool is None:
             return None
         try:
             return (pool, pool.start(zs), zs)
         except Exception:
-            SurfaceEnergies._shutdown_pool()
+            self._without_workers(())
             return None
 
     def gap_finish(self, handle):
@@ -356,10 +359,15 @@ class SurfaceEnergies:
         try:
             return pool.finish(count)
         except Exception:
-            SurfaceEnergies._shutdown_pool()            # (a dead worker: this process does it, now and from now on)
-            import os
-            os.environ["AMC_GAP_WORKERS"] = "0"
-            return [self.gap(z) for z in zs]
+            return self._without_workers(zs)
+
+    def gap_discard(self, handle):
+        """Read the answers to a ``gap_start`` that nobody wants (any more), so that they do not wait in the pipes for the
+        next ``gap_finish``; workers that do not answer are given up like any dead worker."""
+        try:
+            handle[0].finish(handle[1])
+        except Exception:
+            self._without_workers(())
 
     def gap(self, z_value):
         z_value = float(z_value)
@@ -428,15 +436,10 @@ class _GapWorkers:
                         pass
             for fd in (0, 1, 2):
                 os.dup2(null, fd)
-            st = self._struct
             while True:
-                buf = b""
-                while len(buf) < 8:
-                    chunk = os.read(req_r, 8 - len(buf))
-                    if not chunk:
-                        os._exit(0)                                         # the parent closed the pipe
-                    buf += chunk
-                os.write(ans_w, st.pack(energies.gap(st.unpack(buf)[0])))
+                os.write(ans_w, self._struct.pack(energies.gap(self._read(req_r))))
+        except EOFError:
+            pass                                                            # the parent closed the pipe
         except BaseException:
             code = 1
         finally:
@@ -452,47 +455,31 @@ class _GapWorkers:
                 return False
         return bool(self.workers)
 
-    def map(self, zs):
+    def _read(self, fd):
+        """One double from a pipe; EOFError when the other end is gone."""
         import os
-        st, nw = self._struct, len(self.workers)
-        out = [0.0] * len(zs)
-        for base in range(0, len(zs), nw):                       # one request in flight per worker
-            batch = zs[base:base + nw]
-            for k, z in enumerate(batch):
-                os.write(self.workers[k][1], st.pack(z))
-            for k in range(len(batch)):
-                buf = b""
-                while len(buf) < 8:
-                    chunk = os.read(self.workers[k][2], 8 - len(buf))
-                    if not chunk:
-                        raise RuntimeError("a gap-energy worker went away")
-                    buf += chunk
-                out[base + k] = st.unpack(buf)[0]
-        return out
+        buf = b""
+        while len(buf) < 8:
+            chunk = os.read(fd, 8 - len(buf))
+            if not chunk:
+                raise EOFError("a gap-energy worker went away")
+            buf += chunk
+        return self._struct.unpack(buf)[0]
+
+    def map(self, zs):
+        return self.finish(self.start(zs))
 
     # the two halves of map(), for callers that have something else to do while the workers integrate: every request is
     # written at once (worker k gets requests k, k + nw, ...: a pipe holds thousands of them and a worker answers in order),
     # the answers are read later
     def start(self, zs):
         import os
-        st, nw = self._struct, len(self.workers)
         for k, z in enumerate(zs):
-            os.write(self.workers[k % nw][1], st.pack(z))
+            os.write(self.workers[k % len(self.workers)][1], self._struct.pack(z))
         return len(zs)
 
     def finish(self, count):
-        import os
-        st, nw = self._struct, len(self.workers)
-        out = [0.0] * count
-        for k in range(count):
-            buf = b""
-            while len(buf) < 8:
-                chunk = os.read(self.workers[k % nw][2], 8 - len(buf))
-                if not chunk:
-                    raise RuntimeError("a gap-energy worker went away")
-                buf += chunk
-            out[k] = st.unpack(buf)[0]
-        return out
+        return [self._read(self.workers[k % len(self.workers)][2]) for k in range(count)]
 
     def close(self):
         import os
@@ -532,106 +519,10 @@ def format_mpf(value, is_zero_int):
     return str(mpf(float(value)))
 
 
-def drive_energised_cases(hooks, sampler, energies):
-    """The host loop over the seven energised cases of one step (Temp:705-758).
-
-    ``hooks.wall_hits(case)`` -> (idx, normals[n,3], contact_z[n], ok[n]) in ascending particle index;
-    ``hooks.wall_apply(case, dirs[n,3], Es[n])`` -> (dpz[n], dE[n]).  Returns (momentum, energy_cold, energy_hot,
-    had_momentum, had_cold, had_hot) for the step, accumulated in the reference's order.
-
-    Per hit the reference draws the direction first and evaluates the surface energy second (Temp:367-368 and
-    alike); the energy consumes no random numbers, so all directions of a case are drawn first (``sample_case``) and the
-    gap energies of the case are evaluated together afterwards (``gap_many``: worker processes when there are several)."""
-    # The gap case's integrals (mpmath.quad, ~1 ms each, five per step at N = 1e6) are half of the hand-over's host time.  Two
-    # things take them off the critical path; neither assumes anything that is not checked:
-    # * EARLY START.  The gap mask reads positions and prior positions only (Temp:720-721), and what the two cases before it
-    #   change — particles parked on the planes z = h_oa -+ r_ar outside the gap zone — cannot enter or leave it: the gap
-    #   case's hits are looked at once more ahead of case 3 (wall_hits changes nothing) and their contact heights go to the
-    #   worker processes.  When the gap case's turn comes its hits are taken again and the early energies are used only if
-    #   particle indices, contact heights and solve flags are identical.
-    # * PARKING.  At its turn the gap case is parked (hooks.wall_park: completed paths, counters, particles at their contact
-    #   points — all the following masks read) and finished (hooks.wall_finish: new velocities, dp_z) after case 9, when the
-    #   energies have had the whole hand-over to arrive.  A parked particle keeps its old velocity meanwhile; should a later
-    #   case hit one, the gap case is finished first and that case's hits are evaluated anew.
-    # The per-case sums are folded in case order at the end: the same additions in the same order as the reference's loop.
-    import os
-    part = {}                                   # case -> (m_case, e_case, any good hit)
-    early = None
-    can_park = hasattr(hooks, "wall_park") and os.environ.get("AMC_TEMP_NO_PARK") != "1"
-    force_redo = os.environ.get("AMC_TEMP_FORCE_GAP_REDO") == "1"       # (tests: take the finish-first path at the next case with hits)
-    if getattr(hooks, "early_gap", False) and hasattr(energies, "gap_start"):
-        e_idx, _, e_cz, e_ok = hooks.wall_hits(GAP_CASE)
-        if len(e_idx):
-            h = energies.gap_start(np.asarray(e_cz)[np.flatnonzero(np.asarray(e_ok))].tolist())
-            if h is not None:
-                early = (np.array(e_idx), np.array(e_cz), np.array(e_ok), h)
-    parked = None                               # (idx, good, energy handle or contact heights)
-
-    def finish_parked():
-        nonlocal parked
-        p_idx, p_good, p_src = parked
-        Es = np.zeros(len(p_idx))
-        Es[p_good] = energies.gap_finish(p_src) if isinstance(p_src, tuple) else energies.gap_many(p_src)
-        dpz, _ = hooks.wall_finish(GAP_CASE, Es)
-        part[GAP_CASE] = (sequential_sum(np.asarray(dpz, dtype=np.float64)[p_good].tolist()), None, len(p_good) > 0)
-        parked = None
-
-    with (sampler.session() if hasattr(sampler, "session") else _NoSession(sampler)):
-        for case in CASES:
-            idx, normals, contact_z, ok = hooks.wall_hits(case)
-            n = len(idx)
-            if parked is not None and n and (force_redo or np.intersect1d(parked[0], idx).size):
-                # a later case hits a parked particle: its contact solve needs the velocity the gap case gives it
-                force_redo = False
-                finish_parked()
-                hooks.wall_hits_again()
-                idx, normals, contact_z, ok = hooks.wall_hits(case)
-                n = len(idx)
-            if n == 0:
-                if case == GAP_CASE and early is not None:
-                    energies.gap_finish(early[3])           # (drain the workers' answers: nothing hit after all)
-                    early = None
-                continue
-            if hasattr(sampler, "sample_case"):
-                dirs = sampler.sample_case(normals, ok)
-            else:
-                dirs = np.zeros((n, 3))
-                for k in range(n):
-                    if ok[k]:                               # (else: the reference's try-block fails before any RNG draw)
-                        dirs[k] = sampler.random_inbounds_direction(np.array(normals[k]))
-            good = np.flatnonzero(np.asarray(ok))
-            Es = np.zeros(n)
-            if case == GAP_CASE:
-                src = None                                  # the energies: an early handle that matches, or still to be computed
-                if early is not None:
-                    if np.array_equal(early[0], idx) and np.array_equal(early[1], contact_z) and np.array_equal(early[2], ok):
-                        src = early[3]
-                    else:
-                        energies.gap_finish(early[3])       # (discarded)
-                    early = None
-                zs = np.asarray(contact_z)[good].tolist()
-                if can_park:
-                    if src is None and hasattr(energies, "gap_start"):
-                        src = energies.gap_start(zs)
-                    hooks.wall_park(case, dirs)
-                    parked = (np.array(idx), good, src if src is not None else zs)
-                    continue
-                if src is not None:
-                    Es[good] = energies.gap_finish(src)
-                elif hasattr(energies, "gap_many"):
-                    Es[good] = energies.gap_many(zs)
-                else:
-                    for k in good:
-                        Es[k] = energies.gap(contact_z[k])
-            else:
-                Es[good] = energies.cold if case in COLD_CASES else energies.hot
-            dpz, dE = hooks.wall_apply(case, dirs, Es)
-            # (left-to-right sums over plain Python floats: the same additions in the same order as the reference's loop)
-            m_case = sequential_sum(np.asarray(dpz, dtype=np.float64)[good].tolist())
-            e_case = None if case == GAP_CASE else sequential_sum(np.asarray(dE, dtype=np.float64)[good].tolist())
-            part[case] = (m_case, e_case, len(good) > 0)
-        if parked is not None:
-            finish_parked()
+def fold_case_parts(part):
+    """(momentum, energy_cold, energy_hot, had_momentum, had_cold, had_hot) of a step from ``part[case]`` = (m_case, e_case,
+    any good hit) of the cases that had hits, folded in the cases' order: the additions of the reference's loop, in its
+    order (Temp:708-753; the gap case adds momentum only)."""
     mom = cold = hot = 0
     had_m = had_c = had_h = False
     for case in CASES:
@@ -649,15 +540,108 @@ def drive_energised_cases(hooks, sampler, energies):
     return mom, cold, hot, had_m, had_c, had_h
 
 
-class _NoSession:
-    def __init__(self, sampler):
-        self.sampler = sampler
+def drive_energised_cases(hooks, sampler, energies):
+    """The host loop over the seven energised cases of one step (Temp:705-758).  Returns (momentum, energy_cold, energy_hot,
+    had_momentum, had_cold, had_hot) for the step, accumulated in the reference's order.
 
-    def __enter__(self):
-        return self.sampler
+    The protocol.  ``sampler`` is a ``DirectionSampler``, ``energies`` a ``SurfaceEnergies``; ``hooks`` (an
+    ``engine.EnergisedEngine``, ``dist._GlobalWallHooks``) has
+    ``wall_hits(case)`` -> (idx, normals[n,3], contact_z[n], ok[n]) in ascending particle index, changing nothing;
+    ``wall_apply(case, dirs[n,3], Es[n])`` -> (dpz[n], dE[n]);
+    ``wall_park(case, dirs)`` and ``wall_finish(case, Es)`` -> (dpz[n], dE[n]): the two halves of ``wall_apply``;
+    ``wall_hits_again()``: the next ``wall_hits`` evaluates its case anew;
+    ``early_gap``: true when ``wall_hits`` may be called ahead of a case's turn.
+    Two stand-ins are accepted because the sharded driver is tested over gloo with a NumPy engine and constant energies
+    (tests/test_dist_gloo.py): hooks without ``wall_park`` and ``early_gap`` (then nothing is parked or looked at early) and
+    energies that have only ``cold``, ``hot`` and ``gap`` (then every gap energy is ``gap(z)``, in order).
 
-    def __exit__(self, *exc):
-        return False
+    Per hit the reference draws the direction first and evaluates the surface energy second (Temp:367-368 and
+    alike); the energy consumes no random numbers, so all directions of a case are drawn first (``sample_case``) and the
+    gap energies of the case are evaluated together afterwards (``gap_many``: worker processes when there are several).
+
+    A step that fails leaves nothing behind: when an exception passes through, the answers to an energy handle that is
+    still outstanding are read and dropped (``gap_discard``), and ``amc_temp_begin`` forgets the parked case."""
+    # The gap case's integrals (mpmath.quad, ~1 ms each, five per step at N = 1e6) are half of the hand-over's host time.  Two
+    # things take them off the critical path; neither assumes anything that is not checked:
+    # * EARLY START.  The gap mask reads positions and prior positions only (Temp:720-721), and what the two cases before it
+    #   change — particles parked on the planes z = h_oa -+ r_ar outside the gap zone — cannot enter or leave it: the gap
+    #   case's hits are looked at once more ahead of case 3 (wall_hits changes nothing) and their contact heights go to the
+    #   worker processes.  When the gap case's turn comes its hits are taken again and the early energies are used only if
+    #   particle indices, contact heights and solve flags are identical.
+    # * PARKING.  At its turn the gap case is parked (hooks.wall_park: completed paths, counters, particles at their contact
+    #   points — all the following masks read) and finished (hooks.wall_finish: new velocities, dp_z) after case 9, when the
+    #   energies have had the whole hand-over to arrive.  A parked particle keeps its old velocity meanwhile; should a later
+    #   case hit one, the gap case is finished first and that case's hits are evaluated anew.
+    # The per-case sums are folded in case order at the end: the same additions in the same order as the reference's loop.
+    import os
+    workers = hasattr(energies, "gap_start")            # (else: a stand-in with gap(z) alone)
+    can_park = hasattr(hooks, "wall_park") and os.environ.get("AMC_TEMP_NO_PARK") != "1"
+    force_redo = os.environ.get("AMC_TEMP_FORCE_GAP_REDO") == "1"       # (tests: take the finish-first path at the next case with hits)
+    part = {}                                   # case -> (m_case, e_case, any good hit)
+    early = None                                # (idx, contact_z, ok, energy handle) of the gap case's hits ahead of case 3
+    parked = None                               # (idx, good, energy handle or contact heights)
+
+    gap_many = energies.gap_many if workers else (lambda zs: [energies.gap(z) for z in zs])
+
+    def finish_parked():
+        nonlocal parked
+        (p_idx, p_good, p_src), parked = parked, None
+        Es = np.zeros(len(p_idx))
+        Es[p_good] = energies.gap_finish(p_src) if isinstance(p_src, tuple) else gap_many(p_src)
+        dpz, _ = hooks.wall_finish(GAP_CASE, Es)
+        part[GAP_CASE] = (sequential_sum(np.asarray(dpz, dtype=np.float64)[p_good].tolist()), None, len(p_good) > 0)
+
+    try:
+        if workers and getattr(hooks, "early_gap", False):
+            e_idx, _, e_cz, e_ok = hooks.wall_hits(GAP_CASE)
+            if len(e_idx):
+                h = energies.gap_start(np.asarray(e_cz)[np.flatnonzero(np.asarray(e_ok))].tolist())
+                if h is not None:
+                    early = (np.array(e_idx), np.array(e_cz), np.array(e_ok), h)
+        with sampler.session():
+            for case in CASES:
+                idx, normals, contact_z, ok = hooks.wall_hits(case)
+                n = len(idx)
+                if parked is not None and n and (force_redo or np.intersect1d(parked[0], idx).size):
+                    # a later case hits a parked particle: its contact solve needs the velocity the gap case gives it
+                    force_redo = False
+                    finish_parked()
+                    hooks.wall_hits_again()
+                    idx, normals, contact_z, ok = hooks.wall_hits(case)
+                    n = len(idx)
+                src = None                                  # the gap energies: an early handle that matches, or still to be computed
+                if case == GAP_CASE and early is not None:
+                    e, early = early, None
+                    if n and np.array_equal(e[0], idx) and np.array_equal(e[1], contact_z) and np.array_equal(e[2], ok):
+                        src = e[3]
+                    else:
+                        energies.gap_discard(e[3])          # (other hits, or none after all)
+                if n == 0:
+                    continue
+                dirs = sampler.sample_case(normals, ok)
+                good = np.flatnonzero(np.asarray(ok))
+                Es = np.zeros(n)
+                if case == GAP_CASE:
+                    zs = np.asarray(contact_z)[good].tolist()
+                    if can_park:
+                        parked = (np.array(idx), good, src or (workers and energies.gap_start(zs)) or zs)
+                        hooks.wall_park(case, dirs)
+                        continue
+                    Es[good] = energies.gap_finish(src) if src is not None else gap_many(zs)
+                else:
+                    Es[good] = energies.cold if case in COLD_CASES else energies.hot
+                dpz, dE = hooks.wall_apply(case, dirs, Es)
+                # (left-to-right sums over plain Python floats: the same additions in the same order as the reference's loop)
+                m_case = sequential_sum(np.asarray(dpz, dtype=np.float64)[good].tolist())
+                e_case = None if case == GAP_CASE else sequential_sum(np.asarray(dE, dtype=np.float64)[good].tolist())
+                part[case] = (m_case, e_case, len(good) > 0)
+            if parked is not None:
+                finish_parked()
+    finally:
+        for h in (early and early[3], parked and parked[2]):        # (both None unless an exception is passing through)
+            if isinstance(h, tuple):
+                energies.gap_discard(h)
+    return fold_case_parts(part)
 
 
 def device_rng_config(consts, seed, n_gl=32):
@@ -682,19 +666,10 @@ def sum_device_cases(results):
     """Per-step sums from the per-hit results of the seven cases, accumulated like drive_energised_cases does
     (left-to-right in ascending particle index within a case, cases in Temp:708-751 order).  ``results[case]`` =
     (dpz, dE, ok)."""
-    mom = cold = hot = 0
-    had_m = had_c = had_h = False
+    part = {}
     for case in CASES:
         dpz, dE, ok = results[case]
         good = [k for k in range(len(ok)) if ok[k]]
-        if len(ok) == 0:
-            continue
-        mom = mom + sequential_sum(dpz[k] for k in good)
-        had_m = had_m or len(good) > 0
-        if case in COLD_CASES:
-            cold = cold + sequential_sum(dE[k] for k in good)
-            had_c = had_c or len(good) > 0
-        elif case in HOT_CASES:
-            hot = hot + sequential_sum(dE[k] for k in good)
-            had_h = had_h or len(good) > 0
-    return mom, cold, hot, had_m, had_c, had_h
+        if len(ok):
+            part[case] = (sequential_sum(dpz[k] for k in good), sequential_sum(dE[k] for k in good), len(good) > 0)
+    return fold_case_parts(part)

@@ -294,14 +294,17 @@ class EnergisedEngine(Engine):
         ok = np.any(nm != 0.0, axis=1)          # a zero normal marks a failed contact solve (Temp:472-474)
         return idx[:k].copy(), nm, cz[:k].copy(), ok
 
-    def wall_apply(self, case, dirs, Es):
-        dirs = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+    def _wall_results(self, call, case, dirs, Es):
+        """amc_wall_apply / amc_wall_finish (the latter takes no directions) -> (dpz[n], dE[n])"""
         Es = np.ascontiguousarray(Es, dtype=np.float64)
         n = len(Es)
-        dpz = np.zeros(max(1, n))
-        dE = np.zeros(max(1, n))
-        self._ck(self.lib.amc_wall_apply(self._ctx, int(case), _d(dirs), _d(Es), n, _d(dpz), _d(dE)))
+        dpz, dE = np.zeros(max(1, n)), np.zeros(max(1, n))
+        self._ck(call(self._ctx, int(case), *dirs, _d(Es), n, _d(dpz), _d(dE)))
         return dpz[:n], dE[:n]
+
+    def wall_apply(self, case, dirs, Es):
+        dirs = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+        return self._wall_results(self.lib.amc_wall_apply, case, (_d(dirs),), Es)
 
     # a case parked while its surface energies are still being integrated (energised.drive_energised_cases)
     def wall_park(self, case, dirs):
@@ -309,12 +312,7 @@ class EnergisedEngine(Engine):
         self._ck(self.lib.amc_wall_park(self._ctx, int(case), _d(dirs), len(dirs)))
 
     def wall_finish(self, case, Es):
-        Es = np.ascontiguousarray(Es, dtype=np.float64)
-        n = len(Es)
-        dpz = np.zeros(max(1, n))
-        dE = np.zeros(max(1, n))
-        self._ck(self.lib.amc_wall_finish(self._ctx, int(case), _d(Es), n, _d(dpz), _d(dE)))
-        return dpz[:n], dE[:n]
+        return self._wall_results(self.lib.amc_wall_finish, case, (), Es)
 
     def wall_hits_again(self):
         self._ck(self.lib.amc_wall_hits_again(self._ctx))

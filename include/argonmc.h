@@ -220,6 +220,14 @@ int amc_wall_apply(amc_ctx *ctx, int case_id, const double *dir_xyz, const doubl
 int amc_wall_park(amc_ctx *ctx, int case_id, const double *dir_xyz, size_t n);
 int amc_wall_finish(amc_ctx *ctx, int case_id, const double *surface_energy, size_t n, double *dpz, double *dE);
 int amc_wall_hits_again(amc_ctx *ctx);
+/* What these calls leave pending between each other, per context:
+ *   amc_wall_hits(case)            leaves the pending hits of `case` (and their count n);
+ *   amc_wall_apply / amc_wall_park require that (case_id, n) are the pending hits', else AMC_ERR_STATE, and use them up;
+ *                                  amc_wall_park also requires that no case is parked, and leaves `case_id` parked;
+ *   amc_wall_finish(case, n)       requires that (case_id, n) are the parked case's, else AMC_ERR_STATE, and uses it up;
+ *   amc_wall_hits_again            drops the pending hits.
+ * amc_temp_begin (and amc_temp_run_device) start from nothing pending, whatever the step before left: a step that ended
+ * in an error needs no clean-up.  amc_temp_end returns AMC_ERR_STATE, before it enqueues anything, while a case is parked. */
 /* recapture (Temp:804) -> p-p sweep (Temp:813-842) -> recapture (Temp:844); returns the step's counters */
 int amc_temp_end(amc_ctx *ctx, amc_step_stats *out);
 

@@ -484,6 +484,100 @@ def test_gap_case_parked_and_finished_later_equals_oracle(O, monkeypatch, mode):
     eng.close()
 
 
+def test_a_failed_energised_step_leaves_nothing_behind(O, golden_dir, monkeypatch):
+    """A step that raises after the gap case was parked must not poison the context or the worker pipes.  The golden run
+    (N = 2,000, sigma x 100) is driven in lockstep with the oracle to s*, its first step with a gap hit (found from the
+    oracle's own run); there wall_apply raises at the first case after the park.  amc_temp_end on that mid-step context
+    is AMC_ERR_STATE; then the SAME engine, samplers' seeds and SurfaceEnergies run s* + 1 steps from the initial state
+    again: state, counters and the six sums equal a fresh oracle's bit for bit at every step."""
+    import ctypes
+    import random
+    from argon_monte_carlo_amd._abi import AMC_ERR_STATE, AmcStepStats
+    from argon_monte_carlo_amd.energised import DirectionSampler, SurfaceEnergies, drive_energised_cases
+    from argon_monte_carlo_amd.engine import EnergisedEngine
+    from oracle import temp_host as TH
+    from tests.test_oracle_steps import restore_rngs, temp_setup
+    Gs = load_step(golden_dir, "step_temp_a.npz")
+    p, c, dt, _, energies = temp_setup(Gs)
+    init = [Gs[f"s-001_{k}"] for k in STATE_KEYS]
+    p.reserved0 |= 1
+    restore_rngs(Gs)
+    st_np, st_py = np.random.get_state(), random.getstate()
+
+    def reseed(sampler):
+        sampler.np_rng.set_state(st_np)
+        sampler.py_rng.setstate(st_py)
+        return sampler
+
+    class CountingEnergies(TH.Energies):        # (the oracle's own energies: it uses an object of this class as it is)
+        gap_calls = 0
+
+        def gap(self, z):
+            self.gap_calls += 1
+            return super().gap(z)
+
+    # the reference: a fresh oracle up to and including its first step with a gap hit
+    orc = O.Oracle(p, mode="mul")
+    orc.upload(*init[:10], flag=init[10])
+    s_orc, e_orc = reseed(DirectionSampler(np.random.RandomState(), random.Random())), CountingEnergies(c)
+    ref = []
+    for s in range(Gs["per_step"].shape[0]):
+        rc, so, *sums = orc.temp_timestep(dt, s_orc, e_orc)
+        assert rc == 0
+        ref.append((so, tuple(sums), orc.state()))
+        if e_orc.gap_calls:
+            break
+    assert e_orc.gap_calls, "no gap hit in the golden run"
+    s_star = len(ref) - 1
+
+    def step_equals_reference(eng, s_dev, s, ctx):
+        st, *sums = eng.temp_timestep(dt, s_dev, energies)
+        so, sums_o, state_o = ref[s]
+        for k in ("n_pp", "n_wall", "n_oob_walls", "n_oob_pp", "n_paths", "n_fp_errors"):
+            assert st[k] == so[k], (ctx, s, k, st, so)
+        assert tuple(sums) == sums_o, (ctx, s)
+        assert_state_equal(eng.download(), state_o, (ctx, s))
+
+    class Boom(RuntimeError):
+        pass
+
+    monkeypatch.setenv("AMC_GAP_WORKERS", "2")
+    eng = EnergisedEngine(p)
+    eng.upload(*init[:10], flag=init[10])
+    s_dev = reseed(DirectionSampler(np.random.RandomState(), random.Random()))
+    try:
+        for s in range(s_star):
+            step_equals_reference(eng, s_dev, s, "lockstep")
+        # step s*: the gap case is parked, the next case with hits fails
+        parked = []
+        park, apply = eng.wall_park, eng.wall_apply
+
+        def wall_park(case, dirs):
+            parked.append(case)
+            return park(case, dirs)
+
+        def wall_apply(case, dirs, Es):
+            if parked:
+                raise Boom(case)
+            return apply(case, dirs, Es)
+        eng.wall_park, eng.wall_apply = wall_park, wall_apply
+        eng.temp_begin(dt)
+        with pytest.raises(Boom):
+            drive_energised_cases(eng, s_dev, energies)
+        assert parked == [5]
+        del eng.wall_park, eng.wall_apply
+        assert eng.lib.amc_temp_end(eng._ctx, ctypes.byref(AmcStepStats())) == AMC_ERR_STATE
+        # the same engine, seeds and energies, from the start
+        eng.upload(*init[:10], flag=init[10])
+        eng.reset_outputs()
+        reseed(s_dev)
+        for s in range(s_star + 1):
+            step_equals_reference(eng, s_dev, s, "again")
+    finally:
+        SurfaceEnergies._shutdown_pool()
+    eng.close()
+
+
 # ---------------------------------------------------------------------------------------------- edge cases
 @pytest.mark.parametrize("n", [0, 1, 2, 3, 17])
 @pytest.mark.parametrize("kind", ["cube", "pore"])

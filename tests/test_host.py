@@ -339,3 +339,48 @@ def test_philox_reference_known_answers():
     assert philox4x32_10([0xffffffff] * 4, [0xffffffff] * 2) == [0x408f276d, 0x41c83b0e, 0xa20bc7c6, 0x6d5451fd]
     assert philox4x32_10([0x243f6a88, 0x85a308d3, 0x13198a2e, 0x03707344], [0xa4093822, 0x299f31d0]) == \
         [0xd16cfe09, 0x94fdcceb, 0x5001e420, 0x24126ea1]
+
+
+@pytest.mark.parametrize("early_gap", [True, False])
+def test_a_failed_energised_step_leaves_no_gap_answers_behind(monkeypatch, early_gap):
+    """drive_energised_cases unwinds: a step that raises while the gap case is parked (its energies asked of the worker
+    processes, ahead of case 3 or at the case's turn) drains the workers' answers, so the next gap_start / gap_finish /
+    gap_many on the same SurfaceEnergies return exactly the energies of the heights THEY ask for."""
+    import random
+    from argon_monte_carlo_amd.energised import GAP_CASE, DirectionSampler, SurfaceEnergies, drive_energised_cases
+    _, c = PR.pore_params(n=100, energised=True)
+    z0 = c["open_air_height"] + c["hot_coating_height"]
+
+    class Boom(RuntimeError):
+        pass
+
+    class Hooks:
+        parked = None
+
+        def wall_hits(self, case):
+            n = 1 if case in (GAP_CASE, 7) else 0
+            return (np.full(n, 10 + case, dtype=np.int32), np.tile([0.0, 0.0, 1.0], (n, 1)),
+                    np.full(n, z0 + 0.25 * c["gap_height"]), np.ones(n, dtype=bool))
+
+        def wall_park(self, case, dirs):
+            self.parked = case
+
+        def wall_apply(self, case, dirs, Es):
+            raise Boom(case)
+
+    hooks = Hooks()
+    hooks.early_gap = early_gap
+    monkeypatch.setenv("AMC_GAP_WORKERS", "2")
+    en = SurfaceEnergies(c)
+    zs = [z0 + f * c["gap_height"] for f in (0.6, 0.1, 0.9)]
+    want = [en.gap(z) for z in zs]
+    assert en.gap(z0 + 0.25 * c["gap_height"]) not in want
+    try:
+        with pytest.raises(Boom, match="7"):
+            drive_energised_cases(hooks, DirectionSampler(np.random.RandomState(1), random.Random(1)), en)
+        assert hooks.parked == GAP_CASE
+        h = en.gap_start(zs)
+        assert h is not None and en.gap_finish(h) == want
+        assert en.gap_many(zs) == want
+    finally:
+        SurfaceEnergies._shutdown_pool()

@@ -37,7 +37,7 @@ def wrap(obj, name, label=None):
 
 for m in ("temp_begin", "wall_hits", "wall_apply", "wall_park", "wall_finish", "temp_end"):
     wrap(e, m)
-for m in ("gap_start", "gap_finish", "gap_many"):
+for m in ("gap_start", "gap_finish", "gap_discard", "gap_many"):
     wrap(energies, m)
 wrap(sampler, "sample_case")
 steps, warm = 50, 10
