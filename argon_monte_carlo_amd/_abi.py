@@ -94,6 +94,15 @@ class AmcFieldGrid(C.Structure):
                 ("lo", C.c_double * 3), ("hi", C.c_double * 3)]
 
 
+AMC_SURFACE_CASES = 7
+AMC_SURFACE_MAX_BINS = 256
+
+
+class AmcSurfaceGrid(C.Structure):
+    """amc_surface_grid (include/argonmc.h): the wall bins of the sampled surfaces, [case - 3] per energised case."""
+    _fields_ = [("struct_size", C.c_int32), ("nbins", C.c_int32), ("lo", C.c_double * 7), ("hi", C.c_double * 7)]
+
+
 # numpy dtype with the same layout as amc_path_record
 def path_record_dtype():
     import numpy as np

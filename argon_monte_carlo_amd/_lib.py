@@ -8,7 +8,8 @@ import ctypes as C
 import os
 import subprocess
 
-from ._abi import (AMC_ABI_VERSION, AmcFieldGrid, AmcIcConfig, AmcParams, AmcPathRecord, AmcStepStats, AmcTempRng)
+from ._abi import (AMC_ABI_VERSION, AmcFieldGrid, AmcIcConfig, AmcParams, AmcPathRecord, AmcStepStats, AmcSurfaceGrid,
+                   AmcTempRng)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libargonmc.so")
@@ -80,6 +81,12 @@ SIGNATURES = {
     "amc_fields_read": (C.c_int, [_ctx, _i64p, _i64p, _i64p]),
     "amc_fields_load": (C.c_int, [_ctx, _i64p, C.c_int64, C.c_int64]),
     "amc_fields_reset": (C.c_int, [_ctx]),
+    "amc_surface_config": (C.c_int, [_ctx, C.POINTER(AmcSurfaceGrid)]),
+    "amc_surface_read": (C.c_int, [_ctx, _i64p, _i64p, _i64p]),
+    "amc_surface_load": (C.c_int, [_ctx, _i64p, _i64p, C.c_int64]),
+    "amc_surface_reset": (C.c_int, [_ctx]),
+    "amc_temp_device_contacts": (C.c_int, [_ctx, C.c_int, _i32p, _dp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "amc_wall_contacts": (C.c_int, [_ctx, C.c_int, _dp, C.c_size_t]),
 }
 
 

@@ -146,6 +146,7 @@ int amc_wall_apply(amc_ctx *c, int case_id, const double *dir_xyz, const double 
     if (!dir_xyz || !surface_energy) return AMC_ERR_INVALID;
     temp_scatter(T, dir_xyz, surface_energy, n);
     AMC_HIP(c, amc_launch_temp_apply(c, case_id, (int)n));
+    if (c->SF.on) AMC_HIP(c, amc_launch_surface_case(c, case_id, (int)n));      // (in front of the next case's hits: they reuse the records)
     if ((rc = temp_hits_sync(c, case_id + 1))) return rc;
     T.h.ahead_case = case_id < 9 ? case_id + 1 : -1;
     temp_gather(T.h.perm, n, T.h_dpz, T.h_dE, dpz, dE);
@@ -173,6 +174,7 @@ int amc_wall_park(amc_ctx *c, int case_id, const double *dir_xyz, size_t n)
     if (!dir_xyz) return AMC_ERR_INVALID;
     temp_scatter(T, dir_xyz, nullptr, n);
     AMC_HIP(c, amc_launch_temp_apply(c, case_id, (int)n, true));
+    if (c->SF.on && (rc = amc_surface_park(c, case_id, (int)n))) return rc;     // (the contact points do not outlive the next case's hits)
     H.parked_n = (int)n; H.parked_perm = H.perm;
     if ((rc = temp_hits_sync(c, case_id + 1))) return rc;
     H.ahead_case = case_id < 9 ? case_id + 1 : -1;
@@ -192,6 +194,7 @@ int amc_wall_finish(amc_ctx *c, int case_id, const double *surface_energy, size_
     if (!surface_energy) return AMC_ERR_INVALID;
     for (size_t s = 0; s < n; s++) T.h_def_Es[H.parked_perm[s]] = surface_energy[s];
     AMC_HIP(c, amc_launch_temp_velocity(c, case_id, (int)n));
+    if (c->SF.on) AMC_HIP(c, amc_launch_surface_finish(c, case_id, (int)n));
     AMC_HIP(c, hipStreamSynchronize(c->stream));
     temp_gather(H.parked_perm, n, T.h_def_dpz, T.h_def_dE, dpz, dE);
     return AMC_OK;
@@ -241,6 +244,7 @@ int amc_temp_cases_device(amc_ctx *c, const amc_temp_rng *cfg)
     if (!c->keep_prior) return amc_fail(c, AMC_ERR_STATE, "amc_temp_cases_device follows amc_temp_begin");
     c->TD.fetched = false;
     AMC_HIP(c, amc_launch_temp_cases_device(c, cfg));
+    if (c->SF.on) AMC_HIP(c, amc_launch_surface_device(c));
     return AMC_OK;
 }
 
@@ -370,6 +374,45 @@ int amc_temp_device_draws(amc_ctx *c, int case_id, int32_t *idx, double *normal_
     return AMC_OK;
 }
 
+// contact points of the last device-RNG step's hits of a case, ascending particle index (sampled surfaces: inspection)
+int amc_temp_device_contacts(amc_ctx *c, int case_id, int32_t *idx, double *contact_xyz, size_t cap, size_t *n)
+{
+    if (!c || !n || case_id < 3 || case_id > 9 || !c->TD.seg.idx) return AMC_ERR_INVALID;
+    AMC_HIP(c, hipSetDevice(c->device));
+    int rc = temp_dev_fetch(c);
+    if (rc) return rc;
+    amc_temp_dev_ws &D = c->TD;
+    const int s = case_id - 3;
+    const size_t k = (size_t)std::max(D.h_count[s], 0), o = (size_t)s * (size_t)D.seg.cap;
+    if (k > cap) return amc_fail(c, AMC_ERR_CAPACITY, "%zu wall hits, caller buffer holds %zu", k, cap);
+    *n = k;
+    if (!k) return AMC_OK;
+    std::vector<double> hc(3 * k);
+    AMC_HIP(c, hipMemcpy(hc.data(), D.seg.contact + 3 * o, sizeof(double) * 3 * k, hipMemcpyDeviceToHost));
+    std::vector<int> perm;
+    temp_order(D.h_idx[s].data(), k, perm);
+    for (size_t u = 0; u < k; u++) {
+        const int r = perm[u];
+        if (idx) idx[u] = D.h_idx[s][r];
+        for (int e = 0; e < 3 && contact_xyz; e++) contact_xyz[3 * u + e] = hc[3 * r + e];
+    }
+    return AMC_OK;
+}
+
+// ... and of the pending amc_wall_hits, in its order
+int amc_wall_contacts(amc_ctx *c, int case_id, double *contact_xyz, size_t cap)
+{
+    if (!c || !contact_xyz) return AMC_ERR_INVALID;
+    const amc_temp_ws &T = c->T;
+    const amc_temp_handover &H = T.h;
+    if (!T.idx || H.hits_case != case_id)
+        return amc_fail(c, AMC_ERR_STATE, "amc_wall_contacts(case %d): the pending amc_wall_hits is of case %d", case_id, H.hits_case);
+    if ((size_t)H.hits_n > cap) return amc_fail(c, AMC_ERR_CAPACITY, "%d wall hits, caller buffer holds %zu", H.hits_n, cap);
+    for (int s = 0; s < H.hits_n; s++)
+        for (int e = 0; e < 3; e++) contact_xyz[3 * s + e] = T.h_contact[3 * H.perm[s] + e];
+    return AMC_OK;
+}
+
 // ---- the host-free run of the device-RNG mode ------------------------------------------------------------------------------
 // the series buffer for `rows` steps, the ordering scratch and the overflow words of the sums kernel, the pass's constants
 static int temp_run_ensure(amc_ctx *c, int64_t rows)
@@ -438,17 +481,20 @@ int amc_temp_run_device(amc_ctx *c, double dt, int64_t nsteps, const amc_temp_rn
             AMC_HIP(c, amc_launch_stream(c, 0.0, AMC_ST_BOUNDS, 0, fuse));
         }
         AMC_HIP(c, amc_launch_temp_sums(c, s));
+        if (c->SF.on) AMC_HIP(c, amc_launch_surface_device(c));     // (in front of the next step's pass, which clears seg.count)
         if ((rc = amc_enqueue_sweep(c, fuse))) return rc;                               // Temp:813-842
         // a sampled step and the last one end with the state everybody reads: their recapture is a pass of its own
         deferred = fused && s + 1 < nsteps && !amc_fields_due(c, (int64_t)c->out.step + 1);
         if (!deferred) AMC_HIP(c, amc_launch_stream(c, 0.0, AMC_ST_BOUNDS, 1));       // Temp:844
         c->out.step++;
+        if (c->SF.on) c->SF.n_steps++;
         if ((rc = amc_fields_step(c))) return rc;
     }
     D.series_n = nsteps;
     rc = amc_finish_stats(c, sum);      // the one synchronisation; overflow flags and counters of the whole run
     int ovf[4] = {0, 0, 0, 0};
     AMC_HIP(c, hipMemcpy(ovf, D.ovf, sizeof ovf, hipMemcpyDeviceToHost));
+    if (ovf[0] || rc == AMC_ERR_CAPACITY) c->SF.lost = c->SF.on;     // hits are missing from the sampled surfaces
     if (ovf[0]) {
         D.series_n = 0;
         return amc_fail(c, AMC_ERR_CAPACITY, "%d wall hits in case %d exceed the record capacity %d (step %d of the run)", ovf[2], ovf[0], D.seg.cap, ovf[1]);
@@ -501,8 +547,11 @@ int amc_temp_end(amc_ctx *c, amc_step_stats *out)
     if (rc) return rc;
     AMC_HIP(c, amc_launch_stream(c, 0.0, AMC_ST_BOUNDS, 1));        // Temp:844
     c->out.step++;
+    if (c->SF.on) c->SF.n_steps++;
     if ((rc = amc_fields_step(c))) return rc;
-    return amc_finish_stats(c, out);
+    rc = amc_finish_stats(c, out);
+    if (rc == AMC_ERR_CAPACITY) c->SF.lost = c->SF.on;              // hits are missing from the sampled surfaces
+    return rc;
 }
 
 }  // extern "C"

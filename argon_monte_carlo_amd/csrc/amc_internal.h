@@ -236,6 +236,19 @@ struct amc_fields_ws {
     unsigned long long *meta;   // [0] samples, [1] particles outside, [2] lowest particle index out of range (~0: none)
 };
 
+// sampled surfaces (amc_surface.hip): the grid, the 128-bit running totals per (case, bin, quantity) and the counters
+struct amc_surface_ws {
+    bool on;
+    amc_surface_grid g;
+    double w[AMC_SURFACE_CASES];    // bin widths (hi - lo) / nbins, fp64
+    unsigned long long *tot;        // [7][nbins + 1][3][2] running totals, (low, high) words
+    unsigned long long *meta;       // [0] lowest particle index out of the quantisers' range (~0: none), [1 + s] failed contact solves of case 3 + s
+    int *park_bin;                  // [T.cap] bin of every record of the parked case (-1: failed contact solve), allocated at the first park
+    int park_case, park_n;          // the parked case whose bins park_bin holds (0: none)
+    int64_t n_steps;                // energised steps completed with the grid on
+    bool lost;                      // a step or run overflowed its records: hits are missing (amc_surface_read: AMC_ERR_STATE)
+};
+
 // what amc_ctx::owned records (amc_host.h): the context's device / pinned allocations, streams and events
 enum amc_res_kind { AMC_RES_DEVICE, AMC_RES_PINNED, AMC_RES_STREAM, AMC_RES_EVENT };
 struct amc_res { void *p; amc_res_kind kind; };
@@ -295,6 +308,7 @@ struct amc_ctx {
     amc_temp_ws T;
     amc_temp_dev_ws TD;
     amc_fields_ws F;
+    amc_surface_ws SF;
     // outputs
     amc_out out;
     amc_path_record *d_rec;
@@ -442,5 +456,11 @@ hipError_t amc_launch_temp_apply(amc_ctx *c, int case_id, int n, bool park = fal
 hipError_t amc_launch_temp_velocity(amc_ctx *c, int case_id, int n);
 hipError_t amc_launch_temp_cases_device(amc_ctx *c, const amc_temp_rng *cfg);
 hipError_t amc_launch_temp_sums(amc_ctx *c, int64_t row);     // the step's sums -> row `row` of the series (one workgroup)
+// sampled surfaces (amc_surface.hip; callers test c->SF.on first): the records of all seven segments of a device-RNG step, of
+// the hand-over's current case, and the two halves of a parked case
+hipError_t amc_launch_surface_device(amc_ctx *c);
+hipError_t amc_launch_surface_case(amc_ctx *c, int case_id, int n);
+int amc_surface_park(amc_ctx *c, int case_id, int n);             // (allocates park_bin at the first call: an amc_status)
+hipError_t amc_launch_surface_finish(amc_ctx *c, int case_id, int n);
 hipError_t amc_launch_kin_pack(amc_ctx *c, int world, int rank, int unpack);
 int amc_kin_banks(void);         // banks of the velocity-change list in an exchange block

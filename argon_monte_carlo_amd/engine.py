@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._abi import (AMC_K_NAMES, AmcFieldGrid, AmcParams, AmcPathRecord, AmcStepStats, path_record_dtype)
+from ._abi import (AMC_K_NAMES, AmcFieldGrid, AmcParams, AmcPathRecord, AmcStepStats, AmcSurfaceGrid, path_record_dtype)
 
 _dp = C.POINTER(C.c_double)
 _i64p = C.POINTER(C.c_int64)
@@ -31,6 +31,7 @@ class Engine:
         self.params = params
         self.n = int(params.n)
         self.field_grid = None
+        self.surface_grid = None
         self._ctx = C.c_void_p()
         rc = self.lib.amc_create(C.byref(self._ctx), C.byref(params))
         if rc != 0:
@@ -370,6 +371,49 @@ class EnergisedEngine(Engine):
         left = C.c_int64(0)
         self._ck(self.lib.amc_temp_series_read(self._ctx, 0, nsteps, _d(sums), had.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(left)))
         return st.as_dict(), sums[:nsteps], had[:nsteps].astype(bool)
+
+    def device_contacts(self, case):
+        """(particle indices, contact points [n, 3]) of the last device-RNG step's hits of ``case``, ascending particle index."""
+        cap = max(4096, self.n // 64 + 1024)
+        idx = np.empty(cap, dtype=np.int32)
+        xyz = np.empty((cap, 3))
+        n = C.c_size_t(0)
+        self._ck(self.lib.amc_temp_device_contacts(self._ctx, int(case), idx.ctypes.data_as(C.POINTER(C.c_int32)), _d(xyz), cap,
+                                                   C.byref(n)))
+        return idx[:n.value].copy(), xyz[:n.value].copy()
+
+    def wall_contacts(self, case, n):
+        """Contact points [n, 3] of the pending ``wall_hits(case)``, in its order."""
+        xyz = np.empty((max(1, int(n)), 3))
+        self._ck(self.lib.amc_wall_contacts(self._ctx, int(case), _d(xyz), len(xyz)))
+        return xyz[:int(n)].copy()
+
+    # ---- sampled surfaces (surface.py, DESIGN.md 11): hits, z-momentum and heat per wall bin -----------------------------
+    def surface_config(self, grid):
+        """Sample on ``grid`` (an ``AmcSurfaceGrid``, surface.make_grid); None switches sampling off.  Starts from zero."""
+        self._ck(self.lib.amc_surface_config(self._ctx, None if grid is None else C.byref(grid)))
+        self.surface_grid = None if grid is None else AmcSurfaceGrid.from_buffer_copy(grid)
+
+    def surface_read(self):
+        """(int64[7, nbins + 1, 3, 2] totals as (low, high) words, int64[7] failed contact solves, steps); synchronises."""
+        g = self.surface_grid
+        nb = 1 if g is None else int(g.nbins)       # (no grid: the library answers AMC_ERR_STATE)
+        tot = np.zeros((7, nb + 1, 3, 2), dtype=np.int64)
+        nf = np.zeros(7, dtype=np.int64)
+        ns = C.c_int64(0)
+        self._ck(self.lib.amc_surface_read(self._ctx, tot.ctypes.data_as(_i64p), nf.ctypes.data_as(_i64p), C.byref(ns)))
+        return tot, nf, ns.value
+
+    def surface_load(self, totals, n_failed, n_steps):
+        tot = np.ascontiguousarray(totals, dtype=np.int64)
+        nf = np.ascontiguousarray(n_failed, dtype=np.int64)
+        g = self.surface_grid
+        if g is None or tot.size != 7 * (int(g.nbins) + 1) * 6 or nf.size != 7:
+            raise ValueError("totals do not match the configured surface grid")
+        self._ck(self.lib.amc_surface_load(self._ctx, tot.ctypes.data_as(_i64p), nf.ctypes.data_as(_i64p), int(n_steps)))
+
+    def surface_reset(self):
+        self._ck(self.lib.amc_surface_reset(self._ctx))
 
     def set_step(self, step):
         """Index of the next step: the step word of the device draws (a resumed run continues the interrupted one's)."""

@@ -307,10 +307,37 @@ class TemperatureSimulation(Simulation):
         self.steps_done += nsteps
         return st
 
+    # ---- sampled surfaces (surface.py; the reference reports three sums per step) -------------------------
+    def enable_surface(self, grid=None):
+        """Accumulate hits, z-momentum and energy per wall bin of the seven energised surfaces in every step from now on
+        (``grid``: surface.make_grid; None = surface.default_grid, 32 bins per surface).  Starts from zero."""
+        from . import surface as SU
+        self.engine.surface_config(SU.default_grid(self.params) if grid is None else grid)
+
+    def disable_surface(self):
+        self.engine.surface_config(None)
+
+    def surface(self):
+        """dict (surface.derive): per case and bin count, hit_rate, momentum_rate and energy_rate (gas side, per area), the
+        per-case totals, edges, bin_area, n_steps, n_failed and the raw integer totals (int64[7, nbins + 1, 3, 2])."""
+        from . import surface as SU
+        tot, nf, ns = self.engine.surface_read()
+        return SU.derive(tot, ns, self.dt, self.engine.surface_grid, self.params, n_failed=nf)
+
+    def write_surface(self, path):
+        """The dict of ``surface()`` as an .npz: the integers, the grid and the derived arrays."""
+        np.savez(path, **self.surface())
+
     def _checkpoint_extra(self):
         np_state = self.sampler.np_rng.get_state()
         py_state = self.sampler.py_rng.getstate()
-        return dict(momentum=np.array([float(v) for v in self.momentum_z_change_per_step]),
+        surf = {}
+        if self.engine.surface_grid is not None:
+            from . import surface as SU
+            tot, nf, ns = self.engine.surface_read()
+            surf = dict(surface_grid=SU.grid_to_array(self.engine.surface_grid), surface_totals=tot, surface_n_failed=nf,
+                        surface_n_steps=int(ns))
+        return dict(**surf, momentum=np.array([float(v) for v in self.momentum_z_change_per_step]),
                     energy_cold=np.array([float(v) for v in self.energy_transfer_cold_per_step]),
                     energy_hot=np.array([float(v) for v in self.energy_transfer_hot_per_step]),
                     zero_flags=np.array(self._zero_flags, dtype=bool).reshape(-1, 3), total_errs=int(self.total_errs),
@@ -319,6 +346,12 @@ class TemperatureSimulation(Simulation):
                     py_rng_state=np.array(py_state[1], dtype=np.uint64), py_rng_version=int(py_state[0]))
 
     def _restore_extra(self, z):
+        if "surface_grid" in z:
+            from . import surface as SU
+            self.engine.surface_config(SU.grid_from_array(z["surface_grid"]))
+            self.engine.surface_load(z["surface_totals"], z["surface_n_failed"], int(z["surface_n_steps"]))
+        else:                                       # a checkpoint without surface data: sampling is off in the resumed run
+            self.engine.surface_config(None)
         self.momentum_z_change_per_step = z["momentum"].tolist()
         self.energy_transfer_cold_per_step = z["energy_cold"].tolist()
         self.energy_transfer_hot_per_step = z["energy_hot"].tolist()

@@ -241,7 +241,7 @@ int amc_histograms(amc_ctx *ctx, uint64_t *counts, uint64_t *n_paths_total);
 /* Zero histograms, counters, the pending path records and the step index.  Whatever was enqueued before the call is
  * discarded from the outputs — the paths and collisions of a step that has returned without its statistics
  * (amc_mg_finish(ctx, NULL)) included — and its results still reach the particle arrays: the state is the one the steps so
- * far produce, and the next step's outputs and statistics hold that step alone.  Sampled fields are left alone. */
+ * far produce, and the next step's outputs and statistics hold that step alone.  Sampled fields and surfaces are left alone. */
 int amc_reset_outputs(amc_ctx *ctx);
 
 /* Host-only helper of the hand-over above (no GPU, no context): the re-emission directions of one case's hits —
@@ -441,6 +441,50 @@ int amc_fields_read(amc_ctx *ctx, int64_t *totals, int64_t *n_samples, int64_t *
 int amc_fields_load(amc_ctx *ctx, const int64_t *totals, int64_t n_samples, int64_t n_outside);
 /* zero totals and counters (amc_reset_outputs leaves them alone) */
 int amc_fields_reset(amc_ctx *ctx);
+
+/* ---- sampled surfaces: hits, z-momentum and heat per wall bin of the energised pore (opt-in) ---------
+ * The reference reports three sums per step (Temp:756-758).  Every hit of the energised cases 3..9 leaves a record
+ * (particle, contact point, ok, dp_z, dE: amc_temp_device_results / amc_wall_apply); while a grid is configured every
+ * energised step bins its records per case s = case - 3 and adds, per (case, bin), three exact integers:
+ *   count,  sum llrint(ldexp(dpz, 110)),  sum llrint(ldexp(dE, 97))        (round half to even, IEEE double, no FMA)
+ * Coordinate of a hit, from the record's contact point (cx, cy, cz): u = sqrt(cx*cx + cy*cy) for the plane cases
+ * 3, 4, 6, 7 and u = cz for the cylinder cases 5, 8, 9.  Bin: w = (hi[s] - lo[s]) / nbins, i = floor((u - lo[s]) / w);
+ * i == nbins with u <= hi[s] is the last bin; anything else (below lo, beyond hi, NaN) goes into the extra bin `nbins` of
+ * that case ("outside"): per case the nbins + 1 bins always add up to all hits with a contact point.  A record whose
+ * contact solve failed (ok == 0, Temp:472-474) adds only to n_failed[s].
+ * Valid range per hit: |dpz| < 2^-70 kg m/s and |dE| < 2^-57 J, so both quantised values are at most 2^40 in magnitude
+ * and, with at most 2^22 records per launch (contexts of at most 2^24 particles: amc_surface_config refuses larger ones
+ * with AMC_ERR_CAPACITY), a step's sums at most 2^62.  They are added into signed 128-bit totals (low 64 bits, high 64
+ * bits signed).  Everything is integer: the totals do not depend on record order, block size or launch geometry.
+ * A hit out of range (or NaN) stops the accumulation: amc_surface_read fails with AMC_ERR_CAPACITY naming the lowest such
+ * particle index until amc_surface_reset / amc_surface_load / amc_surface_config.
+ * There is no cadence: wall hits are events, every energised step accumulates (amc_temp_cases_device, every step of
+ * amc_temp_run_device, amc_wall_apply, amc_wall_park + amc_wall_finish), and n_steps counts the steps completed with a
+ * grid configured (amc_temp_end, each step of amc_temp_run_device).  amc_reset_outputs leaves the totals alone.  After an
+ * energised step or run that returned AMC_ERR_CAPACITY (hit records or a work buffer overflowed: hits are missing)
+ * amc_surface_read fails with AMC_ERR_STATE until reset, load or config.  Needs AMC_GEOM_PORE_ENERGISED. */
+#define AMC_SURFACE_CASES 7
+#define AMC_SURFACE_MAX_BINS 256
+typedef struct amc_surface_grid {
+    int32_t struct_size;          /* sizeof(amc_surface_grid)                                                    */
+    int32_t nbins;                /* bins per case, 1..AMC_SURFACE_MAX_BINS                                      */
+    double lo[7], hi[7];          /* [case - 3]: range of u, finite, lo < hi                                     */
+} amc_surface_grid;
+/* NULL turns sampling off (nothing is launched or allocated then; a later amc_surface_read / _load / _reset returns
+ * AMC_ERR_STATE).  A (new) grid starts from zero totals. */
+int amc_surface_config(amc_ctx *ctx, const amc_surface_grid *grid);
+/* totals[7][nbins + 1][3][2] (quantities count, dp_z, dE; words low, high), n_failed[7], steps; any may be NULL.
+ * Synchronises; reads what the steps enqueued so far have added (a case still parked has added nothing yet). */
+int amc_surface_read(amc_ctx *ctx, int64_t *totals, int64_t *n_failed, int64_t *n_steps);
+/* the inverse of amc_surface_read (checkpoints) */
+int amc_surface_load(amc_ctx *ctx, const int64_t *totals, const int64_t *n_failed, int64_t n_steps);
+/* zero totals and counters, clear a pending error */
+int amc_surface_reset(amc_ctx *ctx);
+/* Inspection, for tests: the contact points [n][3] of the last device-RNG step's hits of `case_id` in ascending particle
+ * index (the order of amc_temp_device_draws / _results), and of the pending amc_wall_hits(case_id) in its order
+ * (AMC_ERR_STATE when `case_id` is not the pending case; cap counts hits). */
+int amc_temp_device_contacts(amc_ctx *ctx, int case_id, int32_t *idx, double *contact_xyz, size_t cap, size_t *n);
+int amc_wall_contacts(amc_ctx *ctx, int case_id, double *contact_xyz, size_t cap);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,487 @@
+"""Sampled surfaces on the GPU (``amc_surface_*``; -m gpu): the totals the device accumulates against the
+NumPy / Python-int reference (tests/surface_ref.py) applied to the very records the inspection calls return — bit for bit,
+the 128-bit words included — through every path that launches the kernel: single device-RNG steps, the host-free run (fused,
+unfused, another block size), the hand-over with and without a parked gap case, and checkpoints.
+
+The input: the energised pore with the host's synthetic initial conditions (seed 23), device draws keyed by 11, 12 steps.
+N = 1,000,000 is the smaller of {1e5, 1e6} at which such a run has a hit in each of the seven cases (with the oracle on the
+CPU: at N = 1e5 the gap ceiling, case 7, stays without a hit; at 1e6 the cases see 708, 653, 54, 6, 10, 62 and 5,462) and
+steps in which two hits of one case share a bin (51 of the 84 case-steps at 8 bins): the LDS atomic on a contended address.
+Both conditions are asserted below.
+
+The runs that need other environment switches (read when a context is created) happen in fresh child processes:
+``python -m tests.test_gpu_surface <job> <out.npz>``."""
+import os
+import random
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+from argon_monte_carlo_amd import ic as IC  # noqa: E402
+from argon_monte_carlo_amd import params as PR  # noqa: E402
+from argon_monte_carlo_amd import surface as SU  # noqa: E402
+from argon_monte_carlo_amd.energised import CASES, GAP_CASE  # noqa: E402
+from tests import surface_ref as REF  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+N, STEPS, NBINS, IC_SEED, RNG_SEED = 1_000_000, 12, 8, 23, 11
+STATE_KEYS = ("x", "y", "z", "vx", "vy", "vz", "d", "dx", "dy", "dz", "flag")
+STAT_KEYS = ("n_pp", "n_wall", "n_oob_walls", "n_oob_pp", "n_paths", "n_candidates", "n_fp_errors")
+ERR_CAPACITY, ERR_STATE = -4, -6
+_INIT = {}
+
+
+def engine(n=N, grid="default", nbins=NBINS):
+    """An energised context with the test's initial state; ``grid``: "default", an AmcSurfaceGrid, or None (sampling off)."""
+    from argon_monte_carlo_amd.energised import SurfaceEnergies, device_rng_config
+    from argon_monte_carlo_amd.engine import EnergisedEngine
+    p, c = PR.pore_params(n=n, energised=True)
+    p.reserved0 |= 1
+    if n not in _INIT:
+        _INIT[n] = IC.pore_ic(p, c, seed=IC_SEED)
+    energies = SurfaceEnergies(c)
+    p.E_cold, p.E_hot = energies.cold, energies.hot
+    eng = EnergisedEngine(p)
+    eng.upload(*_INIT[n])
+    if grid is not None:
+        eng.surface_config(SU.default_grid(p, nbins) if isinstance(grid, str) else grid)
+    return eng, device_rng_config(c, RNG_SEED), c["dt"], energies
+
+
+def narrowed(g):
+    """Every range narrowed to its middle half."""
+    lo, hi = np.array(g.lo), np.array(g.hi)
+    return SU.make_grid(g.nbins, lo + 0.25 * (hi - lo), hi - 0.25 * (hi - lo))
+
+
+def snapshot(eng, stats, series, had):
+    out = {f"state_{k}": v for k, v in eng.download().items()}
+    out["stats"] = np.array([stats[k] for k in STAT_KEYS], dtype=np.int64)
+    counts, tot = eng.histograms()
+    out["hist"], out["hist_total"] = counts, np.array([tot], dtype=np.uint64)
+    out["paths"] = np.frombuffer(eng.drain_paths(sort=True).tobytes(), dtype=np.uint8)
+    out["series"], out["had"] = np.asarray(series, dtype=np.float64).reshape(-1, 3), np.asarray(had, dtype=bool).reshape(-1, 3)
+    return out
+
+
+def surface_of(eng):
+    tot, nf, ns = eng.surface_read()
+    return {"surf_totals": tot, "surf_failed": nf, "surf_steps": np.array([ns], dtype=np.int64)}
+
+
+def assert_same(a, b, what, keys=None):
+    for k in sorted(a if keys is None else keys):
+        assert a[k].shape == b[k].shape and a[k].dtype == b[k].dtype, (what, k, a[k].shape, b[k].shape)
+        if a[k].dtype.kind == "f":
+            assert np.array_equal(a[k].view(np.uint64), b[k].view(np.uint64)), (what, k)
+        else:
+            assert np.array_equal(a[k], b[k]), (what, k)
+
+
+def step_records(eng):
+    """The records of the last device-RNG step, as the inspection calls return them: (case, contact, ok, dpz, dE, particle)."""
+    recs = []
+    for case in CASES:
+        idx, xyz = eng.device_contacts(case)
+        ridx, dpz, dE, ok = eng.device_results(case)
+        assert np.array_equal(idx, ridx) and np.all(np.diff(idx) > 0), case        # the same hits, ascending particle index
+        recs += [(case, tuple(xyz[k]), bool(ok[k]), float(dpz[k]), float(dE[k]), int(idx[k])) for k in range(len(idx))]
+    return recs
+
+
+# ---- jobs (this process or a child with another environment) ------------------------------------------------------------------
+def job_run(grid="default", nbins=NBINS):
+    eng, cfg, dt, _ = engine(grid=grid, nbins=nbins)
+    st, series, had = eng.temp_run_device(dt, STEPS, cfg)
+    out = snapshot(eng, st, series, had)
+    if grid is not None:
+        out.update(surface_of(eng))
+    eng.close()
+    return out
+
+
+def job_capacity():
+    """Eight records per case at N = 2e5 (about 17 hits per case and step): the run fails, the totals are not to be trusted."""
+    from argon_monte_carlo_amd._lib import ArgonMCError
+    eng, cfg, dt, _ = engine(200_000)
+    codes = []
+    for call in (lambda: eng.temp_run_device(dt, 3, cfg), eng.surface_read, eng.surface_read, eng.surface_reset, eng.surface_read):
+        try:
+            call()
+            codes.append(0)
+        except ArgonMCError as e:
+            codes.append(e.code)
+    tot, nf, ns = eng.surface_read()
+    eng.close()
+    return {"codes": np.array(codes), "after_reset": np.array([np.count_nonzero(tot), np.count_nonzero(nf), ns])}
+
+
+JOBS = {"run": job_run, "capacity": job_capacity}
+
+
+def child(job, env, tmp_path):
+    out = os.path.join(str(tmp_path), job + "_" + "_".join(sorted(env)) + ".npz")
+    e = dict(os.environ)
+    for k in ("AMC_TEMP_RUN_UNFUSED", "AMC_TEMP_RUN_FUSED", "AMC_TEMP_UNFUSED", "AMC_STREAM_BS", "AMC_TEMP_DEV_CAP", "AMC_TEMP_NO_PARK"):
+        e.pop(k, None)
+    e.update(env)
+    r = subprocess.run([sys.executable, "-m", "tests.test_gpu_surface", job, out], cwd=ROOT, env=e, timeout=600,
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+    assert r.returncode == 0, r.stdout.decode(errors="replace")[-3000:]
+    with np.load(out) as z:
+        return {k: z[k] for k in z.files}
+
+
+# ---- 1. single steps ----------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def stepped():
+    """12 single device-RNG steps with 8 bins, the totals read and checked after every one; what the other tests compare with."""
+    eng, cfg, dt, _ = engine()
+    g = eng.surface_grid
+    lo, hi = list(g.lo), list(g.hi)
+    ref_tot, ref_failed = REF.empty(NBINS)
+    records, hits, contended = [], dict.fromkeys(CASES, 0), 0
+    q_sum = {case: [0, 0, 0] for case in CASES}            # per case, without any binning: hits, sum q(dpz), sum q(dE)
+    tot_stats = dict.fromkeys(STAT_KEYS, 0)
+    series, had = [], []
+    for t in range(STEPS):
+        st, mom, cold, hot, hm, hc, hh = eng.temp_timestep_device(dt, cfg)
+        for k in STAT_KEYS:
+            tot_stats[k] += st[k]
+        series.append((mom, cold, hot))
+        had.append((hm, hc, hh))
+        recs = step_records(eng)
+        records.append(recs)
+        REF.accumulate(ref_tot, ref_failed, NBINS, lo, hi, recs)
+        seen = set()
+        for case, xyz, ok, dpz, dE, _ in recs:
+            if not ok:
+                continue
+            hits[case] += 1
+            q_sum[case][0] += 1
+            q_sum[case][1] += REF.quantise(dpz, REF.DPZ_EXP)
+            q_sum[case][2] += REF.quantise(dE, REF.DE_EXP)
+            key = (case, REF.bin_of(REF.coordinate(case, *xyz), lo[case - 3], hi[case - 3], NBINS))
+            contended += key in seen
+            seen.add(key)
+        tot, nf, ns = eng.surface_read()
+        assert np.array_equal(tot, REF.to_words(ref_tot)), ("totals after step", t)
+        assert nf.tolist() == ref_failed and ns == t + 1, (t, nf, ref_failed, ns)
+        got = REF.from_words(tot)
+        for case in CASES:                                  # independently: the nbins + 1 bins of a case add up to all its hits
+            assert [sum(b[q] for b in got[case - 3]) for q in range(3)] == q_sum[case], (t, case)
+    out = dict(records=records, hits=hits, contended=contended, q_sum=q_sum, grid=SU.copy_grid(g), lo=lo, hi=hi)
+    out.update(snapshot(eng, tot_stats, series, had))
+    out.update(surface_of(eng))
+    eng.close()
+    return out
+
+
+def test_single_steps_equal_the_reference_on_the_inspected_records(stepped):
+    """(The per-step comparisons are in the fixture.)  The input exercises what it is there for: every case has a hit, and
+    two hits of one case shared a bin within a step — the LDS atomic met a contended address."""
+    assert all(stepped["hits"][case] >= 1 for case in CASES), stepped["hits"]
+    assert stepped["contended"] >= 1, stepped["contended"]
+    assert stepped["surf_steps"][0] == STEPS
+    assert int(np.count_nonzero(stepped["surf_totals"][:, :, 1:, :])) > 0
+
+
+# ---- 2. run equals steps, 3. sampling does not perturb ------------------------------------------------------------------------
+SURF_KEYS = ("surf_totals", "surf_failed", "surf_steps")
+
+
+@pytest.fixture(scope="module")
+def run_on():
+    return job_run()
+
+
+def test_run_equals_steps(stepped, run_on):
+    assert_same(run_on, stepped, "run(12) vs 12 steps", SURF_KEYS)
+    assert_same(run_on, stepped, "run(12) vs 12 steps", [k for k in run_on if k not in SURF_KEYS])
+
+
+@pytest.mark.parametrize("env", [{"AMC_TEMP_RUN_UNFUSED": "1"}, {"AMC_STREAM_BS": "64"}], ids=["unfused", "bs64"])
+def test_run_in_another_form_equals_steps(stepped, env, tmp_path):
+    """The single step's three passes per step (own context: the switch is read at amc_create), and the fused pass at another
+    block size — other kernels append the records, in other orders; the integer totals do not notice."""
+    assert_same(child("run", env, tmp_path), stepped, str(env), SURF_KEYS)
+
+
+def test_sampling_does_not_perturb_the_run(run_on):
+    off = job_run(grid=None)
+    assert_same(off, run_on, "grid off vs on", list(off))       # state, counters, histograms, sorted path records, series
+    assert off["stats"][1] > 0 and off["paths"].size > 0
+
+
+# ---- 4. the hand-over path ------------------------------------------------------------------------------------------------------
+class RecordingHooks:
+    """The engine's hooks, and a note of what passed through them: one list of records per kernel launch."""
+    early_gap = True
+
+    def __init__(self, eng):
+        self.eng, self.launches, self.pending, self.parked, self.parked_n = eng, [], {}, None, 0
+
+    def wall_hits(self, case):
+        idx, normals, cz, ok = self.eng.wall_hits(case)
+        xyz = self.eng.wall_contacts(case, len(idx))
+        assert np.array_equal(xyz[:, 2], cz), case
+        self.pending[case] = (idx, xyz, ok)
+        return idx, normals, cz, ok
+
+    def _records(self, case, hits, dpz, dE):
+        idx, xyz, ok = hits
+        return [(case, tuple(xyz[k]), bool(ok[k]), float(dpz[k]), float(dE[k]), int(idx[k])) for k in range(len(idx))]
+
+    def wall_apply(self, case, dirs, Es):
+        dpz, dE = self.eng.wall_apply(case, dirs, Es)
+        self.launches.append(self._records(case, self.pending.pop(case), dpz, dE))
+        return dpz, dE
+
+    def wall_park(self, case, dirs):
+        self.eng.wall_park(case, dirs)
+        self.parked = (case, self.pending.pop(case))
+        self.parked_n = max(self.parked_n, len(self.parked[1][0]))
+
+    def wall_finish(self, case, Es):
+        dpz, dE = self.eng.wall_finish(case, Es)
+        self.launches.append(self._records(case, self.parked[1], dpz, dE))
+        self.parked = None
+        return dpz, dE
+
+    def wall_hits_again(self):
+        self.eng.wall_hits_again()
+
+
+def handover(monkeypatch, no_park):
+    from argon_monte_carlo_amd.energised import DirectionSampler, drive_energised_cases
+    monkeypatch.setenv("AMC_GAP_WORKERS", "0")
+    if no_park:
+        monkeypatch.setenv("AMC_TEMP_NO_PARK", "1")
+    else:
+        monkeypatch.delenv("AMC_TEMP_NO_PARK", raising=False)
+    eng, _, dt, energies = engine()
+    sampler = DirectionSampler(np.random.RandomState(5), random.Random(5))
+    hooks = RecordingHooks(eng)
+    for _ in range(2):
+        eng.temp_begin(dt)
+        drive_energised_cases(hooks, sampler, energies)
+        eng.temp_end()
+    out = surface_of(eng)
+    eng.close()
+    return hooks, out
+
+
+def test_handover_path_with_a_parked_gap_case_and_without(monkeypatch):
+    hooks, parked = handover(monkeypatch, no_park=False)
+    assert hooks.parked_n > 0                                       # a gap case with hits was parked (and finished)
+    g = SU.default_grid(PR.pore_params(n=N, energised=True)[0], NBINS)
+    tot, nf = REF.empty(NBINS)
+    for recs in hooks.launches:
+        REF.accumulate(tot, nf, NBINS, list(g.lo), list(g.hi), recs)
+    assert np.array_equal(parked["surf_totals"], REF.to_words(tot))
+    assert parked["surf_failed"].tolist() == nf and parked["surf_steps"][0] == 2
+    assert sum(t[0] for t in tot[GAP_CASE - 3]) > 0 and any(t[1] != 0 for t in tot[GAP_CASE - 3])
+    hooks2, plain = handover(monkeypatch, no_park=True)
+    assert hooks2.parked_n == 0
+    assert_same(plain, parked, "AMC_TEMP_NO_PARK=1 vs parked", SURF_KEYS)
+
+
+# ---- 5. grid edges ---------------------------------------------------------------------------------------------------------------
+def case_sums(words):
+    return [[sum(b[q] for b in case) for q in range(3)] for case in REF.from_words(words)]
+
+
+@pytest.mark.parametrize("nbins", [1, 256])
+def test_one_bin_and_256_bins(stepped, nbins):
+    got = job_run(nbins=nbins)
+    g = SU.default_grid(PR.pore_params(n=N, energised=True)[0], nbins)
+    tot, nf = REF.empty(nbins)
+    for recs in stepped["records"]:
+        REF.accumulate(tot, nf, nbins, list(g.lo), list(g.hi), recs)
+    assert got["surf_totals"].shape == (7, nbins + 1, 3, 2)
+    assert np.array_equal(got["surf_totals"], REF.to_words(tot)) and got["surf_failed"].tolist() == nf
+    assert case_sums(got["surf_totals"]) == case_sums(stepped["surf_totals"])
+
+
+def test_narrowed_ranges_reconfiguring_and_no_grid(stepped):
+    from argon_monte_carlo_amd._lib import ArgonMCError
+    g = narrowed(stepped["grid"])
+    eng, cfg, dt, _ = engine(grid=g)
+    eng.temp_run_device(dt, STEPS, cfg)
+    tot, nf, ns = eng.surface_read()
+    tot2, nf2, ns2 = eng.surface_read()                             # (reading twice gives the same answer)
+    assert np.array_equal(tot, tot2) and np.array_equal(nf, nf2) and ns == ns2 == STEPS
+    outside = [REF.from_words(tot)[s][NBINS][0] for s in range(7)]
+    assert all(v > 0 for v in outside), outside                    # every case has hits outside the middle half of its range ...
+    assert case_sums(tot) == case_sums(stepped["surf_totals"])      # ... and they are in the case's sums all the same
+    ref, rf = REF.empty(NBINS)
+    for recs in stepped["records"]:
+        REF.accumulate(ref, rf, NBINS, list(g.lo), list(g.hi), recs)
+    assert np.array_equal(tot, REF.to_words(ref))
+    eng.surface_config(g)                                           # re-configuring zeroes the totals
+    tot, nf, ns = eng.surface_read()
+    assert not tot.any() and not nf.any() and ns == 0
+    eng.surface_config(None)                                        # no grid: the run accumulates nothing, a read is refused
+    eng.temp_run_device(dt, 2, cfg)
+    for call in (eng.surface_read, eng.surface_reset):
+        with pytest.raises(ArgonMCError) as ei:
+            call()
+        assert ei.value.code == ERR_STATE
+    eng.close()
+
+
+def test_arguments_are_checked():
+    import ctypes as C
+    from argon_monte_carlo_amd.engine import Engine
+    p, c = PR.pore_params(n=2000)
+    eng = Engine(p)                                                 # the specular pore leaves no hit records
+    g = SU.default_grid(PR.pore_params(n=2000, energised=True)[0], 4)
+    assert eng.lib.amc_surface_config(eng._ctx, C.byref(g)) == ERR_STATE
+    assert eng.lib.amc_surface_config(eng._ctx, None) == 0          # (turning off what is off is fine anywhere)
+    eng.close()
+    eng, cfg, dt, _ = engine(2000, grid=None)
+    lib, ctx = eng.lib, eng._ctx
+    for change in (("struct_size", g.struct_size - 8), ("nbins", 0), ("nbins", 257)):
+        bad = SU.copy_grid(g)
+        setattr(bad, *change)
+        assert lib.amc_surface_config(ctx, C.byref(bad)) == -1, change
+    for s, (lo, hi) in ((0, (1.0, 1.0)), (3, (2.0, 1.0)), (6, (float("nan"), 1.0)), (2, (0.0, float("inf")))):
+        bad = SU.copy_grid(g)
+        bad.lo[s], bad.hi[s] = lo, hi
+        assert lib.amc_surface_config(ctx, C.byref(bad)) == -1, (s, lo, hi)
+    tot, nf = np.zeros((7, 5, 3, 2), dtype=np.int64), np.zeros(7, dtype=np.int64)
+    i64 = C.POINTER(C.c_int64)
+    assert lib.amc_surface_load(ctx, tot.ctypes.data_as(i64), nf.ctypes.data_as(i64), 0) == ERR_STATE      # no grid yet
+    eng.surface_config(g)
+    assert lib.amc_surface_load(ctx, None, nf.ctypes.data_as(i64), 0) == -1
+    assert lib.amc_surface_load(ctx, tot.ctypes.data_as(i64), nf.ctypes.data_as(i64), -1) == -1
+    tot[6, 4, 2] = (-1, -1)                                         # load is the inverse of read, the high words included
+    tot[0, 0, 1] = (0, -(2 ** 63))
+    nf[5] = 3
+    eng.surface_load(tot, nf, 9)
+    got = eng.surface_read()
+    assert np.array_equal(got[0], tot) and np.array_equal(got[1], nf) and got[2] == 9
+    assert lib.amc_wall_contacts(ctx, 3, np.zeros(3).ctypes.data_as(C.POINTER(C.c_double)), 1) == ERR_STATE   # no pending amc_wall_hits
+    eng.close()
+
+
+# ---- 6. capacity, 7. quantiser range --------------------------------------------------------------------------------------------
+def test_record_overflow_invalidates_the_totals_until_reset(tmp_path):
+    got = child("capacity", {"AMC_TEMP_DEV_CAP": "8"}, tmp_path)
+    assert got["codes"].tolist() == [ERR_CAPACITY, ERR_STATE, ERR_STATE, 0, 0], got["codes"]
+    assert got["after_reset"].tolist() == [0, 0, 0]
+
+
+def test_a_hit_beyond_the_quantisers_range_is_reported_by_particle_and_reset_clears_it():
+    """Particle 7 of a small system flies up into the hot plate (case 4) at 30 km/s: |dpz| = m (30,000 + its new speed) is
+    about 2.4e-21 kg m/s > 2^-70, and |dE| = 0.95 (E - Es) about 2.8e-17 J > 2^-57."""
+    from argon_monte_carlo_amd._lib import ArgonMCError
+    n = 2000
+    eng, cfg, dt, _ = engine(n)
+    p = eng.params
+    st = {k: np.array(v, copy=True) for k, v in zip(STATE_KEYS[:6], _INIT[n][:6])}
+    v = 30_000.0
+    st["x"][7], st["y"][7], st["z"][7] = 2 * p.R_p, 0.0, p.t_z3_hot - 0.5 * v * dt
+    st["vx"][7], st["vy"][7], st["vz"][7] = 0.0, 0.0, v
+    eng.upload(*[st[k] for k in STATE_KEYS[:6]])
+    eng.temp_timestep_device(dt, cfg)
+    idx, dpz, dE, ok = eng.device_results(4)
+    k = int(np.flatnonzero(idx == 7)[0])
+    assert ok[k] and abs(dpz[k]) >= REF.DPZ_LIMIT and abs(dE[k]) >= REF.DE_LIMIT, (dpz[k], dE[k])
+    for _ in range(2):
+        with pytest.raises(ArgonMCError) as ei:
+            eng.surface_read()
+        assert ei.value.code == ERR_CAPACITY and "particle 7 " in str(ei.value), str(ei.value)
+    eng.temp_timestep_device(dt, cfg)                               # the accumulation has stopped: still the same error
+    with pytest.raises(ArgonMCError):
+        eng.surface_read()
+    eng.surface_reset()
+    tot, nf, ns = eng.surface_read()
+    assert not tot.any() and ns == 0
+    eng.temp_timestep_device(dt, cfg)                               # ... and goes on after the reset
+    recs = step_records(eng)
+    ref, rf = REF.empty(NBINS)
+    REF.accumulate(ref, rf, NBINS, list(eng.surface_grid.lo), list(eng.surface_grid.hi), recs)
+    tot, nf, ns = eng.surface_read()
+    assert np.array_equal(tot, REF.to_words(ref)) and ns == 1
+    eng.close()
+
+
+# ---- 8. checkpoint, 9. reads in between --------------------------------------------------------------------------------------------
+def temp_sim(monkeypatch, n=N):
+    from argon_monte_carlo_amd.sim import TemperatureSimulation
+    monkeypatch.setenv("AMC_GAP_WORKERS", "0")
+    sim = TemperatureSimulation(n=n, device_rng_seed=RNG_SEED)
+    sim.init_synthetic(seed=IC_SEED)
+    return sim
+
+
+def test_checkpoint_carries_the_surface_totals(stepped, monkeypatch, tmp_path):
+    sim = temp_sim(monkeypatch)
+    sim.enable_surface(SU.default_grid(sim.params, NBINS))
+    sim.run(6)
+    ck = str(tmp_path / "after6.npz")
+    sim.save_checkpoint(ck)
+    sim.close()
+    sim = temp_sim(monkeypatch)
+    sim.load_checkpoint(ck)
+    assert sim.engine.surface_grid is not None and sim.engine.surface_read()[2] == 6
+    sim.run(6)
+    assert_same(surface_of(sim.engine), stepped, "6 steps, checkpoint, 6 steps vs 12 steps", SURF_KEYS)
+    d = sim.surface()
+    assert d["n_steps"] == STEPS and d["count"].sum() + d["case_outside"].sum() == sum(stepped["hits"].values())
+    path = str(tmp_path / "surface.npz")
+    sim.write_surface(path)
+    with np.load(path) as z:
+        assert np.array_equal(z["totals"], stepped["surf_totals"]) and z["hit_rate"].shape == (7, NBINS)
+    sim.close()
+
+
+def test_checkpoint_without_surface_data_loads_with_sampling_off(monkeypatch, tmp_path):
+    from argon_monte_carlo_amd._lib import ArgonMCError
+    sim = temp_sim(monkeypatch, 2000)
+    sim.run(3)
+    ck = str(tmp_path / "plain.npz")
+    sim.save_checkpoint(ck)
+    with np.load(ck) as z:
+        assert not [k for k in z.files if k.startswith("surface_")]
+    sim.close()
+    sim = temp_sim(monkeypatch, 2000)
+    sim.enable_surface()
+    sim.load_checkpoint(ck)
+    assert sim.engine.surface_grid is None
+    sim.run(2)
+    with pytest.raises(ArgonMCError) as ei:
+        sim.surface()
+    assert ei.value.code == ERR_STATE
+    sim.close()
+
+
+def test_a_read_between_runs_changes_nothing(stepped, run_on):
+    """run(5), read, read, run(7): the reads see five steps' totals (the same twice) and the whole equals run(12) — the read
+    settles nothing it should not (a sweep's commit and results are still pending behind a run: DESIGN.md 4.1)."""
+    eng, cfg, dt, _ = engine()
+    st1, s1, h1 = eng.temp_run_device(dt, 5, cfg)
+    a, b = surface_of(eng), surface_of(eng)
+    assert_same(a, b, "read twice", SURF_KEYS)
+    ref, rf = REF.empty(NBINS)
+    for recs in stepped["records"][:5]:
+        REF.accumulate(ref, rf, NBINS, stepped["lo"], stepped["hi"], recs)
+    assert np.array_equal(a["surf_totals"], REF.to_words(ref)) and a["surf_steps"][0] == 5
+    st2, s2, h2 = eng.temp_run_device(dt, 7, cfg)
+    st = {k: st1[k] + st2[k] for k in STAT_KEYS}
+    got = snapshot(eng, st, np.concatenate([s1, s2]), np.concatenate([h1, h2]))
+    got.update(surface_of(eng))
+    eng.close()
+    assert_same(got, run_on, "run(5); read; run(7) vs run(12)", list(got))
+
+
+if __name__ == "__main__":
+    np.savez(sys.argv[2], **JOBS[sys.argv[1]]())

@@ -1,0 +1,183 @@
+"""CPU only: the sampled surfaces' host side — the reference (tests/surface_ref.py) at the contract's edges, the derived
+rates (argon_monte_carlo_amd/surface.py), the grid helpers, and the new entry points in the header and the bindings."""
+import ctypes as C
+import math
+import os
+import re
+
+import numpy as np
+import pytest
+
+from argon_monte_carlo_amd import _abi, _lib
+from argon_monte_carlo_amd import params as PR
+from argon_monte_carlo_amd import surface as SU
+from argon_monte_carlo_amd.fields import ints_to_words
+from tests import surface_ref as REF
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = {"amc_surface_config": 2, "amc_surface_read": 4, "amc_surface_load": 4, "amc_surface_reset": 1,
+       "amc_temp_device_contacts": 6, "amc_wall_contacts": 4}
+
+
+# ---- the reference at the contract's edges --------------------------------------------------------------------------------
+def test_bin_rule_on_lo_on_hi_on_an_interior_edge_below_and_nan():
+    lo, hi, n = 2.0, 10.0, 8                    # w = 1 exactly: edges 2, 3, ..., 10
+    assert REF.bin_of(2.0, lo, hi, n) == 0
+    assert REF.bin_of(10.0, lo, hi, n) == n - 1                      # u == hi: the last bin
+    assert REF.bin_of(5.0, lo, hi, n) == 3                           # an interior edge belongs to the bin above it
+    assert REF.bin_of(math.nextafter(5.0, 0.0), lo, hi, n) == 2
+    assert REF.bin_of(math.nextafter(2.0, 0.0), lo, hi, n) == n      # below lo: outside
+    assert REF.bin_of(math.nextafter(10.0, 20.0), lo, hi, n) == n    # beyond hi
+    assert REF.bin_of(11.5, lo, hi, n) == n and REF.bin_of(-3.0, lo, hi, n) == n
+    assert REF.bin_of(float("nan"), lo, hi, n) == n and REF.bin_of(float("inf"), lo, hi, n) == n
+    # a width that is not exact: i == nbins with u <= hi is still the last bin, with the geometry's own numbers
+    p, _ = PR.pore_params(n=1000, energised=True)
+    g = SU.default_grid(p, 7)
+    for s in range(7):
+        assert REF.bin_of(g.hi[s], g.lo[s], g.hi[s], 7) == 6 and REF.bin_of(g.lo[s], g.lo[s], g.hi[s], 7) == 0
+
+
+def test_coordinate_is_r_on_the_planes_and_z_on_the_cylinders():
+    for case in (3, 4, 6, 7):
+        assert REF.coordinate(case, 3e-8, -4e-8, 9.0) == float(np.sqrt(np.float64(3e-8) ** 2 + np.float64(4e-8) ** 2))
+    for case in (5, 8, 9):
+        assert REF.coordinate(case, 3e-8, -4e-8, 1.25e-7) == 1.25e-7
+    assert math.isnan(REF.coordinate(3, float("nan"), 0.0, 0.0))
+
+
+@pytest.mark.parametrize("exp", [REF.DPZ_EXP, REF.DE_EXP])
+def test_quantisers_round_half_to_even_and_keep_the_sign(exp):
+    ulp = 2.0 ** -exp
+    got = [REF.quantise(k * ulp, exp) for k in (0.5, 1.5, 2.5, -0.5, -1.5, -2.5, 0.75, -0.75, 3.0, -0.0)]
+    assert got == [0, 2, 2, 0, -2, -2, 1, -1, 3, 0]
+    big = math.nextafter(2.0 ** (40 - exp), 0.0)                    # the largest value in range: 2^40 - 2^-13 scaled, rounds to 2^40
+    assert REF.quantise(big, exp) == 2 ** 40 and REF.quantise(-big, exp) == -(2 ** 40)
+    assert REF.quantise(2.0 ** (39 - exp) + 2.0 ** (-exp), exp) == 2 ** 39 + 1
+
+
+def test_range_is_open_at_the_limits_and_nan_is_out():
+    assert REF.DPZ_LIMIT == 2.0 ** -70 and REF.DE_LIMIT == 2.0 ** -57 == SU.DE_LIMIT and SU.DPZ_LIMIT == REF.DPZ_LIMIT
+    assert REF.in_range(math.nextafter(2.0 ** -70, 0.0), -math.nextafter(2.0 ** -57, 0.0))
+    assert not REF.in_range(2.0 ** -70, 0.0) and not REF.in_range(0.0, -(2.0 ** -57))
+    assert not REF.in_range(float("nan"), 0.0) and not REF.in_range(0.0, float("nan"))
+    # the exponents against the physics: an argon atom turned round at 6,000 m/s, or stopped at 14,000 m/s
+    p, _ = PR.pore_params(n=1000, energised=True)
+    assert 2 * p.argon_mass * 6000.0 < REF.DPZ_LIMIT < 2 * p.argon_mass * 6500.0
+    assert 0.5 * p.argon_mass * 14000.0 ** 2 < REF.DE_LIMIT
+    assert (2 ** 40) * (2 ** 22) == 2 ** 62
+
+
+def test_accumulate_counts_bins_failed_solves_and_refuses_a_hit_out_of_range():
+    lo, hi = [0.0] * 7, [8.0] * 7
+    tot, nf = REF.empty(8)
+    u = 2.0 ** -110
+    recs = [(3, (3.0, 4.0, 99.0), 1, 1.5 * u, 2.0 ** -97, 10),       # r = 5: bin 5
+            (3, (0.0, 5.0, 0.0), 1, -0.5 * u, -3 * 2.0 ** -97, 11),  # the same bin: sums add
+            (5, (3.0, 4.0, 8.0), 1, 7 * u, 0.0, 12),                # cylinder: z = hi -> last bin
+            (5, (0.0, 0.0, -1.0), 1, 1 * u, 2.0 ** -97, 13),         # below lo -> outside bin
+            (9, (0.0, 0.0, float("nan")), 1, 2 * u, 0.0, 14),        # NaN -> outside bin
+            (8, (1.0, 1.0, 1.0), 0, 123.0, 456.0, 15)]               # failed contact solve: n_failed only, values ignored
+    REF.accumulate(tot, nf, 8, lo, hi, recs)
+    assert tot[0][5] == [2, 2 + 0, 1 - 3] and tot[2][7] == [1, 7, 0] and tot[2][8] == [1, 1, 1] and tot[6][8] == [1, 2, 0]
+    assert nf == [0, 0, 0, 0, 0, 1, 0]
+    assert sum(t[0] for s in tot for t in s) == 5                   # per case the bins add up to all hits with a contact point
+    before = (REF.to_words(tot).copy(), list(nf))
+    with pytest.raises(REF.OutOfRange) as ei:
+        REF.accumulate(tot, nf, 8, lo, hi, [(3, (1.0, 0.0, 0.0), 1, u, 0.0, 5), (4, (1.0, 0.0, 0.0), 1, 2.0 ** -70, 0.0, 9),
+                                            (4, (1.0, 0.0, 0.0), 1, 0.0, float("nan"), 7)])
+    assert ei.value.particle == 7                                   # the lowest such particle; the launch added nothing
+    assert np.array_equal(REF.to_words(tot), before[0]) and nf == before[1]
+
+
+def test_words_carry_into_the_high_word():
+    tot, _ = REF.empty(1)
+    tot[0][0] = [2 ** 64, -(2 ** 64), -1]
+    tot[6][1] = [2 ** 63, -(2 ** 63) - 1, 2 ** 100 + 5]
+    w = REF.to_words(tot)
+    assert w[0, 0].tolist() == [[0, 1], [0, -1], [-1, -1]]
+    assert w[6, 1].tolist() == [[-(2 ** 63), 0], [2 ** 63 - 1, -1], [5, 2 ** 36]]
+    assert REF.from_words(w) == tot
+    assert np.array_equal(w, ints_to_words(np.array(tot, dtype=object)))         # the product's own conversion agrees
+    # a sum that crosses -2^64 on the way: the words of the sum are the sum of the integers
+    a, _ = REF.empty(1)
+    a[3][0][1] = -(2 ** 64) + 3
+    b = REF.from_words(REF.to_words(a))
+    b[3][0][1] += -7
+    assert REF.to_words(b)[3, 0, 1].tolist() == [-4, -2]
+
+
+# ---- derived rates ---------------------------------------------------------------------------------------------------------
+def _grid_and_params(nbins=4):
+    p, c = PR.pore_params(n=1000, energised=True)
+    return SU.default_grid(p, nbins), p, c
+
+
+def test_default_grid_follows_the_mask_constants():
+    g, p, _ = _grid_and_params(32)
+    assert g.nbins == 32 and g.struct_size == C.sizeof(_abi.AmcSurfaceGrid) == 8 + 14 * 8
+    assert (g.lo[0], g.hi[0]) == (p.R_p, p.R_oa) == (g.lo[1], g.hi[1])
+    assert (g.lo[2], g.hi[2]) == (p.t_zgap_lo, p.t_zgap_hi)
+    assert (g.lo[3], g.hi[3]) == (p.R_p_c, p.R_g) == (g.lo[4], g.hi[4])
+    assert (g.lo[5], g.hi[5]) == (p.t_z3_hot, p.t_zgap_lo) and (g.lo[6], g.hi[6]) == (p.t_zgap_hi, p.t_z3_cold)
+    h = SU.grid_from_array(SU.grid_to_array(g))
+    assert bytes(h) == bytes(g)
+    for bad in ((0, g.lo, g.hi), (257, g.lo, g.hi), (4, list(g.lo)[:6], list(g.hi)[:6]), (4, g.hi, g.lo),
+                (4, [float("nan")] * 7, g.hi)):
+        with pytest.raises(ValueError):
+            SU.make_grid(*bad)
+
+
+def test_derive_known_integers_give_known_values():
+    g, p, c = _grid_and_params(4)
+    dt, n_steps = 2.5e-12, 8
+    tot, _ = REF.empty(4)
+    tot[0][1] = [16, 3 * 2 ** 110, -5 * 2 ** 97]         # plate, bin 1: ring between edges 1 and 2
+    tot[2][3] = [4, -(2 ** 109), 2 ** 96]                # gap cylinder, last bin
+    tot[2][4] = [2, 2 ** 110, 2 ** 97]                   # ... and two hits outside its range
+    d = SU.derive(REF.to_words(tot), n_steps, dt, g, p, n_failed=[0, 0, 1, 0, 0, 0, 0])
+    e = np.linspace(p.R_p, p.R_oa, 5)
+    ring = math.pi * (e[2] * e[2] - e[1] * e[1])
+    assert d["bin_area"][0, 1] == ring and d["count"][0, 1] == 16
+    assert d["hit_rate"][0, 1] == (16 / 8) / (dt * ring)
+    assert d["momentum_rate"][0, 1] == (3 / 8) / (dt * ring) and d["energy_rate"][0, 1] == (-5 / 8) / (dt * ring)
+    band = 2 * math.pi * p.R_g * ((p.t_zgap_hi - p.t_zgap_lo) / 4)
+    assert d["bin_area"][2, 3] == band
+    assert d["momentum_rate"][2, 3] == (-0.5 / 8) / (dt * band) and d["energy_rate"][2, 3] == (0.5 / 8) / (dt * band)
+    # hits outside the range are in the per-case totals and in no bin
+    assert d["count"][2].tolist() == [0, 0, 0, 4] and d["case_count"][2] == 6 and d["case_outside"][2] == 2
+    assert d["case_hit_rate"][2] == (6 / 8) / dt
+    assert d["case_momentum_rate"][2] == (0.5 / 8) / dt and d["case_energy_rate"][2] == (1.5 / 8) / dt
+    assert d["case_count"].tolist() == [16, 0, 6, 0, 0, 0, 0] and d["n_failed"][2] == 1 and d["n_steps"] == 8
+    assert d["hit_rate"][5].tolist() == [0.0] * 4 and d["edges"].shape == (7, 5)
+    assert d["bin_area"][5, 0] == 2 * math.pi * p.R_p * ((p.t_zgap_lo - p.t_z3_hot) / 4)
+    # one correctly rounded int / int per value: a total of 2^200 + 1 quanta is still finite and exact to the last bit
+    tot[1][0][1] = 3 ** 70
+    d = SU.derive(REF.to_words(tot), 3, dt, g, p)
+    assert d["case_momentum_rate"][1] == (3 ** 70 / (2 ** 110 * 3)) / dt
+
+
+def test_derive_without_steps_is_nan_not_an_exception():
+    g, p, _ = _grid_and_params(4)
+    tot, _ = REF.empty(4)
+    d = SU.derive(REF.to_words(tot), 0, 1e-12, g, p)
+    for k in ("hit_rate", "momentum_rate", "energy_rate", "case_hit_rate", "case_momentum_rate", "case_energy_rate"):
+        assert np.all(np.isnan(d[k])), k
+    assert d["count"].sum() == 0 and d["n_steps"] == 0
+
+
+# ---- header and bindings ------------------------------------------------------------------------------------------------
+def test_new_entry_points_are_declared_bound_and_exported_with_matching_arguments():
+    hdr = open(os.path.join(ROOT, "include", "argonmc.h")).read()
+    assert "sampled surfaces" in hdr and "typedef struct amc_surface_grid" in hdr
+    lib = _lib.load()
+    for name, nargs in NEW.items():
+        m = re.search(r"^int " + name + r"\(([^;]*)\);", hdr, flags=re.M)
+        assert m, name
+        declared = [a for a in re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S).split(",") if a.strip()]
+        res, args = _lib.SIGNATURES[name]
+        assert res is C.c_int and len(args) == len(declared) == nargs, (name, declared, args)
+        assert hasattr(lib, name), name
+    assert _lib.SIGNATURES["amc_surface_config"][1][1] is C.POINTER(_abi.AmcSurfaceGrid)
+    assert len(_lib.SIGNATURES) == 56 + len(NEW)                   # new functions only
+    assert lib.amc_abi_version() == 2 and len(_abi.AMC_K_NAMES) == 13
+    assert "#define AMC_K_COUNT 13" in hdr and "#define AMC_ABI_VERSION 2" in hdr
