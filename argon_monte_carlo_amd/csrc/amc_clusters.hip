@@ -240,26 +240,55 @@ AMC_DEV void cw_candidate_slots(const amc_resolve_ws &W, cw_lds &L, int own, int
 template <int GEOM, bool DBG>
 __global__ __launch_bounds__(64 * CW_WPB) void k_clusters_wide(rs_args A_in_kernarg)
 {
-    RS_STAGE_ARGS(A);
-    const amc_resolve_ws &W = A.W;
-    rs_shared *wc = (rs_shared *)W.wctl;
-    __shared__ cw_lds L_all[CW_WPB];
-    cw_lds &L = L_all[threadIdx.x >> 6];
+    // The argument block is 1 KB.  Read field by field from the kernarg segment it costs every wave a long train of
+    // dependent scalar loads (and SGPR spills) at the head of every phase — measured: most of these latency-bound kernels'
+    // time.  The workgroup therefore copies the block into LDS once and reads the fields from there.  A lane's words of the
+    // copy are loaded into registers first and stored afterwards, with a trip count that is a constant (the launch's block
+    // size), so that the loads can go out together; a loop over blockDim.x compiled to one load, one wait and one store
+    // per 256 bytes.  Only what the first hop needs — the candidate arrays, the counters, the stall word, the candidates per
+    // wave — is taken from the segment itself (scalar loads), and asked for between the copy's loads and its stores.
+    // (How the compiler schedules this was read from its output, `hipcc --save-temps`, amc_clusters-hip-*.s: four
+    // global_load_dword, the s_loads, the first hop's loads, then the ds_writes.  The source allows that order; it does not
+    // force it.  DESIGN.md 7 has the measurement.)
+    long long *const dbg__ = DBG ? A_in_kernarg.dbg : nullptr;     // (the phase timers are compiled out of the product's instantiation)
+    const long long t_enter__ = dbg__ ? wall_clock64() : 0;
+    __shared__ rs_args s_args;
+    constexpr int ARG_WORDS = (int)(sizeof(rs_args) / 4), ARG_T = 64 * CW_WPB, ARG_TRIPS = (ARG_WORDS + ARG_T - 1) / ARG_T;
+    const int *arg_src = (const int *)__builtin_amdgcn_kernarg_segment_ptr();
+    int arg_w[ARG_TRIPS];
+#pragma unroll
+    for (int j = 0; j < ARG_TRIPS; j++) {       // (the last trip's index is clamped, not branched around: its store is conditional)
+        const int i = (int)threadIdx.x + j * ARG_T;
+        arg_w[j] = arg_src[i < ARG_WORDS ? i : ARG_WORDS - 1];
+    }
     const int lane = threadIdx.x & 63;
     const int nwaves = gridDim.x * CW_WPB;
     const int wave_id = blockIdx.x * CW_WPB + (threadIdx.x >> 6);
-    long long *const dbg__ = DBG ? A.dbg : nullptr;     // (the phase timers are compiled out of the product's instantiation)
-    const long long t_enter__ = dbg__ ? wall_clock64() : 0;
-    const int per = A.wide_per;         // candidates per wave and pass, fixed by the host: the first pass's candidate is
-                                        // known before the sweep's candidate count has arrived
+    const int per = A_in_kernarg.wide_per;      // candidates per wave and pass, fixed by the host: the first pass's candidate is
+                                                // known before the sweep's candidate count has arrived
     // speculative: record and state of my first candidate (valid memory for any k below the capacity)
     const int k_first = wave_id * per + lane;
     int4 c4_first = make_int4(0, 0, -1, -1);
     unsigned long long mark_first = 0;
-    if (lane < per && k_first < W.max_cand) { c4_first = W.cand4[k_first]; mark_first = W.cand_mark[k_first]; }
-    int ncand = (int)A.O.cnt->cand_count;
+    if (lane < per && k_first < A_in_kernarg.W.max_cand) {
+        c4_first = A_in_kernarg.W.cand4[k_first]; mark_first = A_in_kernarg.W.cand_mark[k_first];
+    }
+    // (a relaxed atomic load, because the compiler was seen to sink a plain one behind the stall test, where pointer and
+    // count are two dependent trips of their own; an atomic one it left here)
+    int ncand = (int)__hip_atomic_load(&A_in_kernarg.O.cnt->cand_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     // (on demand: a sweep before this one waits for the ordered workgroup — this step does nothing, the host enqueues it again)
-    const int stalled = A.od_stall ? *A.od_stall : 0;
+    const int stalled = A_in_kernarg.od_stall ? *A_in_kernarg.od_stall : 0;
+#pragma unroll
+    for (int j = 0; j < ARG_TRIPS; j++) {
+        const int i = (int)threadIdx.x + j * ARG_T;
+        if (i < ARG_WORDS) ((int *)&s_args)[i] = arg_w[j];
+    }
+    __syncthreads();
+    const rs_args &A = s_args;        // everything from here on reads the LDS copy
+    const amc_resolve_ws &W = A.W;
+    rs_shared *wc = (rs_shared *)W.wctl;
+    __shared__ cw_lds L_all[CW_WPB];
+    cw_lds &L = L_all[threadIdx.x >> 6];
     if (stalled && A.od_tick > stalled) return;
     if (ncand > W.max_cand) ncand = W.max_cand;
     if (wave_id == 0 && lane == 0) {

@@ -44,19 +44,8 @@ struct rs_args {
     int od_tick;
 };
 
-// The argument block of the resolve kernels is 1.3 KB.  Read field by field from the kernarg segment it costs every wave a
-// long train of dependent scalar loads (and SGPR spills) at the head of every phase — measured: most of these
-// latency-bound kernels' time.  Each workgroup therefore copies the block into LDS once, with one coalesced vector
-// load, and reads the fields from there.  The kernel's only formal parameter is the block (offset 0 of the segment).
-#define RS_STAGE_ARGS(A)                                                                              \
-    __shared__ rs_args s_args__;                                                                      \
-    {                                                                                                 \
-        const int *src__ = (const int *)__builtin_amdgcn_kernarg_segment_ptr();                       \
-        int *dst__ = (int *)&s_args__;                                                                \
-        for (int i__ = threadIdx.x; i__ < (int)(sizeof(rs_args) / 4); i__ += blockDim.x) dst__[i__] = src__[i__];   \
-        __syncthreads();                                                                              \
-    }                                                                                                 \
-    const rs_args &A = s_args__
+// The resolve kernels' only formal parameter is this block (offset 0 of the kernarg segment).  k_clusters_wide copies it
+// into LDS at its entry (amc_clusters.hip); the ordered workgroup reads it from the segment (amc_resolve.hip).
 
 struct amc_ctx;
 hipError_t amc_launch_clusters_wide(amc_ctx *c, const rs_args &A);      // amc_clusters.hip
