@@ -457,6 +457,7 @@ int amc_upload(amc_ctx *c, const double *x, const double *y, const double *z, co
     AMC_HIP(c, hipSetDevice(c->device));
     { int rc_ = amc_flush(c); if (rc_) return rc_; }
     c->step.lists_age = -1;          // (kept lists: a new state starts with a full build)
+    amc_mg_step_fresh(c);            // (and a pending pack describes the old one)
     const size_t nb = sizeof(double) * (size_t)c->n;
     const double *src[] = {x, y, z, vx, vy, vz, dist, dist_x, dist_y, dist_z};
     double *dst[] = {c->S.x, c->S.y, c->S.z, c->S.vx, c->S.vy, c->S.vz, c->S.d, c->S.dx, c->S.dy, c->S.dz};
@@ -471,11 +472,11 @@ int amc_upload(amc_ctx *c, const double *x, const double *y, const double *z, co
 
 int amc_publish_velocities(amc_ctx *c)
 {
-    if (!c->kin_vpub || c->n <= 0) return AMC_OK;       // not a sharded context
+    if (!c->MG.kin_vpub || c->n <= 0) return AMC_OK;       // not a sharded context
     const size_t nb = sizeof(double) * (size_t)c->n;
     const double *src[3] = {c->S.vx, c->S.vy, c->S.vz};
     for (int e = 0; e < 3; e++)
-        AMC_HIP(c, hipMemcpyAsync(c->kin_vpub + (size_t)e * (size_t)c->n, src[e], nb, hipMemcpyDeviceToDevice, c->stream));
+        AMC_HIP(c, hipMemcpyAsync(c->MG.kin_vpub + (size_t)e * (size_t)c->n, src[e], nb, hipMemcpyDeviceToDevice, c->stream));
     return AMC_OK;
 }
 

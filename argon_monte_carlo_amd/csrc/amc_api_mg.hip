@@ -8,9 +8,10 @@ int amc_set_shard(amc_ctx *c, int64_t lo, int64_t hi)
 {
     if (!c || lo < 0 || hi < lo || hi > c->n) return AMC_ERR_INVALID;
     c->lo = lo; c->hi = hi;
-    c->mg_count_pp = (lo == 0);     // the rank that owns particle 0 reports the sweep's collision count
+    c->MG.count_pp = (lo == 0);     // the rank that owns particle 0 reports the sweep's collision count
+    amc_mg_step_fresh(c);           // (a pending pack describes the old range and the velocities published before)
     AMC_HIP(c, hipSetDevice(c->device));
-    if (!c->kin_vpub) AMC_HIP(c, dalloc(c, &c->kin_vpub, 3 * (size_t)std::max<int64_t>(c->n, 1)));
+    if (!c->MG.kin_vpub) AMC_HIP(c, dalloc(c, &c->MG.kin_vpub, 3 * (size_t)std::max<int64_t>(c->n, 1)));
     if (c->uploaded) return amc_publish_velocities(c);
     return AMC_OK;
 }
@@ -21,6 +22,7 @@ int amc_mg_local(amc_ctx *c, double dt)
     if (c->allpairs || c->P.geometry == AMC_GEOM_CELL || c->P.geometry == AMC_GEOM_PORE_ENERGISED)
         return amc_fail(c, AMC_ERR_INVALID, "amc_mg_local needs the binned detector and the cube / specular pore geometry (energised walls: amc_temp_begin)");
     AMC_HIP(c, hipSetDevice(c->device));
+    amc_mg_step_fresh(c);
     AMC_HIP(c, amc_launch_stream(c, dt, amc_step_stages(c->P.geometry), 0));
     return AMC_OK;
 }
@@ -29,7 +31,8 @@ int amc_mg_exchange_view(amc_ctx *c, int world, void **send, void **recv, int64_
 {
     if (!c || world < 1 || !send || !recv || !block) return AMC_ERR_INVALID;
     AMC_HIP(c, hipSetDevice(c->device));
-    if (c->kin_world != world) {
+    amc_mg_ws &M = c->MG;
+    if (M.kin_world != world) {
         AMC_HIP(c, hipStreamSynchronize(c->stream));
         const int64_t m = std::max<int64_t>((c->n + world - 1) / world, 1);
         int64_t cap = std::max<int64_t>(4096, m / 8);
@@ -61,41 +64,62 @@ int amc_mg_exchange_view(amc_ctx *c, int world, void **send, void **recv, int64_
         if (keep) AMC_HIP(c, dalloc(c, &wave_count, waves));
         if (keep) AMC_HIP(c, hipMemsetAsync(wave_count, 0, sizeof(int) * waves, c->stream));
         group.keep();
-        ctx_free(c, c->kin_send, c->kin_recv, c->mg_wave_count);
-        c->kin_send = ksend; c->kin_recv = krecv; c->mg_wave_count = wave_count;
-        c->kin_m = m; c->kin_cap = cap; c->kin_block = blk;
-        c->kin_counts_clear = false;
+        ctx_free(c, M.kin_send, M.kin_recv, M.wave_count);
+        M.kin_send = ksend; M.kin_recv = krecv; M.wave_count = wave_count;
+        M.kin_m = m; M.kin_cap = cap; M.kin_block = blk;
+        amc_mg_step_fresh(c, true);     // (a pending pack filled the block that has just been freed)
         c->step.lists_age = -1;
         if (grow) {
             ctx_free(c, c->B.rec, c->B.extra);
             c->B.rec = rec; c->B.extra = extra; c->keep_pool = pool;
             c->B_buf[0].rec = rec; c->B_buf[0].extra = extra;
         }
-        if (kept_lists) { c->mg_waves_pack = waves_pack; c->mg_waves_unpack = waves_unpack; }
-        c->mg_keep = keep;
-        c->kin_world = world;       // (the guard: last)
+        if (kept_lists) { M.waves_pack = waves_pack; M.waves_unpack = waves_unpack; }
+        M.keep = keep;
+        M.kin_world = world;        // (the guard: last)
     }
-    *send = c->kin_send; *recv = c->kin_recv; *block = c->kin_block;
+    *send = M.kin_send; *recv = M.kin_recv; *block = M.kin_block;
     return AMC_OK;
 }
 
 // this rank's range must be the driver's shard of that world size (the unpack side recomputes the ranges)
 static int mg_check_shard(amc_ctx *c, int world, int rank)
 {
-    if (world != c->kin_world || rank < 0 || rank >= world) return amc_fail(c, AMC_ERR_STATE, "world/rank do not match amc_mg_exchange_view");
+    if (world != c->MG.kin_world || rank < 0 || rank >= world) return amc_fail(c, AMC_ERR_STATE, "world/rank do not match amc_mg_exchange_view");
     const int64_t base = c->n / world, rem = c->n % world;
     const int64_t lo = rank * base + std::min<int64_t>(rank, rem), hi = lo + base + (rank < rem ? 1 : 0);
     if (lo != c->lo || hi != c->hi) return amc_fail(c, AMC_ERR_STATE, "rank %d of %d owns [%lld,%lld), amc_set_shard says [%lld,%lld)", rank, world, (long long)lo, (long long)hi, (long long)c->lo, (long long)c->hi);
     return AMC_OK;
 }
 
+static const char *mg_phase_name(const amc_mg_step &s)
+{
+    static const char *const names[] = {"no step is pending", "amc_mg_pack is pending", "amc_mg_detect is pending", "the sweep is done: amc_mg_finish is next"};
+    return names[s.phase];
+}
+
+// `who`(world) needs the pack of this step and of this world size behind it (amc_mg_step's rule)
+static int mg_need_pack(amc_ctx *c, const char *who, int world)
+{
+    const amc_mg_step &s = c->MG.step;
+    if (s.phase == AMC_MG_IDLE) return amc_fail(c, AMC_ERR_STATE, "%s(world=%d) without amc_mg_pack in this step", who, world);
+    if (s.phase != AMC_MG_PACKED) return amc_fail(c, AMC_ERR_STATE, "%s(world=%d) needs a pending amc_mg_pack: %s", who, world, mg_phase_name(s));
+    if (s.world != world) return amc_fail(c, AMC_ERR_STATE, "%s(world=%d) after amc_mg_pack(world=%d)", who, world, s.world);
+    return AMC_OK;
+}
+
 int amc_mg_pack(amc_ctx *c, int world)
 {
     if (!c || !c->uploaded) return AMC_ERR_STATE;
-    if (world != c->kin_world) return amc_fail(c, AMC_ERR_STATE, "amc_mg_exchange_view(world=%d) has not been called", world);
+    amc_mg_step &s = c->MG.step;
+    if (world < 1 || world != c->MG.kin_world) return amc_fail(c, AMC_ERR_STATE, "amc_mg_exchange_view(world=%d) has not been called", world);
+    if (s.phase != AMC_MG_IDLE) return amc_fail(c, AMC_ERR_STATE, "amc_mg_pack(world=%d) needs a step without a pack yet: %s", world, mg_phase_name(s));
     AMC_HIP(c, hipSetDevice(c->device));
     { int rc_ = amc_flush(c); if (rc_) return rc_; }
-    AMC_HIP(c, amc_launch_kin_pack(c, world, 0, 0));
+    const int mode = amc_list_build_mode(c, 2, c->MG.keep);
+    AMC_HIP(c, amc_launch_kin_pack(c, mode, !s.counts_clear));
+    s.phase = AMC_MG_PACKED; s.world = world; s.mode = mode;
+    s.counts_clear = false;         // (the pack kernel counts this step's velocity changes into them)
     return AMC_OK;
 }
 
@@ -103,21 +127,27 @@ int amc_mg_sweep(amc_ctx *c, int world, int rank)
 {
     if (!c || !c->uploaded) return AMC_ERR_STATE;
     if (c->allpairs || c->P.geometry == AMC_GEOM_CELL) return amc_fail(c, AMC_ERR_INVALID, "multi-GPU needs the binned detector");
+    amc_mg_step &s = c->MG.step;
+    if (world > 1 || s.phase != AMC_MG_IDLE) {          // (one rank, nothing packed: the lists are built below)
+        if (int rc = mg_need_pack(c, "amc_mg_sweep", world)) return rc;
+    }
+    if (world > 1) {
+        if (int rc = mg_check_shard(c, world, rank)) return rc;
+    }
     AMC_HIP(c, hipSetDevice(c->device));
     { int rc_ = amc_flush(c); if (rc_) return rc_; }
+    const bool lists = s.phase == AMC_MG_PACKED;
     if (world > 1) {
-        int rc = mg_check_shard(c, world, rank);
-        if (rc) return rc;
-        if (!c->kin_lists) return amc_fail(c, AMC_ERR_STATE, "amc_mg_sweep(world=%d) without amc_mg_pack in this step", world);
-        AMC_HIP(c, amc_launch_kin_pack(c, world, rank, 1));
+        AMC_HIP(c, amc_launch_kin_unpack(c, world, rank, s.mode));
+        s.counts_clear = true;
     }
     // the single-GPU sweep over all n particles; the per-cell lists were built by the pack / unpack kernels (if nothing
     // was packed — one rank, no exchange — they are built here).  The scatter of the results is deferred as on one GPU:
     // the next streaming pass over the shard picks up those of its own particles, the next unpack releases the slots of
     // the others (whose results arrive from their owners).
-    const bool lists = c->kin_lists;
-    c->kin_lists = false;
-    return amc_enqueue_sweep(c, lists, true);
+    if (int rc = amc_enqueue_sweep(c, lists, true)) return rc;
+    s.phase = AMC_MG_SWEPT;
+    return AMC_OK;
 }
 
 // ---- detection sharded by index: unpack + detect over [lo, hi) | second all-gather (candidate pairs) | graph + resolve ----
@@ -125,7 +155,8 @@ int amc_mg_candidates_view(amc_ctx *c, int world, void **send, void **recv, int6
 {
     if (!c || world < 1 || !send || !recv || !block_ints) return AMC_ERR_INVALID;
     AMC_HIP(c, hipSetDevice(c->device));
-    if (c->cand_world != world) {
+    amc_mg_ws &M = c->MG;
+    if (M.cand_world != world) {
         AMC_HIP(c, hipStreamSynchronize(c->stream));
         // a quarter of the context's candidate capacity (n / 32 pairs by default; amc_params.max_candidates scales it): ~60x the
         // pairs a rank of eight finds per step at the reference's density, and room for the first step of a synthetic start,
@@ -142,11 +173,14 @@ int amc_mg_candidates_view(amc_ctx *c, int world, void **send, void **recv, int6
         AMC_HIP(c, hipMemsetAsync(crecv, 0, sizeof(int) * blk * (size_t)world, c->stream));
         AMC_HIP(c, hipStreamSynchronize(c->stream));
         group.keep();
-        ctx_free(c, c->cand_send, c->cand_recv);
-        c->cand_send = csend; c->cand_recv = crecv; c->cand_cap = cand_cap;
-        c->cand_world = world;      // (the guard: last)
+        ctx_free(c, M.cand_send, M.cand_recv);
+        M.cand_send = csend; M.cand_recv = crecv; M.cand_cap = cand_cap;
+        // (pending candidates were in the blocks that have just been freed; a pending pack is none of this view's business:
+        // the driver asks for the view between the first all-gather and amc_mg_detect, dist.ShardedSimulation._sweep)
+        if (M.step.phase == AMC_MG_DETECTED) amc_mg_step_fresh(c);
+        M.cand_world = world;       // (the guard: last)
     }
-    *send = c->cand_send; *recv = c->cand_recv; *block_ints = 2 + 2 * (int64_t)c->cand_cap;
+    *send = M.cand_send; *recv = M.cand_recv; *block_ints = 2 + 2 * (int64_t)M.cand_cap;
     return AMC_OK;
 }
 
@@ -154,32 +188,40 @@ int amc_mg_detect(amc_ctx *c, int world, int rank)
 {
     if (!c || !c->uploaded) return AMC_ERR_STATE;
     if (c->allpairs || c->detect_ap || c->P.geometry == AMC_GEOM_CELL) return amc_fail(c, AMC_ERR_INVALID, "multi-GPU needs the binned detector");
-    if (world != c->cand_world) return amc_fail(c, AMC_ERR_STATE, "amc_mg_candidates_view(world=%d) has not been called", world);
+    amc_mg_step &s = c->MG.step;
+    if (world != c->MG.cand_world) return amc_fail(c, AMC_ERR_STATE, "amc_mg_candidates_view(world=%d) has not been called", world);
+    if (int rc = mg_need_pack(c, "amc_mg_detect", world)) return rc;
+    if (int rc = mg_check_shard(c, world, rank)) return rc;
     AMC_HIP(c, hipSetDevice(c->device));
     { int rc_ = amc_flush(c); if (rc_) return rc_; }
-    int rc = mg_check_shard(c, world, rank);
-    if (rc) return rc;
-    if (!c->kin_lists) return amc_fail(c, AMC_ERR_STATE, "amc_mg_detect(world=%d) without amc_mg_pack in this step", world);
-    if (world > 1) AMC_HIP(c, amc_launch_kin_pack(c, world, rank, 1));          // the other shards' positions in, lists completed
-    c->kin_lists = false;
+    if (world > 1) {                                    // the other shards' positions in, lists completed
+        AMC_HIP(c, amc_launch_kin_unpack(c, world, rank, s.mode));
+        s.counts_clear = true;
+    }
     AMC_HIP(c, amc_launch_detect_own(c));
+    s.phase = AMC_MG_DETECTED;
     return AMC_OK;
 }
 
 int amc_mg_resolve(amc_ctx *c, int world)
 {
     if (!c || !c->uploaded) return AMC_ERR_STATE;
-    if (world != c->cand_world) return amc_fail(c, AMC_ERR_STATE, "amc_mg_candidates_view(world=%d) has not been called", world);
+    amc_mg_step &s = c->MG.step;
+    if (world != c->MG.cand_world) return amc_fail(c, AMC_ERR_STATE, "amc_mg_candidates_view(world=%d) has not been called", world);
+    if (s.phase != AMC_MG_DETECTED) return amc_fail(c, AMC_ERR_STATE, "amc_mg_resolve(world=%d) without amc_mg_detect in this step: %s", world, mg_phase_name(s));
+    if (s.world != world) return amc_fail(c, AMC_ERR_STATE, "amc_mg_resolve(world=%d) after amc_mg_detect(world=%d)", world, s.world);
     AMC_HIP(c, hipSetDevice(c->device));
     AMC_HIP(c, amc_launch_ingest(c, world));
     AMC_HIP(c, amc_launch_resolve(c, true));
     c->step.lazy_pending = true;
+    s.phase = AMC_MG_SWEPT;
     return AMC_OK;
 }
 
 int amc_mg_bounds(amc_ctx *c)
 {
     if (!c || !c->uploaded) return AMC_ERR_STATE;
+    if (c->MG.step.phase != AMC_MG_IDLE) return amc_fail(c, AMC_ERR_STATE, "amc_mg_bounds belongs in front of amc_mg_pack: %s", mg_phase_name(c->MG.step));
     AMC_HIP(c, hipSetDevice(c->device));
     { int rc_ = amc_flush(c); if (rc_) return rc_; }
     AMC_HIP(c, amc_launch_stream(c, 0.0, AMC_ST_BOUNDS, 0));        // Temp:804 on the owned range, counters read later
@@ -189,6 +231,9 @@ int amc_mg_bounds(amc_ctx *c)
 int amc_mg_finish(amc_ctx *c, amc_step_stats *out)
 {
     if (!c) return AMC_ERR_INVALID;
+    amc_mg_step &s = c->MG.step;
+    if (s.phase != AMC_MG_SWEPT) return amc_fail(c, AMC_ERR_STATE, "amc_mg_finish without amc_mg_sweep / amc_mg_resolve in this step: %s", mg_phase_name(s));
+    s.phase = AMC_MG_IDLE;          // the step is over, whatever is returned below
     AMC_HIP(c, hipSetDevice(c->device));
     if (c->P.geometry == AMC_GEOM_PORE || c->P.geometry == AMC_GEOM_PORE_ENERGISED)
         AMC_HIP(c, amc_launch_stream(c, 0.0, AMC_ST_BOUNDS, 1));                     // Pore:550 / Temp:844

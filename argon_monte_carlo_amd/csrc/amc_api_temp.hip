@@ -54,6 +54,7 @@ int amc_temp_begin(amc_ctx *c, double dt)
     if ((rc = amc_flush(c))) return rc;
     c->keep_prior = true;       // the energised masks read prior_*_vals (Temp:708-750)
     c->T.h.fresh();
+    amc_mg_step_fresh(c);
     AMC_HIP(c, amc_launch_stream(c, dt, AMC_ST_DRIFT | AMC_ST_WALLS, 0));
     return AMC_OK;
 }
@@ -456,6 +457,7 @@ int amc_temp_run_device(amc_ctx *c, double dt, int64_t nsteps, const amc_temp_rn
     D.series_n = 0;
     D.fetched = false;
     c->T.h.fresh();
+    amc_mg_step_fresh(c);
     c->keep_prior = true;               // (as after amc_temp_begin)
     AMC_HIP(c, hipMemsetAsync(D.ovf, 0, 4 * sizeof(int), c->stream));
     const bool fuse = !c->allpairs;     // the detection grid's lists are filed by the last pass in front of the sweep

@@ -136,36 +136,51 @@ __global__ __launch_bounds__(256) void k_kin_unpack(kin_arrays S, long long n, i
     }
 }
 
-hipError_t amc_launch_kin_pack(amc_ctx *c, int world, int rank, int unpack)
+// what both exchange kernels take from the context: the state arrays and the published velocities, the lists with the
+// exchange kernels' own wave pools (kept lists)
+static void kin_views(amc_ctx *c, kin_arrays &S, amc_lists &Bm)
 {
-    const long long m = c->kin_m, capb = c->kin_cap / AMC_KIN_BANKS;
+    const amc_mg_ws &M = c->MG;
+    S.a[0] = c->S.x; S.a[1] = c->S.y; S.a[2] = c->S.z; S.a[3] = c->S.vx; S.a[4] = c->S.vy; S.a[5] = c->S.vz;
+    S.pub[0] = M.kin_vpub; S.pub[1] = M.kin_vpub + c->n; S.pub[2] = M.kin_vpub + 2 * c->n;
+    Bm = c->B;
+    Bm.wave_count = M.wave_count;
+}
+
+// a new set of lists — this shard now, the other shards at the unpack — or, with kept lists (pore), a step of a cycle: `mode`
+// (amc_list_build_mode, owner 2: the caller's, before this launch reads c->B)
+hipError_t amc_launch_kin_pack(amc_ctx *c, int mode, bool clear_counts)
+{
+    const amc_mg_ws &M = c->MG;
+    const long long m = M.kin_m, capb = M.kin_cap / AMC_KIN_BANKS;
     if (m <= 0) return hipSuccess;
     kin_arrays S;
-    S.a[0] = c->S.x; S.a[1] = c->S.y; S.a[2] = c->S.z; S.a[3] = c->S.vx; S.a[4] = c->S.vy; S.a[5] = c->S.vz;
-    S.pub[0] = c->kin_vpub; S.pub[1] = c->kin_vpub + c->n; S.pub[2] = c->kin_vpub + 2 * c->n;
+    amc_lists Bm;
+    kin_views(c, S, Bm);
     amc_prof_begin(c, AMC_K_BIN_COUNT);       // (the list build is what these kernels cost)
-    amc_lists Bm = c->B;
-    Bm.wave_count = c->mg_wave_count;       // (kept lists: the exchange kernels' own pools)
-    if (!unpack) {
-        // a new set of lists — this shard now, the other shards at the unpack — or, with kept lists (pore), a step of a cycle
-        c->kin_mode = amc_list_build_mode(c, 2, c->mg_keep);
-        Bm = c->B;
-        Bm.wave_count = c->mg_wave_count;
-        c->kin_lists = true;
-        if (!c->kin_counts_clear) {             // (normally the previous step's unpack kernel has cleared the banks' counters)
-            hipError_t e = hipMemsetAsync(c->kin_send + 3 * m, 0, sizeof(double) * AMC_KIN_BANKS, c->stream);
-            if (e != hipSuccess) return e;
-        }
-        c->kin_counts_clear = false;
-        AMC_LAUNCH(c, k_kin_pack, dim3((unsigned)((m + 255) / 256)), dim3(256), S, (long long)c->lo,
-                           (long long)c->hi, m, capb, c->kin_send, c->G, Bm, c->d_cnt, c->kin_mode);
-    } else {
-        const long long per = m > c->kin_cap ? m : c->kin_cap;
-        AMC_LAUNCH(c, k_kin_unpack, dim3((unsigned)(((long long)world * per + 255) / 256)), dim3(256), S,
-                           (long long)c->n, world, rank, m, capb, c->kin_recv, c->G, Bm, c->d_cnt, c->W.slot_of, c->kin_send, c->kin_mode,
-                           c->mg_waves_pack);
-        c->kin_counts_clear = true;
+    if (clear_counts) {                       // (normally the previous step's unpack kernel has cleared the banks' counters)
+        hipError_t e = hipMemsetAsync(M.kin_send + 3 * m, 0, sizeof(double) * AMC_KIN_BANKS, c->stream);
+        if (e != hipSuccess) return e;
     }
+    AMC_LAUNCH(c, k_kin_pack, dim3((unsigned)((m + 255) / 256)), dim3(256), S, (long long)c->lo,
+                       (long long)c->hi, m, capb, M.kin_send, c->G, Bm, c->d_cnt, mode);
+    amc_prof_end(c);
+    return hipGetLastError();
+}
+
+hipError_t amc_launch_kin_unpack(amc_ctx *c, int world, int rank, int mode)
+{
+    const amc_mg_ws &M = c->MG;
+    const long long m = M.kin_m, capb = M.kin_cap / AMC_KIN_BANKS;
+    if (m <= 0) return hipSuccess;
+    kin_arrays S;
+    amc_lists Bm;
+    kin_views(c, S, Bm);
+    amc_prof_begin(c, AMC_K_BIN_COUNT);
+    const long long per = m > M.kin_cap ? m : M.kin_cap;
+    AMC_LAUNCH(c, k_kin_unpack, dim3((unsigned)(((long long)world * per + 255) / 256)), dim3(256), S,
+                       (long long)c->n, world, rank, m, capb, M.kin_recv, c->G, Bm, c->d_cnt, c->W.slot_of, M.kin_send, mode,
+                       M.waves_pack);
     amc_prof_end(c);
     return hipGetLastError();
 }

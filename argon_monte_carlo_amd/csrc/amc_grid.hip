@@ -485,7 +485,7 @@ hipError_t amc_launch_detect_own(amc_ctx *c)
     amc_prof_begin(c, AMC_K_DETECT);
     if (cnt > 0)
         AMC_LAUNCH(c, k_detect_own, dim3((unsigned)((cnt + 255) / 256)), dim3(256), c->G, c->B, (long long)c->lo, (long long)c->hi,
-                   c->G.cr2_probe, c->G.cr_probe, c->cand_send, c->cand_cap, c->d_cnt);
+                   c->G.cr2_probe, c->G.cr_probe, c->MG.cand_send, c->MG.cand_cap, c->d_cnt);
     amc_prof_end(c);
     return hipGetLastError();
 }
@@ -498,8 +498,8 @@ hipError_t amc_launch_ingest(amc_ctx *c, int world)
     D.head = c->W.adj_head; D.rec = c->W.cand4; D.sd = c->W.cand_s; D.epoch = c->step.sweep_epoch;
     D.sl_meta = c->W.sl_meta; D.sl_hits = c->W.sl_hits; D.ev_gen = c->W.ev_gen; D.mark = c->W.cand_mark;
     amc_prof_begin(c, AMC_K_DETECT);
-    AMC_LAUNCH(c, k_ingest_candidates, dim3(16), dim3(256), (const int *)c->cand_recv, world, 2 + 2 * c->cand_cap, c->cand_cap,
-               c->W.max_cand, c->d_cnt, D, c->cand_send);
+    AMC_LAUNCH(c, k_ingest_candidates, dim3(16), dim3(256), (const int *)c->MG.cand_recv, world, 2 + 2 * c->MG.cand_cap, c->MG.cand_cap,
+               c->W.max_cand, c->d_cnt, D, c->MG.cand_send);
     amc_prof_end(c);
     return hipGetLastError();
 }

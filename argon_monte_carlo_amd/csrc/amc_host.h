@@ -100,6 +100,14 @@ AMC_INTERNAL int amc_flush(amc_ctx *c);                                 // write
 AMC_INTERNAL int amc_enqueue_sweep(amc_ctx *c, bool counted = false, bool defer_commit = false);   // bin (unless counted) + detect + resolve
 AMC_INTERNAL int amc_fields_step(amc_ctx *c);                         // the cadence hook after a completed step (amc_fields.hip)
 
+// amc_timestep, amc_run and the stage calls: not in the middle of a sharded step (the rule above amc_mg_step)
+static inline int amc_mg_step_idle(amc_ctx *c, const char *who)
+{
+    if (c->MG.step.phase == AMC_MG_IDLE) return AMC_OK;
+    return amc_fail(c, AMC_ERR_STATE, "%s in the middle of a sharded step (amc_mg_pack ... amc_mg_finish): finish it, or start over with "
+                                      "amc_mg_local / amc_upload", who);
+}
+
 // a sample is due after the step that leaves the step counter at `step`
 static inline bool amc_fields_due(const amc_ctx *c, int64_t step)
 {

@@ -54,7 +54,6 @@ extern "C" int amc_init_synthetic(amc_ctx *c, const amc_ic_config *cfg)
     if (!c || !cfg || cfg->struct_size != (int32_t)sizeof(amc_ic_config)) return AMC_ERR_INVALID;
     if (cfg->n_regions < 0 || cfg->n_regions > 8 || !(cfg->a_shape >= 0.0)) return amc_fail(c, AMC_ERR_INVALID, "amc_init_synthetic: bad configuration");
     if (c->n > 0xffffffffLL) return amc_fail(c, AMC_ERR_INVALID, "amc_init_synthetic: particle index exceeds the 32-bit counter word");
-    c->step.lists_age = -1;          // (kept lists: a new state starts with a full build)
     if (cfg->n_regions == 0 && c->P.geometry != AMC_GEOM_CUBE && c->P.geometry != AMC_GEOM_CELL)
         return amc_fail(c, AMC_ERR_INVALID, "amc_init_synthetic: this geometry needs the region table");
     for (int r = 0; r < cfg->n_regions; r++)
@@ -63,6 +62,8 @@ extern "C" int amc_init_synthetic(amc_ctx *c, const amc_ic_config *cfg)
     if (cfg->n_regions > 0 && cfg->first[cfg->n_regions] != c->n) return amc_fail(c, AMC_ERR_INVALID, "amc_init_synthetic: the regions hold %lld particles, the context %lld", (long long)cfg->first[cfg->n_regions], (long long)c->n);
     AMC_HIP(c, hipSetDevice(c->device));
     { int rc_ = amc_flush(c); if (rc_) return rc_; }
+    c->step.lists_age = -1;          // (kept lists: a new state starts with a full build)
+    amc_mg_step_fresh(c);            // (and a pending pack describes the old one)
     if (c->n > 0) {
         AMC_LAUNCH(c, k_ic, dim3((unsigned)((c->n + 255) / 256)), dim3(256), c->S, c->P, *cfg, (long long)c->n);
         AMC_HIP(c, hipGetLastError());

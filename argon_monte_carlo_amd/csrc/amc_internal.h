@@ -249,6 +249,56 @@ struct amc_surface_ws {
     bool lost;                      // a step or run overflowed its records: hits are missing (amc_surface_read: AMC_ERR_STATE)
 };
 
+// What the sharded step leaves pending between two amc_mg_* calls (amc_api_mg.hip).  The rule — a call whose requirement fails
+// returns AMC_ERR_STATE before it enqueues anything and leaves the record as it was:
+//   amc_mg_pack(world)         requires idle and the exchange view of `world`; leaves packed(world) and `mode`.
+//   amc_mg_sweep(world, rank)  world > 1: requires packed(world) and the shard check; world == 1: idle (it builds the lists
+//                              itself) or packed(1).  Leaves swept.
+//   amc_mg_detect(world, rank) requires packed(world), the candidates view of `world` and the shard check; leaves
+//                              detected(world).
+//   amc_mg_resolve(world)      requires detected(world); leaves swept.
+//   amc_mg_bounds              requires idle (it moves particles: after the pack their positions have been sent); leaves idle.
+//   amc_mg_finish              requires swept; leaves idle, whatever it goes on to return: the step is over.
+//   amc_timestep, amc_run and the four amc_stage_* calls require idle too (amc_mg_step_idle, amc_host.h).  A step or sweep of
+//                              the context's own between the pack and the unpack would run over the other shards' old
+//                              positions, and — unless something flushed in between — over their slot_of[] entries of the last
+//                              sweep, which only the unpack kernel releases: rs_claim_slot (amc_resolve_dev.h) would take such an
+//                              index for a slot of the new sweep.
+// An entry point that begins a sharded step or replaces particle state abandons what is pending (amc_mg_step_fresh below):
+// amc_mg_local, amc_temp_begin, amc_temp_run_device; amc_upload, amc_init_synthetic, amc_set_shard; amc_mg_exchange_view when
+// it reallocates, and amc_mg_candidates_view when it reallocates under pending candidates (detected: under a pending pack it
+// changes nothing — the driver asks for it between the first all-gather and amc_mg_detect).  A later amc_mg_sweep /
+// amc_mg_detect then fails ("without amc_mg_pack in this step").  The kept lists start with a full build afterwards.  What
+// an abandoned pack had published is lost to the other ranks: the job recovers when every rank uploads the state again.
+// Only the entry points of amc_api_mg.hip and amc_mg_step_fresh write the record; the launchers (amc_exchange.hip) are handed
+// what they need and report nothing back through the context.
+enum amc_mg_phase { AMC_MG_IDLE = 0, AMC_MG_PACKED, AMC_MG_DETECTED, AMC_MG_SWEPT };
+struct amc_mg_step {
+    amc_mg_phase phase;            // (zero: idle)
+    int world;                     // the world size of the pending pack (packed, detected)
+    int mode = 1;                  // this step's list build: 1 anew, 2 full build of a kept cycle, 3 a step in between — written by
+                                   // the pack, read by the unpack
+    bool counts_clear;             // the bank counters in kin_send are zero (the unpack kernel clears them for the next pack)
+    void fresh() { phase = AMC_MG_IDLE; counts_clear = false; }     // (costs the next pack one 128-byte memset)
+};
+
+// multi-GPU (amc_api_mg.hip, amc_exchange.hip)
+struct amc_mg_ws {
+    bool count_pp = true;          // this rank adds the p-p collision count to its counters
+    double *kin_send, *kin_recv;   // per-step exchange (amc_exchange.hip): one block of kin_block doubles, and world of them
+    double *kin_vpub;              // [3][n] velocities as last published to the other ranks (allocated by amc_set_shard;
+                                   // every upload publishes: all ranks upload the same full state)
+    int kin_world;
+    int64_t kin_m, kin_cap, kin_block;   // shard length (padded), capacity of the velocity-change list (all banks), 3m + banks + 4cap
+    int *cand_send, *cand_recv;    // detection sharded by index: this rank's candidate block ([0] count, [2 + 2k] pairs)
+    int cand_cap, cand_world;      // and the blocks of all ranks (the second all-gather of a step); pairs per block
+    // kept lists in the exchange kernels (pore, amc_lists): pools per wave of the pack and of the unpack kernel
+    int *wave_count;               // [waves_pack + waves_unpack]
+    int waves_pack, waves_unpack;
+    bool keep;                     // the pools exist for the current world size
+    amc_mg_step step;
+};
+
 // what amc_ctx::owned records (amc_host.h): the context's device / pinned allocations, streams and events
 enum amc_res_kind { AMC_RES_DEVICE, AMC_RES_PINNED, AMC_RES_STREAM, AMC_RES_EVENT };
 struct amc_res { void *p; amc_res_kind kind; };
@@ -262,6 +312,8 @@ struct amc_res { void *p; amc_res_kind kind; };
 
 // What the launchers change as they enqueue a step: everything a rewind of amc_run's on-demand loop has to put back (it keeps
 // a copy per step, together with c->B and c->out.step).  A new per-step member of the host's goes HERE.
+// (What the SHARDED step leaves pending between two amc_mg_* calls is amc_mg_step, amc_ctx::MG.step: amc_run requires an idle
+// one and never touches it, so a rewind has nothing of it to put back.)
 // The rule for what a step leaves pending: an entry point that reads outputs runs the pending commit before its first copy
 // (amc_settle_commit, or amc_read_counters which starts with it); one that reads or replaces particle arrays calls amc_flush
 // first; amc_reset_outputs runs the pending commit and then zeroes, and leaves lazy_pending alone.
@@ -372,23 +424,18 @@ struct amc_ctx {
     int64_t od_ordered_launches;   // launches of k_resolve<GEOM,0> so far
     int64_t od_steps;              // steps enqueued without it
     int64_t od_stalls, od_stalls_last;   // stalls the host has answered; those raised by the last step of their run
-    // multi-GPU (amc_api_mg.hip, amc_exchange.hip)
-    bool mg_count_pp = true;       // this rank adds the p-p collision count to its counters
-    double *kin_send, *kin_recv;   // per-step exchange (amc_exchange.hip): one block of kin_block doubles, and world of them
-    double *kin_vpub;              // [3][n] velocities as last published to the other ranks (allocated by amc_set_shard;
-                                   // every upload publishes: all ranks upload the same full state)
-    int kin_world;
-    int64_t kin_m, kin_cap, kin_block;   // shard length (padded), capacity of the velocity-change list (all banks), 3m + banks + 4cap
-    int *cand_send, *cand_recv;    // detection sharded by index: this rank's candidate block ([0] count, [2 + 2k] pairs)
-    int cand_cap, cand_world;      // and the blocks of all ranks (the second all-gather of a step); pairs per block
-    // kept lists in the exchange kernels (pore, amc_lists): pools per wave of the pack and of the unpack kernel
-    int *mg_wave_count;            // [mg_waves_pack + mg_waves_unpack]
-    int mg_waves_pack, mg_waves_unpack;
-    bool mg_keep;                  // the pools exist for the current world size
-    int kin_mode = 1;              // this step's list build: 1 anew, 2 full build of a kept cycle, 3 a step in between
-    bool kin_lists;                // amc_mg_pack started this step's per-cell lists (the unpack completes them)
-    bool kin_counts_clear;         // the bank counters in kin_send are zero (cleared by the last unpack kernel)
+    amc_mg_ws MG;                  // multi-GPU (amc_api_mg.hip, amc_exchange.hip)
 };
+
+// Abandon what the sharded step has pending (the rule above amc_mg_step): the one call of every entry point named there.
+// An idle record stays as it is — after a completed step the unpack kernel has cleared the bank counters, so a correct run
+// enqueues no memset of them.  send_replaced: the send block is a new allocation, whatever the phase.
+static inline void amc_mg_step_fresh(amc_ctx *c, bool send_replaced = false)
+{
+    if (!send_replaced && c->MG.step.phase == AMC_MG_IDLE) return;
+    c->MG.step.fresh();
+    c->step.lists_age = -1;         // (an abandoned pack may have begun a kept cycle with its own shard only)
+}
 
 int amc_fail(amc_ctx *c, int code, const char *fmt, ...);
 #define AMC_HIP(c, call)                                                                                      \
@@ -462,5 +509,8 @@ hipError_t amc_launch_surface_device(amc_ctx *c);
 hipError_t amc_launch_surface_case(amc_ctx *c, int case_id, int n);
 int amc_surface_park(amc_ctx *c, int case_id, int n);             // (allocates park_bin at the first call: an amc_status)
 hipError_t amc_launch_surface_finish(amc_ctx *c, int case_id, int n);
-hipError_t amc_launch_kin_pack(amc_ctx *c, int world, int rank, int unpack);
+// the exchange kernels (amc_exchange.hip): they read c->MG and change nothing in it.  clear_counts: zero the send block's bank
+// counters in front of the pack kernel
+hipError_t amc_launch_kin_pack(amc_ctx *c, int mode, bool clear_counts);
+hipError_t amc_launch_kin_unpack(amc_ctx *c, int world, int rank, int mode);
 int amc_kin_banks(void);         // banks of the velocity-change list in an exchange block

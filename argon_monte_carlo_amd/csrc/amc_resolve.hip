@@ -628,7 +628,7 @@ static rs_args rs_make_args(amc_ctx *c)
     A.apply_only = 0;
     A.sweep_epoch = c->step.sweep_epoch;
     A.wide_plan = 0;
-    A.count_pp = c->mg_count_pp ? 1 : 0;
+    A.count_pp = c->MG.count_pp ? 1 : 0;
     A.lo = c->lo; A.hi = c->hi;
     A.inv_dx = c->P.dx > 0 ? 1.0 / c->P.dx : 0.0; A.inv_dy = c->P.dy > 0 ? 1.0 / c->P.dy : 0.0; A.inv_dz = c->P.dz > 0 ? 1.0 / c->P.dz : 0.0;
     A.W.raise_dev = nullptr; A.W.raise_host = nullptr; A.W.raise_tick = 0;

@@ -125,6 +125,7 @@ int amc_timestep(amc_ctx *c, double dt, amc_step_stats *out)
 {
     if (!c) return AMC_ERR_INVALID;
     if (!c->uploaded) return amc_fail(c, AMC_ERR_STATE, "amc_timestep before amc_upload");
+    if (int rc = amc_mg_step_idle(c, "amc_timestep")) return rc;
     AMC_HIP(c, hipSetDevice(c->device));
     int rc = enqueue_step(c, dt);
     if (rc) return rc;
@@ -343,6 +344,7 @@ int amc_run(amc_ctx *c, double dt, int64_t nsteps, amc_step_stats *sum)
 {
     if (!c) return AMC_ERR_INVALID;
     if (!c->uploaded) return amc_fail(c, AMC_ERR_STATE, "amc_run before amc_upload");
+    if (int rc = amc_mg_step_idle(c, "amc_run")) return rc;
     AMC_HIP(c, hipSetDevice(c->device));
     const bool whole = c->lo == 0 && c->hi == c->n && !c->allpairs;
     // (sampled fields with a cadence: the plain loop, whose steps end with the state a sample reads)
@@ -373,10 +375,11 @@ int amc_run(amc_ctx *c, double dt, int64_t nsteps, amc_step_stats *sum)
     return amc_finish_stats(c, sum);
 }
 
-// a stage on its own starts from complete particle arrays
+// a stage on its own starts from complete particle arrays, and is no part of a sharded step
 static int stage_begin(amc_ctx *c)
 {
     if (!c || !c->uploaded) return AMC_ERR_STATE;
+    if (int rc = amc_mg_step_idle(c, "a stage call")) return rc;
     AMC_HIP(c, hipSetDevice(c->device));
     return amc_flush(c);
 }

@@ -343,7 +343,7 @@ amc_commit_args amc_make_commit_args(amc_ctx *c)
     amc_commit_args C;
     C.ctl = (amc_resolve_ctl *)W.ctl; C.hist = W.hist; C.ov_head = W.ov_head; C.ev_gen = W.ev_gen; C.ev = W.ev;
     C.sl_meta = W.sl_meta; C.sl_hits = W.sl_hits; C.sl_moved = W.sl_moved; C.sl_state = W.sl_state; C.slot_of = W.slot_of;
-    C.max_slots = W.max_slots; C.max_hist = W.max_hist; C.lo = c->lo; C.hi = c->hi; C.count_pp = c->mg_count_pp ? 1 : 0;
+    C.max_slots = W.max_slots; C.max_hist = W.max_hist; C.lo = c->lo; C.hi = c->hi; C.count_pp = c->MG.count_pp ? 1 : 0;
     C.defer = c->step.commit_defer ? 1 : 0; C.nogrid = c->allpairs ? 1 : 0; C.enabled = 0;
     C.step = c->step.commit_step;
     C.od_stall = nullptr; C.od_tick = 0; C.from_wide = 0; C.wctl = nullptr; C.host_ncand = nullptr;

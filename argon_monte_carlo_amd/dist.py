@@ -140,29 +140,13 @@ class ShardedSimulation:
         if not (self.world == 1 and self.comm.shortcut):
             send, recv = e.exchange_buffers(self.world)
             e.mg_pack(self.world)
-            if self._comm_events is None:
-                self.comm.allgather_packed(send, recv)
-            else:                                   # measurement: the collective bracketed by events on the launch stream
-                import torch
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                a.record()
-                self.comm.allgather_packed(send, recv)
-                b.record()
-                self._comm_events.append((a, b))
+            self._allgather(send, recv)
         if self.replicated_detect or (self.world == 1 and self.comm.shortcut) or not hasattr(e, "mg_detect"):
             e.mg_sweep(self.world, self.rank)
         else:
             csend, crecv = e.candidate_buffers(self.world)
             e.mg_detect(self.world, self.rank)              # the other shards in, then my particles against everybody
-            if self._comm_events is None:
-                self.comm.allgather_packed(csend, crecv)    # everybody's candidate pairs to everybody
-            else:
-                import torch
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                a.record()
-                self.comm.allgather_packed(csend, crecv)
-                b.record()
-                self._comm_events.append((a, b))
+            self._allgather(csend, crecv)                   # everybody's candidate pairs to everybody
             e.mg_resolve(self.world)                        # the same candidate graph and ordered resolve on every rank
         st = e.mg_finish(want_stats)
         if st is None:
@@ -171,6 +155,17 @@ class ShardedSimulation:
             tot = self.comm.allreduce_sum_ints([st[k] for k in self.SUM_KEYS])
             st.update(dict(zip(self.SUM_KEYS, tot)))
         return st
+
+    def _allgather(self, send, recv):
+        if self._comm_events is None:
+            self.comm.allgather_packed(send, recv)
+            return
+        import torch                            # measurement: the collective bracketed by events on the launch stream
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        self.comm.allgather_packed(send, recv)
+        b.record()
+        self._comm_events.append((a, b))
 
     def profile_collective(self, enable):
         """Bracket every all-gather with events on the launch stream (bench.py's per-kernel pass, GPU engines only)."""
@@ -271,6 +266,73 @@ class ShardedSimulation:
             return counts, tot
         flat = self.comm.allreduce_sum_ints(list(counts.astype(np.int64).ravel()) + [int(tot)])
         return np.array(flat[:-1], dtype=np.uint64).reshape(counts.shape), flat[-1]
+
+
+class LocalRanks:
+    """All ranks of a sharded job in ONE process on one GPU: the ``ShardEngine`` of every rank (all on one stream), their
+    exchange and candidate buffers, and device-to-device copies on that stream in place of the two all-gathers (what the
+    collectives deliver, without their time).  Every phase of the step (include/argonmc.h, "multi-GPU") is a method of its
+    own, over all ranks; ``step`` is the phases in order.  One rank exchanges nothing: ``mg_local``, ``mg_sweep(1, 0)``,
+    ``mg_finish``, the driver's shortcut.  (tools/rehearse_ranks.py; the GPU tests that drive ranks out of order.)"""
+
+    def __init__(self, engines, replicated=True):
+        self.engines, self.world, self.replicated = list(engines), len(engines), bool(replicated)
+        self.buffers()
+
+    def buffers(self):
+        """(again after a call that made an engine reallocate its views)"""
+        one = self.world == 1
+        self.xb = None if one else [e.exchange_buffers(self.world) for e in self.engines]
+        self.cb = None if one or self.replicated else [e.candidate_buffers(self.world) for e in self.engines]
+
+    @staticmethod
+    def gather(bufs):
+        """every rank's send block into every rank's receive buffer, in rank order"""
+        blk = bufs[0][0].numel()
+        for _, recv in bufs:
+            for q, (send, _) in enumerate(bufs):
+                recv[q * blk:(q + 1) * blk].copy_(send)
+
+    def local(self, dt):
+        for e in self.engines:
+            e.mg_local(dt)
+
+    def pack(self):
+        if self.world > 1:
+            for e in self.engines:
+                e.mg_pack(self.world)
+
+    def exchange(self, candidates=False):
+        """the step's first all-gather (behind ``pack``), or its second one: the candidate pairs (behind ``detect``)"""
+        if self.world > 1:
+            self.gather(self.cb if candidates else self.xb)
+
+    def sweep(self):
+        for r, e in enumerate(self.engines):
+            e.mg_sweep(self.world, r)
+
+    def detect(self):
+        for r, e in enumerate(self.engines):
+            e.mg_detect(self.world, r)
+
+    def resolve(self):
+        for e in self.engines:
+            e.mg_resolve(self.world)
+
+    def finish(self, want_stats=False):
+        return [e.mg_finish(want_stats) for e in self.engines]
+
+    def step(self, dt, want_stats=False):
+        self.local(dt)
+        self.pack()
+        self.exchange()
+        if self.replicated or self.world == 1:
+            self.sweep()
+        else:
+            self.detect()
+            self.exchange(candidates=True)
+            self.resolve()
+        return self.finish(want_stats)
 
 
 class _GlobalWallHooks:

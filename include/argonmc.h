@@ -342,7 +342,22 @@ int amc_init_synthetic(amc_ctx *ctx, const amc_ic_config *cfg);
  * amc_wall_hits / amc_wall_apply act on [lo,hi); the host concatenates the hits of all ranks in rank order (=
  * ascending particle index) before drawing the random directions, so every rank consumes the two RNG streams
  * identically.  amc_mg_bounds is the bounds check between the walls and the sweep (Temp:804) on [lo,hi)
- * without a counter read-back; the sweep then runs as above. */
+ * without a counter read-back; the sweep then runs as above.
+ * The call order is checked.  A call whose requirement fails returns AMC_ERR_STATE before it enqueues anything and leaves the
+ * pending step as it was:
+ *   amc_mg_pack(world)           no pack pending, the exchange view of `world`
+ *   amc_mg_sweep(world, rank)    the pack of this step and this world size (world == 1: that, or nothing pending: it
+ *                                builds the lists)
+ *   amc_mg_detect(world, rank)   the pack of this step and this world size, the candidates view of `world`
+ *   amc_mg_resolve(world)        amc_mg_detect(world) of this step
+ *   amc_mg_bounds                nothing pending (after the pack the positions it would move have been sent)
+ *   amc_mg_finish                the sweep (amc_mg_sweep or amc_mg_resolve) of this step; it ends the step whatever it returns
+ *   amc_timestep, amc_run, amc_stage_*   nothing pending: no step of the context's own in the middle of a sharded one
+ * A call that begins a sharded step or replaces particle state abandons what is pending, so that the next amc_mg_sweep /
+ * amc_mg_detect fails ("without amc_mg_pack in this step"): amc_mg_local, amc_temp_begin, amc_temp_run_device, amc_upload,
+ * amc_init_synthetic, amc_set_shard, amc_mg_exchange_view when it reallocates and amc_mg_candidates_view when it reallocates
+ * between amc_mg_detect and amc_mg_resolve (between the pack and amc_mg_detect it may: the driver asks for the view there).
+ * What an abandoned pack had published is lost to the other ranks: the job recovers when every rank uploads the state again. */
 int amc_set_shard(amc_ctx *ctx, int64_t lo, int64_t hi);
 int amc_mg_local(amc_ctx *ctx, double dt);
 /* Buffers of the all-gather.  One block per rank: with m = ceil(n / world) and cap = max(4096, m / 8),

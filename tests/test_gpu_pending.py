@@ -38,7 +38,7 @@ from argon_monte_carlo_amd import fields as FL
 from argon_monte_carlo_amd import ic as IC
 from argon_monte_carlo_amd import params as PR
 from argon_monte_carlo_amd._abi import AmcParams
-from argon_monte_carlo_amd.dist import shard_range
+from argon_monte_carlo_amd.dist import LocalRanks, shard_range
 
 pytestmark = pytest.mark.gpu
 
@@ -373,44 +373,18 @@ class Rig:
             e.upload(*self.T.init, flag=self.T.flag0)
             if fields:
                 e.fields_config(FL.default_grid(self.p))
-        if self.world > 1:
-            self.xb = [e.exchange_buffers(self.world) for e in self.engs]
-            self.cb = [e.candidate_buffers(self.world) for e in self.engs] if self.prod == "shard2_idx" else None
+        if self.prod.startswith("shard"):
+            # (the exchange is the helper's copy on the contexts' one stream, in launch order: the same bytes a copy through
+            # the host delivers — tools/rehearse_ranks.py compares that path with a single context bit for bit)
+            self.job = LocalRanks(self.engs, replicated=self.prod != "shard2_idx")
 
     def close(self):
         for e in self.engs:
             e.close()
 
     # -- stepping ---------------------------------------------------------------------------------------------------------
-    @staticmethod
-    def _gather(bufs):
-        """what the all-gather delivers, through host copies of the ranks' blocks"""
-        blk = bufs[0][0].numel()
-        host = [send.cpu() for send, _ in bufs]
-        for _, recv in bufs:
-            for q, h in enumerate(host):
-                recv[q * blk:(q + 1) * blk].copy_(h)
-
     def _shard_step(self, want):
-        es, w = self.engs, self.world
-        if w == 1:
-            es[0].mg_local(self.dt)
-            es[0].mg_sweep(1, 0)
-        else:
-            for e in es:
-                e.mg_local(self.dt)
-                e.mg_pack(w)
-            self._gather(self.xb)
-            if self.cb is None:
-                for r, e in enumerate(es):
-                    e.mg_sweep(w, r)
-            else:
-                for r, e in enumerate(es):
-                    e.mg_detect(w, r)
-                self._gather(self.cb)
-                for e in es:
-                    e.mg_resolve(w)
-        sts = [e.mg_finish(want) for e in es]
+        sts = self.job.step(self.dt, want)
         if not want:
             return None
         return {"n_pp": sts[0]["n_pp"], "n_paths": sum(s["n_paths"] for s in sts)}

@@ -20,7 +20,7 @@ import torch
 
 from argon_monte_carlo_amd import ic as IC
 from argon_monte_carlo_amd import params as PR
-from argon_monte_carlo_amd.dist import shard_range
+from argon_monte_carlo_amd.dist import LocalRanks, shard_range
 from argon_monte_carlo_amd.engine import Engine, ShardEngine
 
 
@@ -48,38 +48,14 @@ def main():
         e.set_stream(stream)
         e.upload(*init)
         ranks.append(e)
-    xb = [e.exchange_buffers(world) for e in ranks]
-    cb = [e.candidate_buffers(world) for e in ranks] if not replicated else None
-
-    def gather(bufs):
-        blk = bufs[0][0].numel()
-        for r, (_, recv) in enumerate(bufs):
-            for q, (send, _) in enumerate(bufs):
-                recv[q * blk:(q + 1) * blk].copy_(send)
-
-    def step(want=False):
-        for e in ranks:
-            e.mg_local(dt)
-            e.mg_pack(world)
-        gather(xb)
-        if replicated:
-            for r, e in enumerate(ranks):
-                e.mg_sweep(world, r)
-        else:
-            for r, e in enumerate(ranks):
-                e.mg_detect(world, r)
-            gather(cb)
-            for e in ranks:
-                e.mg_resolve(world)
-        return [e.mg_finish(want) for e in ranks]
-
+    job = LocalRanks(ranks, replicated=replicated)
     for _ in range(5):
-        step()
+        job.step(dt)
     torch.cuda.synchronize()
     ranks[0].profile(True)
     t0 = time.perf_counter()
     for s in range(steps):
-        st = step(want=(s == steps - 1))
+        st = job.step(dt, s == steps - 1)
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
     kt = ranks[0].kernel_times()
@@ -103,8 +79,8 @@ def main():
            "rank0_kernel_us_per_step": per_step, "rank0_kernel_us_per_step_sum": sum(per_step.values()),
            "pp_collisions_per_step": (sum(s["n_pp"] for s in st if s) / (steps + 5)) if st[0] else None,
            "all_ranks_equal_single_context_bit_for_bit": equal,
-           "bytes_gathered_per_step": {"positions_and_velocity_changes": int(xb[0][1].numel() * 8),
-                                       "candidate_pairs": int(cb[0][1].numel() * 4) if cb else 0}}
+           "bytes_gathered_per_step": {"positions_and_velocity_changes": int(job.xb[0][1].numel() * 8),
+                                       "candidate_pairs": int(job.cb[0][1].numel() * 4) if job.cb else 0}}
     print(json.dumps(out, indent=1))
 
 
