@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Generate the golden vectors under tests/golden/ from the REFERENCE ITSELF (build container only).
 
-    MPLBACKEND=Agg PYTHONDONTWRITEBYTECODE=1 python3 oracle/gen_golden.py [--only func|edge|cube|pore|temp|consts|cube_natural|pore_natural]
+    MPLBACKEND=Agg PYTHONDONTWRITEBYTECODE=1 python3 oracle/gen_golden.py [--only func|edge|temp_edge|cube|pore|temp|consts|cube_natural|pore_natural]
 
 * function level: imports /root/reference/Open_Air_Pore_MC.py (its main loop is __main__-guarded) and calls
   pairwise_particles_in_cell / hit_vertical_wall / hit_cylinder_side_wall / num_out_of_bounds on seeded inputs
@@ -467,6 +467,23 @@ def dump(step, ncoll=None, lists=None):
                    float(np.sum(arr('x_vals'))), float(np.sum(arr('y_vals'))), float(np.sum(arr('z_vals'))),
                    float(np.sum(vx)), float(np.sum(vy)), float(np.sum(vz)), float(np.sum(vx*vx+vy*vy+vz*vz)),
                    float(np.sum(arr('dist_since_collision'))), float(np.sum(arr('full_path_traveled')))])
+def load_state(path):
+    # crafted inputs (tests/edge_states.py) in place of the script's own initial state: its arrays are module globals
+    g = sys.modules['__main__'].__dict__
+    with np.load(path) as d:
+        for k in _KEYS:
+            assert g[k].shape == d[k].shape and g[k].dtype == d[k].dtype, k
+            g[k] = d[k].copy()
+def dump_cases(masks, scalars, lists):
+    # after the last energised case of a step: the masks by their names in the script, the state, the sums, the paths
+    g = sys.modules['__main__'].__dict__
+    for k in masks:
+        _store['c_' + k] = np.asarray(g[k]).astype(bool).copy()
+    for k in _KEYS:
+        _store['c_' + k] = np.asarray(g[k]).reshape(-1).copy()
+    for k, v in scalars.items():
+        _store['c_' + k] = np.asarray(v)
+    _store['c_paths'] = np.array([list(l) for l in lists], dtype=np.float64).reshape(4, -1).T.copy()
 def finish(lists, extra=None):
     _store['per_step'] = np.array(_store.get('per_step', []), dtype=np.float64).reshape(-1, 12)
     for name, l in zip(['completed_paths', 'completed_x_paths', 'completed_y_paths', 'completed_z_paths'], lists):
@@ -493,8 +510,23 @@ def _indent_of(line):
     return line[:len(line) - len(line.lstrip())]
 
 
-def run_patched(script, subs, inserts, snap_steps, out_name, meta, timeout=3600, hash_all=False):
-    """inserts: list of (regex of anchor line, 'before'|'after', code string using the anchor's indentation)."""
+def save_npz_deterministic(path, arrays):
+    """np.savez_compressed with fixed member times and order: the same arrays give the same bytes on every run"""
+    import zipfile
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
+        for k in sorted(arrays):
+            info = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            with z.open(info, "w") as fh:
+                np.lib.format.write_array(fh, np.asanyarray(arrays[k]), allow_pickle=False)
+
+
+def run_patched(script, subs, inserts, snap_steps, out_name, meta, timeout=3600, hash_all=False, files=None, keep_text=True,
+                post=None):
+    """inserts: list of (regex of anchor line, 'before'|'after', code string using the anchor's indentation).
+    files: {name: {key: array}} written as .npz beside the patched script; post(d): last word on the dump, which is then
+    written with fixed member times (byte-identical from run to run)."""
     work = tempfile.mkdtemp(prefix="amc_golden_", dir="/tmp")
     try:
         lines = open(os.path.join(REF, script)).read().split("\n")
@@ -515,6 +547,8 @@ def run_patched(script, subs, inserts, snap_steps, out_name, meta, timeout=3600,
         with open(os.path.join(work, "_golden_hook.py"), "w") as f:
             f.write(HOOK % (STATE_KEYS, sorted(snap_steps), bool(hash_all)))
         shutil.copy(os.path.join(REF, "utils.py"), os.path.join(work, "utils.py"))
+        for name, arrays in (files or {}).items():
+            np.savez(os.path.join(work, name), **arrays)
         env = dict(os.environ, MPLBACKEND="Agg", PYTHONDONTWRITEBYTECODE="1")
         r = subprocess.run([sys.executable, "-u", "patched.py"], cwd=work, env=env, stdout=subprocess.PIPE,
                            stderr=subprocess.STDOUT, timeout=timeout)
@@ -526,11 +560,16 @@ def run_patched(script, subs, inserts, snap_steps, out_name, meta, timeout=3600,
         for k, v in meta.items():
             d["meta_" + k] = np.asarray(v)
         # the text outputs the script wrote (format goldens)
-        for fn in sorted(os.listdir(work)):
+        for fn in sorted(os.listdir(work)) if keep_text else ():
             if fn.startswith("hist_") and fn.endswith(".txt") or fn == "momentum_energy.csv":
                 d["file_" + fn] = np.frombuffer(open(os.path.join(work, fn), "rb").read(), dtype=np.uint8)
-        np.savez_compressed(os.path.join(OUT, out_name), **d)
-        print(out_name, "written;", "steps:", d["per_step"].shape[0], "paths:", d["completed_paths"].shape[0])
+        if post is not None:
+            post(d)
+            save_npz_deterministic(os.path.join(OUT, out_name), d)
+        else:
+            np.savez_compressed(os.path.join(OUT, out_name), **d)
+        print(out_name, "written;", "steps:", d["per_step"].shape[0], "paths:",
+              (d["completed_paths"] if "completed_paths" in d else d["completed_rows"]).shape[0])
     finally:
         shutil.rmtree(work, ignore_errors=True)
 
@@ -574,6 +613,62 @@ def gen_temp(tag, K, sigma_mult, slice_, steps, snaps):
     ]
     run_patched("Temperature_Pore_MC.py", subs, inserts, set(snaps) | {-1},
                 f"step_temp_{tag}.npz", dict(K=K, sigma_mult=sigma_mult, slice=slice_, steps=steps))
+
+
+TEMP_MASKS = {3: "hit_vertical_int_open_air_cold", 4: "hit_vertical_int_open_air_hot", 5: "hit_gap_cylinder_wall",
+              6: "hit_gap_cylinder_base_bottom", 7: "hit_gap_cylinder_base_top", 8: "hit_pore_coating_hot",
+              9: "hit_pore_coating_cold"}        # case id -> the mask's name in Temperature_Pore_MC.py (Temp:708-749)
+
+
+def temp_edge_inputs():
+    """The inputs of --only temp_edge: tests/edge_states.temp_walls(reference_safe=True) under the reference's names (also
+    used by tests/test_oracle_edges.py to check that the fixture still belongs to the builder)."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    from tests import edge_states as E
+    w = E.temp_walls(reference_safe=True)
+    a = w.arrays()
+    st = {k: v for k, v in zip(STATE_KEYS[:10], a[:10])}
+    st["full_path_traveled"] = a[10].astype(bool)
+    return st
+
+
+def gen_temp_edge():
+    """Temperature_Pore_MC.py for ONE step on the crafted energised edge state: its own masks (inline in its main loop, so
+    no function-level fixture reaches them), the state after the seven cases and after the step, its error count, paths
+    and sums.  num_molecules is the state's size; the state arrays are overwritten just before the time loop."""
+    st = temp_edge_inputs()
+    n = len(st["x_vals"])
+    subs = [
+        (r"^num_molecules\s+= np\.round\(", f"num_molecules               = np.int64({n})"),
+        (r"^        for step in range\(num_timesteps\):", "        for step in range(1):"),
+    ]
+    names = [TEMP_MASKS[k] for k in sorted(TEMP_MASKS)]
+    inserts = [
+        (r"^        for step in range\(\d+\):", "before", "_golden_hook.load_state('edge_state.npz')"),
+        (r"^        for step in range\(\d+\):", "before", "_golden_hook.dump(-1)"),
+        (r"^            energy_transfer_cold_per_step\.append\(energy_change_cold_in_step\)", "after",
+         f"_golden_hook.dump_cases({names!r}, dict(total_errs=total_errs, "
+         "momentum_z_change_in_step=float(momentum_z_change_in_step), "
+         "energy_change_cold_in_step=float(energy_change_cold_in_step), "
+         "energy_change_hot_in_step=float(energy_change_hot_in_step)), "
+         "[completed_paths, completed_x_paths, completed_y_paths, completed_z_paths])"),
+        (r"^            print\('   ',num_collisions_per_step\.value,' collisions from this timestep'\)", "after",
+         "_golden_hook.dump(step, num_collisions_per_step.value, [completed_paths])"),
+        (r"^        print\('Num of measured full paths total: '", "after",
+         "_golden_hook.finish([completed_paths, completed_x_paths, completed_y_paths, completed_z_paths], "
+         "dict(dt=dt, collision_range=collision_range, total_cols=total_cols, total_errs=total_errs))"),
+    ]
+
+    def post(d):
+        # the sweep's workers append their paths in scheduling order: store the rows sorted (they are compared as a multiset)
+        rows = np.stack([d.pop("completed_paths"), d.pop("completed_x_paths"), d.pop("completed_y_paths"),
+                         d.pop("completed_z_paths")], axis=1)
+        d["completed_rows"] = rows[np.lexsort(rows.T[::-1])]
+        for k in TEMP_MASKS.values():
+            d["c_" + k] = np.packbits(d["c_" + k])
+
+    run_patched("Temperature_Pore_MC.py", subs, inserts, {-1, 0}, "func_temp_edge.npz", dict(K=n, steps=1),
+                files={"edge_state.npz": st}, keep_text=False, post=post)
 
 
 def gen_cube(tag, K, sigma_mult, steps, snaps):
@@ -670,6 +765,8 @@ def main():
         gen_graph_hist()
     if a.only == "edge":
         gen_edge()
+    if a.only == "temp_edge":
+        gen_temp_edge()
     if a.only == "cube_natural":
         gen_cube_natural()
     if a.only == "pore_natural":

@@ -600,3 +600,274 @@ def field_positions(edges_r, edges_z):
     put("z_hi", rmid, 0.0, float(edges_z[-1]))
     put("z_beyond", rmid, 0.0, float(np.nextafter(edges_z[-1], np.inf)))
     return np.array(xs), np.array(ys), np.array(zs), cases
+
+
+# ---------------------------------------------------------------------------------------------------------- energised walls
+TEMP_SLOTS = 140      # azimuth slots of a ring: 1.34 nm of arc at R_p_c, more than three collision ranges
+
+
+def _temp():
+    return PR.pore_params(n=0, energised=True)
+
+
+def _unit(k):
+    """the unit vector of azimuth slot k; slots 0, 35, 70, 105 are the four axes, exactly"""
+    q = k % TEMP_SLOTS
+    if q % (TEMP_SLOTS // 4) == 0:
+        return [(1.0, 0.0), (0.0, 1.0), (-1.0, 0.0), (0.0, -1.0)][q // (TEMP_SLOTS // 4)]
+    a = 2.0 * np.pi * q / TEMP_SLOTS
+    return float(np.cos(a)), float(np.sin(a))
+
+
+def radius_side(Rsq, c, s, want):
+    """(x, y) at sqrt(Rsq) * (c, s), the larger coordinate moved by up to 6 ulp so that x*x + y*y is "below", "on" or
+    "above" Rsq by as little as doubles allow (the search of pore_bounds()); None if no such value is among them"""
+    r0 = np.sqrt(np.float64(Rsq))
+    x, y = float(r0 * c), float(r0 * s)
+    major_x = abs(c) >= abs(s)
+    best = None
+    for v in around(x if major_x else y, 6):
+        xx, yy = (v, y) if major_x else (x, v)
+        q = xx * xx + yy * yy
+        side = "on" if q == Rsq else ("above" if q > Rsq else "below")
+        if side == want and (best is None or abs(q - Rsq) < best[0]):
+            best = (abs(q - Rsq), xx, yy)
+    return None if best is None else (best[1], best[2])
+
+
+class _Slots:
+    """azimuth slots per (zone, band): a zone is a z level, a band a radius; two particles of one zone and band never
+    share a slot, and a fast particle takes two"""
+
+    def __init__(self):
+        self.cursor, self.axes = {}, {}
+
+    def take(self, key, axis=False, wide=False):
+        if axis:
+            k = self.axes.get(key, 0)
+            assert k < 4, key
+            self.axes[key] = k + 1
+            return k * (TEMP_SLOTS // 4)
+        k = self.cursor.get(key, 1)
+        if wide:
+            k += 1
+        while k % (TEMP_SLOTS // 4) == 0 or (wide and (k + 1) % (TEMP_SLOTS // 4) == 0):
+            k += 1
+        self.cursor[key] = k + (2 if wide else 1)
+        assert self.cursor[key] <= TEMP_SLOTS, key
+        return k
+
+
+def temp_walls(reference_safe=False, far=True):
+    """Particles on every plane and squared radius the energised wall sequence compares against (Temp:708-751, case ids
+    3..9 in evaluation order), and at the corners where one particle is hit by two cases in one step.
+
+    Zones are z levels (the four planes t_z3_hot, t_zgap_lo, t_zgap_hi, t_z3_cold and levels inside the hot coating, the
+    gap and the cold coating), bands are radii (A: over the coatings / mid annulus, B: at R_p_c .. R_p, C: at R_g_c); every
+    particle has an azimuth slot of its own in its zone and band.
+
+    cases: ``cur_z_case<k>`` / ``prior_z_case<k>`` (z on a plane of case k and +-1, +-2 ulp, landed / uploaded),
+    ``far_prior_case6|7`` (prior z on the OTHER gap plane), ``cur_r_<R>_case<k>_<side>`` / ``prior_r_<R>_case<k>_<side>``
+    (x*x + y*y below / on / above a squared radius), ``corner_4_8``, ``corner_3_9``, ``corner_5_6``, ``corner_5_7``,
+    ``prior_on_Rpc_6_8``, ``prior_on_Rpc_7_9``, ``vz0_on_plane`` and, unless reference_safe, ``tiny_vx_plane``.
+    There is no corner_7_9 of its own: case 7 wants a prior radius^2 >= R_p_c_sq and case 9 one <= R_p_c_sq, so the pair
+    can only meet on a prior radius^2 == R_p_c_sq, which is prior_on_Rpc_7_9.
+
+    far=False leaves out far_prior_case6|7: 160 km/s, a momentum change beyond the range of the sampled surfaces' quantisers.
+    reference_safe drops what the reference cannot execute under np.seterr(all='raise'): a plane hit whose vx**2
+    underflows (hit_vertical_coated_wall has no try block)."""
+    p, c = _temp()
+    dt = c["dt"]
+    s = EdgeState(p, dt)
+    slots = _Slots()
+    zc, zh, zlo, zhi = p.t_z3_cold, p.t_z3_hot, p.t_zgap_lo, p.t_zgap_hi
+    v, vfast = 431.0, 2600.0
+    hop, step = v * dt, vfast * dt
+    R_out, R_ann = p.R_p + 2.0e-9, 0.5 * (p.R_p_c + p.R_g_c)
+
+    def put(case, key, z, vr, vt, vz, landed, r=None, side=None, axis=False, wide=False, tries=1, jitter=True):
+        """one particle of `case` in the next free slot of `key`: at radius r, or on `side` = (Rsq, want) of a squared
+        radius; the velocity is vr along the radius and vt across it.  flag alternates within the case."""
+        for _ in range(tries):
+            k = slots.take(key, axis=axis, wide=wide)
+            cs, sn = _unit(k)
+            xy = (r * cs, r * sn) if side is None else radius_side(side[0], cs, sn, side[1])
+            if xy is None:
+                if axis:
+                    return None
+                continue
+            i = s.add(case, xy[0], xy[1], z, vr * cs - vt * sn, vr * sn + vt * cs, vz, flag=len(s.cases.get(case, [])) % 2,
+                      landed=landed, jitter=jitter)
+            if i is not None:
+                return i
+        return None
+
+    # ---- planes: z on the plane and next to it, current (landed) and prior (uploaded), both signs of vz
+    planes = {3: (zc, "cold_mouth", R_out), 4: (zh, "hot_mouth", R_out), 6: (zlo, "gap_lo", R_ann), 7: (zhi, "gap_hi", R_ann)}
+    for k, (zp, zone, r) in planes.items():
+        for zv in around(zp):
+            for vz in (-v, v):
+                assert put(f"cur_z_case{k}", (zone, "A"), zv, 97.0, -61.0, vz, True, r=r, tries=3) is not None
+                put(f"prior_z_case{k}", (zone, "A"), zv, 97.0, -61.0, vz, False, r=r)
+        for vz in (0.0, -0.0):
+            put("vz0_on_plane", (zone, "A"), zp, 97.0, -61.0, vz, False, r=r)
+        if not reference_safe:
+            vz = -v if k in (3, 6) else v
+            put("tiny_vx_plane", (zone, "A"), zp + 0.5 * dt * vz, 3.0 * TINY, 0.0, vz, True, r=r, axis=True, jitter=False)
+    # prior z on the OTHER gap plane: through the whole gap in one step (pz <= t_zgap_hi in case 6, pz >= t_zgap_lo in case 7)
+    span = zhi - zlo
+    for zv in around(zhi) if far else ():
+        put("far_prior_case6", ("gap_hi", "A"), zv, 97.0, -61.0, -(span + 0.5 * hop) / dt, False, r=R_ann)
+    for zv in around(zlo) if far else ():
+        put("far_prior_case7", ("gap_lo", "A"), zv, 97.0, -61.0, (span + 0.5 * hop) / dt, False, r=R_ann)
+    # case 5's strict pz > t_zgap_lo, pz < t_zgap_hi: leaving the annulus across R_g_c with the prior z on a gap plane
+    for zp, zone, sgn in ((zlo, "gap_lo", 1.0), (zhi, "gap_hi", -1.0)):
+        for zv in around(zp):
+            for vz in (40.0 * sgn, -40.0 * sgn):
+                put("prior_z_case5", (zone, "C"), zv, v, -61.0, vz, False, r=p.R_g_c - 0.4 * hop)
+    # crossing R_p_c with the current z on a plane: closed ends in case 8 (>= t_z3_hot, <= t_zgap_lo), open in case 9
+    for zp, zone, k in ((zh, "hot_mouth", 8), (zlo, "gap_lo", 8), (zhi, "gap_hi", 9), (zc, "cold_mouth", 9)):
+        for zv in around(zp, 1):
+            for vz in (-40.0, 40.0, 0.0):
+                if zv != zp and vz == 0.0:
+                    continue
+                put(f"cur_z_case{k}", (zone, "B"), zv, v, -61.0, vz, True, r=p.R_p_c + 0.5 * hop, tries=3)
+    # ---- squared radii: below / on / above, on an axis and at an oblique azimuth
+    def radii(name, key, Rsq, z, vr, vz, landed):
+        for want in ("below", "on", "above"):
+            for axis in (True, False):
+                put(f"{name}_{want}", key, z, vr, -61.0, vz, landed, side=(Rsq, want), axis=axis, tries=1 if axis else 40)
+
+    radii("cur_r_Rp_case4", ("hot_mouth", "B"), p.R_p_sq, zh + 0.5 * hop, 97.0, v, True)
+    radii("cur_r_Rp_case3", ("cold_mouth", "B"), p.R_p_sq, zc - 0.5 * hop, 97.0, -v, True)
+    radii("cur_r_Rgc_case5", ("gap_140", "C"), p.R_g_c_sq, 140.0e-9, v, 40.0, True)
+    radii("prior_r_Rgc_case5", ("gap_150", "C"), p.R_g_c_sq, 150.0e-9, v, 40.0, False)
+    radii("cur_r_Rpc_case8", ("hot_110", "B"), p.R_p_c_sq, 110.0e-9, v, 40.0, True)
+    radii("cur_r_Rpc_case9", ("cold_200", "B"), p.R_p_c_sq, 200.0e-9, v, 40.0, True)
+    radii("prior_r_Rpc_case8", ("hot_118", "B"), p.R_p_c_sq, 118.0e-9, v, 40.0, False)
+    radii("prior_r_Rpc_case9", ("cold_210", "B"), p.R_p_c_sq, 210.0e-9, v, 40.0, False)
+    radii("prior_r_Rpc_case6", ("gap_lo", "B"), p.R_p_c_sq, zlo + 0.5 * hop, 97.0, -v, False)
+    radii("prior_r_Rpc_case7", ("gap_hi", "B"), p.R_p_c_sq, zhi - 0.5 * hop, 97.0, v, False)
+    # ---- corners: two cases on one particle in one step (fast particles, uploaded), each at its own azimuth
+    for q in range(12):
+        f, g = 0.06 + 0.04 * q, 0.25 + 0.05 * q
+        # up and outward past the hot mouth: case 4 parks it on t_z3_hot, case 8's z >= t_z3_hot then holds
+        put("corner_4_8", ("hot_mouth", "B"), zh - g * step, vfast, 0.0, vfast, False, r=p.R_p_c - f * step, wide=True)
+    # the same with a radial speed that puts the contact with the plane 2 nm outside R_p_c: case 8's solve, on the redrawn
+    # velocity, then misses the cylinder for a fifth of the directions (slots 100 .. 133 of bands A and B, kept free)
+    assert max(slots.cursor[("hot_mouth", "A")], slots.cursor[("hot_mouth", "B")]) <= 99
+    for q in range(12):
+        cs, sn = _unit(100 + 3 * q)
+        r0, vr = p.R_p_c - 0.02e-9 * (q + 1), 1.15e4        # (11.5 km/s: its energy is still inside the sampled surfaces' range)
+        s.add("corner_4_8", r0 * cs, r0 * sn, zh - 0.9 * step, vr * cs, vr * sn, vfast, flag=q % 2, landed=False)
+    for q in range(8):        # (eight of each: the reference's own initialisation needs 268 particles or more to populate every region)
+        f, g = 0.06 + 0.08 * q, 0.2 + 0.1 * q
+        # the mirrored cold mouth: case 3 parks it on t_z3_cold, case 9 asks z < t_z3_cold
+        put("corner_3_9", ("cold_mouth", "B"), zc + g * step, vfast, 0.0, -vfast, False, r=p.R_p_c - f * step, wide=True)
+        # out of the gap annulus across R_g_c and a gap plane: the plane is crossed first, so case 5's contact lies beyond it
+        f = 0.2 + 0.1 * q
+        put("corner_5_6", ("gap_lo", "C"), zlo + 0.5 * f * step, vfast, 0.0, -vfast, False, r=p.R_g_c - f * step, wide=True)
+        put("corner_5_7", ("gap_hi", "C"), zhi - 0.5 * f * step, vfast, 0.0, vfast, False, r=p.R_g_c - f * step, wide=True)
+        # prior radius^2 == R_p_c_sq: both r02 >= (cases 6, 7) and r02 <= (cases 8, 9) hold
+        put("prior_on_Rpc_6_8", ("gap_lo", "B"), zlo + f * step, vfast, 0.0, -vfast, False, side=(p.R_p_c_sq, "on"), wide=True,
+            tries=20)
+        put("prior_on_Rpc_7_9", ("gap_hi", "B"), zhi - f * step, vfast, 0.0, vfast, False, side=(p.R_p_c_sq, "on"), wide=True,
+            tries=20)
+    return s.finish()
+
+
+def temp_many_hits(n=2700):
+    """A few thousand particles that all cross coated planes in the first step: more hits in that one step than the device
+    sums' tile holds (2048), fewer than the record capacity (4096) in any one case, spread over cases 3, 4, 6, 7 and 8.
+    The kinds are interleaved by particle index, so that no case's records arrive in index order.  Case 8 is hit only by
+    corner_4_8-style particles, after case 4 has redrawn their velocity: whether its solve has a real root depends on the
+    drawn direction, so some of them fail and some do not.  Case 9 is hit by five overflowing particles only: every one of
+    its hits is a failed solve."""
+    p, c = _temp()
+    dt = c["dt"]
+    s = EdgeState(p, dt)
+    zc, zh, zlo, zhi = p.t_z3_cold, p.t_z3_hot, p.t_zgap_lo, p.t_zgap_hi
+    v, vfast = 431.0, 2600.0
+    hop, step = v * dt, vfast * dt
+    third = n // 3
+    # over the coatings at the two mouths: a square grid, 1.3 nm
+    g = np.arange(-62.0e-9, 62.0e-9, 1.3e-9)
+    X, Y = np.meshgrid(g, g, indexing="ij")
+    R = np.hypot(X, Y)
+    keep = (R > p.R_p + 1.6e-9) & (R < 60.0e-9)
+    order = np.argsort(R[keep], kind="stable")
+    grid = list(zip(X[keep][order].tolist(), Y[keep][order].tolist()))
+    assert len(grid) >= third
+    k3 = [("many_case3", x, y, zc + 0.4 * hop, 30.0 + 0.01 * j, -20.0 - 0.02 * j, -(v + 0.37 * j)) for j, (x, y) in enumerate(grid[:third])]
+    k4 = [("many_case4", x, y, zh - 0.4 * hop, -25.0 - 0.01 * j, 35.0 + 0.02 * j, v + 0.41 * j) for j, (x, y) in enumerate(grid[:third])]
+    # the corner of the hot mouth (cases 4 and 8) and the two bases of the gap annulus (cases 6, 7), on rings
+    n48 = 130
+    a48 = []
+    for j in range(n48):
+        cs, sn = float(np.cos(2.0 * np.pi * j / TEMP_SLOTS)), float(np.sin(2.0 * np.pi * j / TEMP_SLOTS))
+        f, gz = 0.06 + 0.003 * j, 0.25 + 0.004 * j
+        r0 = p.R_p_c - f * step
+        a48.append(("many_corner_4_8", r0 * cs, r0 * sn, zh - gz * step, vfast * cs, vfast * sn, vfast))
+    per = (n - 2 * third - n48 + 1) // 2
+    k6, k7 = [], []
+    rings = (p.R_p_c + 0.6e-9, p.R_p_c + 1.9e-9, p.R_p_c + 3.2e-9)
+    for j in range(per):
+        a = 2.0 * np.pi * (j % TEMP_SLOTS + 0.5 * ((j // TEMP_SLOTS) % 2)) / TEMP_SLOTS     # (staggered from ring to ring)
+        cs, sn = float(np.cos(a)), float(np.sin(a))
+        r = rings[j // TEMP_SLOTS]
+        k6.append(("many_case6", r * cs, r * sn, zlo + 0.4 * hop, 20.0 + 0.03 * j, -15.0, -(v + 0.29 * j)))
+        k7.append(("many_case7", r * cs, r * sn, zhi - 0.4 * hop, -20.0 - 0.03 * j, 15.0, v + 0.31 * j))
+    rest, streams = [], [a48, k6, k7]
+    while any(streams):
+        for st in streams:
+            if st:
+                rest.append(st.pop(0))
+    rest = rest[:n - 2 * third]
+    for i in range(n):
+        src = (k3, k4, rest)[i % 3]
+        case, x, y, z, vx, vy, vz = src[i // 3]
+        s.add(case, x, y, z, vx, vy, vz, flag=(i // 3) % 2, landed=False, jitter=False)
+    for k in range(5):                  # case 9: every hit a failed solve
+        _overflowing(s, "many_failed_case9", 204.0e-9 + 5.0e-9 * k, k)
+    return s.finish()
+
+
+def assert_temp_coverage(s, masks, failed):
+    """What a run of temp_walls() must have exercised in its first step, whoever ran it (the reference in the fixture, the
+    oracle beside the GPU): ``masks[case]`` = the particle indices hit by case 3 .. 9, ``failed`` = the number of contact
+    solves without a real root."""
+    m = {k: set(int(i) for i in masks[k]) for k in range(3, 10)}
+    assert all(len(m[k]) > 0 for k in m), {k: len(v) for k, v in m.items()}
+    corner = {k: set(s.cases[k]) for k in ("corner_4_8", "corner_3_9", "corner_5_6", "corner_5_7", "prior_on_Rpc_6_8",
+                                          "prior_on_Rpc_7_9")}
+    assert len(corner["corner_4_8"] & m[4] & m[8]) >= 6                  # parked on t_z3_hot by case 4, taken by case 8's z >= t_z3_hot
+    assert len(corner["corner_5_6"] & m[5] & m[6]) >= 6 and len(corner["corner_5_7"] & m[5] & m[7]) >= 6
+    on = corner["prior_on_Rpc_6_8"] | corner["prior_on_Rpc_7_9"]
+    assert all(s.x[i] * s.x[i] + s.y[i] * s.y[i] == s.p.R_p_c_sq for i in on)
+    assert len(corner["prior_on_Rpc_6_8"] & m[6] & m[8]) >= 6            # r02 >= R_p_c_sq and r02 <= R_p_c_sq both hold
+    assert corner["corner_3_9"] <= m[3] and not corner["corner_3_9"] & m[9]          # z == t_z3_cold is not < t_z3_cold
+    assert corner["prior_on_Rpc_7_9"] <= m[7] and not corner["prior_on_Rpc_7_9"] & m[9]      # z == t_zgap_hi is not > t_zgap_hi
+    assert failed >= 1
+
+
+def _overflowing(s, name, z, k):
+    """A particle whose cylinder solve fails for certain: vx = 1e155 carries it from inside the pore far beyond every radius
+    (x*x stays finite) and makes a = vx*vx infinite, so b*b - 4*a*c is inf - inf.  The open-air wall's specular solve fails the
+    same way first (counted, particle left alone), then case 8 or 9 by its z; the bounds check takes the particle back to the
+    axis.  Not for the reference: it raises on the overflow."""
+    s.add(name, 1.0e-9 + 0.1e-9 * k, 0.0, z, 1.0e155, 0.0, 0.0, flag=k % 2, landed=False, jitter=False)
+
+
+def temp_failed_only():
+    """One step in which the hot sum's only hits are failed solves (case 8, overflowing) while the cold sum has good hits
+    (case 3) and failed ones (case 9): the device sums fold + 0.0 for case 8 and leave the hot flag clear."""
+    p, c = _temp()
+    s = EdgeState(p, c["dt"])
+    hop = 431.0 * c["dt"]
+    for k in range(5):
+        _overflowing(s, "only_failed_case8", 104.0e-9 + 5.0e-9 * k, k)
+        _overflowing(s, "only_failed_case9", 204.0e-9 + 5.0e-9 * k, k)
+        cs, sn = _unit(7 * k + 1)
+        s.add("good_case3", (p.R_p + 2.0e-9) * cs, (p.R_p + 2.0e-9) * sn, p.t_z3_cold + 0.4 * hop, 30.0, -20.0, -431.0 - k, flag=k % 2,
+              landed=False)
+    return s.finish()

@@ -151,6 +151,130 @@ def test_pairs_at_the_collision_distance(G):
     assert 0 < hit < n                                                 # both sides of the collision distance
 
 
+# ---------------------------------------------------------------------------------------------------------- energised walls
+# tests/golden/func_temp_edge.npz (`oracle/gen_golden.py --only temp_edge`): Temperature_Pore_MC.py itself for one step on
+# tests/edge_states.temp_walls(reference_safe=True) — its seven masks (inline in its main loop: no function-level fixture
+# reaches them), the state after the cases and after the step, its error count, paths and sums.
+@pytest.fixture(scope="module")
+def GT(golden_dir):
+    return np.load(os.path.join(golden_dir, "func_temp_edge.npz"))
+
+
+def _ref_masks(GT):
+    n = len(GT["s-001_x_vals"])
+    return {k: np.unpackbits(GT["c_" + name])[:n].astype(bool) for k, name in GG.TEMP_MASKS.items()}
+
+
+def test_temp_fixture_inputs_are_the_builders(GT):
+    """the fixture still belongs to tests/edge_states.py (rerun `gen_golden.py --only temp_edge` after changing temp_walls)"""
+    for k, v in GG.temp_edge_inputs().items():
+        assert np.array_equal(np.asarray(v), GT["s-001_" + k]), k
+
+
+def test_oracle_reproduces_the_reference_on_the_energised_edges(GT):
+    """The oracle (`pow`, the reference's RNG states, its own host loop) on the crafted energised state: the seven masks,
+    the state after the cases and after the step, the paths (a multiset: the sweep's workers append in scheduling order),
+    total_errs and the three sums, bit for bit."""
+    import random
+    from oracle import temp_host as TH
+    from tests.test_oracle_steps import restore_rngs
+    n = int(GT["meta_K"])
+    p, c = PR.pore_params(n=n, energised=True)
+    assert p.collision_range == float(GT["collision_range"]) and c["dt"] == float(GT["dt"])
+    restore_rngs(GT)
+    o = O.Oracle(p, mode="pow")
+    o.upload(*[GT[f"s-001_{k}"] for k in STATE_KEYS[:10]], flag=GT["s-001_full_path_traveled"])
+
+    class Recording:
+        masks = {}
+
+        def wall_hits(self, case):
+            r = o.wall_hits(case)
+            self.masks[case] = np.isin(np.arange(n), r[0])
+            return r
+
+        def wall_apply(self, *a):
+            return o.wall_apply(*a)
+
+    o._temp_wall_count = o._temp_errs = 0
+    o.drift(c["dt"], True)
+    o._temp_errs += o.temp_specular()
+    mom, cold, hot, *_ = TH.run_cases(Recording(), TH.Directions(np.random, random), TH.Energies(c))
+    ref = _ref_masks(GT)
+    for k in ref:
+        assert np.array_equal(Recording.masks[k], ref[k]), (k, np.flatnonzero(Recording.masks[k] != ref[k]))
+
+    def same_state(tag):
+        st = o.state()
+        for k, f in zip(STATE_KEYS[:10], O.STATE_FIELDS):
+            assert np.array_equal(st[f], GT[f"{tag}_{k}"]), (tag, k, np.flatnonzero(st[f] != GT[f"{tag}_{k}"])[:5])
+        assert np.array_equal(st["flag"].astype(bool), GT[f"{tag}_full_path_traveled"]), tag
+
+    def rows(r):
+        a = np.stack([r["total"], r["px"], r["py"], r["pz"]], axis=1)
+        return a[np.lexsort(a.T[::-1])]
+
+    same_state("c")
+    cp = GT["c_paths"]
+    assert np.array_equal(rows(o.paths()), cp[np.lexsort(cp.T[::-1])])
+    assert o._temp_errs == int(GT["c_total_errs"]) == int(GT["total_errs"])
+    for got, key in ((mom, "momentum_z_change_in_step"), (cold, "energy_change_cold_in_step"), (hot, "energy_change_hot_in_step")):
+        assert float(got) == float(GT["c_" + key]) != 0.0, key
+    o.bounds(True)
+    rc, npp, _ = o.sweep()
+    o.bounds(True)
+    assert rc == 0 and npp + o._temp_wall_count == int(GT["per_step"][0, 1]) == int(GT["total_cols"])
+    same_state("s0000")
+    assert np.array_equal(rows(o.paths()), GT["completed_rows"])
+
+
+# Temp:708-751, one row per comparison: (case id, left side, operator, threshold, where a particle EXACTLY on the threshold is)
+TEMP_COMPARISONS = [
+    (3, "pz", ">=", "t_z3_cold", "in"), (3, "z", "<", "t_z3_cold", "out"), (3, "r2", ">", "R_p_sq", "out"),
+    (4, "pz", "<=", "t_z3_hot", "in"), (4, "z", ">", "t_z3_hot", "out"), (4, "r2", ">", "R_p_sq", "out"),
+    (5, "pz", "<", "t_zgap_hi", "out"), (5, "pz", ">", "t_zgap_lo", "out"), (5, "r02", "<=", "R_g_c_sq", "in"),
+    (5, "r2", ">", "R_g_c_sq", "out"),
+    (6, "r02", ">=", "R_p_c_sq", "in"), (6, "z", "<", "t_zgap_lo", "out"), (6, "pz", "<=", "t_zgap_hi", "in"),
+    (6, "pz", ">=", "t_zgap_lo", "in"),
+    (7, "r02", ">=", "R_p_c_sq", "in"), (7, "z", ">", "t_zgap_hi", "out"), (7, "pz", "<=", "t_zgap_hi", "in"),
+    (7, "pz", ">=", "t_zgap_lo", "in"),
+    (8, "r02", "<=", "R_p_c_sq", "in"), (8, "r2", ">", "R_p_c_sq", "out"), (8, "z", "<=", "t_zgap_lo", "in"),
+    (8, "z", ">=", "t_z3_hot", "in"),
+    (9, "r02", "<=", "R_p_c_sq", "in"), (9, "r2", ">", "R_p_c_sq", "out"), (9, "z", "<", "t_z3_cold", "out"),
+    (9, "z", ">", "t_zgap_hi", "out"),
+]
+
+
+def test_the_reference_ran_the_energised_edges(GT):
+    """On the FIXTURE: the reference itself hit every case, took the corner sequences (4 then 8, 5 then 6, 5 then 7, 6 then
+    8 from a prior radius^2 == R_p_c_sq; 3 then 9 and 7 then 9 blocked), met a solve without a real root, and put the
+    particle exactly on each threshold inside or outside the mask as the operator of Temp:708-751 says."""
+    import operator
+    s = E.temp_walls(reference_safe=True)
+    masks = _ref_masks(GT)
+    E.assert_temp_coverage(s, {k: np.flatnonzero(v) for k, v in masks.items()}, int(GT["total_errs"]))
+    assert len(TEMP_COMPARISONS) == 26 and len(set(TEMP_COMPARISONS)) == 26
+    # what a mask saw of a particle that no earlier case moved: the prior position as uploaded, the drift's own arithmetic
+    dt, p = float(GT["dt"]), s.p
+    x, y, z = s.x + dt * s.vx, s.y + dt * s.vy, s.z + dt * s.vz
+    val = {"z": z, "pz": s.z, "r2": x ** 2 + y ** 2, "r02": s.x ** 2 + s.y ** 2}
+    ops = {"<": operator.lt, "<=": operator.le, ">": operator.gt, ">=": operator.ge}
+    untouched = np.ones(s.n, dtype=bool)
+    for case in range(3, 10):
+        mine = [row for row in TEMP_COMPARISONS if row[0] == case]
+        for row in mine:
+            _, lhs, op, thr, side = row
+            assert side == ("in" if "=" in op else "out"), row
+            others = np.ones(s.n, dtype=bool)
+            for _, l2, o2, t2, _ in mine:
+                if (l2, o2, t2) != (lhs, op, thr):
+                    others &= ops[o2](val[l2], getattr(p, t2))
+            on = np.flatnonzero(untouched & others & (val[lhs] == getattr(p, thr)))
+            assert len(on) >= 1, ("no particle exactly on", row)
+            assert np.all(masks[case][on] == (side == "in")), (row, on, masks[case][on])
+        untouched &= ~masks[case]
+
+
 # ---------------------------------------------------------------------------------------------------------- the builders
 def _through_oracle(s, steps, **prm):
     for k, v in prm.items():
