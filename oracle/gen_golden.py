@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Generate the golden vectors under tests/golden/ from the REFERENCE ITSELF (build container only).
 
-    MPLBACKEND=Agg PYTHONDONTWRITEBYTECODE=1 python3 oracle/gen_golden.py [--only func|edge|temp_edge|cube|pore|temp|consts|cube_natural|pore_natural]
+    MPLBACKEND=Agg PYTHONDONTWRITEBYTECODE=1 python3 oracle/gen_golden.py [--only func|edge|clusters|temp_edge|cube|pore|temp|consts|cube_natural|pore_natural]
 
 * function level: imports /root/reference/Open_Air_Pore_MC.py (its main loop is __main__-guarded) and calls
   pairwise_particles_in_cell / hit_vertical_wall / hit_cylinder_side_wall / num_out_of_bounds on seeded inputs
@@ -375,6 +375,86 @@ def gen_edge():
     np.savez_compressed(os.path.join(OUT, "func_edge.npz"), **out)
     print("func_edge.npz:", len(out), "arrays,", int(outcome.sum()), "side-wall solves without a real root,",
           int(pnc.sum()), "pair collisions")
+
+
+# ------------------------------------------------------------------------------------------------ crafted clusters
+CLUSTER_FIELDS = ["cont", "cx", "cy", "cz", "flag", "x", "y", "z", "vx", "vy", "vz"]
+CLUSTER_PERMS = ("identity", "reversed")
+
+
+def cluster_inputs():
+    """The inputs of --only clusters, built from tests/cluster_states.py: every cluster of every catalogue state (pore
+    geometry; the 80 copies of items_over / items_fit are left out, pair_pull1 has them already) as ONE cell — the
+    particles of its site in ascending index, positions and accumulators after the drift (Pore:427-437) — under the
+    identity and the reversed permutation."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    from tests import cluster_states as CS
+    cells, names = {f: [] for f in CLUSTER_FIELDS}, []
+    off = [0]
+    for perm in CLUSTER_PERMS:
+        for which in ("within",) + CS.HANDOVER:
+            s = CS.catalogue("pore", perm, which)
+            sx, sy, sz = s.dt * s.vx, s.dt * s.vy, s.dt * s.vz
+            st = dict(cont=s.d + np.abs(np.sqrt(sx * sx + sy * sy + sz * sz)), cx=s.dx + np.abs(sx), cy=s.dy + np.abs(sy),
+                      cz=s.dz + np.abs(sz), flag=s.flag.astype(np.float64), x=s.x + sx, y=s.y + sy, z=s.z + sz,
+                      vx=s.vx, vy=s.vy, vz=s.vz)
+            site = s.extra["site"]
+            case_of = np.empty(s.n, dtype=object)
+            for case, idx in s.cases.items():
+                case_of[idx] = case
+            for q in range(int(site.max()) + 1):
+                idx = np.flatnonzero(site == q)         # (ascending particle index)
+                if which != "within" and case_of[idx[0]] == "pair":
+                    continue                            # (the company of a hand-over state: `within` has that pair)
+                for f in CLUSTER_FIELDS:
+                    cells[f].append(st[f][idx])
+                names.append(f"{perm}/{case_of[idx[0]]}")
+                off.append(off[-1] + len(idx))
+    out = {"cl_in_" + f: np.concatenate(cells[f]) for f in CLUSTER_FIELDS}
+    out["cl_off"] = np.array(off, dtype=np.int64)
+    out["cl_name"] = np.array(names, dtype="U40")
+    return out
+
+
+def gen_clusters():
+    """The reference's own pairwise_particles_in_cell on the crafted clusters (tests/cluster_states.py), one cell each."""
+    out = cluster_inputs()              # (before the import: the reference turns every floating-point warning into an error)
+    os.environ.setdefault("MPLBACKEND", "Agg")
+    sys.path.insert(0, REF)
+    import multiprocessing
+    import Open_Air_Pore_MC as P  # noqa
+    off = out["cl_off"]
+    ncell = len(off) - 1
+    res_all = {f: out["cl_in_" + f].copy() for f in CLUSTER_FIELDS}
+    paths, path_off = [], [0]
+    ncoll = np.zeros(ncell, dtype=np.int64)
+    outcome = np.zeros(ncell, dtype=np.int64)
+    for c in range(ncell):
+        sl = slice(int(off[c]), int(off[c + 1]))
+        counter = multiprocessing.Value('i', 0)
+        P.init_globals(counter)
+        args = [out["cl_in_" + f][sl].copy() for f in CLUSTER_FIELDS]
+        args[4] = args[4].astype(bool)
+        lists = [[], [], [], []]
+        try:
+            res = P.pairwise_particles_in_cell(*lists, np.ones(sl.stop - sl.start, dtype=bool), *args)
+        except FloatingPointError:      # (equal velocities: a == 0 in the contact solve ends the reference's run)
+            outcome[c] = 1
+            path_off.append(len(paths))
+            continue
+        for f, a in zip(CLUSTER_FIELDS, res[1:]):
+            res_all[f][sl] = np.asarray(a, dtype=np.float64)
+        paths.extend(zip(*lists))
+        path_off.append(len(paths))
+        ncoll[c] = counter.value
+    for f in CLUSTER_FIELDS:
+        out["cl_out_" + f] = res_all[f]
+    out["cl_paths"] = np.array(paths, dtype=np.float64).reshape(-1, 4)
+    out["cl_path_off"] = np.array(path_off, dtype=np.int64)
+    out["cl_ncoll"] = ncoll
+    out["cl_outcome"] = outcome
+    save_npz_deterministic(os.path.join(OUT, "func_clusters.npz"), out)
+    print("func_clusters.npz:", ncell, "cells,", int(ncoll.sum()), "collisions,", int(outcome.sum()), "cells the reference raised on")
 
 
 # ------------------------------------------------------------------------------------------------ constants
@@ -765,6 +845,8 @@ def main():
         gen_graph_hist()
     if a.only == "edge":
         gen_edge()
+    if a.only == "clusters":
+        gen_clusters()
     if a.only == "temp_edge":
         gen_temp_edge()
     if a.only == "cube_natural":

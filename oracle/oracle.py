@@ -238,8 +238,9 @@ class Oracle:
         return r
 
 
-def pair_cell(params, cont, cx, cy, cz, flag, x, y, z, vx, vy, vz, mode="pow"):
-    """pairwise_particles_in_cell (Pore:160-255) on one cell; returns (outputs dict, paths[k,4], ncoll, rc)."""
+def pair_cell(params, cont, cx, cy, cz, flag, x, y, z, vx, vy, vz, mode="pow", with_records=False):
+    """pairwise_particles_in_cell (Pore:160-255) on one cell; returns (outputs dict, paths[k,4], ncoll, rc) and, with
+    with_records, the completed-path records themselves (i, j, which of every flagged partner of every hit, in order)."""
     L = lib()
     n = len(x)
     arrs = [np.array(a, dtype=np.float64, copy=True) for a in (cont, cx, cy, cz)]
@@ -255,4 +256,6 @@ def pair_cell(params, cont, cx, cy, cz, flag, x, y, z, vx, vy, vz, mode="pow"):
     paths = np.stack([r["total"], r["px"], r["py"], r["pz"]], axis=1) if sink.n else np.zeros((0, 4))
     out = dict(cont=arrs[0], cx=arrs[1], cy=arrs[2], cz=arrs[3], flag=f.astype(bool), x=parr[0], y=parr[1], z=parr[2],
                vx=parr[3], vy=parr[4], vz=parr[5])
+    if with_records:
+        return out, paths, nc.value, rc, r.copy()
     return out, paths, nc.value, rc
