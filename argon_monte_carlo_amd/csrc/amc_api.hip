@@ -652,6 +652,36 @@ int amc_overlap_stats(amc_ctx *c, int64_t *out)
     return AMC_OK;
 }
 
+// The kept lists as they stand (amc_lists, amc_step_state): reads only — one synchronisation and one copy of the owner's wave
+// counters, no kernel, nothing settled or flushed: whatever a step left pending stays pending.
+int amc_lists_stats(amc_ctx *c, int64_t *out)
+{
+    if (!c || !out) return AMC_ERR_INVALID;
+    AMC_HIP(c, hipSetDevice(c->device));
+    const amc_step_state &T = c->step;
+    const bool cycle = c->keep_K >= 2 && T.lists_age >= 0;
+    const int owner = cycle ? T.lists_owner : 0;
+    const int *counts = nullptr;
+    size_t waves = 0;
+    // (the counters are the last owner's, also once its cycle has ended: lists_owner outlives lists_age)
+    if (c->keep_K >= 2 && T.lists_owner == 2 && c->MG.keep && c->MG.wave_count) {
+        counts = c->MG.wave_count; waves = (size_t)c->MG.waves_pack + (size_t)c->MG.waves_unpack;
+    } else if (c->keep_K >= 2 && c->B.wave_count) {
+        // (the streaming pass's own waves, as alloc_grid_lists counted them: keep_pool may have grown for the exchange kernels)
+        counts = c->B.wave_count; waves = (size_t)((c->n + c->stream_bs - 1) / c->stream_bs) * (size_t)(c->stream_bs / 64);
+    }
+    int64_t sum = 0, top = 0;
+    AMC_HIP(c, hipStreamSynchronize(c->stream));
+    if (counts && waves) {
+        std::vector<int> h(waves);
+        AMC_HIP(c, hipMemcpy(h.data(), counts, sizeof(int) * waves, hipMemcpyDeviceToHost));
+        for (int v : h) { sum += v; top = std::max<int64_t>(top, v); }
+    }
+    out[0] = c->keep_K >= 2 ? c->keep_K : 0; out[1] = c->keep_K >= 2 ? c->B.wave_cap : 0; out[2] = (int64_t)waves;
+    out[3] = cycle ? T.lists_age : -1; out[4] = owner; out[5] = sum; out[6] = top; out[7] = T.full_builds;
+    return AMC_OK;
+}
+
 int amc_kernel_times(amc_ctx *c, double *total_ms, int64_t *launches)
 {
     if (!c) return AMC_ERR_INVALID;

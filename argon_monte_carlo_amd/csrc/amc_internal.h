@@ -327,6 +327,7 @@ struct amc_step_state {
     int lists_age = -1;            // steps since the last full build of a kept cycle (-1: the lists are not a kept cycle's)
     int lists_owner;               // who runs the cycle: 1 the streaming pass, 2 the multi-GPU exchange kernels (their node pools differ)
     bool od_prev_ordered = true;   // the last sweep had its ordered pass: W.ctl holds its counts (else the wide kernel's words do)
+    int64_t full_builds = 0;       // full builds of a kept cycle since amc_create (amc_lists_stats; a rewound step takes its own back)
 };
 
 // Created by amc_create with value-initialisation: every member without an initialiser below starts at zero.

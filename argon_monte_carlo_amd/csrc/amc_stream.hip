@@ -359,7 +359,7 @@ int amc_list_build_mode(amc_ctx *c, int owner, bool kept)
     // kept lists: a full build when the lists are not this owner's or the cycle is over, else a step in between
     if (T.lists_owner != owner) T.lists_age = -1;
     T.lists_owner = owner;
-    if (T.lists_age < 0 || T.lists_age + 1 >= c->keep_K) { c->B.epoch++; T.lists_age = 0; return 2; }
+    if (T.lists_age < 0 || T.lists_age + 1 >= c->keep_K) { c->B.epoch++; T.lists_age = 0; T.full_builds++; return 2; }
     T.lists_age++;
     return 3;
 }

@@ -199,6 +199,15 @@ class Engine:
                     ordered_launches=int(out[4]), on_demand_steps=int(out[5]),
                     stalls=int(out[6]), stalls_at_last_step=int(out[7]))
 
+    def lists_stats(self):
+        """The kept per-cell lists as they stand (amc_lists_stats): K (0: not kept), nodes per wave pool, waves with a pool,
+        steps since the last full build (-1: no cycle), the cycle's owner (1 the streaming pass, 2 the exchange kernels), sum
+        and maximum of the owner's wave counters, full builds since the context was created.  Reads only."""
+        out = np.zeros(8, dtype=np.int64)
+        self._ck(self.lib.amc_lists_stats(self._ctx, out.ctypes.data_as(C.POINTER(C.c_int64))))
+        return dict(keep_K=int(out[0]), wave_cap=int(out[1]), waves=int(out[2]), lists_age=int(out[3]), owner=int(out[4]),
+                    count_sum=int(out[5]), count_max=int(out[6]), full_builds=int(out[7]))
+
     def profile(self, on=True):
         self._ck(self.lib.amc_profile(self._ctx, int(on)))
 

@@ -416,6 +416,14 @@ const char *amc_kernel_name(int k);
  * NOTE: `out` must hold EIGHT values.  Up to the release that launched the ordered workgroup in every sweep the call wrote
  * four: a caller built against that header has to enlarge its buffer (nothing else of the ABI changed). */
 int amc_overlap_stats(amc_ctx *ctx, int64_t *out /*[8]*/);
+/* The kept per-cell lists as they stand (a diagnostic for tests; AMC_LIST_KEEP).  out[0] = K, a full build every K
+ * steps (0: the lists are not kept), out[1] = list nodes in the pool of one wave (64 (K - 1)), out[2] = waves that have a pool,
+ * out[3] = steps since the last full build (-1: no cycle is running, the next step builds in full), out[4] = who runs the cycle
+ * (1 the streaming pass, 2 the multi-GPU exchange kernels, 0 nobody), out[5] / out[6] = sum / maximum over the waves of the
+ * nodes handed out since the last full build, out[7] = full builds since amc_create.  Synchronises the stream and copies
+ * the owner's counters; launches nothing and changes nothing, whatever the last step left pending.  While out[3] is -1,
+ * out[2], out[5] and out[6] are still those of whoever ran the cycle that ended.  Additive: AMC_ABI_VERSION stays 2. */
+int amc_lists_stats(amc_ctx *ctx, int64_t *out /*[8]*/);
 
 /* ---- sampled fields: number density, flow velocity, temperature per spatial bin (opt-in) -----------
  * The reference has no such output.  A sample bins every particle of the context's range [lo, hi) and adds, per bin,

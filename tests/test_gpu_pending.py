@@ -754,11 +754,13 @@ def test_measurement_calls_change_nothing(rig, case):
     for e in r.engs:
         e.overlap_stats()
         e.kernel_times()
-    r.assert_histograms(r.T.paths(r.k), "histograms after overlap_stats / kernel_times")
+        e.lists_stats()
+    r.assert_histograms(r.T.paths(r.k), "histograms after overlap_stats / kernel_times / lists_stats")
     r.assert_state(r.T.state(r.k), "download after overlap_stats / kernel_times")
     for e in r.engs:
         e.overlap_stats()
         e.kernel_times()
+        e.lists_stats()
     r.one_more()
     r.assert_state(r.T.state(r.k), "a step after overlap_stats / kernel_times")
     r.assert_records(r.drain(), r.T.paths(r.k), "records after overlap_stats / kernel_times")
