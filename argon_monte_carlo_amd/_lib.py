@@ -90,6 +90,15 @@ SIGNATURES = {
     "amc_wall_contacts": (C.c_int, [_ctx, C.c_int, _dp, C.c_size_t]),
 }
 
+# ... and every symbol include/argonmc_shard.h declares (the device-RNG energised pore over shards; argonmc.h includes it)
+SHARD_SIGNATURES = {
+    "amc_mg_hits_view": (C.c_int, [_ctx, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
+    "amc_mg_hits_pack": (C.c_int, [_ctx, C.c_int]),
+    "amc_mg_hits_sums": (C.c_int, [_ctx, C.c_int, C.c_int64]),
+    "amc_temp_shard_run_begin": (C.c_int, [_ctx, C.c_int64]),
+    "amc_temp_shard_run_end": (C.c_int, [_ctx, C.c_int64, C.POINTER(AmcStepStats)]),
+}
+
 
 class ArgonMCError(RuntimeError):
     def __init__(self, code, msg):
@@ -117,11 +126,12 @@ def _source_files():
     src_dir = os.path.join(_HERE, "csrc")
     files = [os.path.join(src_dir, f) for f in sorted(os.listdir(src_dir)) if f.endswith((".hip", ".h")) or f == "Makefile"]
     files.append(os.path.join(os.path.dirname(_HERE), "include", "argonmc.h"))
+    files.append(os.path.join(os.path.dirname(_HERE), "include", "argonmc_shard.h"))
     return files
 
 
 def source_digest():
-    """sha256 over the library's sources (csrc/*.hip, csrc/*.h, the Makefile, include/argonmc.h)."""
+    """sha256 over the library's sources (csrc/*.hip, csrc/*.h, the Makefile, include/argonmc.h and argonmc_shard.h)."""
     import hashlib
     h = hashlib.sha256()
     for f in _source_files():
@@ -159,7 +169,7 @@ def load():
         raise ArgonMCError(-3, f"{LIB_PATH} does not match the sources {stale[0]}: rebuild it "
                                "(`python -c 'import __graft_entry__ as g; g.build()'`)")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(SHARD_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError = missing export
         fn.restype = res
         fn.argtypes = args

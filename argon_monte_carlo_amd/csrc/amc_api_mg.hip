@@ -218,6 +218,77 @@ int amc_mg_resolve(amc_ctx *c, int world)
     return AMC_OK;
 }
 
+// ---- the hits exchange of a sharded device-RNG step: pack | third all-gather | the step's sums from all blocks (amc_hits.hip) ----
+int amc_mg_hits_view(amc_ctx *c, int world, void **send, void **recv, int64_t *block_words)
+{
+    if (!c || world < 1 || !send || !recv || !block_words) return AMC_ERR_INVALID;
+    if (world > AMC_MG_HITS_MAX_WORLD) return amc_fail(c, AMC_ERR_INVALID, "amc_mg_hits_view: %d ranks (at most %d)", world, AMC_MG_HITS_MAX_WORLD);
+    AMC_HIP(c, hipSetDevice(c->device));
+    amc_mg_ws &M = c->MG;
+    if (M.hits_view_world != world) {
+        AMC_HIP(c, hipStreamSynchronize(c->stream));
+        // five times the ~n / 11,000 hits per case and step even if one shard owns them all; n is the whole
+        // system's, so that all ranks agree on the block
+        long long cap = std::max<long long>(512, c->n / 2048 + 512);
+        if (const char *e = getenv("AMC_MG_HITS_CAP")) { const long long v = atoll(e); if (v > 0 && v < cap) cap = v; }      // (tests)
+        int tile = 0x7fffffff;
+        if (const char *e = getenv("AMC_MG_HITS_TILE")) { const int v = atoi(e); if (v >= 0) tile = v; }                  // (tests)
+        const size_t blk = (size_t)amc_hits_block_words((int)cap);
+        amc_alloc_group group(c);
+        long long *hsend, *hrecv;
+        int *perm;
+        AMC_HIP(c, dalloc(c, &hsend, blk));
+        AMC_HIP(c, dalloc(c, &hrecv, blk * (size_t)world));
+        AMC_HIP(c, dalloc(c, &perm, (size_t)7 * (size_t)world * (size_t)cap));
+        AMC_HIP(c, hipMemsetAsync(hsend, 0, sizeof(long long) * blk, c->stream));
+        AMC_HIP(c, hipMemsetAsync(hrecv, 0, sizeof(long long) * blk * (size_t)world, c->stream));
+        AMC_HIP(c, hipStreamSynchronize(c->stream));
+        group.keep();
+        ctx_free(c, M.hits_send, M.hits_recv, M.hits_perm);
+        M.hits_send = hsend; M.hits_recv = hrecv; M.hits_perm = perm; M.hits_cap = (int)cap; M.hits_tile = tile;
+        if (M.step.hits >= AMC_MG_HITS_PACKED) M.step.hits = AMC_MG_HITS_NONE;      // (the pending pack filled the block that has just been freed)
+        M.hits_view_world = world;  // (the guard: last)
+    }
+    *send = M.hits_send; *recv = M.hits_recv; *block_words = amc_hits_block_words(M.hits_cap);
+    return AMC_OK;
+}
+
+static const char *mg_hits_name(const amc_mg_step &s)
+{
+    static const char *const names[] = {"no device cases have been launched since amc_temp_begin", "amc_temp_cases_device is done, amc_mg_hits_pack is next",
+                                        "amc_mg_hits_pack is done, amc_mg_hits_sums is next", "the hits exchange of this step is done"};
+    return names[s.hits];
+}
+
+int amc_mg_hits_pack(amc_ctx *c, int world)
+{
+    if (!c || !c->uploaded) return AMC_ERR_STATE;
+    amc_mg_step &s = c->MG.step;
+    if (world < 1 || world != c->MG.hits_view_world) return amc_fail(c, AMC_ERR_STATE, "amc_mg_hits_view(world=%d) has not been called", world);
+    if (s.hits != AMC_MG_HITS_LAUNCHED) return amc_fail(c, AMC_ERR_STATE, "amc_mg_hits_pack(world=%d) follows amc_temp_cases_device: %s", world, mg_hits_name(s));
+    if (s.phase != AMC_MG_IDLE) return amc_fail(c, AMC_ERR_STATE, "amc_mg_hits_pack belongs in front of amc_mg_pack: %s", mg_phase_name(s));
+    if (!c->TD.ovf) return amc_fail(c, AMC_ERR_STATE, "amc_mg_hits_pack without amc_temp_shard_run_begin");
+    AMC_HIP(c, hipSetDevice(c->device));
+    AMC_HIP(c, amc_launch_hits_pack(c));
+    s.hits = AMC_MG_HITS_PACKED; s.hits_world = world;
+    return AMC_OK;
+}
+
+int amc_mg_hits_sums(amc_ctx *c, int world, int64_t row)
+{
+    if (!c || !c->uploaded) return AMC_ERR_STATE;
+    amc_mg_step &s = c->MG.step;
+    if (world < 1 || world != c->MG.hits_view_world) return amc_fail(c, AMC_ERR_STATE, "amc_mg_hits_view(world=%d) has not been called", world);
+    if (s.hits != AMC_MG_HITS_PACKED) return amc_fail(c, AMC_ERR_STATE, "amc_mg_hits_sums(world=%d) without amc_mg_hits_pack in this step: %s", world, mg_hits_name(s));
+    if (s.hits_world != world) return amc_fail(c, AMC_ERR_STATE, "amc_mg_hits_sums(world=%d) after amc_mg_hits_pack(world=%d)", world, s.hits_world);
+    if (row < 0 || row >= c->MG.hits_rows)
+        return amc_fail(c, AMC_ERR_STATE, "amc_mg_hits_sums: row %lld of a run of %lld steps (amc_temp_shard_run_begin)", (long long)row, (long long)c->MG.hits_rows);
+    AMC_HIP(c, hipSetDevice(c->device));
+    AMC_HIP(c, amc_launch_hits_sums(c, world, row));
+    s.hits = AMC_MG_HITS_SUMMED;
+    return AMC_OK;
+}
+
 int amc_mg_bounds(amc_ctx *c)
 {
     if (!c || !c->uploaded) return AMC_ERR_STATE;
@@ -234,10 +305,13 @@ int amc_mg_finish(amc_ctx *c, amc_step_stats *out)
     amc_mg_step &s = c->MG.step;
     if (s.phase != AMC_MG_SWEPT) return amc_fail(c, AMC_ERR_STATE, "amc_mg_finish without amc_mg_sweep / amc_mg_resolve in this step: %s", mg_phase_name(s));
     s.phase = AMC_MG_IDLE;          // the step is over, whatever is returned below
+    const bool exchanged = s.hits >= AMC_MG_HITS_PACKED;    // a sharded device-RNG step: its hits went into the surface totals
+    s.hits = AMC_MG_HITS_NONE;
     AMC_HIP(c, hipSetDevice(c->device));
     if (c->P.geometry == AMC_GEOM_PORE || c->P.geometry == AMC_GEOM_PORE_ENERGISED)
         AMC_HIP(c, amc_launch_stream(c, 0.0, AMC_ST_BOUNDS, 1));                     // Pore:550 / Temp:844
     c->out.step++;
+    if (exchanged && c->SF.on) c->SF.n_steps++;
     { int rc_ = amc_fields_step(c); if (rc_) return rc_; }
     if (!out) return AMC_OK;        // asynchronous: the caller reads the counters later
     return amc_finish_stats(c, out);

@@ -246,6 +246,7 @@ int amc_temp_cases_device(amc_ctx *c, const amc_temp_rng *cfg)
     c->TD.fetched = false;
     AMC_HIP(c, amc_launch_temp_cases_device(c, cfg));
     if (c->SF.on) AMC_HIP(c, amc_launch_surface_device(c));
+    c->MG.step.hits = AMC_MG_HITS_LAUNCHED;     // (a sharded step's hits exchange may follow: amc_mg_hits_pack)
     return AMC_OK;
 }
 
@@ -500,6 +501,54 @@ int amc_temp_run_device(amc_ctx *c, double dt, int64_t nsteps, const amc_temp_rn
     if (ovf[0]) {
         D.series_n = 0;
         return amc_fail(c, AMC_ERR_CAPACITY, "%d wall hits in case %d exceed the record capacity %d (step %d of the run)", ovf[2], ovf[0], D.seg.cap, ovf[1]);
+    }
+    if (rc) D.series_n = 0;
+    return rc;
+}
+
+// ---- the host-free run over shards: the steps themselves are the amc_temp_* / amc_mg_* calls ------------------
+int amc_temp_shard_run_begin(amc_ctx *c, int64_t nsteps)
+{
+    if (!c) return AMC_ERR_INVALID;
+    if (c->P.geometry != AMC_GEOM_PORE_ENERGISED) return amc_fail(c, AMC_ERR_STATE, "amc_temp_shard_run_begin needs AMC_GEOM_PORE_ENERGISED");
+    if (nsteps < 0 || nsteps > 0x3fffffffLL) return amc_fail(c, AMC_ERR_INVALID, "amc_temp_shard_run_begin: nsteps %lld out of range", (long long)nsteps);
+    if (!c->uploaded) return amc_fail(c, AMC_ERR_STATE, "amc_temp_shard_run_begin before amc_upload");
+    if (int rc = amc_mg_step_idle(c, "amc_temp_shard_run_begin")) return rc;
+    AMC_HIP(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = temp_dev_ensure(c))) return rc;
+    if ((rc = temp_run_ensure(c, std::max<int64_t>(nsteps, 1)))) return rc;
+    amc_temp_dev_ws &D = c->TD;
+    D.series_n = 0;
+    D.fetched = false;
+    c->MG.hits_rows = nsteps;
+    AMC_HIP(c, hipMemsetAsync(D.ovf, 0, 4 * sizeof(int), c->stream));
+    return AMC_OK;
+}
+
+int amc_temp_shard_run_end(amc_ctx *c, int64_t nsteps, amc_step_stats *sum)
+{
+    if (!c) return AMC_ERR_INVALID;
+    amc_temp_dev_ws &D = c->TD;
+    if (!D.ovf || nsteps < 0 || nsteps > c->MG.hits_rows)
+        return amc_fail(c, AMC_ERR_STATE, "amc_temp_shard_run_end(%lld steps) does not match amc_temp_shard_run_begin(%lld)", (long long)nsteps, (long long)c->MG.hits_rows);
+    AMC_HIP(c, hipSetDevice(c->device));
+    c->MG.hits_rows = 0;
+    D.series_n = nsteps;
+    int rc = amc_finish_stats(c, sum);  // the one synchronisation; overflow flags and counters of the whole run
+    int ovf[4] = {0, 0, 0, 0};
+    AMC_HIP(c, hipMemcpy(ovf, D.ovf, sizeof ovf, hipMemcpyDeviceToHost));
+    if (ovf[0] || ovf[3] || rc == AMC_ERR_CAPACITY) c->SF.lost = c->SF.on;      // hits are missing from the sampled surfaces
+    if (ovf[0]) {
+        D.series_n = 0;
+        if (ovf[2] == 0x7fffffff)
+            return amc_fail(c, AMC_ERR_CAPACITY, "the wall hits of one rank in case %d exceed its record capacity %d (step %d of the run)", ovf[0], D.seg.cap, ovf[1]);
+        return amc_fail(c, AMC_ERR_CAPACITY, "%d wall hits of one rank in case %d exceed the hits exchange's capacity %d (step %d of the run)", ovf[2], ovf[0],
+                        c->MG.hits_cap, ovf[1]);
+    }
+    if (ovf[3] && !rc) {                // (flagged by this rank's pack alone: no sums call followed it)
+        D.series_n = 0;
+        return amc_fail(c, AMC_ERR_CAPACITY, "wall hits of this rank exceed the hits exchange's capacity %d", c->MG.hits_cap);
     }
     if (rc) D.series_n = 0;
     return rc;

@@ -272,9 +272,19 @@ struct amc_surface_ws {
 // an abandoned pack had published is lost to the other ranks: the job recovers when every rank uploads the state again.
 // Only the entry points of amc_api_mg.hip and amc_mg_step_fresh write the record; the launchers (amc_exchange.hip) are handed
 // what they need and report nothing back through the context.
+// The hits exchange of a sharded device-RNG step (amc_hits.hip) is part of the same record, beside the phase:
+//   amc_temp_cases_device      leaves hits = launched (the one writer outside amc_api_mg.hip: it completes the segments).
+//   amc_mg_hits_pack(world)    requires launched and the hits view of `world`; leaves packed(world).  A second pack is refused.
+//   amc_mg_hits_sums(world, row)   requires packed(world) and a row of the run begun by amc_temp_shard_run_begin; leaves summed.
+//   amc_mg_finish              clears it (and counts the step for the sampled surfaces when the exchange took place).
+// amc_mg_step_fresh abandons a pending hits exchange with everything else: amc_temp_begin, amc_upload, amc_set_shard.
 enum amc_mg_phase { AMC_MG_IDLE = 0, AMC_MG_PACKED, AMC_MG_DETECTED, AMC_MG_SWEPT };
+enum amc_mg_hits_phase { AMC_MG_HITS_NONE = 0, AMC_MG_HITS_LAUNCHED, AMC_MG_HITS_PACKED, AMC_MG_HITS_SUMMED };
+#define AMC_MG_HITS_MAX_WORLD 64   // ranks whose segment offsets fit k_hits_sums's LDS table
 struct amc_mg_step {
     amc_mg_phase phase;            // (zero: idle)
+    amc_mg_hits_phase hits;        // (zero: none)
+    int hits_world;                // the world size of the pending hits pack
     int world;                     // the world size of the pending pack (packed, detected)
     int mode = 1;                  // this step's list build: 1 anew, 2 full build of a kept cycle, 3 a step in between — written by
                                    // the pack, read by the unpack
@@ -296,6 +306,13 @@ struct amc_mg_ws {
     int *wave_count;               // [waves_pack + waves_unpack]
     int waves_pack, waves_unpack;
     bool keep;                     // the pools exist for the current world size
+    // the hits exchange of a sharded device-RNG step (amc_hits.hip): this rank's block, the blocks of all ranks, the ordering
+    // scratch of a step with more records than the sums kernel's LDS tile; hits_cap records per case and rank
+    long long *hits_send, *hits_recv;
+    int *hits_perm;                // [7 * world * hits_cap]
+    int hits_cap, hits_view_world;
+    int hits_tile;                 // records up to which k_hits_sums orders a step in LDS (AMC_MG_HITS_TILE, else its whole tile)
+    int64_t hits_rows;             // rows of the series the run in progress may write (amc_temp_shard_run_begin; 0: none)
     amc_mg_step step;
 };
 
@@ -433,6 +450,8 @@ struct amc_ctx {
 // enqueues no memset of them.  send_replaced: the send block is a new allocation, whatever the phase.
 static inline void amc_mg_step_fresh(amc_ctx *c, bool send_replaced = false)
 {
+    if (!send_replaced) c->MG.step.hits = AMC_MG_HITS_NONE;     // (a pending hits exchange goes with it; a new send block of
+                                                                // the position exchange and the lists are none of its business)
     if (!send_replaced && c->MG.step.phase == AMC_MG_IDLE) return;
     c->MG.step.fresh();
     c->step.lists_age = -1;         // (an abandoned pack may have begun a kept cycle with its own shard only)
@@ -514,4 +533,8 @@ hipError_t amc_launch_surface_finish(amc_ctx *c, int case_id, int n);
 // counters in front of the pack kernel
 hipError_t amc_launch_kin_pack(amc_ctx *c, int mode, bool clear_counts);
 hipError_t amc_launch_kin_unpack(amc_ctx *c, int world, int rank, int mode);
-int amc_kin_banks(void);         // banks of the velocity-change list in an exchange block
+int amc_kin_banks(void);
+// the hits exchange of a sharded device-RNG step (amc_hits.hip): they read c->MG / c->TD and change nothing in them
+int64_t amc_hits_block_words(int hits_cap);
+hipError_t amc_launch_hits_pack(amc_ctx *c);
+hipError_t amc_launch_hits_sums(amc_ctx *c, int world, int64_t row);         // banks of the velocity-change list in an exchange block

@@ -284,6 +284,7 @@ class LocalRanks:
         one = self.world == 1
         self.xb = None if one else [e.exchange_buffers(self.world) for e in self.engines]
         self.cb = None if one or self.replicated else [e.candidate_buffers(self.world) for e in self.engines]
+        self.hb = [e.hits_buffers(self.world) for e in self.engines] if all(hasattr(e, "hits_buffers") for e in self.engines) else None
 
     @staticmethod
     def gather(bufs):
@@ -306,6 +307,31 @@ class LocalRanks:
         """the step's first all-gather (behind ``pack``), or its second one: the candidate pairs (behind ``detect``)"""
         if self.world > 1:
             self.gather(self.cb if candidates else self.xb)
+
+    def exchange_hits(self):
+        """the third all-gather of a device-RNG step (behind ``mg_hits_pack``): every rank's hit results to every rank"""
+        self.gather(self.hb)
+
+    def step_device(self, dt, cfg, row, want_stats=False):
+        """One sharded device-RNG step (include/argonmc_shard.h) writing row ``row`` of the run every engine has begun
+        (``shard_run_begin``): cases on the shards, the hits exchange, the bounds check, then the sweep's phases."""
+        for e in self.engines:
+            e.temp_begin(dt)
+            e.temp_cases_device(cfg)
+            e.mg_hits_pack(self.world)
+        self.exchange_hits()
+        for e in self.engines:
+            e.mg_hits_sums(self.world, row)
+            e.mg_bounds()
+        self.pack()
+        self.exchange()
+        if self.replicated or self.world == 1:
+            self.sweep()
+        else:
+            self.detect()
+            self.exchange(candidates=True)
+            self.resolve()
+        return self.finish(want_stats)
 
     def sweep(self):
         for r, e in enumerate(self.engines):
@@ -375,7 +401,24 @@ class ShardedTemperatureSimulation(ShardedSimulation):
     """Temperature_Pore_MC.py's step (Temp:662-853) over index-range shards.  ``sampler`` / ``energies`` are the host
     objects of argon_monte_carlo_amd.energised; every rank must construct them with the same seeds."""
 
-    def __init__(self, params, rank, world, backend="nccl", stream_ptr=None, engine=None, comm=None):
+    def __init__(self, params, rank, world, backend="nccl", stream_ptr=None, engine=None, comm=None, device_rng_seed=None,
+                 consts=None):
+        """``device_rng_seed``: the opt-in, NON-PARITY device-RNG mode (``sim.TemperatureSimulation``) over shards — the draws
+        are keyed by (particle, step, case, attempt), so nothing of a step goes through the host: ``temp_timestep_device`` and
+        ``run`` replace ``temp_timestep``, and the sampled surfaces work over shards.  ``consts``: the constants the
+        parameters were made from (default: ``params.pore_params`` for this particle count).  Every rank passes the same seed."""
+        self._device_rng = None
+        if device_rng_seed is not None:
+            from . import params as PR
+            from .energised import device_rng_config
+            if consts is None:
+                consts = PR.pore_params(n=int(params.n), energised=True)[1]
+            self._device_rng = device_rng_config(consts, device_rng_seed)
+            self.dt = consts["dt"]
+            if engine is None:                      # the device draws read the walls' surface energies from the parameters
+                from .energised import SurfaceEnergies
+                energies = SurfaceEnergies(consts)
+                params.E_cold, params.E_hot = energies.cold, energies.hot
         if engine is None:
             from .engine import ShardEnergisedEngine
             lo, hi = shard_range(int(params.n), rank, world)
@@ -396,3 +439,115 @@ class ShardedTemperatureSimulation(ShardedSimulation):
         e.mg_bounds()                                                   # Temp:804
         st = self._sweep(reduce_stats, True)                            # Temp:813-844
         return (st,) + res
+
+    # ---- the device-RNG mode over shards (include/argonmc_shard.h): no host work inside a step ------------------
+    def _need_device_rng(self):
+        if self._device_rng is None:
+            raise ValueError("this ShardedTemperatureSimulation was built without device_rng_seed")
+
+    def _device_step(self, dt, row):
+        """cases on the shard | the hit results of all ranks, summed in ascending particle index on every rank | bounds |
+        the sweep of the whole system: all enqueued, nothing waits for the host"""
+        e, w = self.engine, self.world
+        send, recv = e.hits_buffers(w)
+        e.temp_begin(dt)                                                # drift + specular cases on the shard
+        e.temp_cases_device(self._device_rng)                           # cases 3..9, draws keyed by (particle, step, case, attempt)
+        e.mg_hits_pack(w)
+        if w == 1 and self.comm.shortcut:
+            recv.copy_(send)
+        else:
+            self._allgather(send, recv)                                 # the third, small collective
+        e.mg_hits_sums(w, row)
+        e.mg_bounds()                                                   # Temp:804
+        self._sweep(False, False)                                       # Temp:813-844, mg_finish without statistics
+
+    def _run_end(self, nsteps):
+        """The run's one synchronisation, then ONE all-reduce: every rank's status and counters.  A rank whose run failed still
+        takes part, so that every rank raises from this call: its own error when all of them failed (an overflowing hits block
+        is seen by every rank's sums kernel: the same message everywhere), else one that names the first failing rank."""
+        from ._lib import ArgonMCError
+        status, err = [0] * self.world, None
+        try:
+            st, sums, had = self.engine.shard_run_end(nsteps)
+        except ArgonMCError as e:
+            err, st = e, dict.fromkeys(self.SUM_KEYS, 0)
+            status[self.rank] = min(int(e.code), -1)
+        flat = status + [int(st[k]) for k in self.SUM_KEYS]
+        if self.world > 1 or not self.comm.shortcut:
+            flat = self.comm.allreduce_sum_ints(flat)
+        failed = [(r, c) for r, c in enumerate(flat[:self.world]) if c != 0]
+        if failed:
+            if err is not None and len(failed) == self.world:
+                raise err
+            r, c = failed[0]
+            raise ArgonMCError(c, f"the sharded device-RNG run failed on rank {r}") from err
+        st.update(dict(zip(self.SUM_KEYS, flat[self.world:])))
+        return st, sums, had
+
+    def run(self, dt, nsteps):
+        """Without a seed: ``ShardedSimulation.run``.  With one: ``nsteps`` device-RNG steps enqueued back to back, one
+        synchronisation at the end -> (counters summed over steps and ranks, float64[nsteps, 3] per-step sums of the whole
+        system, bool[nsteps, 3]) as ``EnergisedEngine.temp_run_device`` returns them, identical on every rank."""
+        if self._device_rng is None:
+            return super().run(dt, nsteps)
+        nsteps = int(nsteps)
+        self.engine.shard_run_begin(nsteps)
+        for k in range(nsteps):
+            self._device_step(dt, k)
+        return self._run_end(nsteps)
+
+    def temp_timestep_device(self, dt):
+        """One device-RNG step -> the tuple of ``EnergisedEngine.temp_timestep_device`` for the whole system, identical on
+        every rank (synchronises, like the single-context call)."""
+        self._need_device_rng()
+        self.engine.shard_run_begin(1)
+        self._device_step(dt, 0)
+        st, sums, had = self._run_end(1)
+        return (st, float(sums[0, 0]), float(sums[0, 1]), float(sums[0, 2]), bool(had[0, 0]), bool(had[0, 1]), bool(had[0, 2]))
+
+    # ---- sampled surfaces over shards: every rank accumulates its own hits, the totals are summed exactly ----------------------
+    def enable_surface(self, grid=None):
+        from . import surface as SU
+        self._need_device_rng()
+        self.engine.surface_config(SU.default_grid(self.params) if grid is None else grid)
+
+    def surface_reset(self):
+        self.engine.surface_reset()
+
+    def surface(self):
+        """``TemperatureSimulation.surface()`` of the whole system (a collective: every rank calls it).  The ranks' 128-bit
+        totals and ``n_failed`` are summed as 32-bit limbs in one int64 all-reduce, whose first ``world`` entries carry each
+        rank's status as in ``ShardedSimulation.fields``: a read that fails on one rank fails on every rank, from this call."""
+        from . import fields as FL, surface as SU
+        from ._lib import ArgonMCError
+        status, err = [0] * self.world, None
+        g = self.engine.surface_grid
+        try:
+            tot, nf, ns = self.engine.surface_read()
+        except ArgonMCError as e:
+            if g is None:                           # (not configured: there is no shape to take part with)
+                raise
+            err = e
+            tot, nf, ns = np.zeros((7, int(g.nbins) + 1, 3, 2), dtype=np.int64), np.zeros(7, dtype=np.int64), 0
+            status[self.rank] = min(int(e.code), -1)
+        tot, nf = sum_surface_limbs(self.comm, self.world, status, tot, nf, err)
+        return SU.derive(tot, ns, self.dt, g, self.params, n_failed=nf)
+
+
+def sum_surface_limbs(comm, world, status, tot, nf, err=None):
+    """(totals, n_failed) summed over the ranks: the 128-bit words as four 32-bit limbs each, in one ``allreduce_sum_ints``
+    together with every rank's status (0, or its negative error code) — exact, never through floats."""
+    from . import fields as FL
+    from ._lib import ArgonMCError
+    limbs = FL.words_to_limbs(tot)
+    flat = list(status) + [int(v) for v in limbs.ravel()] + [int(v) for v in np.asarray(nf).ravel()]
+    if world > 1 or not getattr(comm, "shortcut", True):
+        flat = comm.allreduce_sum_ints(flat)
+    failed = [(r, c) for r, c in enumerate(flat[:world]) if c != 0]
+    if failed:
+        if err is not None and len(failed) == world:
+            raise err
+        r, c = failed[0]
+        raise ArgonMCError(c, f"surface_read failed on rank {r}") from err
+    k = world + limbs.size
+    return FL.limbs_to_words(np.array(flat[world:k], dtype=np.int64).reshape(limbs.shape)), np.array(flat[k:], dtype=np.int64)

@@ -443,3 +443,36 @@ class ShardEnergisedEngine(ShardEngine, EnergisedEngine):
 
     def mg_bounds(self):
         self._ck(self.lib.amc_mg_bounds(self._ctx))
+
+    # ---- the device-RNG mode over shards (include/argonmc_shard.h) -------------------------------------------
+    def hits_buffers(self, world):
+        """(send, recv) tensors of the step's THIRD all-gather (device-RNG mode): this rank's hit results (int64[block]: seven
+        counts, then per case particle | ok << 32, dp_z and dE as 8-byte words) and the blocks of all ranks."""
+        if getattr(self, "_hb_world", None) != world:
+            send, recv, blk = C.c_void_p(), C.c_void_p(), C.c_int64(0)
+            self._ck(self.lib.amc_mg_hits_view(self._ctx, int(world), C.byref(send), C.byref(recv), C.byref(blk)))
+            self._hb = (self._wrap(send.value, blk.value, "<i8"), self._wrap(recv.value, blk.value * world, "<i8"))
+            self._hb_world = world
+        return self._hb
+
+    def mg_hits_pack(self, world):
+        self._ck(self.lib.amc_mg_hits_pack(self._ctx, int(world)))
+
+    def mg_hits_sums(self, world, row):
+        self._ck(self.lib.amc_mg_hits_sums(self._ctx, int(world), int(row)))
+
+    def shard_run_begin(self, nsteps):
+        """Size the per-step series for ``nsteps`` sharded device-RNG steps and clear the overflow words."""
+        self._ck(self.lib.amc_temp_shard_run_begin(self._ctx, int(nsteps)))
+
+    def shard_run_end(self, nsteps):
+        """The run's one synchronisation -> (this rank's counters summed over the steps, float64[nsteps, 3] sums of the whole
+        system, bool[nsteps, 3]: a hit contributed) — the rows ``EnergisedEngine.temp_run_device`` returns."""
+        nsteps = int(nsteps)
+        st = AmcStepStats()
+        self._ck(self.lib.amc_temp_shard_run_end(self._ctx, nsteps, C.byref(st)))
+        sums = np.zeros((max(nsteps, 1), 3))
+        had = np.zeros((max(nsteps, 1), 3), dtype=np.uint8)
+        left = C.c_int64(0)
+        self._ck(self.lib.amc_temp_series_read(self._ctx, 0, nsteps, _d(sums), had.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(left)))
+        return st.as_dict(), sums[:nsteps], had[:nsteps].astype(bool)

@@ -390,8 +390,8 @@ int amc_mg_finish(amc_ctx *ctx, amc_step_stats *out);      /* out == NULL: no ho
 /* With profiling on, every kernel launch is bracketed by hipEvents on the launch stream. */
 #define AMC_K_DRIFT_WALLS 0
 #define AMC_K_BIN_COUNT 1        /* k_bin_lists (stand-alone list build; the step driver fuses it into k_stream) and the multi-GPU pack / unpack kernels, which build the lists too */
-#define AMC_K_BIN_SCAN 2         /* reserved (no such pass: the lists need neither scan nor scatter) */
-#define AMC_K_BIN_SCATTER 3      /* reserved */
+#define AMC_K_BIN_SCAN 2         /* (the lists need neither scan nor scatter: the class now times k_hits_pack, the hits exchange of a sharded device-RNG step, argonmc_shard.h) */
+#define AMC_K_BIN_SCATTER 3      /* (likewise: k_hits_sums, that step's sums from the blocks of all ranks) */
 #define AMC_K_DETECT 4
 #define AMC_K_RESOLVE 5          /* k_resolve: the ordered workgroup (entangled remainder, later rounds; no-grid mode: everything) */
 #define AMC_K_BOUNDS 6
@@ -508,6 +508,9 @@ int amc_surface_reset(amc_ctx *ctx);
  * (AMC_ERR_STATE when `case_id` is not the pending case; cap counts hits). */
 int amc_temp_device_contacts(amc_ctx *ctx, int case_id, int32_t *idx, double *contact_xyz, size_t cap, size_t *n);
 int amc_wall_contacts(amc_ctx *ctx, int case_id, double *contact_xyz, size_t cap);
+
+/* ---- the device-RNG energised pore over shards: the hits exchange and the host-free sharded run ---------------------------- */
+#include "argonmc_shard.h"
 
 #ifdef __cplusplus
 }
