@@ -94,6 +94,17 @@ class AmcFieldGrid(C.Structure):
                 ("lo", C.c_double * 3), ("hi", C.c_double * 3)]
 
 
+AMC_CORR_MAX_GROUPS = 256
+AMC_CORR_MAX_CELLS = 65536
+
+
+class AmcCorrGrid(C.Structure):
+    """amc_corr_grid (include/argonmc.h): the groups, the lags and the cadence of the sampled correlations."""
+    _fields_ = [("struct_size", C.c_int32), ("kind", C.c_int32), ("n1", C.c_int32), ("n2", C.c_int32), ("n3", C.c_int32),
+                ("n_lags", C.c_int32), ("every", C.c_int64), ("step_offset", C.c_int64),
+                ("lo", C.c_double * 3), ("hi", C.c_double * 3), ("reserved", C.c_int64 * 2)]
+
+
 AMC_SURFACE_CASES = 7
 AMC_SURFACE_MAX_BINS = 256
 

@@ -8,7 +8,7 @@ import ctypes as C
 import os
 import subprocess
 
-from ._abi import (AMC_ABI_VERSION, AmcFieldGrid, AmcIcConfig, AmcParams, AmcPathRecord, AmcStepStats, AmcSurfaceGrid,
+from ._abi import (AMC_ABI_VERSION, AmcCorrGrid, AmcFieldGrid, AmcIcConfig, AmcParams, AmcPathRecord, AmcStepStats, AmcSurfaceGrid,
                    AmcTempRng)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -90,6 +90,16 @@ SIGNATURES = {
     "amc_wall_contacts": (C.c_int, [_ctx, C.c_int, _dp, C.c_size_t]),
 }
 
+# ... and every symbol include/argonmc_corr.h declares (the sampled correlations; argonmc.h includes it)
+CORR_SIGNATURES = {
+    "amc_corr_config": (C.c_int, [_ctx, C.POINTER(AmcCorrGrid)]),
+    "amc_corr_sample": (C.c_int, [_ctx]),
+    "amc_corr_read": (C.c_int, [_ctx, _i64p, _i64p, _i64p, _i64p, _i64p]),
+    "amc_corr_origin": (C.c_int, [_ctx] + [_dp] * 6),
+    "amc_corr_load": (C.c_int, [_ctx, _i64p, C.c_int64, C.c_int64, C.c_int64, C.c_int64] + [_dp] * 6),
+    "amc_corr_reset": (C.c_int, [_ctx]),
+}
+
 # ... and every symbol include/argonmc_shard.h declares (the device-RNG energised pore over shards; argonmc.h includes it)
 SHARD_SIGNATURES = {
     "amc_mg_hits_view": (C.c_int, [_ctx, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
@@ -127,11 +137,12 @@ def _source_files():
     files = [os.path.join(src_dir, f) for f in sorted(os.listdir(src_dir)) if f.endswith((".hip", ".h")) or f == "Makefile"]
     files.append(os.path.join(os.path.dirname(_HERE), "include", "argonmc.h"))
     files.append(os.path.join(os.path.dirname(_HERE), "include", "argonmc_shard.h"))
+    files.append(os.path.join(os.path.dirname(_HERE), "include", "argonmc_corr.h"))
     return files
 
 
 def source_digest():
-    """sha256 over the library's sources (csrc/*.hip, csrc/*.h, the Makefile, include/argonmc.h and argonmc_shard.h)."""
+    """sha256 over the library's sources (csrc/*.hip, csrc/*.h, the Makefile, include/argonmc.h, argonmc_shard.h and argonmc_corr.h)."""
     import hashlib
     h = hashlib.sha256()
     for f in _source_files():
@@ -169,7 +180,7 @@ def load():
         raise ArgonMCError(-3, f"{LIB_PATH} does not match the sources {stale[0]}: rebuild it "
                                "(`python -c 'import __graft_entry__ as g; g.build()'`)")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(SHARD_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(SHARD_SIGNATURES.items()) + list(CORR_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError = missing export
         fn.restype = res
         fn.argtypes = args

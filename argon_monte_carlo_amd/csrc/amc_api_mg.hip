@@ -312,7 +312,7 @@ int amc_mg_finish(amc_ctx *c, amc_step_stats *out)
         AMC_HIP(c, amc_launch_stream(c, 0.0, AMC_ST_BOUNDS, 1));                     // Pore:550 / Temp:844
     c->out.step++;
     if (exchanged && c->SF.on) c->SF.n_steps++;
-    { int rc_ = amc_fields_step(c); if (rc_) return rc_; }
+    { int rc_ = amc_samplers_step(c); if (rc_) return rc_; }
     if (!out) return AMC_OK;        // asynchronous: the caller reads the counters later
     return amc_finish_stats(c, out);
 }

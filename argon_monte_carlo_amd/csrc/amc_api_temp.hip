@@ -487,11 +487,11 @@ int amc_temp_run_device(amc_ctx *c, double dt, int64_t nsteps, const amc_temp_rn
         if (c->SF.on) AMC_HIP(c, amc_launch_surface_device(c));     // (in front of the next step's pass, which clears seg.count)
         if ((rc = amc_enqueue_sweep(c, fuse))) return rc;                               // Temp:813-842
         // a sampled step and the last one end with the state everybody reads: their recapture is a pass of its own
-        deferred = fused && s + 1 < nsteps && !amc_fields_due(c, (int64_t)c->out.step + 1);
+        deferred = fused && s + 1 < nsteps && !amc_samplers_due(c, (int64_t)c->out.step + 1);
         if (!deferred) AMC_HIP(c, amc_launch_stream(c, 0.0, AMC_ST_BOUNDS, 1));       // Temp:844
         c->out.step++;
         if (c->SF.on) c->SF.n_steps++;
-        if ((rc = amc_fields_step(c))) return rc;
+        if ((rc = amc_samplers_step(c))) return rc;
     }
     D.series_n = nsteps;
     rc = amc_finish_stats(c, sum);      // the one synchronisation; overflow flags and counters of the whole run
@@ -599,7 +599,7 @@ int amc_temp_end(amc_ctx *c, amc_step_stats *out)
     AMC_HIP(c, amc_launch_stream(c, 0.0, AMC_ST_BOUNDS, 1));        // Temp:844
     c->out.step++;
     if (c->SF.on) c->SF.n_steps++;
-    if ((rc = amc_fields_step(c))) return rc;
+    if ((rc = amc_samplers_step(c))) return rc;
     rc = amc_finish_stats(c, out);
     if (rc == AMC_ERR_CAPACITY) c->SF.lost = c->SF.on;              // hits are missing from the sampled surfaces
     return rc;

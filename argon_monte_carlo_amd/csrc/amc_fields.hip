@@ -10,25 +10,12 @@
 //   k_fields_reduce  sums the slab rows per (bin, quantity) and adds the result into the 128-bit running totals.
 // Integer sums do not depend on the order of the adds, so the totals are bitwise the same for any number of workgroups.
 #include "amc_host.h"
+#include "amc_sample_dev.h"
 
 #define AMC_FIELDS_Q 7                  // count, q1(c1..c3), q2(c1..c3)
 #define AMC_FIELDS_THREADS 1024         // the 112 KiB table leaves room for one workgroup per CU: 16 waves
 #define AMC_FIELDS_PER_BLOCK 8192       // particles per workgroup below which fewer workgroups are launched
 #define AMC_FIELDS_MAX_PARTICLES (1LL << 24)
-
-struct amc_fields_grid_dev {
-    int kind, n1, n2, n3, bins;
-    double lo[3], hi[3], w[3];
-};
-
-// bin of one coordinate: -1 outside (below lo, at or beyond n bins, NaN); u == hi lands in the last bin
-AMC_DEV int amc_fields_axis(double u, double lo, double hi, double w, int n)
-{
-    const double f = floor((u - lo) / w);
-    if (!(f >= 0.0)) return -1;
-    if (f >= (double)n) return (f == (double)n && u <= hi) ? n - 1 : -1;
-    return (int)f;
-}
 
 // one particle into the workgroup's table; returns false if a component is out of the quantisation range
 AMC_DEV bool amc_fields_particle(const amc_fields_grid_dev &G, unsigned long long *tab, unsigned int &outside, double x, double y,
@@ -65,20 +52,6 @@ AMC_DEV bool amc_fields_particle(const amc_fields_grid_dev &G, unsigned long lon
     atomicAdd(t + 5, (unsigned long long)(long long)rint((c2 * c2) * 1024.0));
     atomicAdd(t + 6, (unsigned long long)(long long)rint((c3 * c3) * 1024.0));
     return true;
-}
-
-// The state is read through the deferred results of the last sweep (amc_lazy: a particle that collided has its final state
-// in the slot arrays until the next streaming pass picks it up) without consuming them: the step sequence is untouched.
-AMC_DEV void amc_fields_lazy(const amc_state &S, const amc_lazy &L, long long p, double &x, double &y, double &z, double &vx,
-                             double &vy, double &vz)
-{
-    if (L.enabled) {
-        const int sl = L.slot_of[p];
-        if (sl >= 0 && L.moved[sl]) {
-            const double *t = L.state + (size_t)sl * RS_SLOT_DOUBLES;
-            x = t[0]; y = t[1]; z = t[2]; vx = t[3]; vy = t[4]; vz = t[5];
-        }
-    }
 }
 
 __global__ __launch_bounds__(AMC_FIELDS_THREADS) void k_fields_accum(amc_state S, amc_lazy L, long long lo, long long hi,

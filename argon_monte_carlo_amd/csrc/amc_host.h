@@ -98,7 +98,8 @@ AMC_INTERNAL int amc_finish_stats(amc_ctx *c, amc_step_stats *out);     // per-s
 AMC_INTERNAL int amc_publish_velocities(amc_ctx *c);                    // multi-GPU: vpub = current velocities (after an upload)
 AMC_INTERNAL int amc_flush(amc_ctx *c);                                 // write deferred sweep results to the particle arrays
 AMC_INTERNAL int amc_enqueue_sweep(amc_ctx *c, bool counted = false, bool defer_commit = false);   // bin (unless counted) + detect + resolve
-AMC_INTERNAL int amc_fields_step(amc_ctx *c);                         // the cadence hook after a completed step (amc_fields.hip)
+AMC_INTERNAL int amc_fields_step(amc_ctx *c);                         // the fields' part of the cadence hook (amc_fields.hip)
+AMC_INTERNAL int amc_corr_step(amc_ctx *c);                           // the correlations' part (amc_corr.hip)
 
 // amc_timestep, amc_run and the stage calls: not in the middle of a sharded step (the rule above amc_mg_step)
 static inline int amc_mg_step_idle(amc_ctx *c, const char *who)
@@ -112,4 +113,18 @@ static inline int amc_mg_step_idle(amc_ctx *c, const char *who)
 static inline bool amc_fields_due(const amc_ctx *c, int64_t step)
 {
     return c->F.on && c->F.g.every > 0 && (step + c->F.g.step_offset) % c->F.g.every == 0;
+}
+static inline bool amc_corr_due(const amc_ctx *c, int64_t step)
+{
+    return c->CR.on && c->CR.g.every > 0 && (step + c->CR.g.step_offset) % c->CR.g.every == 0;
+}
+// ... for any sampler of the particle state: such a step ends with the state everybody reads (no deferred bounds pass)
+static inline bool amc_samplers_due(const amc_ctx *c, int64_t step) { return amc_fields_due(c, step) || amc_corr_due(c, step); }
+// a sampler runs on a cadence: amc_run takes its plain loop
+static inline bool amc_samplers_cadence(const amc_ctx *c) { return (c->F.on && c->F.g.every > 0) || (c->CR.on && c->CR.g.every > 0); }
+// the cadence hook after a completed step
+static inline int amc_samplers_step(amc_ctx *c)
+{
+    if (int rc = amc_fields_step(c)) return rc;
+    return c->CR.on ? amc_corr_step(c) : AMC_OK;
 }

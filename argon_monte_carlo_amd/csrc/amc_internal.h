@@ -249,6 +249,23 @@ struct amc_surface_ws {
     bool lost;                      // a step or run overflowed its records: hits are missing (amc_surface_read: AMC_ERR_STATE)
 };
 
+// sampled correlations (amc_corr.hip): the group grid, the window position, the origin arrays, the per-workgroup slab rows of
+// one sample and the 128-bit running totals
+struct amc_corr_ws {
+    bool on;
+    amc_corr_grid g;
+    int groups;                 // n1 * n2 * n3
+    double w[3];                // group widths (hi - lo) / n, fp64 like NumPy
+    int64_t pos;                // window position: the lag of the next sample (0: it is an origin)
+    int max_blocks;             // slab rows allocated (AMC_CORR_BLOCKS, else the number of CUs)
+    int blocks_env;             // AMC_CORR_BLOCKS at configuration (0: by particle count)
+    int64_t stride;             // doubles per origin array (n rounded up to even: every array starts 16-byte aligned)
+    double *origin;             // [6][stride] x0 y0 z0 vx0 vy0 vz0, indexed by particle like the state
+    unsigned long long *slab;   // [max_blocks][2 * groups * 7 + 1] one sample's sums per workgroup (+ particles outside)
+    unsigned long long *tot;    // [groups][n_lags + 1][7][2] running totals, (low, high) words
+    unsigned long long *meta;   // [0] origins, [1] samples, [2] particles outside, [3] lowest particle index out of range (~0: none)
+};
+
 // What the sharded step leaves pending between two amc_mg_* calls (amc_api_mg.hip).  The rule — a call whose requirement fails
 // returns AMC_ERR_STATE before it enqueues anything and leaves the record as it was:
 //   amc_mg_pack(world)         requires idle and the exchange view of `world`; leaves packed(world) and `mode`.
@@ -379,6 +396,7 @@ struct amc_ctx {
     amc_temp_dev_ws TD;
     amc_fields_ws F;
     amc_surface_ws SF;
+    amc_corr_ws CR;
     // outputs
     amc_out out;
     amc_path_record *d_rec;

@@ -118,7 +118,7 @@ static int enqueue_step(amc_ctx *c, double dt, bool fold_prev_bounds = false, bo
     }
     c->out.step++;
     // (a step that leaves its post-sweep bounds check to the next pass is never sampled: amc_run does not defer it)
-    return amc_fields_step(c);
+    return amc_samplers_step(c);
 }
 
 int amc_timestep(amc_ctx *c, double dt, amc_step_stats *out)
@@ -347,8 +347,8 @@ int amc_run(amc_ctx *c, double dt, int64_t nsteps, amc_step_stats *sum)
     if (int rc = amc_mg_step_idle(c, "amc_run")) return rc;
     AMC_HIP(c, hipSetDevice(c->device));
     const bool whole = c->lo == 0 && c->hi == c->n && !c->allpairs;
-    // (sampled fields with a cadence: the plain loop, whose steps end with the state a sample reads)
-    const bool sampling = c->F.on && c->F.g.every > 0;
+    // (sampled fields or correlations with a cadence: the plain loop, whose steps end with the state a sample reads)
+    const bool sampling = amc_samplers_cadence(c);
     if (c->overlap_mode && whole && nsteps >= 2 && !c->keep_prior && !c->detect_ap && c->n > 0 && !sampling &&
         (c->P.geometry == AMC_GEOM_CUBE || c->P.geometry == AMC_GEOM_PORE)) {
         int rc = run_overlapped(c, dt, nsteps);
@@ -357,7 +357,7 @@ int amc_run(amc_ctx *c, double dt, int64_t nsteps, amc_step_stats *sum)
     }
     // inside the run only the last step needs its own post-sweep bounds pass (needs the whole range in one context) — and
     // every step that is sampled: the sample sees the step's final state
-    if (!c->ordered_always && whole && nsteps >= AMC_OD_MIN_STEPS && nsteps < (1 << 30) && !c->F.on && !c->keep_prior && !c->detect_ap &&
+    if (!c->ordered_always && whole && nsteps >= AMC_OD_MIN_STEPS && nsteps < (1 << 30) && !c->F.on && !c->CR.on && !c->keep_prior && !c->detect_ap &&
         !c->d_dbg && c->n > 0 && c->n <= c->od_max_n && c->h_od_stall && c->od_tick < (1 << 30) &&
         (c->P.geometry == AMC_GEOM_CUBE || c->P.geometry == AMC_GEOM_PORE)) {
         int rc = run_on_demand(c, dt, nsteps);
@@ -367,7 +367,7 @@ int amc_run(amc_ctx *c, double dt, int64_t nsteps, amc_step_stats *sum)
     const bool fold = c->P.geometry == AMC_GEOM_PORE && whole;
     bool deferred = false;
     for (int64_t s = 0; s < nsteps; s++) {
-        const bool defer = fold && s + 1 < nsteps && !amc_fields_due(c, (int64_t)c->out.step + 1);
+        const bool defer = fold && s + 1 < nsteps && !amc_samplers_due(c, (int64_t)c->out.step + 1);
         int rc = enqueue_step(c, dt, deferred, defer);
         if (rc) return rc;
         deferred = defer;

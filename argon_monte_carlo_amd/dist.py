@@ -259,6 +259,58 @@ class ShardedSimulation:
         no = flat[-1]
         return FL.derive(self.engine.field_grid, tot, ns, no, float(self.params.argon_mass), FL.boltzmann_constant(self.params))
 
+    # ---- sampled correlations (correlations.py): every rank samples its own index range, the totals are summed exactly ------
+    def enable_correlations(self, grid=None, every=0, n_lags=None):
+        from . import correlations as CO
+        g = CO.default_grid(self.params) if grid is None else grid
+        self.engine.corr_config(CO.copy_grid(g, every=every, n_lags=n_lags))
+
+    def correlations_sample(self):
+        self.engine.corr_sample()
+
+    def correlations_reset(self):
+        self.engine.corr_reset()
+
+    def correlations(self, dt=None, every=None):
+        """Simulation.correlations() of the whole system (a collective: every rank calls it).  The ranks' 128-bit totals and
+        the outside counter are summed as 32-bit limbs in one int64 all-reduce, exactly as ``fields()`` does, with every rank's
+        status in its first ``world`` entries: a read that fails on one rank fails on every rank, from this same call.
+        ``dt``: the time step for the lag times (None: the simulation's own where it has one, else 1.0)."""
+        from . import correlations as CO
+        import re
+        from ._abi import AMC_ERR_CAPACITY
+        from ._lib import ArgonMCError
+        g = self.engine.corr_grid
+        status, err = [0] * self.world, None
+        try:
+            tot, counters = self.engine.corr_read()
+        except ArgonMCError as e:
+            if g is None:                           # (not configured: there is no shape to take part with)
+                raise
+            err = e
+            tot, counters = np.zeros(CO.totals_shape(g), dtype=np.int64), (0, 0, 0, 0)
+            m = re.search(r"particle (\d+) ", str(e))
+            status[self.rank] = int(m.group(1)) + 1 if (m and e.code == AMC_ERR_CAPACITY) else min(int(e.code), -1)
+        if self.world > 1:
+            limbs = CO.words_to_limbs(tot)
+            flat = self.comm.allreduce_sum_ints(status + [int(v) for v in limbs.ravel()] + [int(counters[2])])
+            failed = [(r, s) for r, s in enumerate(flat[:self.world]) if s != 0]
+            if failed:
+                r, s = failed[0]
+                if s > 0:
+                    raise ArgonMCError(AMC_ERR_CAPACITY, f"amc_corr: particle {s - 1} (rank {r}) is outside the quantisers' range; "
+                                                         "sampling stopped until correlations_reset") from err
+                raise ArgonMCError(s, f"corr_read failed on rank {r}") from err
+            tot = CO.limbs_to_words(np.array(flat[self.world:-1], dtype=np.int64).reshape(limbs.shape))
+            counters = (counters[0], counters[1], flat[-1], counters[3])
+        elif err is not None:
+            raise err
+        if every is None:
+            every = int(g.every) if int(g.every) > 0 else 1
+        if dt is None:
+            dt = getattr(self, "dt", 1.0)
+        return CO.derive(g, tot, counters, dt, every)
+
     def histograms(self):
         """Global free-path histograms = sum over ranks (every completed path is emitted by its particle's owner)."""
         counts, tot = self.engine.histograms()

@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._abi import (AMC_K_NAMES, AmcFieldGrid, AmcParams, AmcPathRecord, AmcStepStats, AmcSurfaceGrid, path_record_dtype)
+from ._abi import (AMC_K_NAMES, AmcCorrGrid, AmcFieldGrid, AmcParams, AmcPathRecord, AmcStepStats, AmcSurfaceGrid, path_record_dtype)
 
 _dp = C.POINTER(C.c_double)
 _i64p = C.POINTER(C.c_int64)
@@ -32,6 +32,7 @@ class Engine:
         self.n = int(params.n)
         self.field_grid = None
         self.surface_grid = None
+        self.corr_grid = None
         self._ctx = C.c_void_p()
         rc = self.lib.amc_create(C.byref(self._ctx), C.byref(params))
         if rc != 0:
@@ -177,6 +178,53 @@ class Engine:
 
     def fields_reset(self):
         self._ck(self.lib.amc_fields_reset(self._ctx))
+
+    # -- sampled correlations (correlations.py) ----------------------------------------------------------------------
+    def corr_config(self, grid):
+        """Sample on ``grid`` (an ``AmcCorrGrid``, correlations.make_grid); None switches sampling off.  Starts from zero
+        totals; the first sample is a time origin."""
+        self._ck(self.lib.amc_corr_config(self._ctx, None if grid is None else C.byref(grid)))
+        self.corr_grid = None if grid is None else AmcCorrGrid.from_buffer_copy(grid)
+
+    def _corr_range(self):
+        return int(getattr(self, "hi", self.n)) - int(getattr(self, "lo", 0))
+
+    def corr_sample(self):
+        """One sample of the current state at the window position, enqueued on the context's stream."""
+        self._ck(self.lib.amc_corr_sample(self._ctx))
+
+    def corr_read(self):
+        """(int64[groups, n_lags + 1, 7, 2] totals as (low, high) words, (n_origins, n_samples, n_outside, window_pos));
+        synchronises."""
+        g = self.corr_grid
+        if g is None:
+            raise _lib.ArgonMCError(-6, "corr_read before corr_config")
+        tot = np.zeros((int(g.n1) * int(g.n2) * int(g.n3), int(g.n_lags) + 1, 7, 2), dtype=np.int64)
+        c = [C.c_int64(0) for _ in range(4)]
+        self._ck(self.lib.amc_corr_read(self._ctx, tot.ctypes.data_as(_i64p), *[C.byref(v) for v in c]))
+        return tot, tuple(v.value for v in c)
+
+    def corr_origin(self):
+        """The six origin arrays (x0, y0, z0, vx0, vy0, vz0) of the context's index range."""
+        if self.corr_grid is None:
+            raise _lib.ArgonMCError(-6, "corr_origin before corr_config")
+        arrs = [np.zeros(self._corr_range()) for _ in range(6)]
+        self._ck(self.lib.amc_corr_origin(self._ctx, *[_d(a) for a in arrs]))
+        return arrs
+
+    def corr_load(self, totals, counters, origin=None):
+        """The inverse of ``corr_read`` + ``corr_origin``: totals, (n_origins, n_samples, n_outside, window_pos) and the six
+        origin arrays (None only at window position 0)."""
+        tot = np.ascontiguousarray(totals, dtype=np.int64)
+        g = self.corr_grid
+        if g is None or tot.size != int(g.n1) * int(g.n2) * int(g.n3) * (int(g.n_lags) + 1) * 14:
+            raise ValueError("totals do not match the configured grid")
+        arrs = [None] * 6 if origin is None else [_f64(a, self._corr_range()) for a in origin]
+        no, ns, nout, pos = (int(v) for v in counters)
+        self._ck(self.lib.amc_corr_load(self._ctx, tot.ctypes.data_as(_i64p), no, ns, nout, pos, *[_d(a) for a in arrs]))
+
+    def corr_reset(self):
+        self._ck(self.lib.amc_corr_reset(self._ctx))
 
     # -- measurement -----------------------------------------------------------------------------------------------
     def set_stream(self, stream_ptr):

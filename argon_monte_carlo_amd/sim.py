@@ -172,6 +172,58 @@ class Simulation:
         elif self.engine.field_grid is not None:      # fields on here, not in the checkpoint: they start with the resumed run
             self.engine.fields_config(FL.copy_grid(self.engine.field_grid, step_offset=self._step_base))
 
+    # ---- sampled correlations (correlations.py; the reference has no such output) ---------------------------
+    def enable_correlations(self, grid=None, every=0, n_lags=None):
+        """Sample the mean-square displacement and the velocity autocorrelation per group of ``grid`` (correlations.make_grid;
+        None = the geometry's default, correlations.default_grid) and lag 0 .. ``n_lags`` (None: the grid's), one sample after
+        every ``every``-th step (0: only on ``correlations_sample()``).  Starts from zero; the first sample is a time origin."""
+        from . import correlations as CO
+        g = CO.default_grid(self.params) if grid is None else grid
+        self.engine.corr_config(CO.copy_grid(g, every=every, step_offset=getattr(self, "_step_base", 0), n_lags=n_lags))
+
+    def disable_correlations(self):
+        self.engine.corr_config(None)
+
+    def correlations_sample(self):
+        """One sample of the current state now (asynchronous): an origin, or the next lag of the window."""
+        self.engine.corr_sample()
+
+    def correlations_reset(self):
+        self.engine.corr_reset()
+
+    def correlations(self, every=None):
+        """dict (correlations.derive): count, msd, vacf and D_msd per (group, lag, component), D_vacf per (group, component),
+        lag_time, n_origins, n_samples, n_outside, window_pos and the raw integer totals (int64[groups, n_lags + 1, 7, 2]).
+        ``every``: steps between two samples for the lag times (None: the cadence's, or 1 for manual samples)."""
+        from . import correlations as CO
+        tot, counters = self.engine.corr_read()
+        g = self.engine.corr_grid
+        if every is None:
+            every = int(g.every) if int(g.every) > 0 else 1
+        return CO.derive(g, tot, counters, self.dt, every)
+
+    def write_correlations(self, path):
+        """The dict of ``correlations()`` as an .npz (edges as edges_1, edges_2[, edges_3])."""
+        f = self.correlations()
+        e = f.pop("edges")
+        np.savez(path, **f, **{f"edges_{k + 1}": v for k, v in enumerate(e)})
+
+    def _corr_checkpoint(self):
+        if self.engine.corr_grid is None:
+            return {}
+        from . import correlations as CO
+        tot, counters = self.engine.corr_read()
+        return dict(corr_grid=CO.grid_to_array(self.engine.corr_grid), corr_totals=tot, corr_counters=np.array(counters, dtype=np.int64),
+                    corr_origin=np.stack(self.engine.corr_origin()))
+
+    def _corr_restore(self, z):
+        from . import correlations as CO
+        if "corr_grid" in z:
+            self.engine.corr_config(CO.copy_grid(CO.grid_from_array(z["corr_grid"]), step_offset=self._step_base))
+            self.engine.corr_load(z["corr_totals"], z["corr_counters"], list(z["corr_origin"]))
+        else:                                           # a checkpoint without them: sampling is off in the resumed run
+            self.engine.corr_config(None)
+
     # ---- checkpoint / resume (the reference has none: a 10^4-step run is one process lifetime there) ---------------
     def _checkpoint_extra(self):
         return {}
@@ -182,7 +234,8 @@ class Simulation:
     def save_checkpoint(self, path):
         """Everything a later ``load_checkpoint`` needs to continue bit-identically: the particle arrays, the
         completed-path lists, the device histograms and the counters (+ RNG streams and per-step lists for Temp, + the
-        grid and the totals of the sampled fields when they are on)."""
+        grid and the totals of the sampled fields when they are on, + the grid, totals, counters, window position and origin
+        arrays of the sampled correlations when they are on)."""
         st = self.engine.download()
         self._collect()
         counts, _ = self.engine.histograms()
@@ -195,7 +248,8 @@ class Simulation:
                  completed_y_paths=np.array(self.completed_y_paths, dtype=np.float64),
                  completed_z_paths=np.array(self.completed_z_paths, dtype=np.float64),
                  total_cols=int(self.total_cols), steps_done=int(self.steps_done),
-                 **{f"state_{k}": v for k, v in st.items()}, **self._checkpoint_extra(), **self._fields_checkpoint())
+                 **{f"state_{k}": v for k, v in st.items()}, **self._checkpoint_extra(), **self._fields_checkpoint(),
+                 **self._corr_checkpoint())
 
     def load_checkpoint(self, path):
         z = np.load(path if str(path).endswith(".npz") else str(path) + ".npz", allow_pickle=False)
@@ -215,6 +269,7 @@ class Simulation:
         self._cache = None
         self._restore_extra(z)
         self._fields_restore(z)
+        self._corr_restore(z)
 
     def close(self):
         self.engine.close()

@@ -241,7 +241,7 @@ int amc_histograms(amc_ctx *ctx, uint64_t *counts, uint64_t *n_paths_total);
 /* Zero histograms, counters, the pending path records and the step index.  Whatever was enqueued before the call is
  * discarded from the outputs — the paths and collisions of a step that has returned without its statistics
  * (amc_mg_finish(ctx, NULL)) included — and its results still reach the particle arrays: the state is the one the steps so
- * far produce, and the next step's outputs and statistics hold that step alone.  Sampled fields and surfaces are left alone. */
+ * far produce, and the next step's outputs and statistics hold that step alone.  Sampled fields, surfaces and correlations are left alone. */
 int amc_reset_outputs(amc_ctx *ctx);
 
 /* Host-only helper of the hand-over above (no GPU, no context): the re-emission directions of one case's hits —
@@ -400,7 +400,7 @@ int amc_mg_finish(amc_ctx *ctx, amc_step_stats *out);      /* out == NULL: no ho
 #define AMC_K_COMMIT 9           /* k_commit: a sweep's commit as a launch of its own (else it rides along with the next k_stream) */
 #define AMC_K_CLUSTERS_WIDE 10   /* k_clusters_wide: every small cluster emulated and validated wide, before the ordered workgroup */
 #define AMC_K_FIXUP 11           /* k_fixup: joins an overlapped run's early streaming pass with the sweep's results (below) */
-#define AMC_K_FIELDS 12          /* k_fields_accum + k_fields_reduce: one sample of the fields (below) */
+#define AMC_K_FIELDS 12          /* k_fields_accum + k_fields_reduce: one sample of the fields (below); the surfaces' and the correlations' kernels too */
 #define AMC_K_COUNT 13
 int amc_profile(amc_ctx *ctx, int enable);
 int amc_kernel_times(amc_ctx *ctx, double *total_ms /*[AMC_K_COUNT]*/, int64_t *launches /*[AMC_K_COUNT]*/);
@@ -508,6 +508,9 @@ int amc_surface_reset(amc_ctx *ctx);
  * (AMC_ERR_STATE when `case_id` is not the pending case; cap counts hits). */
 int amc_temp_device_contacts(amc_ctx *ctx, int case_id, int32_t *idx, double *contact_xyz, size_t cap, size_t *n);
 int amc_wall_contacts(amc_ctx *ctx, int case_id, double *contact_xyz, size_t cap);
+
+/* ---- sampled correlations: velocity autocorrelation and mean-square displacement per group and lag (opt-in) -- */
+#include "argonmc_corr.h"
 
 /* ---- the device-RNG energised pore over shards: the hits exchange and the host-free sharded run ---------------------------- */
 #include "argonmc_shard.h"
