@@ -12,10 +12,11 @@ import ctypes as C
 
 import numpy as np
 
-from ._abi import (AMC_CORR_MAX_CELLS, AMC_CORR_MAX_GROUPS, AMC_FIELDS_AXISYMMETRIC, AMC_FIELDS_CARTESIAN, AMC_GEOM_CUBE,
-                   AmcCorrGrid)
+from ._abi import AMC_CORR_MAX_CELLS, AMC_CORR_MAX_GROUPS, AMC_GEOM_CUBE, AmcCorrGrid
+from ._abi import AMC_FIELDS_AXISYMMETRIC, AMC_FIELDS_CARTESIAN     # the grid kinds, for callers that build an AmcCorrGrid
 from . import fields as FL
-from .fields import edges, ints_to_words, limbs_to_words, widths, words_to_ints, words_to_limbs  # noqa: F401  (shared helpers)
+from .fields import edges, widths  # noqa: F401  (shared helpers)
+from .totals import ints_to_words, limbs_to_words, words_to_ints, words_to_limbs  # noqa: F401
 
 M_SCALE = 2 ** 74
 C_SCALE = 2 ** 10
@@ -35,27 +36,24 @@ def make_grid(kind, n, lo, hi, every=0, step_offset=0, n_lags=DEFAULT_N_LAGS):
         groups *= max(int(v), 1)
     if groups > AMC_CORR_MAX_GROUPS:        # (tighter than the fields' limit on bins)
         raise ValueError(f"{groups} groups: at most {AMC_CORR_MAX_GROUPS} in all")
-    f = FL.make_grid(kind, n, lo, hi, every, step_offset)
-    n_lags = int(n_lags)
-    if n_lags < 1 or groups * (n_lags + 1) > AMC_CORR_MAX_CELLS:
-        raise ValueError(f"n_lags {n_lags}: at least 1 and groups * (n_lags + 1) at most {AMC_CORR_MAX_CELLS}")
+    return _from_field_grid(FL.make_grid(kind, n, lo, hi, every, step_offset), n_lags)
+
+
+def _from_field_grid(f, n_lags):
+    """the ``AmcFieldGrid`` f as the group grid of an ``AmcCorrGrid`` with ``n_lags`` lags"""
     g = AmcCorrGrid()
     g.struct_size = C.sizeof(AmcCorrGrid)
-    g.kind, g.n1, g.n2, g.n3, g.n_lags = f.kind, f.n1, f.n2, f.n3, n_lags
+    g.kind, g.n1, g.n2, g.n3 = f.kind, f.n1, f.n2, f.n3
     g.every, g.step_offset = f.every, f.step_offset
     for a in range(3):
         g.lo[a], g.hi[a] = f.lo[a], f.hi[a]
-    return g
+    return copy_grid(g, n_lags=n_lags)
 
 
 def copy_grid(g, every=None, step_offset=None, n_lags=None):
-    out = AmcCorrGrid.from_buffer_copy(g)
-    if every is not None:
-        if int(every) < 0:
-            raise ValueError("every must be >= 0")
-        out.every = int(every)
-    if step_offset is not None:
-        out.step_offset = int(step_offset)
+    if every is not None and int(every) < 0:
+        raise ValueError("every must be >= 0")
+    out = FL.copy_grid(g, every, step_offset)
     if n_lags is not None:
         n_lags = int(n_lags)
         if n_lags < 1 or grid_groups(g) * (n_lags + 1) > AMC_CORR_MAX_CELLS:
@@ -82,17 +80,15 @@ def totals_shape(g):
 
 def grid_to_array(g):
     """float64[13] for a checkpoint: kind, n1, n2, n3, every, lo[3], hi[3], step_offset, n_lags."""
-    return np.array([g.kind, g.n1, g.n2, g.n3, g.every] + list(g.lo) + list(g.hi) + [g.step_offset, g.n_lags], dtype=np.float64)
+    return np.append(FL.grid_to_array(g), float(g.n_lags))
 
 
 def grid_from_array(a):
     a = np.asarray(a, dtype=np.float64)
-    kind = int(a[0])
-    n = [int(a[1]), int(a[2]), int(a[3])]
-    lo, hi = list(a[5:8]), list(a[8:11])
-    if kind == AMC_FIELDS_AXISYMMETRIC:
-        return make_grid(kind, n[:2], lo[:2], hi[:2], int(a[4]), int(a[11]), int(a[12]))
-    return make_grid(kind, n, lo, hi, int(a[4]), int(a[11]), int(a[12]))
+    f = FL.grid_from_array(a[:12])
+    if FL.grid_bins(f) > AMC_CORR_MAX_GROUPS:
+        raise ValueError(f"{FL.grid_bins(f)} groups: at most {AMC_CORR_MAX_GROUPS} in all")
+    return _from_field_grid(f, int(a[12]))
 
 
 # ---- derived quantities -----------------------------------------------------------------------------------------------

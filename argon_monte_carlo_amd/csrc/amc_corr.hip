@@ -12,17 +12,14 @@
 //                       (group, 7 sums) in registers and flushes it to LDS (64-bit integer LDS atomics) only when the group
 //                       changes and at the end: with one group every lane would otherwise hit the same seven words.  The
 //                       table leaves as one slab row with plain stores — no global atomics but the atomicMin on the error word.
-//   k_corr_reduce       sums the slab rows per (group, quantity) into the 128-bit totals at the launch's lag or lags, with
-//                       carry, and bumps the counters.  It adds nothing once the error word is set.
-// Integer sums do not depend on the order of the adds, so the totals are bitwise the same for any number of workgroups.
+//   k_sample_reduce     (amc_fields.hip, the fields' own reduce) sums the slab rows per (group, quantity) into the 128-bit
+//                       totals at the launch's lag or lags, with carry, and bumps the counters.
+// The group rule (amc_sample_bin), the speed test and the lazy read are amc_sample_dev.h's.
 #include "amc_host.h"
 #include "amc_sample_dev.h"
 
-#define AMC_CORR_Q 7                    // count, m(x y z), c(x y z)
+#define AMC_CORR_Q AMC_SAMPLE_Q          // count, m(x y z), c(x y z)
 #define AMC_CORR_THREADS 512            // 8 waves per CU: the lag-and-origin instance needs more than the 128 VGPRs 16 waves leave
-#define AMC_CORR_REDUCE_THREADS 1024
-#define AMC_CORR_PER_BLOCK 8192         // particles per workgroup below which fewer workgroups are launched
-#define AMC_CORR_MAX_PARTICLES (1LL << 24)
 #define AMC_CORR_ORIGIN 0
 #define AMC_CORR_LAG 1
 #define AMC_CORR_LAG_ORIGIN 2
@@ -55,25 +52,6 @@ AMC_DEV void corr_enter(unsigned long long *tab, corr_run &r, int g)
     for (int q = 0; q < AMC_CORR_Q; q++) r.s[q] = 0;
 }
 
-// the group of a position: the linear bin of the group grid, -1 outside
-AMC_DEV int corr_group(const amc_fields_grid_dev &G, double x, double y, double z)
-{
-    int i1, i2, i3;
-    if (G.kind == AMC_FIELDS_CARTESIAN) {
-        i1 = amc_fields_axis(x, G.lo[0], G.hi[0], G.w[0], G.n1);
-        i2 = amc_fields_axis(y, G.lo[1], G.hi[1], G.w[1], G.n2);
-        i3 = amc_fields_axis(z, G.lo[2], G.hi[2], G.w[2], G.n3);
-    } else {
-        const double r = sqrt(x * x + y * y);
-        i1 = amc_fields_axis(r, G.lo[0], G.hi[0], G.w[0], G.n1);
-        i2 = amc_fields_axis(z, G.lo[1], G.hi[1], G.w[1], G.n2);
-        i3 = 0;
-    }
-    if (i1 < 0 || i2 < 0 || i3 < 0) return -1;
-    return (i1 * G.n2 + i2) * G.n3 + i3;
-}
-
-AMC_DEV bool corr_speed_ok(double a, double b, double c) { return fabs(a) < 16384.0 && fabs(b) < 16384.0 && fabs(c) < 16384.0; }
 AMC_DEV unsigned long long corr_m(double d) { return (unsigned long long)(long long)rint(ldexp(d * d, 74)); }
 AMC_DEV unsigned long long corr_c(double v, double v0) { return (unsigned long long)(long long)rint((v * v0) * 1024.0); }
 
@@ -81,9 +59,9 @@ AMC_DEV unsigned long long corr_c(double v, double v0) { return (unsigned long l
 AMC_DEV bool corr_origin_particle(const amc_fields_grid_dev &G, unsigned long long *tab, corr_run &r, unsigned int &outside, double x,
                                   double y, double z, double vx, double vy, double vz)
 {
-    const int g = corr_group(G, x, y, z);
+    const int g = amc_sample_bin(G, x, y, z);
     if (g < 0) { outside++; return true; }
-    if (!corr_speed_ok(vx, vy, vz)) return false;
+    if (!amc_sample_speed_ok(vx, vy, vz)) return false;
     corr_enter(tab, r, g);
     r.s[0] += 1ULL;
     r.s[4] += corr_c(vx, vx);
@@ -96,11 +74,11 @@ AMC_DEV bool corr_origin_particle(const amc_fields_grid_dev &G, unsigned long lo
 AMC_DEV bool corr_lag_particle(const amc_fields_grid_dev &G, unsigned long long *tab, corr_run &r, double x, double y, double z,
                                double vx, double vy, double vz, double x0, double y0, double z0, double vx0, double vy0, double vz0)
 {
-    const int g = corr_group(G, x0, y0, z0);
+    const int g = amc_sample_bin(G, x0, y0, z0);
     if (g < 0) return true;             // (no part in this window: counted when the origin was stored)
     const double ex = x - x0, ey = y - y0, ez = z - z0;
     const double lim = 3.814697265625e-06;      // 2^-18
-    if (!(fabs(ex) < lim && fabs(ey) < lim && fabs(ez) < lim) || !corr_speed_ok(vx, vy, vz) || !corr_speed_ok(vx0, vy0, vz0)) return false;
+    if (!(fabs(ex) < lim && fabs(ey) < lim && fabs(ez) < lim) || !amc_sample_speed_ok(vx, vy, vz) || !amc_sample_speed_ok(vx0, vy0, vz0)) return false;
     corr_enter(tab, r, g);
     r.s[0] += 1ULL;
     r.s[1] += corr_m(ex);
@@ -194,45 +172,6 @@ __global__ __launch_bounds__(AMC_CORR_THREADS) void k_corr_accum(amc_state S, am
     if (threadIdx.x == 0) row[TABLES * M] = outside_sum;
 }
 
-// column j of the slab (j < tables * M: table j / M, (group, quantity) j % M; j == tables * M: particles outside) summed over
-// the rows -> running totals at lag_a (table 0) or lag_b (table 1).  64 columns per workgroup, its sixteen waves take every
-// sixteenth row, four loads in flight each: the rows are a chain of memory round trips otherwise (measured: 10 us for 123 rows
-// with four waves).
-// meta: [0] origins, [1] samples, [2] particles outside, [3] lowest particle out of range (~0: none)
-__global__ __launch_bounds__(AMC_CORR_REDUCE_THREADS) void k_corr_reduce(const unsigned long long *slab, int rows, int M, int tables, int lag_a, int lag_b,
-                                                     int lags1, int origin, unsigned long long *tot, unsigned long long *meta)
-{
-    if (meta[3] != ~0ULL) return;       // a sample with a particle out of range adds nothing, nor does a later one (amc_corr_read reports it)
-    constexpr int WAVES = AMC_CORR_REDUCE_THREADS / 64;
-    __shared__ unsigned long long part[WAVES][64];
-    const int W = tables * M;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int j = blockIdx.x * 64 + lane;
-    unsigned long long s = 0;           // (wraps modulo 2^64; the true sum of one sample is below 2^62 in magnitude)
-    if (j <= W) {
-#pragma unroll 4
-        for (int b = wave; b < rows; b += WAVES) s += slab[(size_t)b * (size_t)(W + 1) + j];
-    }
-    part[wave][lane] = s;
-    __syncthreads();
-    if (wave != 0 || j > W) return;
-    s = 0;
-#pragma unroll
-    for (int k = 0; k < WAVES; k++) s += part[k][lane];
-    if (j == W) {
-        meta[0] += (unsigned long long)origin;
-        meta[1] += 1;
-        meta[2] += s;
-        return;
-    }
-    const int t = j / M, jj = j - t * M;
-    const int g = jj / AMC_CORR_Q, q = jj - g * AMC_CORR_Q;
-    const size_t at = ((size_t)g * (size_t)lags1 + (size_t)(t == 0 ? lag_a : lag_b)) * AMC_CORR_Q + (size_t)q;
-    const unsigned long long old = tot[2 * at], now = old + s;
-    tot[2 * at] = now;
-    tot[2 * at + 1] += (unsigned long long)(((long long)s < 0 ? -1LL : 0LL) + (now < old ? 1LL : 0LL));
-}
-
 static amc_corr_arrays corr_arrays(const amc_corr_ws &R)
 {
     amc_corr_arrays O;
@@ -245,22 +184,12 @@ static amc_corr_arrays corr_arrays(const amc_corr_ws &R)
 static int corr_enqueue(amc_ctx *c)
 {
     amc_corr_ws &R = c->CR;
-    const long long cnt = c->hi - c->lo;
-    if (cnt > AMC_CORR_MAX_PARTICLES)
-        return amc_fail(c, AMC_ERR_CAPACITY, "amc_corr: %lld particles in one sample (at most 2^24 keep the sums exact)", cnt);
-    int blocks = R.blocks_env > 0 ? R.blocks_env : (int)std::min<long long>(R.max_blocks, std::max<long long>(1, (cnt + AMC_CORR_PER_BLOCK - 1) / AMC_CORR_PER_BLOCK));
-    blocks = std::min(blocks, R.max_blocks);
-    amc_lazy L;
-    memset(&L, 0, sizeof L);
-    if (c->step.lazy_pending) { L.slot_of = c->W.slot_of; L.state = c->W.sl_state; L.moved = c->W.sl_moved; L.enabled = 1; }
-    amc_fields_grid_dev G;
-    G.kind = R.g.kind; G.n1 = R.g.n1; G.n2 = R.g.n2; G.n3 = R.g.n3; G.bins = R.groups;
-    for (int k = 0; k < 3; k++) { G.lo[k] = R.g.lo[k]; G.hi[k] = R.g.hi[k]; G.w[k] = R.w[k]; }
+    int blocks;
+    if (int rc = amc_sample_blocks(c, "amc_corr", R.blocks_env, R.max_blocks, &blocks)) return rc;
+    const amc_lazy L = amc_sample_lazy(c);
+    const amc_fields_grid_dev &G = R.G;
     const amc_corr_arrays O = corr_arrays(R);
-    const int M = R.groups * AMC_CORR_Q;
     const int mode = R.pos == 0 ? AMC_CORR_ORIGIN : R.pos < R.g.n_lags ? AMC_CORR_LAG : AMC_CORR_LAG_ORIGIN;
-    const int tables = mode == AMC_CORR_LAG_ORIGIN ? 2 : 1;
-    const int lag_a = (int)R.pos, lag_b = 0;
     amc_prof_begin(c, AMC_K_FIELDS);
     if (mode == AMC_CORR_ORIGIN)
         AMC_LAUNCH(c, k_corr_accum<AMC_CORR_ORIGIN>, dim3(blocks), dim3(AMC_CORR_THREADS), c->S, L, O, (long long)c->lo, (long long)c->hi, G, R.slab, R.meta + 3);
@@ -270,32 +199,23 @@ static int corr_enqueue(amc_ctx *c)
         AMC_LAUNCH(c, k_corr_accum<AMC_CORR_LAG_ORIGIN>, dim3(blocks), dim3(AMC_CORR_THREADS), c->S, L, O, (long long)c->lo, (long long)c->hi, G, R.slab, R.meta + 3);
     amc_prof_end(c);
     AMC_HIP(c, hipGetLastError());
-    amc_prof_begin(c, AMC_K_FIELDS);
-    AMC_LAUNCH(c, k_corr_reduce, dim3((tables * M + 1 + 63) / 64), dim3(AMC_CORR_REDUCE_THREADS), (const unsigned long long *)R.slab, blocks, M, tables, lag_a, lag_b,
-               R.g.n_lags + 1, mode == AMC_CORR_LAG ? 0 : 1, R.tot, R.meta);
-    amc_prof_end(c);
-    AMC_HIP(c, hipGetLastError());
+    // table 0 at the window position; the lag-and-origin pass has a second table, the new origin's lag 0
+    AMC_HIP(c, amc_launch_sample_reduce(c, R.slab, blocks, G.bins * AMC_CORR_Q, mode == AMC_CORR_LAG_ORIGIN ? 2 : 1, (int)R.pos, 0,
+                                        R.g.n_lags + 1, mode == AMC_CORR_LAG ? 0 : 1, R.tot, R.meta));
     R.pos = mode == AMC_CORR_LAG ? R.pos + 1 : 1;
     return AMC_OK;
 }
 
-static size_t corr_total_words(const amc_corr_ws &R) { return (size_t)2 * AMC_CORR_Q * (size_t)R.groups * (size_t)(R.g.n_lags + 1); }
+// meta: [0] origins, [1] samples, [2] particles outside, [3] the error word
+static amc_totals corr_totals(const amc_corr_ws &R)
+{
+    return amc_totals{R.tot, (size_t)2 * AMC_CORR_Q * (size_t)R.G.bins * (size_t)(R.g.n_lags + 1), R.meta, 4, 3};
+}
 
 static void corr_free(amc_ctx *c)
 {
     ctx_free(c, c->CR.slab, c->CR.tot, c->CR.meta, c->CR.origin);
     c->CR = amc_corr_ws();
-}
-
-static int corr_clear(amc_ctx *c)
-{
-    amc_corr_ws &R = c->CR;
-    const unsigned long long meta[4] = {0, 0, 0, ~0ULL};
-    AMC_HIP(c, hipMemsetAsync(R.tot, 0, sizeof(unsigned long long) * corr_total_words(R), c->stream));
-    AMC_HIP(c, hipMemcpyAsync(R.meta, meta, sizeof meta, hipMemcpyHostToDevice, c->stream));
-    AMC_HIP(c, hipStreamSynchronize(c->stream));
-    R.pos = 0;
-    return AMC_OK;
 }
 
 extern "C" {
@@ -316,35 +236,21 @@ int amc_corr_config(amc_ctx *c, const amc_corr_grid *g)
         return AMC_OK;
     }
     if (g->struct_size != (int32_t)sizeof(amc_corr_grid)) return amc_fail(c, AMC_ERR_INVALID, "amc_corr_grid.struct_size mismatch (ABI)");
-    if (g->kind != AMC_FIELDS_CARTESIAN && g->kind != AMC_FIELDS_AXISYMMETRIC)
-        return amc_fail(c, AMC_ERR_INVALID, "amc_corr_grid.kind %d is neither Cartesian (0) nor axisymmetric (1)", g->kind);
-    if (g->n1 < 1 || g->n2 < 1 || g->n3 < 1 || (long long)g->n1 * g->n2 * g->n3 > AMC_CORR_MAX_GROUPS)
-        return amc_fail(c, AMC_ERR_INVALID, "amc_corr_grid: %d x %d x %d groups (each >= 1, at most %d in all)", g->n1, g->n2, g->n3,
-                        AMC_CORR_MAX_GROUPS);
+    char lags_fault[96] = "";           // (reported behind the group count, as before the grid check was shared)
     if (g->n_lags < 1 || (long long)g->n1 * g->n2 * g->n3 * ((long long)g->n_lags + 1) > AMC_CORR_MAX_CELLS)
-        return amc_fail(c, AMC_ERR_INVALID, "amc_corr_grid: n_lags %d (>= 1, groups * (n_lags + 1) at most %d)", g->n_lags, AMC_CORR_MAX_CELLS);
-    if (g->kind == AMC_FIELDS_AXISYMMETRIC && (g->n3 != 1 || g->lo[0] != 0.0))
-        return amc_fail(c, AMC_ERR_INVALID, "amc_corr_grid: an axisymmetric grid has n3 == 1 and r from lo[0] == 0");
-    if (g->every < 0 || g->step_offset < 0 || g->reserved[0] != 0 || g->reserved[1] != 0)
-        return amc_fail(c, AMC_ERR_INVALID, "amc_corr_grid: every and step_offset must be >= 0, reserved 0");
-    const int axes = g->kind == AMC_FIELDS_CARTESIAN ? 3 : 2;
-    for (int k = 0; k < axes; k++)
-        if (!(isfinite(g->lo[k]) && isfinite(g->hi[k]) && g->lo[k] < g->hi[k]))
-            return amc_fail(c, AMC_ERR_INVALID, "amc_corr_grid: axis %d needs finite bounds lo < hi", k + 1);
+        snprintf(lags_fault, sizeof lags_fault, "n_lags %d (>= 1, groups * (n_lags + 1) at most %d)", g->n_lags, AMC_CORR_MAX_CELLS);
+    amc_fields_grid_dev G;
+    if (int rc = amc_sample_grid_check(c, "amc_corr_grid", "groups", g->kind, g->n1, g->n2, g->n3, AMC_CORR_MAX_GROUPS, g->lo, g->hi, g->every,
+                                       g->step_offset, g->reserved[0] == 0 && g->reserved[1] == 0, lags_fault[0] ? lags_fault : nullptr, &G))
+        return rc;
     corr_free(c);
     amc_corr_ws &R = c->CR;
     R.g = *g;
-    R.groups = g->n1 * g->n2 * g->n3;
-    const int n[3] = {g->n1, g->n2, g->n3};
-    for (int k = 0; k < 3; k++) R.w[k] = k < axes ? (g->hi[k] - g->lo[k]) / (double)n[k] : 1.0;
-    if (g->kind == AMC_FIELDS_AXISYMMETRIC) { R.g.lo[2] = 0.0; R.g.hi[2] = 1.0; }
-    R.blocks_env = getenv("AMC_CORR_BLOCKS") ? atoi(getenv("AMC_CORR_BLOCKS")) : 0;
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || cus < 1) cus = 256;
-    R.max_blocks = R.blocks_env > 0 ? R.blocks_env : cus;
+    R.G = G;
+    amc_sample_blocks_config(c, "AMC_CORR_BLOCKS", &R.blocks_env, &R.max_blocks);
     R.stride = (std::max<int64_t>(c->n, 1) + 1) & ~(int64_t)1;
-    const size_t M = (size_t)R.groups * AMC_CORR_Q;
-    if (dalloc(c, &R.slab, (size_t)R.max_blocks * (2 * M + 1)) != hipSuccess || dalloc(c, &R.tot, corr_total_words(R)) != hipSuccess ||
+    const size_t M = (size_t)G.bins * AMC_CORR_Q;
+    if (dalloc(c, &R.slab, (size_t)R.max_blocks * (2 * M + 1)) != hipSuccess || dalloc(c, &R.tot, corr_totals(R).words) != hipSuccess ||
         dalloc(c, &R.meta, 4) != hipSuccess || dalloc(c, &R.origin, (size_t)6 * (size_t)R.stride) != hipSuccess) {
         corr_free(c);
         return amc_fail(c, AMC_ERR_HIP, "amc_corr_config: device allocation failed");
@@ -352,7 +258,7 @@ int amc_corr_config(amc_ctx *c, const amc_corr_grid *g)
     R.on = true;
     int rc = AMC_OK;
     if (hipMemsetAsync(R.origin, 0, sizeof(double) * 6 * (size_t)R.stride, c->stream) != hipSuccess) rc = amc_fail(c, AMC_ERR_HIP, "amc_corr_config: hipMemsetAsync failed");
-    if (!rc) rc = corr_clear(c);
+    if (!rc) rc = amc_corr_reset(c);
     if (rc) { corr_free(c); return rc; }
     return AMC_OK;
 }
@@ -372,16 +278,11 @@ int amc_corr_read(amc_ctx *c, int64_t *totals, int64_t *n_origins, int64_t *n_sa
     if (!c->CR.on) return amc_fail(c, AMC_ERR_STATE, "amc_corr_read before amc_corr_config");
     AMC_HIP(c, hipSetDevice(c->device));
     amc_corr_ws &R = c->CR;
-    unsigned long long meta[4];
-    {
-        amc_stage st(c);
-        if (totals) AMC_HIP(c, st.get(totals, R.tot, sizeof(unsigned long long) * corr_total_words(R)));
-        AMC_HIP(c, st.get(meta, R.meta, sizeof meta));
-        AMC_HIP(c, st.finish());
-    }
-    if (meta[3] != ~0ULL)
+    unsigned long long meta[4], bad;
+    if (int rc = amc_totals_get(c, corr_totals(R), totals, meta, &bad)) return rc;
+    if (bad != ~0ULL)
         return amc_fail(c, AMC_ERR_CAPACITY, "amc_corr: particle %llu is outside the quantisers' range (a displacement component of 2^-18 m or more "
-                        "from its origin, a velocity component of 2^14 m/s or more, or NaN); sampling stopped until amc_corr_reset", meta[3]);
+                        "from its origin, a velocity component of 2^14 m/s or more, or NaN); sampling stopped until amc_corr_reset", bad);
     if (n_origins) *n_origins = (int64_t)meta[0];
     if (n_samples) *n_samples = (int64_t)meta[1];
     if (n_outside) *n_outside = (int64_t)meta[2];
@@ -415,9 +316,8 @@ int amc_corr_load(amc_ctx *c, const int64_t *totals, int64_t n_origins, int64_t 
     for (int k = 0; k < 6; k++)
         if (window_pos > 0 && !src[k]) return amc_fail(c, AMC_ERR_INVALID, "amc_corr_load: a window position > 0 needs the six origin arrays");
     AMC_HIP(c, hipSetDevice(c->device));
-    const unsigned long long meta[4] = {(unsigned long long)n_origins, (unsigned long long)n_samples, (unsigned long long)n_outside, ~0ULL};
-    AMC_HIP(c, hipMemcpyAsync(R.tot, totals, sizeof(unsigned long long) * corr_total_words(R), hipMemcpyHostToDevice, c->stream));
-    AMC_HIP(c, hipMemcpyAsync(R.meta, meta, sizeof meta, hipMemcpyHostToDevice, c->stream));
+    const unsigned long long meta[4] = {(unsigned long long)n_origins, (unsigned long long)n_samples, (unsigned long long)n_outside, 0};
+    if (int rc = amc_totals_put(c, corr_totals(R), totals, meta)) return rc;
     const size_t bytes = sizeof(double) * (size_t)(c->hi - c->lo);
     for (int k = 0; k < 6; k++)
         if (src[k] && bytes) AMC_HIP(c, hipMemcpyAsync(R.origin + (size_t)k * (size_t)R.stride + c->lo, src[k], bytes, hipMemcpyHostToDevice, c->stream));
@@ -431,7 +331,10 @@ int amc_corr_reset(amc_ctx *c)
     if (!c) return AMC_ERR_INVALID;
     if (!c->CR.on) return amc_fail(c, AMC_ERR_STATE, "amc_corr_reset before amc_corr_config");
     AMC_HIP(c, hipSetDevice(c->device));
-    return corr_clear(c);
+    const unsigned long long meta[4] = {0, 0, 0, 0};
+    if (int rc = amc_totals_put(c, corr_totals(c->CR), nullptr, meta)) return rc;
+    c->CR.pos = 0;
+    return AMC_OK;
 }
 
 }  // extern "C"

@@ -7,17 +7,18 @@
 //                    (x, y, z, vx, vy, vz: 48 B per particle, 16-B loads of particle pairs), computes the bin and the seven
 //                    integers of each particle and adds them into a table in LDS (64-bit integer LDS atomics: exact and
 //                    order-free).  It stores the table as one slab row with plain stores — no global atomics.
-//   k_fields_reduce  sums the slab rows per (bin, quantity) and adds the result into the 128-bit running totals.
+//   k_sample_reduce  sums the slab rows per (bin, quantity) and adds the result into the 128-bit running totals, with carry; it
+//                    serves the sampled correlations too (amc_launch_sample_reduce) and adds nothing once the error word is set.
 // Integer sums do not depend on the order of the adds, so the totals are bitwise the same for any number of workgroups.
 #include "amc_host.h"
 #include "amc_sample_dev.h"
 
-#define AMC_FIELDS_Q 7                  // count, q1(c1..c3), q2(c1..c3)
+#define AMC_FIELDS_Q AMC_SAMPLE_Q        // count, q1(c1..c3), q2(c1..c3)
 #define AMC_FIELDS_THREADS 1024         // the 112 KiB table leaves room for one workgroup per CU: 16 waves
-#define AMC_FIELDS_PER_BLOCK 8192       // particles per workgroup below which fewer workgroups are launched
-#define AMC_FIELDS_MAX_PARTICLES (1LL << 24)
+#define AMC_SAMPLE_REDUCE_THREADS 1024
 
-// one particle into the workgroup's table; returns false if a component is out of the quantisation range
+// one particle into the workgroup's table; returns false if a component is out of the quantisation range.  (The bin is
+// amc_sample_bin's rule written out: calling it here measured + 0.5 us on the cube's 16 us sample)
 AMC_DEV bool amc_fields_particle(const amc_fields_grid_dev &G, unsigned long long *tab, unsigned int &outside, double x, double y,
                                  double z, double vx, double vy, double vz)
 {
@@ -42,7 +43,7 @@ AMC_DEV bool amc_fields_particle(const amc_fields_grid_dev &G, unsigned long lon
         c3 = vz;
     }
     if (i1 < 0 || i2 < 0 || i3 < 0) { outside++; return true; }
-    if (!(fabs(c1) < 16384.0) || !(fabs(c2) < 16384.0) || !(fabs(c3) < 16384.0)) return false;
+    if (!amc_sample_speed_ok(c1, c2, c3)) return false;
     unsigned long long *t = tab + (size_t)((i1 * G.n2 + i2) * G.n3 + i3) * AMC_FIELDS_Q;
     atomicAdd(t + 0, 1ULL);
     atomicAdd(t + 1, (unsigned long long)(long long)rint(c1 * 16777216.0));
@@ -101,56 +102,65 @@ __global__ __launch_bounds__(AMC_FIELDS_THREADS) void k_fields_accum(amc_state S
     if (threadIdx.x == 0) row[M] = outside_sum;
 }
 
-// column j of the slab (j < M: (bin, quantity) j, j == M: particles outside) summed over the rows -> running totals.
-// 64 columns per workgroup, its four waves take every fourth row.
-__global__ __launch_bounds__(256) void k_fields_reduce(const unsigned long long *slab, int rows, int M, unsigned long long *tot,
-                                                       unsigned long long *meta)
+// column j of the slab (j < tables * M: table j / M, (bin, quantity) j % M; j == tables * M: particles outside) summed over
+// the rows -> running totals at lag_a (table 0) or lag_b (table 1).  64 columns per workgroup, its sixteen waves take every
+// sixteenth row, four loads in flight each: the rows are a chain of memory round trips otherwise (measured: 10 us for 123 rows
+// with four waves).
+// meta: [0] origins, [1] samples, [2] particles outside, [3] lowest particle out of range (~0: none)
+__global__ __launch_bounds__(AMC_SAMPLE_REDUCE_THREADS) void k_sample_reduce(const unsigned long long *slab, int rows, int M, int tables, int lag_a,
+                                                                             int lag_b, int lags1, int origin, unsigned long long *tot,
+                                                                             unsigned long long *meta)
 {
-    if (meta[2] != ~0ULL) return;       // a sample with a particle out of range adds nothing (amc_fields_read reports it)
-    __shared__ unsigned long long part[4][64];
+    if (meta[3] != ~0ULL) return;       // a sample with a particle out of range adds nothing, nor does a later one (the read reports it)
+    constexpr int WAVES = AMC_SAMPLE_REDUCE_THREADS / 64;
+    __shared__ unsigned long long part[WAVES][64];
+    const int W = tables * M;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int j = blockIdx.x * 64 + lane;
     unsigned long long s = 0;           // (wraps modulo 2^64; the true sum of one sample is below 2^62 in magnitude)
-    if (j <= M)
-        for (int b = wave; b < rows; b += 4) s += slab[(size_t)b * (size_t)(M + 1) + j];
+    if (j <= W) {
+#pragma unroll 4
+        for (int b = wave; b < rows; b += WAVES) s += slab[(size_t)b * (size_t)(W + 1) + j];
+    }
     part[wave][lane] = s;
     __syncthreads();
-    if (wave != 0 || j > M) return;
-    s = part[0][lane] + part[1][lane] + part[2][lane] + part[3][lane];
-    if (j == M) {
-        meta[0] += 1;
-        meta[1] += s;
+    if (wave != 0 || j > W) return;
+    s = 0;
+#pragma unroll
+    for (int k = 0; k < WAVES; k++) s += part[k][lane];
+    if (j == W) {
+        meta[0] += (unsigned long long)origin;
+        meta[1] += 1;
+        meta[2] += s;
         return;
     }
-    const unsigned long long old = tot[2 * j], now = old + s;
-    tot[2 * j] = now;
-    tot[2 * j + 1] += (unsigned long long)(((long long)s < 0 ? -1LL : 0LL) + (now < old ? 1LL : 0LL));
+    const int t = j / M, jj = j - t * M;
+    const int g = jj / AMC_SAMPLE_Q, q = jj - g * AMC_SAMPLE_Q;
+    const size_t at = ((size_t)g * (size_t)lags1 + (size_t)(t == 0 ? lag_a : lag_b)) * AMC_SAMPLE_Q + (size_t)q;
+    amc_add128(tot[2 * at], tot[2 * at + 1], s);
+}
+
+hipError_t amc_launch_sample_reduce(amc_ctx *c, const unsigned long long *slab, int rows, int M, int tables, int lag_a, int lag_b,
+                                    int lags1, int origin, unsigned long long *tot, unsigned long long *meta)
+{
+    amc_prof_begin(c, AMC_K_FIELDS);
+    AMC_LAUNCH(c, k_sample_reduce, dim3((tables * M + 1 + 63) / 64), dim3(AMC_SAMPLE_REDUCE_THREADS), slab, rows, M, tables, lag_a, lag_b,
+               lags1, origin, tot, meta);
+    amc_prof_end(c);
+    return hipGetLastError();
 }
 
 static int fields_enqueue(amc_ctx *c)
 {
     amc_fields_ws &F = c->F;
-    const long long cnt = c->hi - c->lo;
-    if (cnt > AMC_FIELDS_MAX_PARTICLES)
-        return amc_fail(c, AMC_ERR_CAPACITY, "amc_fields: %lld particles in one sample (at most 2^24 keep the sums exact)", cnt);
-    int blocks = F.blocks_env > 0 ? F.blocks_env : (int)std::min<long long>(F.max_blocks, std::max<long long>(1, (cnt + AMC_FIELDS_PER_BLOCK - 1) / AMC_FIELDS_PER_BLOCK));
-    blocks = std::min(blocks, F.max_blocks);
-    amc_lazy L;
-    memset(&L, 0, sizeof L);
-    if (c->step.lazy_pending) { L.slot_of = c->W.slot_of; L.state = c->W.sl_state; L.moved = c->W.sl_moved; L.enabled = 1; }
-    amc_fields_grid_dev G;
-    G.kind = F.g.kind; G.n1 = F.g.n1; G.n2 = F.g.n2; G.n3 = F.g.n3; G.bins = F.bins;
-    for (int k = 0; k < 3; k++) { G.lo[k] = F.g.lo[k]; G.hi[k] = F.g.hi[k]; G.w[k] = F.w[k]; }
-    const int M = F.bins * AMC_FIELDS_Q;
+    int blocks;
+    if (int rc = amc_sample_blocks(c, "amc_fields", F.blocks_env, F.max_blocks, &blocks)) return rc;
     amc_prof_begin(c, AMC_K_FIELDS);
-    AMC_LAUNCH(c, k_fields_accum, dim3(blocks), dim3(AMC_FIELDS_THREADS), c->S, L, (long long)c->lo, (long long)c->hi, G, F.slab,
-               F.meta + 2);
+    AMC_LAUNCH(c, k_fields_accum, dim3(blocks), dim3(AMC_FIELDS_THREADS), c->S, amc_sample_lazy(c), (long long)c->lo, (long long)c->hi, F.G,
+               F.slab, F.meta + 3);
     amc_prof_end(c);
     AMC_HIP(c, hipGetLastError());
-    amc_prof_begin(c, AMC_K_FIELDS);
-    AMC_LAUNCH(c, k_fields_reduce, dim3((M + 1 + 63) / 64), dim3(256), (const unsigned long long *)F.slab, blocks, M, F.tot, F.meta);
-    amc_prof_end(c);
-    AMC_HIP(c, hipGetLastError());
+    AMC_HIP(c, amc_launch_sample_reduce(c, F.slab, blocks, F.G.bins * AMC_FIELDS_Q, 1, 0, 0, 1, 0, F.tot, F.meta));
     return AMC_OK;
 }
 
@@ -160,15 +170,8 @@ static void fields_free(amc_ctx *c)
     c->F = amc_fields_ws();
 }
 
-static int fields_clear(amc_ctx *c)
-{
-    amc_fields_ws &F = c->F;
-    const unsigned long long meta[3] = {0, 0, ~0ULL};
-    AMC_HIP(c, hipMemsetAsync(F.tot, 0, sizeof(unsigned long long) * 2 * AMC_FIELDS_Q * (size_t)F.bins, c->stream));
-    AMC_HIP(c, hipMemcpyAsync(F.meta, meta, sizeof meta, hipMemcpyHostToDevice, c->stream));
-    AMC_HIP(c, hipStreamSynchronize(c->stream));
-    return AMC_OK;
-}
+// meta: [0] unused, [1] samples, [2] particles outside, [3] the error word (the layout k_sample_reduce writes)
+static amc_totals fields_totals(const amc_fields_ws &F) { return amc_totals{F.tot, (size_t)2 * AMC_FIELDS_Q * (size_t)F.G.bins, F.meta, 4, 3}; }
 
 extern "C" {
 
@@ -188,39 +191,23 @@ int amc_fields_config(amc_ctx *c, const amc_field_grid *g)
         return AMC_OK;
     }
     if (g->struct_size != (int32_t)sizeof(amc_field_grid)) return amc_fail(c, AMC_ERR_INVALID, "amc_field_grid.struct_size mismatch (ABI)");
-    if (g->kind != AMC_FIELDS_CARTESIAN && g->kind != AMC_FIELDS_AXISYMMETRIC)
-        return amc_fail(c, AMC_ERR_INVALID, "amc_field_grid.kind %d is neither Cartesian (0) nor axisymmetric (1)", g->kind);
-    if (g->n1 < 1 || g->n2 < 1 || g->n3 < 1 || (long long)g->n1 * g->n2 * g->n3 > AMC_FIELDS_MAX_BINS)
-        return amc_fail(c, AMC_ERR_INVALID, "amc_field_grid: %d x %d x %d bins (each >= 1, at most %d in all)", g->n1, g->n2, g->n3,
-                        AMC_FIELDS_MAX_BINS);
-    if (g->kind == AMC_FIELDS_AXISYMMETRIC && (g->n3 != 1 || g->lo[0] != 0.0))
-        return amc_fail(c, AMC_ERR_INVALID, "amc_field_grid: an axisymmetric grid has n3 == 1 and r from lo[0] == 0");
-    if (g->every < 0 || g->step_offset < 0 || g->reserved != 0)
-        return amc_fail(c, AMC_ERR_INVALID, "amc_field_grid: every and step_offset must be >= 0, reserved 0");
-    const int axes = g->kind == AMC_FIELDS_CARTESIAN ? 3 : 2;
-    for (int k = 0; k < axes; k++)
-        if (!(isfinite(g->lo[k]) && isfinite(g->hi[k]) && g->lo[k] < g->hi[k]))
-            return amc_fail(c, AMC_ERR_INVALID, "amc_field_grid: axis %d needs finite bounds lo < hi", k + 1);
+    amc_fields_grid_dev G;
+    if (int rc = amc_sample_grid_check(c, "amc_field_grid", "bins", g->kind, g->n1, g->n2, g->n3, AMC_FIELDS_MAX_BINS, g->lo, g->hi, g->every,
+                                       g->step_offset, g->reserved == 0, nullptr, &G))
+        return rc;
     fields_free(c);
     amc_fields_ws &F = c->F;
     F.g = *g;
-    F.bins = g->n1 * g->n2 * g->n3;
-    const int n[3] = {g->n1, g->n2, g->n3};
-    for (int k = 0; k < 3; k++) F.w[k] = k < axes ? (g->hi[k] - g->lo[k]) / (double)n[k] : 1.0;
-    if (g->kind == AMC_FIELDS_AXISYMMETRIC) { F.g.lo[2] = 0.0; F.g.hi[2] = 1.0; }
-    F.blocks_env = getenv("AMC_FIELDS_BLOCKS") ? atoi(getenv("AMC_FIELDS_BLOCKS")) : 0;
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || cus < 1) cus = 256;
-    F.max_blocks = F.blocks_env > 0 ? F.blocks_env : cus;
-    const size_t M = (size_t)F.bins * AMC_FIELDS_Q;
-    int rc = AMC_OK;
+    F.G = G;
+    amc_sample_blocks_config(c, "AMC_FIELDS_BLOCKS", &F.blocks_env, &F.max_blocks);
+    const size_t M = (size_t)G.bins * AMC_FIELDS_Q;
     if (dalloc(c, &F.slab, (size_t)F.max_blocks * (M + 1)) != hipSuccess || dalloc(c, &F.tot, 2 * M) != hipSuccess ||
-        dalloc(c, &F.meta, 3) != hipSuccess) {
+        dalloc(c, &F.meta, 4) != hipSuccess) {
         fields_free(c);
         return amc_fail(c, AMC_ERR_HIP, "amc_fields_config: device allocation failed");
     }
     F.on = true;
-    if ((rc = fields_clear(c))) { fields_free(c); return rc; }
+    if (int rc = amc_fields_reset(c)) { fields_free(c); return rc; }
     return AMC_OK;
 }
 
@@ -238,19 +225,13 @@ int amc_fields_read(amc_ctx *c, int64_t *totals, int64_t *n_samples, int64_t *n_
     if (!c) return AMC_ERR_INVALID;
     if (!c->F.on) return amc_fail(c, AMC_ERR_STATE, "amc_fields_read before amc_fields_config");
     AMC_HIP(c, hipSetDevice(c->device));
-    amc_fields_ws &F = c->F;
-    unsigned long long meta[3];
-    {
-        amc_stage st(c);
-        if (totals) AMC_HIP(c, st.get(totals, F.tot, sizeof(unsigned long long) * 2 * AMC_FIELDS_Q * (size_t)F.bins));
-        AMC_HIP(c, st.get(meta, F.meta, sizeof meta));
-        AMC_HIP(c, st.finish());
-    }
-    if (meta[2] != ~0ULL)
+    unsigned long long meta[4], bad;
+    if (int rc = amc_totals_get(c, fields_totals(c->F), totals, meta, &bad)) return rc;
+    if (bad != ~0ULL)
         return amc_fail(c, AMC_ERR_CAPACITY, "amc_fields: particle %llu has a velocity component outside |c| < 2^14 m/s (or NaN); "
-                        "sampling stopped until amc_fields_reset", meta[2]);
-    if (n_samples) *n_samples = (int64_t)meta[0];
-    if (n_outside) *n_outside = (int64_t)meta[1];
+                        "sampling stopped until amc_fields_reset", bad);
+    if (n_samples) *n_samples = (int64_t)meta[1];
+    if (n_outside) *n_outside = (int64_t)meta[2];
     return AMC_OK;
 }
 
@@ -259,13 +240,8 @@ int amc_fields_load(amc_ctx *c, const int64_t *totals, int64_t n_samples, int64_
     if (!c || !totals || n_samples < 0 || n_outside < 0) return AMC_ERR_INVALID;
     if (!c->F.on) return amc_fail(c, AMC_ERR_STATE, "amc_fields_load before amc_fields_config");
     AMC_HIP(c, hipSetDevice(c->device));
-    amc_fields_ws &F = c->F;
-    const unsigned long long meta[3] = {(unsigned long long)n_samples, (unsigned long long)n_outside, ~0ULL};
-    AMC_HIP(c, hipMemcpyAsync(F.tot, totals, sizeof(unsigned long long) * 2 * AMC_FIELDS_Q * (size_t)F.bins, hipMemcpyHostToDevice,
-                              c->stream));
-    AMC_HIP(c, hipMemcpyAsync(F.meta, meta, sizeof meta, hipMemcpyHostToDevice, c->stream));
-    AMC_HIP(c, hipStreamSynchronize(c->stream));
-    return AMC_OK;
+    const unsigned long long meta[4] = {0, (unsigned long long)n_samples, (unsigned long long)n_outside, 0};
+    return amc_totals_put(c, fields_totals(c->F), totals, meta);
 }
 
 int amc_fields_reset(amc_ctx *c)
@@ -273,7 +249,8 @@ int amc_fields_reset(amc_ctx *c)
     if (!c) return AMC_ERR_INVALID;
     if (!c->F.on) return amc_fail(c, AMC_ERR_STATE, "amc_fields_reset before amc_fields_config");
     AMC_HIP(c, hipSetDevice(c->device));
-    return fields_clear(c);
+    const unsigned long long meta[4] = {0, 0, 0, 0};
+    return amc_totals_put(c, fields_totals(c->F), nullptr, meta);
 }
 
 }  // extern "C"

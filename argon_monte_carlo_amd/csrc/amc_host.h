@@ -109,22 +109,108 @@ static inline int amc_mg_step_idle(amc_ctx *c, const char *who)
                                       "amc_mg_local / amc_upload", who);
 }
 
+// ---- what the samplers share on the host (amc_fields.hip, amc_corr.hip, amc_surface.hip) ------------------------------------
 // a sample is due after the step that leaves the step counter at `step`
-static inline bool amc_fields_due(const amc_ctx *c, int64_t step)
-{
-    return c->F.on && c->F.g.every > 0 && (step + c->F.g.step_offset) % c->F.g.every == 0;
-}
-static inline bool amc_corr_due(const amc_ctx *c, int64_t step)
-{
-    return c->CR.on && c->CR.g.every > 0 && (step + c->CR.g.step_offset) % c->CR.g.every == 0;
-}
+static inline bool amc_cadence_due(bool on, int64_t every, int64_t step_offset, int64_t step) { return on && every > 0 && (step + step_offset) % every == 0; }
+static inline bool amc_fields_due(const amc_ctx *c, int64_t step) { return amc_cadence_due(c->F.on, c->F.g.every, c->F.g.step_offset, step); }
+static inline bool amc_corr_due(const amc_ctx *c, int64_t step) { return amc_cadence_due(c->CR.on, c->CR.g.every, c->CR.g.step_offset, step); }
 // ... for any sampler of the particle state: such a step ends with the state everybody reads (no deferred bounds pass)
 static inline bool amc_samplers_due(const amc_ctx *c, int64_t step) { return amc_fields_due(c, step) || amc_corr_due(c, step); }
-// a sampler runs on a cadence: amc_run takes its plain loop
-static inline bool amc_samplers_cadence(const amc_ctx *c) { return (c->F.on && c->F.g.every > 0) || (c->CR.on && c->CR.g.every > 0); }
+// a sampler runs on a cadence (every > 0: some step is due): amc_run takes its plain loop
+static inline bool amc_samplers_cadence(const amc_ctx *c)
+{
+    return amc_cadence_due(c->F.on, c->F.g.every, 0, 0) || amc_cadence_due(c->CR.on, c->CR.g.every, 0, 0);
+}
 // the cadence hook after a completed step
 static inline int amc_samplers_step(amc_ctx *c)
 {
     if (int rc = amc_fields_step(c)) return rc;
     return c->CR.on ? amc_corr_step(c) : AMC_OK;
+}
+
+// The grid fields amc_field_grid and amc_corr_grid have in common, validated (`who`: the struct's name, `unit`: what it calls its
+// bins; reserved0: its reserved fields are zero; own_fault: a fault in the struct's other fields, reported at its place in the
+// order, behind the bin count, or nullptr) and turned into the grid the kernels take, widths included.
+static inline int amc_sample_grid_check(amc_ctx *c, const char *who, const char *unit, int kind, int n1, int n2, int n3, int max_bins,
+                                 const double *lo, const double *hi, int64_t every, int64_t step_offset, bool reserved0,
+                                 const char *own_fault, amc_fields_grid_dev *G)
+{
+    if (kind != AMC_FIELDS_CARTESIAN && kind != AMC_FIELDS_AXISYMMETRIC)
+        return amc_fail(c, AMC_ERR_INVALID, "%s.kind %d is neither Cartesian (0) nor axisymmetric (1)", who, kind);
+    if (n1 < 1 || n2 < 1 || n3 < 1 || (long long)n1 * n2 * n3 > max_bins)
+        return amc_fail(c, AMC_ERR_INVALID, "%s: %d x %d x %d %s (each >= 1, at most %d in all)", who, n1, n2, n3, unit, max_bins);
+    if (own_fault) return amc_fail(c, AMC_ERR_INVALID, "%s: %s", who, own_fault);
+    if (kind == AMC_FIELDS_AXISYMMETRIC && (n3 != 1 || lo[0] != 0.0))
+        return amc_fail(c, AMC_ERR_INVALID, "%s: an axisymmetric grid has n3 == 1 and r from lo[0] == 0", who);
+    if (every < 0 || step_offset < 0 || !reserved0)
+        return amc_fail(c, AMC_ERR_INVALID, "%s: every and step_offset must be >= 0, reserved 0", who);
+    const int axes = kind == AMC_FIELDS_CARTESIAN ? 3 : 2;
+    for (int k = 0; k < axes; k++)
+        if (!(isfinite(lo[k]) && isfinite(hi[k]) && lo[k] < hi[k]))
+            return amc_fail(c, AMC_ERR_INVALID, "%s: axis %d needs finite bounds lo < hi", who, k + 1);
+    G->kind = kind; G->n1 = n1; G->n2 = n2; G->n3 = n3; G->bins = n1 * n2 * n3;
+    const int n[3] = {n1, n2, n3};
+    for (int k = 0; k < 3; k++) {       // (the unused third axis of an axisymmetric grid: [0, 1], one bin)
+        G->lo[k] = k < axes ? lo[k] : 0.0;
+        G->hi[k] = k < axes ? hi[k] : 1.0;
+        G->w[k] = k < axes ? (hi[k] - lo[k]) / (double)n[k] : 1.0;
+    }
+    return AMC_OK;
+}
+
+// slab rows a sampler allocates: its environment knob `env` if set (blocks_env, else 0), else one workgroup per CU
+static inline void amc_sample_blocks_config(amc_ctx *c, const char *env, int *blocks_env, int *max_blocks)
+{
+    *blocks_env = getenv(env) ? atoi(getenv(env)) : 0;
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || cus < 1) cus = 256;
+    *max_blocks = *blocks_env > 0 ? *blocks_env : cus;
+}
+// workgroups of one sample of the context's index range: the knob, else one per 8,192 particles, at most max_blocks
+#define AMC_SAMPLE_PER_BLOCK 8192
+#define AMC_SAMPLE_MAX_PARTICLES (1LL << 24)
+static inline int amc_sample_blocks(amc_ctx *c, const char *who, int blocks_env, int max_blocks, int *blocks)
+{
+    const long long cnt = c->hi - c->lo;
+    if (cnt > AMC_SAMPLE_MAX_PARTICLES)
+        return amc_fail(c, AMC_ERR_CAPACITY, "%s: %lld particles in one sample (at most 2^24 keep the sums exact)", who, cnt);
+    const long long by_count = std::max<long long>(1, (cnt + AMC_SAMPLE_PER_BLOCK - 1) / AMC_SAMPLE_PER_BLOCK);
+    *blocks = (int)std::min<long long>(max_blocks, blocks_env > 0 ? blocks_env : by_count);
+    return AMC_OK;
+}
+
+// the kernels' view of the last sweep's deferred results, if a step left any pending
+static inline amc_lazy amc_sample_lazy(const amc_ctx *c)
+{
+    amc_lazy L = {};
+    if (c->step.lazy_pending) { L.slot_of = c->W.slot_of; L.state = c->W.sl_state; L.moved = c->W.sl_moved; L.enabled = 1; }
+    return L;
+}
+
+// A sampler's running totals on the device: `words` 64-bit words of (low, high) pairs and nmeta counters, of which
+// meta[bad_slot] is the error word — the lowest particle out of the quantisers' range, ~0: none.
+#define AMC_TOTALS_MAX_META 8
+struct amc_totals { unsigned long long *tot; size_t words; unsigned long long *meta; int nmeta, bad_slot; };
+// totals (zero when nullptr) and counters in, the error word cleared; synchronises
+static inline int amc_totals_put(amc_ctx *c, const amc_totals &T, const int64_t *totals, const unsigned long long *meta_init)
+{
+    unsigned long long meta[AMC_TOTALS_MAX_META];
+    if (T.nmeta > AMC_TOTALS_MAX_META) return amc_fail(c, AMC_ERR_INVALID, "amc_totals_put: %d counters (at most %d)", T.nmeta, AMC_TOTALS_MAX_META);
+    memcpy(meta, meta_init, sizeof(unsigned long long) * (size_t)T.nmeta);
+    meta[T.bad_slot] = ~0ULL;
+    if (totals) AMC_HIP(c, hipMemcpyAsync(T.tot, totals, sizeof(unsigned long long) * T.words, hipMemcpyHostToDevice, c->stream));
+    else AMC_HIP(c, hipMemsetAsync(T.tot, 0, sizeof(unsigned long long) * T.words, c->stream));
+    AMC_HIP(c, hipMemcpyAsync(T.meta, meta, sizeof(unsigned long long) * (size_t)T.nmeta, hipMemcpyHostToDevice, c->stream));
+    AMC_HIP(c, hipStreamSynchronize(c->stream));
+    return AMC_OK;
+}
+// totals (unless nullptr) and counters out through the staging buffer; synchronises.  *bad: the error word (~0: none)
+static inline int amc_totals_get(amc_ctx *c, const amc_totals &T, int64_t *totals, unsigned long long *meta_out, unsigned long long *bad)
+{
+    amc_stage st(c);
+    if (totals) AMC_HIP(c, st.get(totals, T.tot, sizeof(unsigned long long) * T.words));
+    AMC_HIP(c, st.get(meta_out, T.meta, sizeof(unsigned long long) * (size_t)T.nmeta));
+    AMC_HIP(c, st.finish());
+    *bad = meta_out[T.bad_slot];
+    return AMC_OK;
 }

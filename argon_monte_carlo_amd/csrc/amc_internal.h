@@ -223,17 +223,22 @@ struct amc_temp_dev_ws {
     std::vector<unsigned char> h_ok[7];
 };
 
+// the bin grid of a sampler of the particle state as its kernels take it, built once at configuration (amc_sample_grid_check)
+struct amc_fields_grid_dev {
+    int kind, n1, n2, n3, bins; // bins = n1 * n2 * n3
+    double lo[3], hi[3], w[3];  // w: bin widths (hi - lo) / n, fp64 like NumPy
+};
+
 // sampled fields (amc_fields.hip): the grid, the per-workgroup slab rows of one sample and the 128-bit running totals
 struct amc_fields_ws {
     bool on;
     amc_field_grid g;
-    int bins;                   // n1 * n2 * n3
-    double w[3];                // bin widths (hi - lo) / n, fp64 like NumPy
+    amc_fields_grid_dev G;
     int max_blocks;             // slab rows allocated (AMC_FIELDS_BLOCKS, else the number of CUs)
     int blocks_env;             // AMC_FIELDS_BLOCKS at configuration (0: by particle count)
     unsigned long long *slab;   // [max_blocks][bins * 7 + 1] one sample's sums per workgroup (+ particles outside)
     unsigned long long *tot;    // [bins][7][2] running totals, (low, high) words
-    unsigned long long *meta;   // [0] samples, [1] particles outside, [2] lowest particle index out of range (~0: none)
+    unsigned long long *meta;   // [0] unused, [1] samples, [2] particles outside, [3] lowest particle index out of range (~0: none)
 };
 
 // sampled surfaces (amc_surface.hip): the grid, the 128-bit running totals per (case, bin, quantity) and the counters
@@ -254,8 +259,7 @@ struct amc_surface_ws {
 struct amc_corr_ws {
     bool on;
     amc_corr_grid g;
-    int groups;                 // n1 * n2 * n3
-    double w[3];                // group widths (hi - lo) / n, fp64 like NumPy
+    amc_fields_grid_dev G;      // the group grid (bins: the groups)
     int64_t pos;                // window position: the lag of the next sample (0: it is an origin)
     int max_blocks;             // slab rows allocated (AMC_CORR_BLOCKS, else the number of CUs)
     int blocks_env;             // AMC_CORR_BLOCKS at configuration (0: by particle count)
@@ -547,6 +551,10 @@ hipError_t amc_launch_surface_device(amc_ctx *c);
 hipError_t amc_launch_surface_case(amc_ctx *c, int case_id, int n);
 int amc_surface_park(amc_ctx *c, int case_id, int n);             // (allocates park_bin at the first call: an amc_status)
 hipError_t amc_launch_surface_finish(amc_ctx *c, int case_id, int n);
+// the samplers' reduce (amc_fields.hip): `rows` slab rows of `tables` tables of M sums (+ the particles outside) into the 128-bit
+// totals [M / 7][lags1][7][2] at lag_a (table 0) and lag_b (table 1), counters in meta ([0] += origin, [1] += 1, [2] += outside)
+hipError_t amc_launch_sample_reduce(amc_ctx *c, const unsigned long long *slab, int rows, int M, int tables, int lag_a, int lag_b,
+                                    int lags1, int origin, unsigned long long *tot, unsigned long long *meta);
 // the exchange kernels (amc_exchange.hip): they read c->MG and change nothing in it.  clear_counts: zero the send block's bank
 // counters in front of the pack kernel
 hipError_t amc_launch_kin_pack(amc_ctx *c, int mode, bool clear_counts);

@@ -10,6 +10,7 @@
 // step's own kernels is involved: the launch sits behind the kernel that completes the records and in front of whatever
 // clears or overwrites them (stream order).
 #include "amc_host.h"
+#include "amc_sample_dev.h"
 
 #define AMC_SURFACE_Q 3                 // count, q(dp_z), q(dE)
 #define AMC_SURFACE_THREADS 1024
@@ -42,10 +43,8 @@ struct amc_surface_src {
 // bin of a coordinate: nbins = outside (below lo, beyond hi, NaN); u == hi lands in the last bin
 AMC_DEV int amc_surface_bin(double u, double lo, double hi, double w, int n)
 {
-    const double f = floor((u - lo) / w);
-    if (!(f >= 0.0)) return n;
-    if (f >= (double)n) return (f == (double)n && u <= hi) ? n - 1 : n;
-    return (int)f;
+    const int b = amc_fields_axis(u, lo, hi, w, n);
+    return b < 0 ? n : b;
 }
 
 // The kernel is a chain of memory round trips for a few hundred records, not bandwidth: whatever does not depend on anything
@@ -127,9 +126,7 @@ __global__ __launch_bounds__(AMC_SURFACE_THREADS) void k_surface_accum(amc_surfa
         const unsigned long long a = tab[j];        // (wraps modulo 2^64; the true sum of one launch is at most 2^62 in magnitude)
         if (!a) continue;
         ulonglong2 v = t0[i];
-        const unsigned long long now = v.x + a;
-        v.y += (unsigned long long)(((long long)a < 0 ? -1LL : 0LL) + (now < v.x ? 1LL : 0LL));
-        v.x = now;
+        amc_add128(v.x, v.y, a);
         ((ulonglong2 *)tot)[j] = v;
     }
 }
@@ -201,9 +198,10 @@ hipError_t amc_launch_surface_finish(amc_ctx *c, int case_id, int n)
     return surface_launch(c, R, AMC_SURFACE_FINISH);
 }
 
-static size_t surface_words(const amc_surface_ws &F)
+// meta: [0] the error word, [1 + s] failed contact solves of case 3 + s
+static amc_totals surface_totals(const amc_surface_ws &F)
 {
-    return (size_t)2 * AMC_SURFACE_Q * AMC_SURFACE_CASES * (size_t)(F.g.nbins + 1);
+    return amc_totals{F.tot, (size_t)2 * AMC_SURFACE_Q * AMC_SURFACE_CASES * (size_t)(F.g.nbins + 1), F.meta, 1 + AMC_SURFACE_CASES, 0};
 }
 
 static void surface_free(amc_ctx *c)
@@ -216,12 +214,9 @@ static void surface_free(amc_ctx *c)
 static int surface_put(amc_ctx *c, const int64_t *totals, const int64_t *n_failed)
 {
     amc_surface_ws &F = c->SF;
-    unsigned long long meta[1 + AMC_SURFACE_CASES] = {~0ULL};
+    unsigned long long meta[1 + AMC_SURFACE_CASES] = {0};
     for (int s = 0; s < AMC_SURFACE_CASES; s++) meta[1 + s] = n_failed ? (unsigned long long)n_failed[s] : 0ULL;
-    if (totals) AMC_HIP(c, hipMemcpyAsync(F.tot, totals, sizeof(unsigned long long) * surface_words(F), hipMemcpyHostToDevice, c->stream));
-    else AMC_HIP(c, hipMemsetAsync(F.tot, 0, sizeof(unsigned long long) * surface_words(F), c->stream));
-    AMC_HIP(c, hipMemcpyAsync(F.meta, meta, sizeof meta, hipMemcpyHostToDevice, c->stream));
-    AMC_HIP(c, hipStreamSynchronize(c->stream));
+    if (int rc = amc_totals_put(c, surface_totals(F), totals, meta)) return rc;
     F.lost = false;
     F.park_case = 0;            // (a case parked before the totals were replaced finishes without adding to them)
     return AMC_OK;
@@ -251,7 +246,7 @@ int amc_surface_config(amc_ctx *c, const amc_surface_grid *g)
     amc_surface_ws &F = c->SF;
     F.g = *g;
     for (int s = 0; s < AMC_SURFACE_CASES; s++) F.w[s] = (g->hi[s] - g->lo[s]) / (double)g->nbins;
-    if (dalloc(c, &F.tot, surface_words(F)) != hipSuccess || dalloc(c, &F.meta, 1 + AMC_SURFACE_CASES) != hipSuccess) {
+    if (dalloc(c, &F.tot, surface_totals(F).words) != hipSuccess || dalloc(c, &F.meta, 1 + AMC_SURFACE_CASES) != hipSuccess) {
         surface_free(c);
         return amc_fail(c, AMC_ERR_HIP, "amc_surface_config: device allocation failed");
     }
@@ -269,16 +264,11 @@ int amc_surface_read(amc_ctx *c, int64_t *totals, int64_t *n_failed, int64_t *n_
         return amc_fail(c, AMC_ERR_STATE, "amc_surface_read: a step overflowed its hit records or work buffers (AMC_ERR_CAPACITY), hits are "
                         "missing from the totals; amc_surface_reset, amc_surface_load or amc_surface_config start again");
     AMC_HIP(c, hipSetDevice(c->device));
-    unsigned long long meta[1 + AMC_SURFACE_CASES];
-    {
-        amc_stage st(c);
-        if (totals) AMC_HIP(c, st.get(totals, F.tot, sizeof(unsigned long long) * surface_words(F)));
-        AMC_HIP(c, st.get(meta, F.meta, sizeof meta));
-        AMC_HIP(c, st.finish());
-    }
-    if (meta[0] != ~0ULL)
+    unsigned long long meta[1 + AMC_SURFACE_CASES], bad;
+    if (int rc = amc_totals_get(c, surface_totals(F), totals, meta, &bad)) return rc;
+    if (bad != ~0ULL)
         return amc_fail(c, AMC_ERR_CAPACITY, "amc_surface: the hit of particle %llu is outside |dpz| < 2^-70 kg m/s, |dE| < 2^-57 J (or NaN); "
-                        "sampling stopped until amc_surface_reset", meta[0]);
+                        "sampling stopped until amc_surface_reset", bad);
     for (int s = 0; s < AMC_SURFACE_CASES && n_failed; s++) n_failed[s] = (int64_t)meta[1 + s];
     if (n_steps) *n_steps = F.n_steps;
     return AMC_OK;

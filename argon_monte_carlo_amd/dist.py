@@ -222,42 +222,52 @@ class ShardedSimulation:
     def fields_reset(self):
         self.engine.fields_reset()
 
+    def _read_summed(self, read, shapes, n_counters, describe, own_if_all_failed=False):
+        """``read()`` of this rank -> (its 128-bit word arrays, its counters to sum, whatever else the caller wants back), the
+        first two summed over the ranks (``totals.sum_over_ranks``).  ``shapes``: the arrays' shapes, for the zeros a rank whose
+        read failed takes part with; None: the sampler is not configured, the error is raised."""
+        from ._lib import ArgonMCError
+        from .totals import sum_over_ranks
+        err = None
+        try:
+            arrays, counters, rest = read()
+        except ArgonMCError as e:
+            if shapes is None:
+                raise
+            err, rest = e, None
+            arrays, counters = [np.zeros(s, dtype=np.int64) for s in shapes], [0] * n_counters
+        arrays, counters = sum_over_ranks(self.comm, self.world, self.rank, err, arrays, counters, describe, own_if_all_failed)
+        return arrays, counters, rest
+
+    @staticmethod
+    def _describe(read, capacity=None):
+        """the error for the first failing rank r: status s > 0 is particle s - 1 (named where ``capacity`` has the text), else the code"""
+        from ._abi import AMC_ERR_CAPACITY
+        from ._lib import ArgonMCError
+
+        def describe(r, s):
+            if s > 0 and capacity:
+                return ArgonMCError(AMC_ERR_CAPACITY, capacity.format(p=s - 1, r=r))
+            return ArgonMCError(AMC_ERR_CAPACITY if s > 0 else s, f"{read} failed on rank {r}")
+        return describe
+
     def fields(self):
         """Simulation.fields() of the whole system (a collective: every rank calls it).  The ranks' 128-bit totals are summed
-        as 32-bit limbs in int64 all-reduces — exact, never through floats — so the integers equal a single engine's.
+        as 32-bit limbs in one int64 all-reduce — exact, never through floats — so the integers equal a single engine's.
         A read that fails on one rank (a particle out of the sampler's range lives on one shard) fails on every rank, from
         this same call: the failing rank still takes part in the all-reduce, whose first ``world`` entries carry each rank's
         status — 0, the bad particle's index + 1, or the (negative) error code of any other failure."""
         from . import fields as FL
-        if self.world == 1:
+        g = self.engine.field_grid
+
+        def read():
             tot, ns, no = self.engine.fields_read()
-            return FL.derive(self.engine.field_grid, tot, ns, no, float(self.params.argon_mass), FL.boltzmann_constant(self.params))
-        import re
-        from ._abi import AMC_ERR_CAPACITY
-        from ._lib import ArgonMCError
-        status = [0] * self.world
-        err = None
-        try:
-            tot, ns, no = self.engine.fields_read()
-        except ArgonMCError as e:
-            if self.engine.field_grid is None:      # (not configured: there is no shape to take part with)
-                raise
-            err = e
-            tot, ns, no = np.zeros((FL.grid_bins(self.engine.field_grid), 7, 2), dtype=np.int64), 0, 0
-            m = re.search(r"particle (\d+) ", str(e))
-            status[self.rank] = int(m.group(1)) + 1 if (m and e.code == AMC_ERR_CAPACITY) else min(int(e.code), -1)
-        limbs = FL.words_to_limbs(tot)
-        flat = self.comm.allreduce_sum_ints(status + [int(v) for v in limbs.ravel()] + [int(no)])
-        failed = [(r, s) for r, s in enumerate(flat[:self.world]) if s != 0]
-        if failed:
-            r, s = failed[0]
-            if s > 0:
-                raise ArgonMCError(AMC_ERR_CAPACITY, f"amc_fields: particle {s - 1} (rank {r}) has a velocity component outside "
-                                                     "|c| < 2^14 m/s (or NaN); sampling stopped until fields_reset") from err
-            raise ArgonMCError(s, f"fields_read failed on rank {r}") from err
-        tot = FL.limbs_to_words(np.array(flat[self.world:-1], dtype=np.int64).reshape(limbs.shape))
-        no = flat[-1]
-        return FL.derive(self.engine.field_grid, tot, ns, no, float(self.params.argon_mass), FL.boltzmann_constant(self.params))
+            return [tot], [no], ns
+        (tot,), (no,), ns = self._read_summed(
+            read, None if g is None else [(FL.grid_bins(g), 7, 2)], 1,
+            self._describe("fields_read", "amc_fields: particle {p} (rank {r}) has a velocity component outside |c| < 2^14 m/s (or NaN); "
+                                          "sampling stopped until fields_reset"))
+        return FL.derive(g, tot, ns, no, float(self.params.argon_mass), FL.boltzmann_constant(self.params))
 
     # ---- sampled correlations (correlations.py): every rank samples its own index range, the totals are summed exactly ------
     def enable_correlations(self, grid=None, every=0, n_lags=None):
@@ -277,34 +287,16 @@ class ShardedSimulation:
         status in its first ``world`` entries: a read that fails on one rank fails on every rank, from this same call.
         ``dt``: the time step for the lag times (None: the simulation's own where it has one, else 1.0)."""
         from . import correlations as CO
-        import re
-        from ._abi import AMC_ERR_CAPACITY
-        from ._lib import ArgonMCError
         g = self.engine.corr_grid
-        status, err = [0] * self.world, None
-        try:
-            tot, counters = self.engine.corr_read()
-        except ArgonMCError as e:
-            if g is None:                           # (not configured: there is no shape to take part with)
-                raise
-            err = e
-            tot, counters = np.zeros(CO.totals_shape(g), dtype=np.int64), (0, 0, 0, 0)
-            m = re.search(r"particle (\d+) ", str(e))
-            status[self.rank] = int(m.group(1)) + 1 if (m and e.code == AMC_ERR_CAPACITY) else min(int(e.code), -1)
-        if self.world > 1:
-            limbs = CO.words_to_limbs(tot)
-            flat = self.comm.allreduce_sum_ints(status + [int(v) for v in limbs.ravel()] + [int(counters[2])])
-            failed = [(r, s) for r, s in enumerate(flat[:self.world]) if s != 0]
-            if failed:
-                r, s = failed[0]
-                if s > 0:
-                    raise ArgonMCError(AMC_ERR_CAPACITY, f"amc_corr: particle {s - 1} (rank {r}) is outside the quantisers' range; "
-                                                         "sampling stopped until correlations_reset") from err
-                raise ArgonMCError(s, f"corr_read failed on rank {r}") from err
-            tot = CO.limbs_to_words(np.array(flat[self.world:-1], dtype=np.int64).reshape(limbs.shape))
-            counters = (counters[0], counters[1], flat[-1], counters[3])
-        elif err is not None:
-            raise err
+
+        def read():
+            tot, c = self.engine.corr_read()
+            return [tot], [c[2]], c
+        (tot,), (no,), c = self._read_summed(
+            read, None if g is None else [CO.totals_shape(g)], 1,
+            self._describe("corr_read", "amc_corr: particle {p} (rank {r}) is outside the quantisers' range; "
+                                        "sampling stopped until correlations_reset"))
+        counters = (c[0], c[1], no, c[3])
         if every is None:
             every = int(g.every) if int(g.every) > 0 else 1
         if dt is None:
@@ -570,36 +562,12 @@ class ShardedTemperatureSimulation(ShardedSimulation):
         """``TemperatureSimulation.surface()`` of the whole system (a collective: every rank calls it).  The ranks' 128-bit
         totals and ``n_failed`` are summed as 32-bit limbs in one int64 all-reduce, whose first ``world`` entries carry each
         rank's status as in ``ShardedSimulation.fields``: a read that fails on one rank fails on every rank, from this call."""
-        from . import fields as FL, surface as SU
-        from ._lib import ArgonMCError
-        status, err = [0] * self.world, None
+        from . import surface as SU
         g = self.engine.surface_grid
-        try:
+
+        def read():
             tot, nf, ns = self.engine.surface_read()
-        except ArgonMCError as e:
-            if g is None:                           # (not configured: there is no shape to take part with)
-                raise
-            err = e
-            tot, nf, ns = np.zeros((7, int(g.nbins) + 1, 3, 2), dtype=np.int64), np.zeros(7, dtype=np.int64), 0
-            status[self.rank] = min(int(e.code), -1)
-        tot, nf = sum_surface_limbs(self.comm, self.world, status, tot, nf, err)
-        return SU.derive(tot, ns, self.dt, g, self.params, n_failed=nf)
-
-
-def sum_surface_limbs(comm, world, status, tot, nf, err=None):
-    """(totals, n_failed) summed over the ranks: the 128-bit words as four 32-bit limbs each, in one ``allreduce_sum_ints``
-    together with every rank's status (0, or its negative error code) — exact, never through floats."""
-    from . import fields as FL
-    from ._lib import ArgonMCError
-    limbs = FL.words_to_limbs(tot)
-    flat = list(status) + [int(v) for v in limbs.ravel()] + [int(v) for v in np.asarray(nf).ravel()]
-    if world > 1 or not getattr(comm, "shortcut", True):
-        flat = comm.allreduce_sum_ints(flat)
-    failed = [(r, c) for r, c in enumerate(flat[:world]) if c != 0]
-    if failed:
-        if err is not None and len(failed) == world:
-            raise err
-        r, c = failed[0]
-        raise ArgonMCError(c, f"surface_read failed on rank {r}") from err
-    k = world + limbs.size
-    return FL.limbs_to_words(np.array(flat[world:k], dtype=np.int64).reshape(limbs.shape)), np.array(flat[k:], dtype=np.int64)
+            return [tot], [int(v) for v in nf], ns
+        (tot,), nf, ns = self._read_summed(read, None if g is None else [(7, int(g.nbins) + 1, 3, 2)], 7, self._describe("surface_read"),
+                                           own_if_all_failed=True)
+        return SU.derive(tot, ns, self.dt, g, self.params, n_failed=np.array(nf, dtype=np.int64))

@@ -14,6 +14,7 @@ import numpy as np
 from ._abi import (AMC_FIELDS_AXISYMMETRIC, AMC_FIELDS_CARTESIAN, AMC_FIELDS_MAX_BINS, AMC_GEOM_CUBE,
                    AMC_GEOM_PORE_ENERGISED, AmcFieldGrid)
 from . import params as PR
+from .totals import ints_to_words, limbs_to_words, words_to_ints, words_to_limbs  # noqa: F401  (the 128-bit totals: totals.py)
 
 Q1_SCALE = 2 ** 24
 Q2_SCALE = 2 ** 10
@@ -67,7 +68,7 @@ def make_grid(kind, n, lo, hi, every=0, step_offset=0):
 
 
 def copy_grid(g, every=None, step_offset=None):
-    out = AmcFieldGrid.from_buffer_copy(g)
+    out = type(g).from_buffer_copy(g)         # (an AmcFieldGrid, or the AmcCorrGrid of correlations.py)
     if every is not None:
         out.every = int(every)
     if step_offset is not None:
@@ -130,53 +131,6 @@ def bin_volumes(g):
     r = edges(g)[0]
     ring = np.array([math.pi * (r[i + 1] * r[i + 1] - r[i] * r[i]) * w[1] for i in range(g.n1)])
     return np.repeat(ring, g.n2)
-
-
-# ---- 128-bit totals --------------------------------------------------------------------------------------------------
-def words_to_ints(words):
-    """int64[..., 2] (low, high) words -> object array of exact Python ints (signed 128-bit values)."""
-    words = np.asarray(words, dtype=np.int64)
-    lo = words[..., 0].astype(np.uint64)
-    hi = words[..., 1]
-    out = np.empty(lo.shape, dtype=object)
-    for idx in np.ndindex(lo.shape):
-        out[idx] = (int(hi[idx]) << 64) + int(lo[idx])
-    return out
-
-
-def ints_to_words(values):
-    """The inverse of ``words_to_ints``: signed 128-bit Python ints -> int64[..., 2] (low, high)."""
-    values = np.asarray(values, dtype=object)
-    out = np.empty(values.shape + (2,), dtype=np.int64)
-    for idx in np.ndindex(values.shape):
-        v = int(values[idx])
-        if not -(1 << 127) <= v < (1 << 127):
-            raise OverflowError("total outside the signed 128-bit range")
-        u = v & ((1 << 128) - 1)
-        lo, hi = u & ((1 << 64) - 1), u >> 64
-        out[idx + (0,)] = lo - (1 << 64) if lo >= (1 << 63) else lo
-        out[idx + (1,)] = hi - (1 << 64) if hi >= (1 << 63) else hi
-    return out
-
-
-def words_to_limbs(words):
-    """int64[..., 2] words -> int64[..., 4] 32-bit limbs (the top one signed): a sum of limbs over ranks, recombined by
-    ``limbs_to_words``, is the exact sum of the 128-bit values (no float, no overflow below 2^31 ranks)."""
-    words = np.asarray(words, dtype=np.int64)
-    lo = words[..., 0].astype(np.uint64)
-    hi = words[..., 1]
-    m = np.uint64(0xFFFFFFFF)
-    return np.stack([(lo & m).astype(np.int64), (lo >> np.uint64(32)).astype(np.int64),
-                     (hi.astype(np.uint64) & m).astype(np.int64), hi >> 32], axis=-1)
-
-
-def limbs_to_words(limbs):
-    limbs = np.asarray(limbs, dtype=np.int64)
-    vals = np.empty(limbs.shape[:-1], dtype=object)
-    for idx in np.ndindex(vals.shape):
-        l0, l1, l2, l3 = (int(v) for v in limbs[idx])
-        vals[idx] = l0 + (l1 << 32) + (l2 << 64) + (l3 << 96)
-    return ints_to_words(vals)
 
 
 # ---- derived fields --------------------------------------------------------------------------------------------------

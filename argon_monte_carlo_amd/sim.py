@@ -21,6 +21,12 @@ _NAMES = {"x_vals": "x", "y_vals": "y", "z_vals": "z", "x_velocities": "vx", "y_
           "dist_y_since_collision": "dy", "dist_z_since_collision": "dz", "full_path_traveled": "flag"}
 
 
+def _write_npz(path, d):
+    """A sampler's dict as an .npz (edges as edges_1, edges_2[, edges_3])."""
+    e = d.pop("edges")
+    np.savez(path, **d, **{f"edges_{k + 1}": v for k, v in enumerate(e)})
+
+
 class Simulation:
     """``kind``: "cube" (Open_Air_Cube_MC.py), "pore" (Open_Air_Pore_MC.py) — see params.py for the constants."""
 
@@ -154,9 +160,7 @@ class Simulation:
 
     def write_fields(self, path):
         """The dict of ``fields()`` as an .npz (edges as edges_1, edges_2[, edges_3])."""
-        f = self.fields()
-        e = f.pop("edges")
-        np.savez(path, **f, **{f"edges_{k + 1}": v for k, v in enumerate(e)})
+        _write_npz(path, self.fields())
 
     def _fields_checkpoint(self):
         if self.engine.field_grid is None:
@@ -204,9 +208,7 @@ class Simulation:
 
     def write_correlations(self, path):
         """The dict of ``correlations()`` as an .npz (edges as edges_1, edges_2[, edges_3])."""
-        f = self.correlations()
-        e = f.pop("edges")
-        np.savez(path, **f, **{f"edges_{k + 1}": v for k, v in enumerate(e)})
+        _write_npz(path, self.correlations())
 
     def _corr_checkpoint(self):
         if self.engine.corr_grid is None:

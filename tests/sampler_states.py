@@ -1,0 +1,14 @@
+"""States for the samplers' GPU tests (tests/test_gpu_fields.py, tests/test_gpu_corr.py): a few thousand pore particles drifting
+freely, and index ranges that begin or end inside an aligned pair of particles."""
+from argon_monte_carlo_amd import ic as IC
+from argon_monte_carlo_amd import params as PR
+
+ODD_N = 4_099
+ODD_SHARDS = [(1_001, 3_000), (1_000, 3_001), (1_001, 3_001)]      # lo odd / hi odd: the first / the last particle has no partner
+
+
+def drifting_states(n, samples, seed=17):
+    """``samples`` states of n pore particles, each the one before moved on by dt * v: (params, [(x, y, z, vx, vy, vz)])."""
+    p, c = PR.pore_params(n=n)
+    x, y, z, vx, vy, vz = IC.pore_ic(p, c, seed)
+    return p, [(x + k * c["dt"] * vx, y + k * c["dt"] * vy, z + k * c["dt"] * vz, vx, vy, vz) for k in range(samples)]

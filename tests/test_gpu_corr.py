@@ -12,6 +12,7 @@ from argon_monte_carlo_amd import fields as FL
 from argon_monte_carlo_amd import ic as IC
 from argon_monte_carlo_amd import params as PR
 from tests import corr_ref as REF
+from tests.sampler_states import ODD_N, ODD_SHARDS, drifting_states
 
 pytestmark = pytest.mark.gpu
 
@@ -369,3 +370,62 @@ def test_maxwell_initial_condition_reads_back_the_velocity_variance():
         assert abs(f["vacf"][0, 0, k] - a2) < 4 * sigma, (k, f["vacf"][0, 0, k], a2, sigma)
         assert f["msd"][0, 0, k] == 0.0
     sim.close()
+
+
+# ---- 12. the walk's odd ends, in all three modes of the accumulate kernel --------------------------------------------------------
+@pytest.mark.parametrize("lo,hi", ODD_SHARDS)
+def test_index_range_with_odd_ends_equals_reference(lo, hi):
+    """An index range that begins or ends inside an aligned pair (lo odd / hi odd: the first / the last particle has no partner),
+    n_lags = 2 and four samples: an origin, a lag, the lag-and-origin pass, a lag.  The origin arrays outside [lo, hi) stay zero."""
+    from argon_monte_carlo_amd.engine import ShardEngine
+    p, states = drifting_states(ODD_N, 4)
+    eng = ShardEngine(p, lo, hi)
+    eng.corr_config(CO.default_grid(p, n_lags=2))
+    win = REF.Window(eng.corr_grid)
+    for st in states:
+        eng.upload(*st)
+        eng.corr_sample()
+        win.add(tuple(a[lo:hi].copy() for a in st))
+    tot = CO.words_to_ints(_check(eng, win))
+    assert win.counters() == (2, 4, win.n_outside, 2)
+    assert all(any(int(v) != 0 for v in tot[:, lag, 1]) for lag in (1, 2))           # both lags saw displacements
+    origin = eng.corr_origin()
+    assert all(np.array_equal(o, a[lo:hi]) for o, a in zip(origin, states[2]))      # the origin stored by the third sample
+    eng.close()
+
+
+# ---- 13. the carry-add through the correlations' loads ------------------------------------------------------------------------------
+def test_corr_load_carry_and_borrow():
+    """128-bit totals: loaded low words of 2^64 - 1 carry into the high word under a positive sum, low words of 0 borrow from it
+    under a negative one (velocity products against an origin of the opposite sign); the result equals the exact Python-int sum.
+    Three samples with n_lags = 2: every mode of the accumulate kernel feeds the carry-add."""
+    from argon_monte_carlo_amd.engine import Engine
+    n = 40
+    k = np.arange(n)
+    g = CO.make_grid("cartesian", (2, 1, 1), (-1.0e-7, -1.0e-7, 0.0), (1.0e-7, 1.0e-7, 1.0e-6), n_lags=2)
+    x, y, z = np.where(k % 2 == 0, -5.0e-8, 5.0e-8), np.zeros(n), np.full(n, 5.0e-7)
+    vx, vy, vz = 300.0 + k, 120.5 + 0.25 * k, 77.0 + k
+    states = [(x, y, z, vx, vy, vz), (x + 1e-10, y - 2e-10, z + 3e-10, -vx, -vy, -vz), (x + 2e-10, y - 4e-10, z + 6e-10, -vx, -vy, -vz)]
+    win = REF.Window(g)
+    for st in states:
+        win.add(st)
+    sums = win.totals
+    assert win.n_outside == 0 and all(int(v) < 0 for v in sums[:, 1:, 4:].ravel()) and all(int(v) > 0 for v in sums[:, 1:, :4].ravel())
+    loaded = np.empty(sums.shape, dtype=object)
+    for idx in np.ndindex(sums.shape):
+        loaded[idx] = (1 << 64) - 1 if sums[idx] > 0 else 0
+    loaded[0, 0, 0] = (5 << 64) - 1                                  # high word already non-zero
+    lw, ew = CO.ints_to_words(loaded), CO.ints_to_words(loaded + sums)
+    carry, borrow = ew[..., 1] > lw[..., 1], ew[..., 1] < lw[..., 1]
+    assert carry.sum() == (sums > 0).sum() and borrow.sum() == (sums < 0).sum() == 2 * 2 * 3
+    p, _ = PR.pore_params(n=n)
+    eng = Engine(p)
+    eng.corr_config(g)
+    eng.corr_load(lw, (5, 9, 2, 0))
+    for st in states:
+        eng.upload(*st)
+        eng.corr_sample()
+    tot, counters = eng.corr_read()
+    assert counters == (7, 12, 2, 1)
+    assert np.array_equal(tot, ew), np.argwhere(tot != ew)[:5]
+    eng.close()

@@ -11,6 +11,7 @@ from argon_monte_carlo_amd import fields as FL
 from argon_monte_carlo_amd import ic as IC
 from argon_monte_carlo_amd import params as PR
 from tests import fields_ref as REF
+from tests.sampler_states import ODD_N, ODD_SHARDS, drifting_states
 
 pytestmark = pytest.mark.gpu
 
@@ -279,3 +280,54 @@ def test_two_ranks_on_one_gpu_equal_single_engine(kind, n):
     tot, ns, no = _run_ranks(2, (kind, n, steps, every), target=_fields_worker)
     assert ns == ref[1] == steps // every and no == ref[2]
     assert np.array_equal(tot, ref[0])
+
+
+# ---- 9. the walk's odd ends: an index range that begins or ends inside an aligned pair ------------------------------------------
+@pytest.mark.parametrize("lo,hi", ODD_SHARDS)
+def test_index_range_with_odd_ends_equals_reference(lo, hi):
+    from argon_monte_carlo_amd.engine import ShardEngine
+    p, states = drifting_states(ODD_N, 4)
+    eng = ShardEngine(p, lo, hi)
+    eng.fields_config(FL.default_grid(p))
+    acc = _Acc(eng.field_grid)
+    for st in states:
+        eng.upload(*st)
+        eng.fields_sample()
+        acc.add(dict(zip(("x", "y", "z", "vx", "vy", "vz"), st)), lo, hi)
+    acc.check(eng)
+    assert acc.sums[:, 0].sum() + acc.outside == 4 * (hi - lo)
+    eng.close()
+
+
+# ---- 10. the shape of the shared reduce: exactly one workgroup of 64 columns and a little more, rows around its sixteen waves ----
+_REDUCE_REF = {}
+
+
+def _reduce_case(bins):
+    """(params, grid of ``bins`` bins over the lower half of the pore's box, state, reference sums, outside), computed once"""
+    if bins not in _REDUCE_REF:
+        p, (st,) = drifting_states(ODD_N, 1, seed=29)
+        n3 = {9: (3, 3, 1), 10: (5, 2, 1)}[bins]
+        g = FL.make_grid("cartesian", n3, (-p.R_oa, -p.R_oa, 0.0), (p.R_oa, p.R_oa, 0.5 * p.H))
+        _REDUCE_REF[bins] = (p, g, st) + REF.sample(g, *st)
+    return _REDUCE_REF[bins]
+
+
+@pytest.mark.parametrize("blocks", ["1", "17", "33"])
+@pytest.mark.parametrize("bins", [9, 10])
+def test_reduce_shapes_equal_reference(bins, blocks, monkeypatch):
+    """9 bins: 9 * 7 sums + the outside column = 64 columns, one full workgroup of the reduce; 10 bins: 71, a second one with
+    seven live lanes.  1, 17 and 33 slab rows: below, one above and two above a multiple of the reduce's sixteen waves."""
+    from argon_monte_carlo_amd.engine import Engine
+    p, g, st, sums, outside = _reduce_case(bins)
+    assert FL.grid_bins(g) == bins and outside > 0 and (sums[:, 0] > 0).all()
+    monkeypatch.setenv("AMC_FIELDS_BLOCKS", blocks)
+    eng = Engine(p)
+    eng.upload(*st)
+    eng.fields_config(g)
+    for k in (1, 2):                    # (the second sample adds onto non-zero totals)
+        eng.fields_sample()
+        tot, ns, no = eng.fields_read()
+        assert ns == k and no == k * outside
+        assert np.array_equal(tot, FL.ints_to_words(k * sums)), np.argwhere(tot != FL.ints_to_words(k * sums))[:5]
+    eng.close()

@@ -483,5 +483,27 @@ def test_a_read_between_runs_changes_nothing(stepped, run_on):
     assert_same(got, run_on, "run(5); read; run(7) vs run(12)", list(got))
 
 
+# ---- 10. the carry-add through the surfaces' load -----------------------------------------------------------------------------------
+def test_surface_load_carry_and_borrow(stepped):
+    """128-bit totals: loaded low words of 2^64 - 1 carry into the high word under a positive sum of the step, low words of 0
+    borrow from it under a negative one (dp_z < 0, dE < 0); the result equals the exact Python-int sum."""
+    sums, failed = REF.accumulate(*REF.empty(NBINS), NBINS, stepped["lo"], stepped["hi"], stepped["records"][0])
+    loaded = [[[(1 << 64) - 1 if v > 0 else 0 for v in b] for b in case] for case in sums]
+    loaded[0][0][0] += 5 << 64                                      # high word already non-zero
+    expect = [[[u + v for u, v in zip(bl, bs)] for bl, bs in zip(cl, cs)] for cl, cs in zip(loaded, sums)]
+    lw, ew = REF.to_words(loaded), REF.to_words(expect)
+    flat = [v for case in sums for b in case for v in b]
+    carry, borrow = ew[..., 1] > lw[..., 1], ew[..., 1] < lw[..., 1]
+    assert carry.sum() == sum(v > 0 for v in flat) >= 7 and borrow.sum() == sum(v < 0 for v in flat) >= 1
+    assert borrow[:, :, 1].any()                                    # dp_z < 0 among them
+    eng, cfg, dt, _ = engine()
+    eng.surface_load(lw, [3, 0, 0, 1, 0, 0, 2], 41)
+    eng.temp_timestep_device(dt, cfg)
+    tot, nf, ns = eng.surface_read()
+    assert np.array_equal(tot, ew), np.argwhere(tot != ew)[:5]
+    assert nf.tolist() == [a + b for a, b in zip([3, 0, 0, 1, 0, 0, 2], failed)] and ns == 42
+    eng.close()
+
+
 if __name__ == "__main__":
     np.savez(sys.argv[2], **JOBS[sys.argv[1]]())
