@@ -98,7 +98,9 @@ __device__ inline void temp_draw(const amc_params &P, const amc_temp_rng &g, int
                                  double n0, double n1, double n2, double contact_z, double &fx, double &fy, double &fz,
                                  double &Es)
 {
-    const double cos85 = 0.087155742747658166;      // cos(85 deg), Temp:136
+    // Temp:136's cos(85 * pi / 180) as the reference's Python evaluates it (0.08715574274765814; what p.cos85 and the host
+    // helper hold): 2 ulp below the correctly rounded cosine of 85 degrees
+    const double cos85 = 0x1.64fd6b8c28100p-4;
     const double pi = 3.14159265358979323846;
     fx = fy = fz = 0;
     for (unsigned int attempt = 0; attempt < 4096u; attempt++) {                     // Temp:133-141 (acceptance ~91 %)

@@ -832,6 +832,100 @@ def temp_many_hits(n=2700):
     return s.finish()
 
 
+DRAW_PER_CASE, DRAW_LADDER, DRAW_CORNERS = 190, 95, 8
+
+
+def draw_ladder_z(p):
+    """The contact z values of temp_draw_hits()'s ladder: next to either gap plane (1 and 3 ulp inside), the midpoint, the
+    rest evenly spaced across the gap."""
+    zlo, zhi = np.float64(p.t_zgap_lo), np.float64(p.t_zgap_hi)
+    lo1, hi1 = np.nextafter(zlo, np.inf), np.nextafter(zhi, -np.inf)
+    lo3, hi3 = np.nextafter(np.nextafter(lo1, np.inf), np.inf), np.nextafter(np.nextafter(hi1, -np.inf), -np.inf)
+    rest = np.linspace(zlo, zhi, DRAW_LADDER - 4 + 2)[1:-1]          # (an odd number of them: the middle one is the midpoint)
+    rest[len(rest) // 2] = 0.5 * (zlo + zhi)
+    zs = [lo1, lo3, hi1, hi3] + rest.tolist()
+    assert len(zs) == DRAW_LADDER and len(set(float(z) for z in zs)) == DRAW_LADDER
+    return [float(z) for z in zs]
+
+
+def temp_draw_hits():
+    """About 1,350 particles, every one hit by exactly one case in the first step — 190 per case, ``draw_case<k>`` — but for
+    eight ``draw_corner_4_8`` particles, which case 4 parks on t_z3_hot and case 8 takes next: two draws in one step under
+    two case words.  It is there for the device draws (tests/test_gpu_draws.py): many hits of every case whatever the step
+    word is, normals all round the circle, and gap hits at chosen heights.
+
+    The plane cases (3, 4 over the coatings at the mouths, 6, 7 on the bases of the gap annulus) stand on the grids of
+    temp_many_hits(); their normals are (0, 0, +-1) exactly.  The cylinder cases (5 at R_g_c, 8 and 9 at R_p_c) go round the
+    azimuth slots — the first 140 of a case on the slots themselves, the four exact axes included (there without a
+    tangential velocity, so that the normal lies on the axis), the other 50 half a slot on.  The first 95 of case 5 are the
+    ``draw_ladder``: vz = 0, so the contact z is the uploaded z bit for bit (draw_ladder_z()).  Kinds are interleaved by
+    particle index and flags alternate within a kind.  No particle overflows."""
+    p, c = _temp()
+    dt = c["dt"]
+    s = EdgeState(p, dt)
+    zc, zh, zlo, zhi = p.t_z3_cold, p.t_z3_hot, p.t_zgap_lo, p.t_zgap_hi
+    v, vfast = 431.0, 2600.0
+    hop, step = v * dt, vfast * dt
+    n = DRAW_PER_CASE
+    g = np.arange(-62.0e-9, 62.0e-9, 1.3e-9)
+    X, Y = np.meshgrid(g, g, indexing="ij")
+    R = np.hypot(X, Y)
+    keep = (R > p.R_p + 1.6e-9) & (R < 60.0e-9)
+    order = np.argsort(R[keep], kind="stable")
+    grid = list(zip(X[keep][order].tolist(), Y[keep][order].tolist()))[:n]
+    k3 = [("draw_case3", x, y, zc + 0.4 * hop, 30.0 + 0.01 * j, -20.0 - 0.02 * j, -(v + 0.37 * j)) for j, (x, y) in enumerate(grid)]
+    k4 = [("draw_case4", x, y, zh - 0.4 * hop, -25.0 - 0.01 * j, 35.0 + 0.02 * j, v + 0.41 * j) for j, (x, y) in enumerate(grid)]
+
+    def ring(j):
+        """(cos, sin, on an exact axis) of the j-th particle of a ring"""
+        if j < TEMP_SLOTS:
+            cs, sn = _unit(j)
+            return cs, sn, j % (TEMP_SLOTS // 4) == 0
+        a = 2.0 * np.pi * (j - TEMP_SLOTS + 0.5) / TEMP_SLOTS
+        return float(np.cos(a)), float(np.sin(a)), False
+
+    k6, k7 = [], []
+    for j in range(n):
+        cs, sn, _ = ring(j)
+        r = p.R_p_c + (0.6e-9 if j < TEMP_SLOTS else 1.9e-9)
+        k6.append(("draw_case6", r * cs, r * sn, zlo + 0.4 * hop, 20.0 + 0.03 * j, -15.0, -(v + 0.29 * j)))
+        k7.append(("draw_case7", r * cs, r * sn, zhi - 0.4 * hop, -20.0 - 0.03 * j, 15.0, v + 0.31 * j))
+
+    def cylinder(name, Rc, zs, vzs):
+        out = []
+        for j in range(n):
+            cs, sn, axis = ring(j)
+            vr, vt = v + 0.3 * j, 0.0 if axis else -61.0
+            r0 = Rc - 0.4 * hop
+            out.append((name(j), r0 * cs, r0 * sn, zs[j], vr * cs - vt * sn, vr * sn + vt * cs, vzs[j]))
+        return out
+
+    ladder = draw_ladder_z(p)
+    span = zhi - zlo
+    z5 = ladder + [zlo + span * (0.07 + 0.86 * (j / (n - DRAW_LADDER))) for j in range(n - DRAW_LADDER)]
+    vz5 = [0.0] * DRAW_LADDER + [40.0 if j % 2 else -40.0 for j in range(n - DRAW_LADDER)]
+    k5 = cylinder(lambda j: "draw_ladder" if j < DRAW_LADDER else "draw_case5", p.R_g_c, z5, vz5)
+    k8 = cylinder(lambda j: "draw_case8", p.R_p_c, [110.0e-9 if j < TEMP_SLOTS else 118.0e-9 for j in range(n)],
+                  [40.0 if j % 2 else -40.0 for j in range(n)])
+    k9 = cylinder(lambda j: "draw_case9", p.R_p_c, [200.0e-9 if j < TEMP_SLOTS else 210.0e-9 for j in range(n)],
+                  [-40.0 if j % 2 else 40.0 for j in range(n)])
+    a48 = []
+    for j in range(DRAW_CORNERS):
+        cs, sn = _unit(3 + 17 * j)
+        f, gz = 0.06 + 0.04 * j, 0.25 + 0.05 * j
+        r0 = p.R_p_c - f * step
+        a48.append(("draw_corner_4_8", r0 * cs, r0 * sn, zh - gz * step, vfast * cs, vfast * sn, vfast))
+    streams = [k3, k5, k4, k8, k6, k9, k7, a48]
+    count = {}
+    while any(streams):
+        for st in streams:
+            if st:
+                case, x, y, z, vx, vy, vz = st.pop(0)
+                s.add(case, x, y, z, vx, vy, vz, flag=count.get(case, 0) % 2, landed=False, jitter=False)
+                count[case] = count.get(case, 0) + 1
+    return s.finish()
+
+
 def assert_temp_coverage(s, masks, failed):
     """What a run of temp_walls() must have exercised in its first step, whoever ran it (the reference in the fixture, the
     oracle beside the GPU): ``masks[case]`` = the particle indices hit by case 3 .. 9, ``failed`` = the number of contact

@@ -7,7 +7,7 @@ pins the oracle (tests/test_oracle_edges.py); here the bar is GPU == oracle, bit
 The forms: the host hand-over case by case and as a whole step (with the gap case parked, and not), the device-draw single
 step (one kernel for all cases, and AMC_TEMP_UNFUSED=1: a kernel triple per case), the host-free run (fused into the streaming
 pass, and AMC_TEMP_RUN_UNFUSED=1), the device sums past their tile, the sampled surfaces.  The oracle replays a device-draw
-step with the draws the device used (test_device_rng_energised_walls_match_oracle_on_the_same_draws pins the draws).
+step with the draws the device used (tests/test_gpu_draws.py pins the draws themselves, every hit against 40 digits).
 
 Every test asserts on the ORACLE that the state did what it is there for (tests/edge_states.assert_temp_coverage): every case
 hit, the corner sequences taken or blocked, a contact solve without a real root.
