@@ -105,6 +105,14 @@ class AmcCorrGrid(C.Structure):
                 ("lo", C.c_double * 3), ("hi", C.c_double * 3), ("reserved", C.c_int64 * 2)]
 
 
+AMC_FLUX_MAX_BINS = 1024
+
+
+class AmcFluxGrid(C.Structure):
+    """amc_flux_grid (include/argonmc_flux.h): the bins of the sampled fluxes and the sampling cadence; the fields of amc_field_grid."""
+    _fields_ = list(AmcFieldGrid._fields_)
+
+
 AMC_SURFACE_CASES = 7
 AMC_SURFACE_MAX_BINS = 256
 

@@ -270,6 +270,19 @@ struct amc_corr_ws {
     unsigned long long *meta;   // [0] origins, [1] samples, [2] particles outside, [3] lowest particle index out of range (~0: none)
 };
 
+// sampled fluxes (amc_flux.hip): the grid, the per-workgroup slab rows of one sample (two tables of seven integers per bin)
+// and the 128-bit running totals
+struct amc_flux_ws {
+    bool on;
+    amc_flux_grid g;
+    amc_fields_grid_dev G;
+    int max_blocks;             // slab rows allocated (AMC_FLUX_BLOCKS, else the number of CUs)
+    int blocks_env;             // AMC_FLUX_BLOCKS at configuration (0: by particle count)
+    unsigned long long *slab;   // [max_blocks][2 * bins * 7 + 1] one sample's sums per workgroup: rows A, rows B (+ particles outside)
+    unsigned long long *tot;    // [bins][2][7][2] running totals, (low, high) words
+    unsigned long long *meta;   // [0] unused, [1] samples, [2] particles outside, [3] lowest particle index out of range (~0: none)
+};
+
 // What the sharded step leaves pending between two amc_mg_* calls (amc_api_mg.hip).  The rule — a call whose requirement fails
 // returns AMC_ERR_STATE before it enqueues anything and leaves the record as it was:
 //   amc_mg_pack(world)         requires idle and the exchange view of `world`; leaves packed(world) and `mode`.
@@ -401,6 +414,7 @@ struct amc_ctx {
     amc_fields_ws F;
     amc_surface_ws SF;
     amc_corr_ws CR;
+    amc_flux_ws FX;
     // outputs
     amc_out out;
     amc_path_record *d_rec;

@@ -303,6 +303,34 @@ class ShardedSimulation:
             dt = getattr(self, "dt", 1.0)
         return CO.derive(g, tot, counters, dt, every)
 
+    # ---- sampled fluxes (fluxes.py): every rank samples its own index range, the totals are summed exactly -------------------
+    def enable_fluxes(self, grid=None, every=0):
+        from . import fluxes as FX
+        g = FX.default_grid(self.params) if grid is None else grid
+        self.engine.flux_config(FX.copy_grid(g, every=every))
+
+    def fluxes_sample(self):
+        self.engine.flux_sample()
+
+    def fluxes_reset(self):
+        self.engine.flux_reset()
+
+    def fluxes(self):
+        """Simulation.fluxes() of the whole system (a collective: every rank calls it): the ranks' 128-bit totals and the
+        outside counter summed as 32-bit limbs in one int64 all-reduce, exactly as ``fields()`` does — a read that fails on one
+        rank fails on every rank, from this same call."""
+        from . import fluxes as FX
+        g = self.engine.flux_grid
+
+        def read():
+            tot, ns, no = self.engine.flux_read()
+            return [tot], [no], ns
+        (tot,), (no,), ns = self._read_summed(
+            read, None if g is None else [FX.totals_shape(g)], 1,
+            self._describe("flux_read", "amc_flux: particle {p} (rank {r}) has a velocity component outside |c| < 2^14 m/s (or NaN); "
+                                        "sampling stopped until fluxes_reset"))
+        return FX.derive(g, tot, ns, no, float(self.params.argon_mass), FX.boltzmann_constant(self.params))
+
     def histograms(self):
         """Global free-path histograms = sum over ranks (every completed path is emitted by its particle's owner)."""
         counts, tot = self.engine.histograms()

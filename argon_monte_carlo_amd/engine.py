@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._abi import (AMC_K_NAMES, AmcCorrGrid, AmcFieldGrid, AmcParams, AmcPathRecord, AmcStepStats, AmcSurfaceGrid, path_record_dtype)
+from ._abi import (AMC_K_NAMES, AmcCorrGrid, AmcFieldGrid, AmcFluxGrid, AmcParams, AmcPathRecord, AmcStepStats, AmcSurfaceGrid, path_record_dtype)
 
 _dp = C.POINTER(C.c_double)
 _i64p = C.POINTER(C.c_int64)
@@ -33,6 +33,7 @@ class Engine:
         self.field_grid = None
         self.surface_grid = None
         self.corr_grid = None
+        self.flux_grid = None
         self._ctx = C.c_void_p()
         rc = self.lib.amc_create(C.byref(self._ctx), C.byref(params))
         if rc != 0:
@@ -225,6 +226,36 @@ class Engine:
 
     def corr_reset(self):
         self._ck(self.lib.amc_corr_reset(self._ctx))
+
+    # -- sampled fluxes (fluxes.py) ----------------------------------------------------------------------------------
+    def flux_config(self, grid):
+        """Sample on ``grid`` (an ``AmcFluxGrid``, fluxes.make_grid); None switches sampling off.  Starts from zero totals."""
+        self._ck(self.lib.amc_flux_config(self._ctx, None if grid is None else C.byref(grid)))
+        self.flux_grid = None if grid is None else AmcFluxGrid.from_buffer_copy(grid)
+
+    def flux_sample(self):
+        """One sample of the current state, enqueued on the context's stream."""
+        self._ck(self.lib.amc_flux_sample(self._ctx))
+
+    def flux_read(self):
+        """(int64[bins, 2, 7, 2] totals as (low, high) words, samples, particles outside); synchronises."""
+        g = self.flux_grid
+        if g is None:
+            raise _lib.ArgonMCError(-6, "flux_read before flux_config")
+        tot = np.zeros((int(g.n1) * int(g.n2) * int(g.n3), 2, 7, 2), dtype=np.int64)
+        ns, no = C.c_int64(0), C.c_int64(0)
+        self._ck(self.lib.amc_flux_read(self._ctx, tot.ctypes.data_as(_i64p), C.byref(ns), C.byref(no)))
+        return tot, ns.value, no.value
+
+    def flux_load(self, totals, n_samples, n_outside):
+        tot = np.ascontiguousarray(totals, dtype=np.int64)
+        g = self.flux_grid
+        if g is None or tot.size != int(g.n1) * int(g.n2) * int(g.n3) * 28:
+            raise ValueError("totals do not match the configured grid")
+        self._ck(self.lib.amc_flux_load(self._ctx, tot.ctypes.data_as(_i64p), int(n_samples), int(n_outside)))
+
+    def flux_reset(self):
+        self._ck(self.lib.amc_flux_reset(self._ctx))
 
     # -- measurement -----------------------------------------------------------------------------------------------
     def set_stream(self, stream_ptr):

@@ -226,18 +226,61 @@ class Simulation:
         else:                                           # a checkpoint without them: sampling is off in the resumed run
             self.engine.corr_config(None)
 
+    # ---- sampled fluxes (fluxes.py; the reference has no such output) -----------------------------------------
+    def enable_fluxes(self, grid=None, every=0):
+        """Sample the velocity moments behind the pressure tensor, the energy flux and the heat flux per bin of ``grid``
+        (fluxes.make_grid; None = the geometry's default, fluxes.default_grid) after every ``every``-th step (0: only on
+        ``fluxes_sample()``).  Starts from zero.  Independent of ``enable_fields``."""
+        from . import fluxes as FX
+        g = FX.default_grid(self.params) if grid is None else grid
+        self.engine.flux_config(FX.copy_grid(g, every=every, step_offset=getattr(self, "_step_base", 0)))
+
+    def disable_fluxes(self):
+        self.engine.flux_config(None)
+
+    def fluxes_sample(self):
+        """One sample of the current state now (asynchronous)."""
+        self.engine.flux_sample()
+
+    def fluxes_reset(self):
+        self.engine.flux_reset()
+
+    def fluxes(self):
+        """dict (fluxes.derive): count, number_density (m^-3), velocity (bins x 3), pressure_tensor (bins x 3 x 3, Pa), pressure,
+        T, energy_flux and heat_flux (bins x 3, W/m^2) — components x, y, z on a Cartesian grid, r, theta, z on an axisymmetric
+        one — edges, bin_volume, n_samples, n_outside and the raw integer totals (int64[bins, 2, 7, 2], 128-bit (low, high)
+        words).  Bins in linear order (i1 * n2 + i2) * n3 + i3."""
+        from . import fluxes as FX
+        tot, ns, no = self.engine.flux_read()
+        return FX.derive(self.engine.flux_grid, tot, ns, no, float(self.params.argon_mass), FX.boltzmann_constant(self.params))
+
+    def write_fluxes(self, path):
+        """The dict of ``fluxes()`` as an .npz (edges as edges_1, edges_2[, edges_3])."""
+        _write_npz(path, self.fluxes())
+
     # ---- checkpoint / resume (the reference has none: a 10^4-step run is one process lifetime there) ---------------
     def _checkpoint_extra(self):
-        return {}
+        """what a subclass adds to a checkpoint (it extends this dict) — here: grid, totals and counters of the sampled fluxes"""
+        if self.engine.flux_grid is None:
+            return {}
+        from . import fluxes as FX
+        tot, ns, no = self.engine.flux_read()
+        return dict(flux_grid=FX.grid_to_array(self.engine.flux_grid), flux_totals=tot, flux_n_samples=int(ns), flux_n_outside=int(no))
 
     def _restore_extra(self, z):
-        pass
+        """the inverse; a subclass calls it once ``_step_base`` is final (the cadence counts from the run's first step)"""
+        from . import fluxes as FX
+        if "flux_grid" in z:
+            self.engine.flux_config(FX.copy_grid(FX.grid_from_array(z["flux_grid"]), step_offset=self._step_base))
+            self.engine.flux_load(z["flux_totals"], int(z["flux_n_samples"]), int(z["flux_n_outside"]))
+        else:                                           # a checkpoint without them: sampling is off in the resumed run
+            self.engine.flux_config(None)
 
     def save_checkpoint(self, path):
         """Everything a later ``load_checkpoint`` needs to continue bit-identically: the particle arrays, the
         completed-path lists, the device histograms and the counters (+ RNG streams and per-step lists for Temp, + the
         grid and the totals of the sampled fields when they are on, + the grid, totals, counters, window position and origin
-        arrays of the sampled correlations when they are on)."""
+        arrays of the sampled correlations when they are on, + the grid, totals and counters of the sampled fluxes when they are on)."""
         st = self.engine.download()
         self._collect()
         counts, _ = self.engine.histograms()
@@ -394,7 +437,7 @@ class TemperatureSimulation(Simulation):
             tot, nf, ns = self.engine.surface_read()
             surf = dict(surface_grid=SU.grid_to_array(self.engine.surface_grid), surface_totals=tot, surface_n_failed=nf,
                         surface_n_steps=int(ns))
-        return dict(**surf, momentum=np.array([float(v) for v in self.momentum_z_change_per_step]),
+        return dict(**super()._checkpoint_extra(), **surf, momentum=np.array([float(v) for v in self.momentum_z_change_per_step]),
                     energy_cold=np.array([float(v) for v in self.energy_transfer_cold_per_step]),
                     energy_hot=np.array([float(v) for v in self.energy_transfer_hot_per_step]),
                     zero_flags=np.array(self._zero_flags, dtype=bool).reshape(-1, 3), total_errs=int(self.total_errs),
@@ -422,6 +465,7 @@ class TemperatureSimulation(Simulation):
         self.sampler.np_rng.set_state(("MT19937", z["np_rng_keys"], int(z["np_rng_rest"][0]), int(z["np_rng_rest"][1]),
                                        float(z["np_rng_gauss"])))
         self.sampler.py_rng.setstate((int(z["py_rng_version"]), tuple(int(v) for v in z["py_rng_state"]), None))
+        super()._restore_extra(z)
 
     def write_outputs(self, directory="."):
         import os
