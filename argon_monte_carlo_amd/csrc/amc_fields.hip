@@ -1,26 +1,39 @@
-// amc_fields.hip — sampled fields: per spatial bin, the particle count and the first and second moments of the velocity
-// components, accumulated as exact integers (include/argonmc.h "sampled fields").  The reference has no such
-// output; the Python layer derives number density, flow velocity and temperature from the totals.
+// amc_fields.hip — the moment samplers.  Sampled fields: per spatial bin, the particle count and the first and second moments
+// of the velocity components, accumulated as exact integers (include/argonmc.h "sampled fields").  Sampled
+// fluxes: the same seven (row A) and a second row B of the three cross products and the three energy-weighted components
+// (include/argonmc_flux.h).  The reference has neither output; the Python layer derives number density, flow
+// velocity and temperature, the pressure tensor, the energy flux and the heat flux from the totals.
 //
 // One sample is two kernels:
-//   k_fields_accum   a persistent grid of at most one workgroup per CU.  Each workgroup streams a contiguous index range
-//                    (x, y, z, vx, vy, vz: 48 B per particle, 16-B loads of particle pairs), computes the bin and the seven
-//                    integers of each particle and adds them into a table in LDS (64-bit integer LDS atomics: exact and
-//                    order-free).  It stores the table as one slab row with plain stores — no global atomics.
-//   k_sample_reduce  sums the slab rows per (bin, quantity) and adds the result into the 128-bit running totals, with carry; it
-//                    serves the sampled correlations too (amc_launch_sample_reduce) and adds nothing once the error word is set.
+//   k_moments_accum<ROWS>  (ROWS = 1: the fields, 2: the fluxes) a persistent grid of at most one workgroup per CU.  Each
+//                    workgroup streams a contiguous index range (x, y, z, vx, vy, vz: 48 B per particle, 16-B loads of
+//                    particle pairs), computes the bin and the seven or thirteen non-zero integers of each particle and adds
+//                    them into ROWS tables in LDS (64-bit integer LDS atomics: exact and order-free).  It stores the tables
+//                    as one slab row [ROWS][bins * 7][outside] with plain stores — no global atomics but the atomicMin on
+//                    the error word.
+//   k_sample_reduce  sums the slab rows per (bin, quantity) and adds the result into the 128-bit running totals, with carry
+//                    (the fluxes: row A at "lag" 0 and row B at "lag" 1 of two, totals[bins][2][7][2]); it serves the sampled
+//                    correlations too (amc_launch_sample_reduce) and adds nothing once the error word is set.
 // Integer sums do not depend on the order of the adds, so the totals are bitwise the same for any number of workgroups.
 #include "amc_host.h"
 #include "amc_sample_dev.h"
+#include <cstddef>
 
-#define AMC_FIELDS_Q AMC_SAMPLE_Q        // count, q1(c1..c3), q2(c1..c3)
-#define AMC_FIELDS_THREADS 1024         // the 112 KiB table leaves room for one workgroup per CU: 16 waves
+#define AMC_MOMENTS_Q AMC_SAMPLE_Q       // per row — A: count, q1(c1..c3), q2(c1..c3); B: 0, q2(c1c2, c1c3, c2c3), q3(c1..c3)
+#define AMC_MOMENTS_THREADS 1024        // the 112 KiB of tables leave room for one workgroup per CU: 16 waves
 #define AMC_SAMPLE_REDUCE_THREADS 1024
+static_assert(2 * AMC_FLUX_MAX_BINS == AMC_FIELDS_MAX_BINS, "both instances of k_moments_accum fill the one LDS table");
 
-// one particle into the workgroup's table; returns false if a component is out of the quantisation range.  (The bin is
-// amc_sample_bin's rule written out: calling it here measured + 0.5 us on the cube's 16 us sample)
-AMC_DEV bool amc_fields_particle(const amc_fields_grid_dev &G, unsigned long long *tab, unsigned int &outside, double x, double y,
-                                 double z, double vx, double vy, double vz)
+AMC_DEV unsigned long long moments_q1(double c) { return (unsigned long long)(long long)rint(c * 16777216.0); }
+AMC_DEV unsigned long long moments_q2(double a, double b) { return (unsigned long long)(long long)rint((a * b) * 1024.0); }
+AMC_DEV unsigned long long moments_q3(double e, double c) { return (unsigned long long)(long long)rint(ldexp(e * c, -6)); }
+
+// one particle into the workgroup's tables (tab: row A; ROWS == 2: tab + M is row B); returns false if a component is out of
+// the quantisation range.  (The bin is amc_sample_bin's rule written out: calling it here measured + 0.5 us on the cube's
+// 16 us sample)
+template <int ROWS>
+AMC_DEV bool amc_moments_particle(const amc_fields_grid_dev &G, unsigned long long *tab, int M, unsigned int &outside, double x, double y,
+                                  double z, double vx, double vy, double vz)
 {
     int i1, i2, i3;
     double c1, c2, c3;
@@ -44,25 +57,37 @@ AMC_DEV bool amc_fields_particle(const amc_fields_grid_dev &G, unsigned long lon
     }
     if (i1 < 0 || i2 < 0 || i3 < 0) { outside++; return true; }
     if (!amc_sample_speed_ok(c1, c2, c3)) return false;
-    unsigned long long *t = tab + (size_t)((i1 * G.n2 + i2) * G.n3 + i3) * AMC_FIELDS_Q;
-    atomicAdd(t + 0, 1ULL);
-    atomicAdd(t + 1, (unsigned long long)(long long)rint(c1 * 16777216.0));
-    atomicAdd(t + 2, (unsigned long long)(long long)rint(c2 * 16777216.0));
-    atomicAdd(t + 3, (unsigned long long)(long long)rint(c3 * 16777216.0));
-    atomicAdd(t + 4, (unsigned long long)(long long)rint((c1 * c1) * 1024.0));
-    atomicAdd(t + 5, (unsigned long long)(long long)rint((c2 * c2) * 1024.0));
-    atomicAdd(t + 6, (unsigned long long)(long long)rint((c3 * c3) * 1024.0));
+    unsigned long long *a = tab + (size_t)((i1 * G.n2 + i2) * G.n3 + i3) * AMC_MOMENTS_Q;
+    const double s1 = c1 * c1, s2 = c2 * c2, s3 = c3 * c3;
+    atomicAdd(a + 0, 1ULL);
+    atomicAdd(a + 1, moments_q1(c1));
+    atomicAdd(a + 2, moments_q1(c2));
+    atomicAdd(a + 3, moments_q1(c3));
+    atomicAdd(a + 4, (unsigned long long)(long long)rint(s1 * 1024.0));
+    atomicAdd(a + 5, (unsigned long long)(long long)rint(s2 * 1024.0));
+    atomicAdd(a + 6, (unsigned long long)(long long)rint(s3 * 1024.0));
+    if constexpr (ROWS == 2) {
+        unsigned long long *b = a + M;
+        const double e = (s1 + s2) + s3;
+        atomicAdd(b + 1, moments_q2(c1, c2));
+        atomicAdd(b + 2, moments_q2(c1, c3));
+        atomicAdd(b + 3, moments_q2(c2, c3));
+        atomicAdd(b + 4, moments_q3(e, c1));
+        atomicAdd(b + 5, moments_q3(e, c2));
+        atomicAdd(b + 6, moments_q3(e, c3));
+    }
     return true;
 }
 
-__global__ __launch_bounds__(AMC_FIELDS_THREADS) void k_fields_accum(amc_state S, amc_lazy L, long long lo, long long hi,
-                                                                     amc_fields_grid_dev G, unsigned long long *slab,
-                                                                     unsigned long long *bad)
+template <int ROWS>
+__global__ __launch_bounds__(AMC_MOMENTS_THREADS) void k_moments_accum(amc_state S, amc_lazy L, long long lo, long long hi,
+                                                                       amc_fields_grid_dev G, unsigned long long *slab,
+                                                                       unsigned long long *bad)
 {
-    __shared__ unsigned long long tab[AMC_FIELDS_MAX_BINS * AMC_FIELDS_Q];
+    __shared__ unsigned long long tab[AMC_FIELDS_MAX_BINS * AMC_MOMENTS_Q];     // ROWS tables of G.bins * 7 (the sampler's bin limit)
     __shared__ unsigned int outside_sum;
-    const int M = G.bins * AMC_FIELDS_Q;
-    for (int j = threadIdx.x; j < M; j += blockDim.x) tab[j] = 0;
+    const int M = G.bins * AMC_MOMENTS_Q;
+    for (int j = threadIdx.x; j < ROWS * M; j += blockDim.x) tab[j] = 0;
     if (threadIdx.x == 0) outside_sum = 0;
     __syncthreads();
     // this workgroup's particles [b0, b1), walked as aligned pairs (2k, 2k + 1): one 16-byte load per array and pair
@@ -90,16 +115,16 @@ __global__ __launch_bounds__(AMC_FIELDS_THREADS) void k_fields_accum(amc_state S
                 if (!(e == 0 ? v0 : v1)) continue;
                 const long long p = p0 + e;
                 amc_fields_lazy(S, L, p, x[e], y[e], z[e], vx[e], vy[e], vz[e]);
-                if (!amc_fields_particle(G, tab, outside, x[e], y[e], z[e], vx[e], vy[e], vz[e]) && first_bad < 0) first_bad = p;
+                if (!amc_moments_particle<ROWS>(G, tab, M, outside, x[e], y[e], z[e], vx[e], vy[e], vz[e]) && first_bad < 0) first_bad = p;
             }
         }
     }
     if (outside) atomicAdd(&outside_sum, outside);
     if (first_bad >= 0) atomicMin(bad, (unsigned long long)first_bad);
     __syncthreads();
-    unsigned long long *row = slab + (size_t)blockIdx.x * (size_t)(M + 1);
-    for (int j = threadIdx.x; j < M; j += blockDim.x) row[j] = tab[j];
-    if (threadIdx.x == 0) row[M] = outside_sum;
+    unsigned long long *row = slab + (size_t)blockIdx.x * (size_t)(ROWS * M + 1);
+    for (int j = threadIdx.x; j < ROWS * M; j += blockDim.x) row[j] = tab[j];
+    if (threadIdx.x == 0) row[ROWS * M] = outside_sum;
 }
 
 // column j of the slab (j < tables * M: table j / M, (bin, quantity) j % M; j == tables * M: particles outside) summed over
@@ -150,107 +175,151 @@ hipError_t amc_launch_sample_reduce(amc_ctx *c, const unsigned long long *slab, 
     return hipGetLastError();
 }
 
-static int fields_enqueue(amc_ctx *c)
+// ---- the host side: one implementation over a workspace (c->F, c->FX) and its sampler's descriptor -------------------------------------------
+struct moments_desc {
+    const char *name, *grid;            // in the messages: the entry points' prefix and the grid struct
+    const char *env;                    // the workgroups' environment knob
+    int max_bins, rows;
+};
+static const moments_desc FIELDS = {"amc_fields", "amc_field_grid", "AMC_FIELDS_BLOCKS", AMC_FIELDS_MAX_BINS, 1};
+static const moments_desc FLUX = {"amc_flux", "amc_flux_grid", "AMC_FLUX_BLOCKS", AMC_FLUX_MAX_BINS, 2};
+
+// amc_flux_grid is amc_field_grid member for member: the workspace stores either as the latter
+#define MOMENTS_SAME(m) static_assert(offsetof(amc_flux_grid, m) == offsetof(amc_field_grid, m) && \
+                                      sizeof(amc_flux_grid::m) == sizeof(amc_field_grid::m), "amc_flux_grid." #m " differs from amc_field_grid's")
+static_assert(sizeof(amc_flux_grid) == sizeof(amc_field_grid), "amc_flux_grid differs in size from amc_field_grid");
+MOMENTS_SAME(struct_size); MOMENTS_SAME(kind); MOMENTS_SAME(n1); MOMENTS_SAME(n2); MOMENTS_SAME(n3); MOMENTS_SAME(reserved);
+MOMENTS_SAME(every); MOMENTS_SAME(step_offset); MOMENTS_SAME(lo); MOMENTS_SAME(hi);
+#undef MOMENTS_SAME
+
+static int moments_enqueue(amc_ctx *c, amc_moments_ws &W, const moments_desc &D)
 {
-    amc_fields_ws &F = c->F;
     int blocks;
-    if (int rc = amc_sample_blocks(c, "amc_fields", F.blocks_env, F.max_blocks, &blocks)) return rc;
+    if (int rc = amc_sample_blocks(c, D.name, W.blocks_env, W.max_blocks, &blocks)) return rc;
     amc_prof_begin(c, AMC_K_FIELDS);
-    AMC_LAUNCH(c, k_fields_accum, dim3(blocks), dim3(AMC_FIELDS_THREADS), c->S, amc_sample_lazy(c), (long long)c->lo, (long long)c->hi, F.G,
-               F.slab, F.meta + 3);
+    if (D.rows == 1)
+        AMC_LAUNCH(c, k_moments_accum<1>, dim3(blocks), dim3(AMC_MOMENTS_THREADS), c->S, amc_sample_lazy(c), (long long)c->lo, (long long)c->hi,
+                   W.G, W.slab, W.meta + 3);
+    else
+        AMC_LAUNCH(c, k_moments_accum<2>, dim3(blocks), dim3(AMC_MOMENTS_THREADS), c->S, amc_sample_lazy(c), (long long)c->lo, (long long)c->hi,
+                   W.G, W.slab, W.meta + 3);
     amc_prof_end(c);
     AMC_HIP(c, hipGetLastError());
-    AMC_HIP(c, amc_launch_sample_reduce(c, F.slab, blocks, F.G.bins * AMC_FIELDS_Q, 1, 0, 0, 1, 0, F.tot, F.meta));
+    // row A is table 0 -> totals[bin][0], row B table 1 -> totals[bin][1]
+    AMC_HIP(c, amc_launch_sample_reduce(c, W.slab, blocks, W.G.bins * AMC_MOMENTS_Q, D.rows, 0, D.rows - 1, D.rows, 0, W.tot, W.meta));
     return AMC_OK;
 }
 
-static void fields_free(amc_ctx *c)
+static void moments_free(amc_ctx *c, amc_moments_ws &W)
 {
-    ctx_free(c, c->F.slab, c->F.tot, c->F.meta);
-    c->F = amc_fields_ws();
+    ctx_free(c, W.slab, W.tot, W.meta);
+    W = amc_moments_ws();
 }
 
 // meta: [0] unused, [1] samples, [2] particles outside, [3] the error word (the layout k_sample_reduce writes)
-static amc_totals fields_totals(const amc_fields_ws &F) { return amc_totals{F.tot, (size_t)2 * AMC_FIELDS_Q * (size_t)F.G.bins, F.meta, 4, 3}; }
-
-extern "C" {
-
-int amc_fields_step(amc_ctx *c)
+static amc_totals moments_totals(const amc_moments_ws &W, const moments_desc &D)
 {
-    if (!amc_fields_due(c, c->out.step)) return AMC_OK;
-    return fields_enqueue(c);
+    return amc_totals{W.tot, (size_t)2 * D.rows * AMC_MOMENTS_Q * (size_t)W.G.bins, W.meta, 4, 3};
 }
 
-int amc_fields_config(amc_ctx *c, const amc_field_grid *g)
+// the checks every entry point on a configured sampler starts with (`what`: its name behind the sampler's); c is not null here
+// and below: the entry points have looked
+static int moments_ready(amc_ctx *c, const amc_moments_ws &W, const moments_desc &D, const char *what)
 {
-    if (!c) return AMC_ERR_INVALID;
+    if (!W.on) return amc_fail(c, AMC_ERR_STATE, "%s_%s before %s_config", D.name, what, D.name);
     AMC_HIP(c, hipSetDevice(c->device));
-    AMC_HIP(c, hipStreamSynchronize(c->stream));        // (a sample in flight may still use the old buffers)
-    if (!g) {
-        fields_free(c);
-        return AMC_OK;
-    }
-    if (g->struct_size != (int32_t)sizeof(amc_field_grid)) return amc_fail(c, AMC_ERR_INVALID, "amc_field_grid.struct_size mismatch (ABI)");
-    amc_fields_grid_dev G;
-    if (int rc = amc_sample_grid_check(c, "amc_field_grid", "bins", g->kind, g->n1, g->n2, g->n3, AMC_FIELDS_MAX_BINS, g->lo, g->hi, g->every,
-                                       g->step_offset, g->reserved == 0, nullptr, &G))
-        return rc;
-    fields_free(c);
-    amc_fields_ws &F = c->F;
-    F.g = *g;
-    F.G = G;
-    amc_sample_blocks_config(c, "AMC_FIELDS_BLOCKS", &F.blocks_env, &F.max_blocks);
-    const size_t M = (size_t)G.bins * AMC_FIELDS_Q;
-    if (dalloc(c, &F.slab, (size_t)F.max_blocks * (M + 1)) != hipSuccess || dalloc(c, &F.tot, 2 * M) != hipSuccess ||
-        dalloc(c, &F.meta, 4) != hipSuccess) {
-        fields_free(c);
-        return amc_fail(c, AMC_ERR_HIP, "amc_fields_config: device allocation failed");
-    }
-    F.on = true;
-    if (int rc = amc_fields_reset(c)) { fields_free(c); return rc; }
     return AMC_OK;
 }
 
-int amc_fields_sample(amc_ctx *c)
+static int moments_reset(amc_ctx *c, amc_moments_ws &W, const moments_desc &D)
 {
-    if (!c) return AMC_ERR_INVALID;
-    if (!c->F.on) return amc_fail(c, AMC_ERR_STATE, "amc_fields_sample before amc_fields_config");
-    if (!c->uploaded) return amc_fail(c, AMC_ERR_STATE, "amc_fields_sample before amc_upload");
-    AMC_HIP(c, hipSetDevice(c->device));
-    return fields_enqueue(c);
+    if (int rc = moments_ready(c, W, D, "reset")) return rc;
+    const unsigned long long meta[4] = {0, 0, 0, 0};
+    return amc_totals_put(c, moments_totals(W, D), nullptr, meta);
 }
 
-int amc_fields_read(amc_ctx *c, int64_t *totals, int64_t *n_samples, int64_t *n_outside)
+// grid: the sampler's grid struct (the common layout, above), or nullptr
+static int moments_config(amc_ctx *c, amc_moments_ws &W, const moments_desc &D, const void *grid)
 {
-    if (!c) return AMC_ERR_INVALID;
-    if (!c->F.on) return amc_fail(c, AMC_ERR_STATE, "amc_fields_read before amc_fields_config");
     AMC_HIP(c, hipSetDevice(c->device));
+    AMC_HIP(c, hipStreamSynchronize(c->stream));        // (a sample in flight may still use the old buffers)
+    if (!grid) {
+        moments_free(c, W);
+        return AMC_OK;
+    }
+    amc_field_grid g;
+    memcpy(&g, grid, sizeof g);
+    if (g.struct_size != (int32_t)sizeof(amc_field_grid)) return amc_fail(c, AMC_ERR_INVALID, "%s.struct_size mismatch (ABI)", D.grid);
+    amc_fields_grid_dev G;
+    if (int rc = amc_sample_grid_check(c, D.grid, "bins", g.kind, g.n1, g.n2, g.n3, D.max_bins, g.lo, g.hi, g.every, g.step_offset,
+                                       g.reserved == 0, nullptr, &G))
+        return rc;
+    moments_free(c, W);
+    W.g = g;
+    W.G = G;
+    amc_sample_blocks_config(c, D.env, &W.blocks_env, &W.max_blocks);
+    const size_t M = (size_t)G.bins * AMC_MOMENTS_Q;
+    if (dalloc(c, &W.slab, (size_t)W.max_blocks * (D.rows * M + 1)) != hipSuccess || dalloc(c, &W.tot, moments_totals(W, D).words) != hipSuccess ||
+        dalloc(c, &W.meta, 4) != hipSuccess) {
+        moments_free(c, W);
+        return amc_fail(c, AMC_ERR_HIP, "%s_config: device allocation failed", D.name);
+    }
+    W.on = true;
+    if (int rc = moments_reset(c, W, D)) { moments_free(c, W); return rc; }
+    return AMC_OK;
+}
+
+static int moments_sample(amc_ctx *c, amc_moments_ws &W, const moments_desc &D)
+{
+    if (!W.on) return amc_fail(c, AMC_ERR_STATE, "%s_sample before %s_config", D.name, D.name);
+    if (!c->uploaded) return amc_fail(c, AMC_ERR_STATE, "%s_sample before amc_upload", D.name);
+    AMC_HIP(c, hipSetDevice(c->device));
+    return moments_enqueue(c, W, D);
+}
+
+static int moments_read(amc_ctx *c, amc_moments_ws &W, const moments_desc &D, int64_t *totals, int64_t *n_samples, int64_t *n_outside)
+{
+    if (int rc = moments_ready(c, W, D, "read")) return rc;
     unsigned long long meta[4], bad;
-    if (int rc = amc_totals_get(c, fields_totals(c->F), totals, meta, &bad)) return rc;
+    if (int rc = amc_totals_get(c, moments_totals(W, D), totals, meta, &bad)) return rc;
     if (bad != ~0ULL)
-        return amc_fail(c, AMC_ERR_CAPACITY, "amc_fields: particle %llu has a velocity component outside |c| < 2^14 m/s (or NaN); "
-                        "sampling stopped until amc_fields_reset", bad);
+        return amc_fail(c, AMC_ERR_CAPACITY, "%s: particle %llu has a velocity component outside |c| < 2^14 m/s (or NaN); "
+                        "sampling stopped until %s_reset", D.name, bad, D.name);
     if (n_samples) *n_samples = (int64_t)meta[1];
     if (n_outside) *n_outside = (int64_t)meta[2];
     return AMC_OK;
 }
 
-int amc_fields_load(amc_ctx *c, const int64_t *totals, int64_t n_samples, int64_t n_outside)
+static int moments_load(amc_ctx *c, amc_moments_ws &W, const moments_desc &D, const int64_t *totals, int64_t n_samples, int64_t n_outside)
 {
-    if (!c || !totals || n_samples < 0 || n_outside < 0) return AMC_ERR_INVALID;
-    if (!c->F.on) return amc_fail(c, AMC_ERR_STATE, "amc_fields_load before amc_fields_config");
-    AMC_HIP(c, hipSetDevice(c->device));
+    if (!totals || n_samples < 0 || n_outside < 0) return AMC_ERR_INVALID;
+    if (int rc = moments_ready(c, W, D, "load")) return rc;
     const unsigned long long meta[4] = {0, (unsigned long long)n_samples, (unsigned long long)n_outside, 0};
-    return amc_totals_put(c, fields_totals(c->F), totals, meta);
+    return amc_totals_put(c, moments_totals(W, D), totals, meta);
 }
 
-int amc_fields_reset(amc_ctx *c)
-{
-    if (!c) return AMC_ERR_INVALID;
-    if (!c->F.on) return amc_fail(c, AMC_ERR_STATE, "amc_fields_reset before amc_fields_config");
-    AMC_HIP(c, hipSetDevice(c->device));
-    const unsigned long long meta[4] = {0, 0, 0, 0};
-    return amc_totals_put(c, fields_totals(c->F), nullptr, meta);
-}
+extern "C" {
+
+int amc_fields_step(amc_ctx *c) { return amc_fields_due(c, c->out.step) ? moments_enqueue(c, c->F, FIELDS) : AMC_OK; }
+int amc_flux_step(amc_ctx *c) { return amc_flux_due(c, c->out.step) ? moments_enqueue(c, c->FX, FLUX) : AMC_OK; }
+
+int amc_fields_config(amc_ctx *c, const amc_field_grid *g) { return c ? moments_config(c, c->F, FIELDS, g) : AMC_ERR_INVALID; }
+int amc_flux_config(amc_ctx *c, const amc_flux_grid *g) { return c ? moments_config(c, c->FX, FLUX, g) : AMC_ERR_INVALID; }
+
+int amc_fields_sample(amc_ctx *c) { return c ? moments_sample(c, c->F, FIELDS) : AMC_ERR_INVALID; }
+int amc_flux_sample(amc_ctx *c) { return c ? moments_sample(c, c->FX, FLUX) : AMC_ERR_INVALID; }
+
+int amc_fields_read(amc_ctx *c, int64_t *totals, int64_t *n_samples, int64_t *n_outside)
+{ return c ? moments_read(c, c->F, FIELDS, totals, n_samples, n_outside) : AMC_ERR_INVALID; }
+int amc_flux_read(amc_ctx *c, int64_t *totals, int64_t *n_samples, int64_t *n_outside)
+{ return c ? moments_read(c, c->FX, FLUX, totals, n_samples, n_outside) : AMC_ERR_INVALID; }
+
+int amc_fields_load(amc_ctx *c, const int64_t *totals, int64_t n_samples, int64_t n_outside)
+{ return c ? moments_load(c, c->F, FIELDS, totals, n_samples, n_outside) : AMC_ERR_INVALID; }
+int amc_flux_load(amc_ctx *c, const int64_t *totals, int64_t n_samples, int64_t n_outside)
+{ return c ? moments_load(c, c->FX, FLUX, totals, n_samples, n_outside) : AMC_ERR_INVALID; }
+
+int amc_fields_reset(amc_ctx *c) { return c ? moments_reset(c, c->F, FIELDS) : AMC_ERR_INVALID; }
+int amc_flux_reset(amc_ctx *c) { return c ? moments_reset(c, c->FX, FLUX) : AMC_ERR_INVALID; }
 
 }  // extern "C"

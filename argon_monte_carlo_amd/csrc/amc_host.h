@@ -100,7 +100,7 @@ AMC_INTERNAL int amc_flush(amc_ctx *c);                                 // write
 AMC_INTERNAL int amc_enqueue_sweep(amc_ctx *c, bool counted = false, bool defer_commit = false);   // bin (unless counted) + detect + resolve
 AMC_INTERNAL int amc_fields_step(amc_ctx *c);                         // the fields' part of the cadence hook (amc_fields.hip)
 AMC_INTERNAL int amc_corr_step(amc_ctx *c);                           // the correlations' part (amc_corr.hip)
-AMC_INTERNAL int amc_flux_step(amc_ctx *c);                           // the fluxes' part (amc_flux.hip)
+AMC_INTERNAL int amc_flux_step(amc_ctx *c);                           // the fluxes' part (amc_fields.hip)
 
 // amc_timestep, amc_run and the stage calls: not in the middle of a sharded step (the rule above amc_mg_step)
 static inline int amc_mg_step_idle(amc_ctx *c, const char *who)
@@ -110,7 +110,7 @@ static inline int amc_mg_step_idle(amc_ctx *c, const char *who)
                                       "amc_mg_local / amc_upload", who);
 }
 
-// ---- what the samplers share on the host (amc_fields.hip, amc_corr.hip, amc_flux.hip, amc_surface.hip) ------------------------------------
+// ---- what the samplers share on the host (amc_fields.hip, amc_corr.hip, amc_surface.hip) --------------------------------------------------
 // a sample is due after the step that leaves the step counter at `step`
 static inline bool amc_cadence_due(bool on, int64_t every, int64_t step_offset, int64_t step) { return on && every > 0 && (step + step_offset) % every == 0; }
 static inline bool amc_fields_due(const amc_ctx *c, int64_t step) { return amc_cadence_due(c->F.on, c->F.g.every, c->F.g.step_offset, step); }

@@ -229,15 +229,16 @@ struct amc_fields_grid_dev {
     double lo[3], hi[3], w[3];  // w: bin widths (hi - lo) / n, fp64 like NumPy
 };
 
-// sampled fields (amc_fields.hip): the grid, the per-workgroup slab rows of one sample and the 128-bit running totals
-struct amc_fields_ws {
+// a moment sampler (amc_fields.hip; the sampled fields: one table of seven integers per bin, rows = 1; the sampled fluxes:
+// two, rows = 2): the grid, the per-workgroup slab rows of one sample and the 128-bit running totals
+struct amc_moments_ws {
     bool on;
-    amc_field_grid g;
+    amc_field_grid g;           // (amc_flux_grid has the same layout)
     amc_fields_grid_dev G;
-    int max_blocks;             // slab rows allocated (AMC_FIELDS_BLOCKS, else the number of CUs)
-    int blocks_env;             // AMC_FIELDS_BLOCKS at configuration (0: by particle count)
-    unsigned long long *slab;   // [max_blocks][bins * 7 + 1] one sample's sums per workgroup (+ particles outside)
-    unsigned long long *tot;    // [bins][7][2] running totals, (low, high) words
+    int max_blocks;             // slab rows allocated (AMC_FIELDS_BLOCKS / AMC_FLUX_BLOCKS, else the number of CUs)
+    int blocks_env;             // that knob at configuration (0: by particle count)
+    unsigned long long *slab;   // [max_blocks][rows * bins * 7 + 1] one sample's sums per workgroup: row A, row B (+ particles outside)
+    unsigned long long *tot;    // [bins][rows][7][2] running totals, (low, high) words
     unsigned long long *meta;   // [0] unused, [1] samples, [2] particles outside, [3] lowest particle index out of range (~0: none)
 };
 
@@ -268,19 +269,6 @@ struct amc_corr_ws {
     unsigned long long *slab;   // [max_blocks][2 * groups * 7 + 1] one sample's sums per workgroup (+ particles outside)
     unsigned long long *tot;    // [groups][n_lags + 1][7][2] running totals, (low, high) words
     unsigned long long *meta;   // [0] origins, [1] samples, [2] particles outside, [3] lowest particle index out of range (~0: none)
-};
-
-// sampled fluxes (amc_flux.hip): the grid, the per-workgroup slab rows of one sample (two tables of seven integers per bin)
-// and the 128-bit running totals
-struct amc_flux_ws {
-    bool on;
-    amc_flux_grid g;
-    amc_fields_grid_dev G;
-    int max_blocks;             // slab rows allocated (AMC_FLUX_BLOCKS, else the number of CUs)
-    int blocks_env;             // AMC_FLUX_BLOCKS at configuration (0: by particle count)
-    unsigned long long *slab;   // [max_blocks][2 * bins * 7 + 1] one sample's sums per workgroup: rows A, rows B (+ particles outside)
-    unsigned long long *tot;    // [bins][2][7][2] running totals, (low, high) words
-    unsigned long long *meta;   // [0] unused, [1] samples, [2] particles outside, [3] lowest particle index out of range (~0: none)
 };
 
 // What the sharded step leaves pending between two amc_mg_* calls (amc_api_mg.hip).  The rule — a call whose requirement fails
@@ -411,10 +399,10 @@ struct amc_ctx {
     int *d_host_ncand;             // its device address
     amc_temp_ws T;
     amc_temp_dev_ws TD;
-    amc_fields_ws F;
+    amc_moments_ws F;           // the sampled fields
     amc_surface_ws SF;
     amc_corr_ws CR;
-    amc_flux_ws FX;
+    amc_moments_ws FX;          // the sampled fluxes
     // outputs
     amc_out out;
     amc_path_record *d_rec;

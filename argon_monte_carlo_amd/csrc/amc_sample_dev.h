@@ -1,8 +1,8 @@
-// amc_sample_dev.h — what the samplers share on the device: the bin rule of one axis (amc_fields.hip, amc_corr.hip, amc_flux.hip;
-// amc_surface.hip through amc_surface_bin) and of a position (amc_corr.hip; amc_fields_particle and amc_flux_particle have it
-// written out), the velocity quantisers' range (fields, correlations, fluxes), the carry-add into the 128-bit
-// totals (k_sample_reduce, k_surface_accum) and the read of a particle's final state through the deferred results of the last
-// sweep (k_fields_accum, k_corr_accum, k_flux_accum).
+// amc_sample_dev.h — what the samplers share on the device: the bin rule of one axis (amc_fields.hip, amc_corr.hip;
+// amc_surface.hip through amc_surface_bin) and of a position (amc_corr.hip; amc_moments_particle has it written out,
+// DESIGN.md 10), the velocity quantisers' range (fields, correlations, fluxes), the carry-add into the 128-bit totals
+// (k_sample_reduce, k_surface_accum) and the read of a particle's final state through the deferred results of the last sweep
+// (k_moments_accum, k_corr_accum).
 #pragma once
 #include "amc_internal.h"
 

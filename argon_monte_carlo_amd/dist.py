@@ -259,15 +259,19 @@ class ShardedSimulation:
         status — 0, the bad particle's index + 1, or the (negative) error code of any other failure."""
         from . import fields as FL
         g = self.engine.field_grid
+        return self._moments_summed(FL, "fields", g, None if g is None else (FL.grid_bins(g), 7, 2), "fields_reset")
 
+    def _moments_summed(self, mod, name, g, shape, reset):
+        """``fields()`` / ``fluxes()``: the engine's ``<name>_read`` on grid ``g`` (None: not configured) summed over the ranks
+        and derived by ``mod``; ``shape``: the totals', ``reset``: the call the capacity text names."""
         def read():
-            tot, ns, no = self.engine.fields_read()
+            tot, ns, no = getattr(self.engine, name + "_read")()
             return [tot], [no], ns
         (tot,), (no,), ns = self._read_summed(
-            read, None if g is None else [(FL.grid_bins(g), 7, 2)], 1,
-            self._describe("fields_read", "amc_fields: particle {p} (rank {r}) has a velocity component outside |c| < 2^14 m/s (or NaN); "
-                                          "sampling stopped until fields_reset"))
-        return FL.derive(g, tot, ns, no, float(self.params.argon_mass), FL.boltzmann_constant(self.params))
+            read, None if g is None else [shape], 1,
+            self._describe(name + "_read", "amc_" + name + ": particle {p} (rank {r}) has a velocity component outside |c| < 2^14 m/s (or NaN); "
+                                           "sampling stopped until " + reset))
+        return mod.derive(g, tot, ns, no, float(self.params.argon_mass), mod.boltzmann_constant(self.params))
 
     # ---- sampled correlations (correlations.py): every rank samples its own index range, the totals are summed exactly ------
     def enable_correlations(self, grid=None, every=0, n_lags=None):
@@ -321,15 +325,7 @@ class ShardedSimulation:
         rank fails on every rank, from this same call."""
         from . import fluxes as FX
         g = self.engine.flux_grid
-
-        def read():
-            tot, ns, no = self.engine.flux_read()
-            return [tot], [no], ns
-        (tot,), (no,), ns = self._read_summed(
-            read, None if g is None else [FX.totals_shape(g)], 1,
-            self._describe("flux_read", "amc_flux: particle {p} (rank {r}) has a velocity component outside |c| < 2^14 m/s (or NaN); "
-                                        "sampling stopped until fluxes_reset"))
-        return FX.derive(g, tot, ns, no, float(self.params.argon_mass), FX.boltzmann_constant(self.params))
+        return self._moments_summed(FX, "flux", g, None if g is None else FX.totals_shape(g), "fluxes_reset")
 
     def histograms(self):
         """Global free-path histograms = sum over ranks (every completed path is emitted by its particle's owner)."""

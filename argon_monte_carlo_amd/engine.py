@@ -150,11 +150,29 @@ class Engine:
     def reset_outputs(self):
         self._ck(self.lib.amc_reset_outputs(self._ctx))
 
-    # -- sampled fields (fields.py) --------------------------------------------------------------------------------
+    # -- sampled fields (fields.py) and sampled fluxes (fluxes.py): one implementation.  name: the C prefix; attr, grid_type: where
+    # and as what the engine keeps the grid (g); rows: tables of seven totals per bin ---------------------------------------
+    def _moments_config(self, name, attr, grid_type, grid):
+        self._ck(getattr(self.lib, f"amc_{name}_config")(self._ctx, None if grid is None else C.byref(grid)))
+        setattr(self, attr, None if grid is None else grid_type.from_buffer_copy(grid))
+
+    def _moments_read(self, name, g, rows):
+        if g is None:
+            raise _lib.ArgonMCError(-6, f"{name}_read before {name}_config")
+        tot = np.zeros((int(g.n1) * int(g.n2) * int(g.n3),) + (rows,) * (rows > 1) + (7, 2), dtype=np.int64)
+        ns, no = C.c_int64(0), C.c_int64(0)
+        self._ck(getattr(self.lib, f"amc_{name}_read")(self._ctx, tot.ctypes.data_as(_i64p), C.byref(ns), C.byref(no)))
+        return tot, ns.value, no.value
+
+    def _moments_load(self, name, g, rows, totals, n_samples, n_outside):
+        tot = np.ascontiguousarray(totals, dtype=np.int64)
+        if g is None or tot.size != int(g.n1) * int(g.n2) * int(g.n3) * 14 * rows:
+            raise ValueError("totals do not match the configured grid")
+        self._ck(getattr(self.lib, f"amc_{name}_load")(self._ctx, tot.ctypes.data_as(_i64p), int(n_samples), int(n_outside)))
+
     def fields_config(self, grid):
         """Sample on ``grid`` (an ``AmcFieldGrid``, fields.make_grid); None switches sampling off.  Starts from zero totals."""
-        self._ck(self.lib.amc_fields_config(self._ctx, None if grid is None else C.byref(grid)))
-        self.field_grid = None if grid is None else AmcFieldGrid.from_buffer_copy(grid)
+        self._moments_config("fields", "field_grid", AmcFieldGrid, grid)
 
     def fields_sample(self):
         """One sample of the current state, enqueued on the context's stream."""
@@ -162,23 +180,31 @@ class Engine:
 
     def fields_read(self):
         """(int64[bins, 7, 2] totals as (low, high) words, samples, particles outside); synchronises."""
-        g = self.field_grid
-        if g is None:
-            raise _lib.ArgonMCError(-6, "fields_read before fields_config")
-        tot = np.zeros((int(g.n1) * int(g.n2) * int(g.n3), 7, 2), dtype=np.int64)
-        ns, no = C.c_int64(0), C.c_int64(0)
-        self._ck(self.lib.amc_fields_read(self._ctx, tot.ctypes.data_as(_i64p), C.byref(ns), C.byref(no)))
-        return tot, ns.value, no.value
+        return self._moments_read("fields", self.field_grid, 1)
 
     def fields_load(self, totals, n_samples, n_outside):
-        tot = np.ascontiguousarray(totals, dtype=np.int64)
-        g = self.field_grid
-        if g is None or tot.size != int(g.n1) * int(g.n2) * int(g.n3) * 14:
-            raise ValueError("totals do not match the configured grid")
-        self._ck(self.lib.amc_fields_load(self._ctx, tot.ctypes.data_as(_i64p), int(n_samples), int(n_outside)))
+        self._moments_load("fields", self.field_grid, 1, totals, n_samples, n_outside)
 
     def fields_reset(self):
         self._ck(self.lib.amc_fields_reset(self._ctx))
+
+    def flux_config(self, grid):
+        """Sample on ``grid`` (an ``AmcFluxGrid``, fluxes.make_grid); None switches sampling off.  Starts from zero totals."""
+        self._moments_config("flux", "flux_grid", AmcFluxGrid, grid)
+
+    def flux_sample(self):
+        """One sample of the current state, enqueued on the context's stream."""
+        self._ck(self.lib.amc_flux_sample(self._ctx))
+
+    def flux_read(self):
+        """(int64[bins, 2, 7, 2] totals as (low, high) words, samples, particles outside); synchronises."""
+        return self._moments_read("flux", self.flux_grid, 2)
+
+    def flux_load(self, totals, n_samples, n_outside):
+        self._moments_load("flux", self.flux_grid, 2, totals, n_samples, n_outside)
+
+    def flux_reset(self):
+        self._ck(self.lib.amc_flux_reset(self._ctx))
 
     # -- sampled correlations (correlations.py) ----------------------------------------------------------------------
     def corr_config(self, grid):
@@ -226,36 +252,6 @@ class Engine:
 
     def corr_reset(self):
         self._ck(self.lib.amc_corr_reset(self._ctx))
-
-    # -- sampled fluxes (fluxes.py) ----------------------------------------------------------------------------------
-    def flux_config(self, grid):
-        """Sample on ``grid`` (an ``AmcFluxGrid``, fluxes.make_grid); None switches sampling off.  Starts from zero totals."""
-        self._ck(self.lib.amc_flux_config(self._ctx, None if grid is None else C.byref(grid)))
-        self.flux_grid = None if grid is None else AmcFluxGrid.from_buffer_copy(grid)
-
-    def flux_sample(self):
-        """One sample of the current state, enqueued on the context's stream."""
-        self._ck(self.lib.amc_flux_sample(self._ctx))
-
-    def flux_read(self):
-        """(int64[bins, 2, 7, 2] totals as (low, high) words, samples, particles outside); synchronises."""
-        g = self.flux_grid
-        if g is None:
-            raise _lib.ArgonMCError(-6, "flux_read before flux_config")
-        tot = np.zeros((int(g.n1) * int(g.n2) * int(g.n3), 2, 7, 2), dtype=np.int64)
-        ns, no = C.c_int64(0), C.c_int64(0)
-        self._ck(self.lib.amc_flux_read(self._ctx, tot.ctypes.data_as(_i64p), C.byref(ns), C.byref(no)))
-        return tot, ns.value, no.value
-
-    def flux_load(self, totals, n_samples, n_outside):
-        tot = np.ascontiguousarray(totals, dtype=np.int64)
-        g = self.flux_grid
-        if g is None or tot.size != int(g.n1) * int(g.n2) * int(g.n3) * 28:
-            raise ValueError("totals do not match the configured grid")
-        self._ck(self.lib.amc_flux_load(self._ctx, tot.ctypes.data_as(_i64p), int(n_samples), int(n_outside)))
-
-    def flux_reset(self):
-        self._ck(self.lib.amc_flux_reset(self._ctx))
 
     # -- measurement -----------------------------------------------------------------------------------------------
     def set_stream(self, stream_ptr):

@@ -31,24 +31,17 @@ DEFAULT_CUBE_BINS = (8, 8, 8)
 DEFAULT_PORE_BINS = (8, 128)
 
 
-def _from_field_grid(f):
-    """the ``AmcFieldGrid`` f as an ``AmcFluxGrid`` (the same fields), refused beyond AMC_FLUX_MAX_BINS"""
-    if grid_bins(f) > AMC_FLUX_MAX_BINS:            # (tighter than the fields' limit: fourteen integers per bin, not seven)
-        raise ValueError(f"{f.n1} x {f.n2} x {f.n3} bins: at most {AMC_FLUX_MAX_BINS} bins in all")
-    g = AmcFluxGrid.from_buffer_copy(f)
-    g.struct_size = C.sizeof(AmcFluxGrid)
-    return g
-
-
 def make_grid(kind, n, lo, hi, every=0, step_offset=0):
     """An ``AmcFluxGrid``, validated like ``amc_flux_config`` (ValueError instead of AMC_ERR_INVALID): the axes and rules of
     ``fields.make_grid``, at most 1024 bins."""
     bins = 1
     for v in n:
         bins *= max(int(v), 1)
-    if bins > AMC_FLUX_MAX_BINS:
+    if bins > AMC_FLUX_MAX_BINS:                    # (tighter than the fields' limit: fourteen integers per bin, not seven)
         raise ValueError(f"{bins} bins: at most {AMC_FLUX_MAX_BINS} in all")
-    return _from_field_grid(FL.make_grid(kind, n, lo, hi, every, step_offset))
+    g = AmcFluxGrid.from_buffer_copy(FL.make_grid(kind, n, lo, hi, every, step_offset))      # (the same fields)
+    g.struct_size = C.sizeof(AmcFluxGrid)
+    return g
 
 
 def default_grid(params, every=0):
@@ -65,7 +58,8 @@ def totals_shape(g):
 
 def grid_from_array(a):
     """the inverse of ``grid_to_array`` (float64[12], the fields' layout)"""
-    return _from_field_grid(FL.grid_from_array(a))
+    f = FL.grid_from_array(a)
+    return make_grid(f.kind, (f.n1, f.n2, f.n3), list(f.lo), list(f.hi), f.every, f.step_offset)
 
 
 # ---- derived quantities -----------------------------------------------------------------------------------------------

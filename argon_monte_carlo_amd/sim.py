@@ -133,13 +133,35 @@ class Simulation:
         dens, edges = self.histograms()
         OUT.write_histograms(directory, dens, edges)
 
+    # ---- what the sampled fields and the sampled fluxes share.  mod: the sampler's module (fields / fluxes); name: the prefix of
+    # its engine methods and checkpoint keys ("fields" / "flux"); g: the engine's grid of it (None: off)
+    def _moments_enable(self, mod, name, grid, every):
+        g = mod.default_grid(self.params) if grid is None else grid
+        # (the device's step counter restarts at a resumed checkpoint: the cadence counts from the run's first step)
+        getattr(self.engine, name + "_config")(mod.copy_grid(g, every=every, step_offset=getattr(self, "_step_base", 0)))
+
+    def _moments_derive(self, mod, name, g):
+        return mod.derive(g, *getattr(self.engine, name + "_read")(), float(self.params.argon_mass), mod.boltzmann_constant(self.params))
+
+    def _moments_checkpoint(self, mod, name, g):
+        if g is None:
+            return {}
+        tot, ns, no = getattr(self.engine, name + "_read")()
+        return {name + "_grid": mod.grid_to_array(g), name + "_totals": tot, name + "_n_samples": int(ns), name + "_n_outside": int(no)}
+
+    def _moments_restore(self, mod, name, z):
+        """grid, totals and counters from the checkpoint z; False if it has none of this sampler (nothing is changed then)"""
+        if name + "_grid" not in z:
+            return False
+        getattr(self.engine, name + "_config")(mod.copy_grid(mod.grid_from_array(z[name + "_grid"]), step_offset=self._step_base))
+        getattr(self.engine, name + "_load")(z[name + "_totals"], int(z[name + "_n_samples"]), int(z[name + "_n_outside"]))
+        return True
+
     # ---- sampled fields (fields.py, DESIGN.md 10; the reference has no such output) ---------------------------------------
     def enable_fields(self, grid=None, every=0):
         """Sample number density, flow velocity and temperature per bin of ``grid`` (fields.make_grid; None = the geometry's
         default, fields.default_grid) after every ``every``-th step (0: only on ``fields_sample()``).  Starts from zero."""
-        g = FL.default_grid(self.params) if grid is None else grid
-        # (the device's step counter restarts at a resumed checkpoint: the cadence counts from the run's first step)
-        self.engine.fields_config(FL.copy_grid(g, every=every, step_offset=getattr(self, "_step_base", 0)))
+        self._moments_enable(FL, "fields", grid, every)
 
     def disable_fields(self):
         self.engine.fields_config(None)
@@ -155,25 +177,18 @@ class Simulation:
         """dict: count, number_density (m^-3), velocity and temperature (bins x 3: x, y, z components on a Cartesian grid,
         r, theta, z on an axisymmetric one), T (mean of the three), edges, bin_volume, n_samples, n_outside and the raw
         integer totals (int64[bins, 7, 2], 128-bit (low, high) words).  Bins in linear order (i1 * n2 + i2) * n3 + i3."""
-        tot, ns, no = self.engine.fields_read()
-        return FL.derive(self.engine.field_grid, tot, ns, no, float(self.params.argon_mass), FL.boltzmann_constant(self.params))
+        return self._moments_derive(FL, "fields", self.engine.field_grid)
 
     def write_fields(self, path):
         """The dict of ``fields()`` as an .npz (edges as edges_1, edges_2[, edges_3])."""
         _write_npz(path, self.fields())
 
     def _fields_checkpoint(self):
-        if self.engine.field_grid is None:
-            return {}
-        tot, ns, no = self.engine.fields_read()
-        return dict(fields_grid=FL.grid_to_array(self.engine.field_grid), fields_totals=tot, fields_n_samples=int(ns),
-                    fields_n_outside=int(no))
+        return self._moments_checkpoint(FL, "fields", self.engine.field_grid)
 
     def _fields_restore(self, z):
-        if "fields_grid" in z:
-            self.engine.fields_config(FL.copy_grid(FL.grid_from_array(z["fields_grid"]), step_offset=self._step_base))
-            self.engine.fields_load(z["fields_totals"], int(z["fields_n_samples"]), int(z["fields_n_outside"]))
-        elif self.engine.field_grid is not None:      # fields on here, not in the checkpoint: they start with the resumed run
+        if not self._moments_restore(FL, "fields", z) and self.engine.field_grid is not None:
+            # fields on here, not in the checkpoint: they start with the resumed run
             self.engine.fields_config(FL.copy_grid(self.engine.field_grid, step_offset=self._step_base))
 
     # ---- sampled correlations (correlations.py, DESIGN.md 12; the reference has no such output) ---------------------------
@@ -232,8 +247,7 @@ class Simulation:
         (fluxes.make_grid; None = the geometry's default, fluxes.default_grid) after every ``every``-th step (0: only on
         ``fluxes_sample()``).  Starts from zero.  Independent of ``enable_fields``."""
         from . import fluxes as FX
-        g = FX.default_grid(self.params) if grid is None else grid
-        self.engine.flux_config(FX.copy_grid(g, every=every, step_offset=getattr(self, "_step_base", 0)))
+        self._moments_enable(FX, "flux", grid, every)
 
     def disable_fluxes(self):
         self.engine.flux_config(None)
@@ -251,8 +265,7 @@ class Simulation:
         one — edges, bin_volume, n_samples, n_outside and the raw integer totals (int64[bins, 2, 7, 2], 128-bit (low, high)
         words).  Bins in linear order (i1 * n2 + i2) * n3 + i3."""
         from . import fluxes as FX
-        tot, ns, no = self.engine.flux_read()
-        return FX.derive(self.engine.flux_grid, tot, ns, no, float(self.params.argon_mass), FX.boltzmann_constant(self.params))
+        return self._moments_derive(FX, "flux", self.engine.flux_grid)
 
     def write_fluxes(self, path):
         """The dict of ``fluxes()`` as an .npz (edges as edges_1, edges_2[, edges_3])."""
@@ -261,19 +274,13 @@ class Simulation:
     # ---- checkpoint / resume (the reference has none: a 10^4-step run is one process lifetime there) ---------------
     def _checkpoint_extra(self):
         """what a subclass adds to a checkpoint (it extends this dict) — here: grid, totals and counters of the sampled fluxes"""
-        if self.engine.flux_grid is None:
-            return {}
         from . import fluxes as FX
-        tot, ns, no = self.engine.flux_read()
-        return dict(flux_grid=FX.grid_to_array(self.engine.flux_grid), flux_totals=tot, flux_n_samples=int(ns), flux_n_outside=int(no))
+        return self._moments_checkpoint(FX, "flux", self.engine.flux_grid)
 
     def _restore_extra(self, z):
         """the inverse; a subclass calls it once ``_step_base`` is final (the cadence counts from the run's first step)"""
         from . import fluxes as FX
-        if "flux_grid" in z:
-            self.engine.flux_config(FX.copy_grid(FX.grid_from_array(z["flux_grid"]), step_offset=self._step_base))
-            self.engine.flux_load(z["flux_totals"], int(z["flux_n_samples"]), int(z["flux_n_outside"]))
-        else:                                           # a checkpoint without them: sampling is off in the resumed run
+        if not self._moments_restore(FX, "flux", z):   # a checkpoint without them: sampling is off in the resumed run
             self.engine.flux_config(None)
 
     def save_checkpoint(self, path):

@@ -400,7 +400,7 @@ int amc_mg_finish(amc_ctx *ctx, amc_step_stats *out);      /* out == NULL: no ho
 #define AMC_K_COMMIT 9           /* k_commit: a sweep's commit as a launch of its own (else it rides along with the next k_stream) */
 #define AMC_K_CLUSTERS_WIDE 10   /* k_clusters_wide: every small cluster emulated and validated wide, before the ordered workgroup */
 #define AMC_K_FIXUP 11           /* k_fixup: joins an overlapped run's early streaming pass with the sweep's results (below) */
-#define AMC_K_FIELDS 12          /* k_fields_accum + k_fields_reduce: one sample of the fields (below); the surfaces' and the correlations' kernels too */
+#define AMC_K_FIELDS 12          /* k_moments_accum + k_sample_reduce: one sample of the fields (below); the surfaces' and the correlations' kernels too */
 #define AMC_K_COUNT 13
 int amc_profile(amc_ctx *ctx, int enable);
 int amc_kernel_times(amc_ctx *ctx, double *total_ms /*[AMC_K_COUNT]*/, int64_t *launches /*[AMC_K_COUNT]*/);

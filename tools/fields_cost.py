@@ -1,4 +1,4 @@
-"""Cost of the sampled fields on one GPU: the per-sample kernel time (kernel class "fields": k_fields_accum +
+"""Cost of the sampled fields on one GPU: the per-sample kernel time (kernel class "fields": k_moments_accum<1> +
 k_sample_reduce, timed on the dispatch like every other class) and the overhead of run(100) with a sample every 10 steps
 against run(100) without sampling.  Prints one JSON line per workload.
 
