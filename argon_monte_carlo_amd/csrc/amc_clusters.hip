@@ -53,7 +53,7 @@
 
 AMC_DEV int cw_adj_head(const amc_resolve_ws &W, unsigned int epoch, int p)
 {
-    const unsigned long long v = W.adj_head[p];
+    const unsigned long long v = amc_g(W.adj_head)[p];
     return ((unsigned int)(v >> 32) == epoch) ? (int)(unsigned int)(v & 0xffffffffULL) : -1;
 }
 
@@ -62,19 +62,21 @@ AMC_DEV int cw_adj_head(const amc_resolve_ws &W, unsigned int epoch, int p)
 
 AMC_DEV void cw_init_slot(const amc_resolve_ws &W, int s, int p, int label, int gen, bool fresh = false)
 {
-    W.slot_of[p] = s; W.sl_moved[s] = 0;
+    amc_g(W.slot_of)[p] = s; amc_g(W.sl_moved)[s] = 0;
     // (particle, label, round, -) written through: a prober of another workgroup that meets one of this slot's history
     // entries compares rounds
-    unsigned long long *m = (unsigned long long *)&W.sl_meta[s];
+    auto *m = amc_g((unsigned long long *)&W.sl_meta[s]);
     __hip_atomic_store(m + 0, ((unsigned long long)(unsigned int)label << 32) | (unsigned int)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(m + 1, (unsigned long long)(unsigned int)gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (!fresh) atomicAnd(&W.sl_hits[s], 0);    // (an atomic, like the increments that follow; a candidate's own slot was
                                                 // zeroed by the detect kernel when it pushed the candidate)
+    // (the one access of this kernel left FLAT, six copies, none on an isolated pair's path: typed like its neighbours it
+    // costs the pore instantiation two more VGPRs than it had — DESIGN.md 7, round 16)
 }
 
 AMC_DEV double4 cw_load_hist(const amc_resolve_ws &W, int h)
 {
-    const double *d = (const double *)&W.hist[h];
+    const auto *d = amc_g((const double *)&W.hist[h]);       // (global sc1 loads: the reader side of the write-through hand-off)
     double4 r;
     r.x = __hip_atomic_load(d + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     r.y = __hip_atomic_load(d + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -117,7 +119,7 @@ AMC_DEV void cw_probe_grid(const rs_args &A, rs_shared *wc, cw_lds &L, const cw_
     const double x = me.x, y = me.y, z = me.z;
     int q = amc_list_head(A.B, cell);
     while (q >= 0) {
-        const amc_rec r = A.B.rec[q];
+        const amc_rec r = amc_g_load(&A.B.rec[q]);
         const int idx = amc_node_particle(A.B, q);
         q = amc_rec_next(r);
         double rx, ry, rz;
@@ -130,20 +132,20 @@ AMC_DEV void cw_probe_grid(const rs_args &A, rs_shared *wc, cw_lds &L, const cw_
         if (cw_adj_head(W, A.sweep_epoch, idx) < 0) {
             // in no candidate: pull it into this cluster, unless somebody else got it first
             const int tag = -(lab + 2);
-            const int old = atomicCAS(&W.slot_of[idx], -1, tag);
+            const int old = amc_atomic_cas(amc_g(W.slot_of) + idx, -1, tag);
             if (old == tag) continue;                           // another position of my cluster found it too
             if (old == -1) {
-                const int s = s_off + atomicAdd(&wc->nslots, 1);
+                const int s = s_off + rs_count_add(&amc_g(wc)->nslots, 1);      // (one atomic for the lanes that are here)
                 const int k = atomicAdd(&L.npull[own], 1);
-                W.victim[idx] = A.sweep_epoch;                  // (in no candidate: an overlapped streaming pass has advanced it)
+                amc_g(W.victim)[idx] = A.sweep_epoch;           // (in no candidate: an overlapped streaming pass has advanced it)
                 if (s < W.max_slots && k < CW_PULLS) {
                     L.pull[own][k] = idx; L.psl[own][k] = s;   // (slot_of keeps the tag until the owner initialises the slot)
                     L.redo[own] = 1;
                     continue;
                 }
-                if (s >= W.max_slots) { wc->ovf = 1; rs_raise(W); }
-                else { W.sl_meta[s] = make_int4(idx, s, 0, 0); W.sl_moved[s] = 0; atomicAnd(&W.sl_hits[s], 0); }
-                W.slot_of[idx] = s < W.max_slots ? s : -1;      // too many at once: a plain merge edge instead
+                if (s >= W.max_slots) { amc_g(wc)->ovf = 1; rs_raise(W); }
+                else { amc_g_store(&W.sl_meta[s], make_int4(idx, s, 0, 0)); amc_g(W.sl_moved)[s] = 0; amc_atomic_and(amc_g(W.sl_hits) + s, 0); }
+                amc_g(W.slot_of)[idx] = s < W.max_slots ? s : -1;       // too many at once: a plain merge edge instead
             }
         }
         rs_add_edge(W, wc, me.p, idx);
@@ -172,12 +174,12 @@ AMC_DEV void cw_probe_overlay(const rs_args &A, rs_shared *wc, cw_lds &L, const 
         }
         return h2;
     };
-    int h2 = skip_own(__hip_atomic_load(&W.ov_head[cell], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    int h2 = skip_own(__hip_atomic_load(amc_g(W.ov_head) + cell, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
     int guard = 0;
     while (h2 >= 0) {
-        if (++guard > W.max_hist) { wc->ovf = 1; rs_raise(W); break; }      // (a list cannot be longer than there are entries: reported, not spun on)
+        if (++guard > W.max_hist) { amc_g(wc)->ovf = 1; rs_raise(W); break; }      // (a list cannot be longer than there are entries: reported, not spun on)
         const double4 o = cw_load_hist(W, h2);
-        const int nx = __hip_atomic_load(&W.ov_next[h2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int nx = __hip_atomic_load(amc_g(W.ov_next) + h2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         h2 = skip_own(nx);
         const double ax = o.x - x, ay = o.y - y, az = o.z - z;
         if (!(ax * ax + ay * ay + az * az < cr2i)) continue;
@@ -186,7 +188,7 @@ AMC_DEV void cw_probe_overlay(const rs_args &A, rs_shared *wc, cw_lds &L, const 
         for (int m = 0; m < nm; m++) mine |= L.msl[own][m] == s2;
         if (mine) continue;
         // (only final emulations are ever published, but the ordered workgroup's rounds are told apart the same way)
-        if (rs_hist_gen(o) != __hip_atomic_load(((int *)&W.sl_meta[s2]) + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) continue;
+        if (rs_hist_gen(o) != __hip_atomic_load(amc_g((int *)&W.sl_meta[s2]) + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) continue;
         rs_add_edge(W, wc, me.p, -(s2 + 2));                    // (the other end as a slot)
     }
 }
@@ -231,10 +233,10 @@ AMC_DEV void cw_wide_hooks(rs_wide &wd, cw_lds &L, int own, int h_off)
 AMC_DEV void cw_candidate_slots(const amc_resolve_ws &W, cw_lds &L, int own, int e)
 {
     const int c = L.cnd[own][e], m = L.nm[own];
-    const int4 cc = W.cand4[c];
+    const int4 cc = amc_g_load(&W.cand4[c]);
     int ai = 0, aj = 0;
     for (int t = 0; t < m; t++) { if (L.mem[own][t] == cc.x) ai = t; if (L.mem[own][t] == cc.y) aj = t; }
-    W.cand_s[c] = make_int4(L.msl[own][ai], L.msl[own][aj], 1, 0);
+    amc_g_store(&W.cand_s[c], make_int4(L.msl[own][ai], L.msl[own][aj], 1, 0));
 }
 
 template <int GEOM, bool DBG>
@@ -292,8 +294,8 @@ __global__ __launch_bounds__(64 * CW_WPB) void k_clusters_wide(rs_args A_in_kern
     if (stalled && A.od_tick > stalled) return;
     if (ncand > W.max_cand) ncand = W.max_cand;
     if (wave_id == 0 && lane == 0) {
-        wc->active = 1; wc->ncand = ncand;
-        if (A.od_done) *A.od_done = A.od_tick;          // (host-mapped: how far the host may run ahead)
+        amc_g(wc)->active = 1; amc_g(wc)->ncand = ncand;
+        if (A.od_done) *amc_g(A.od_done) = A.od_tick;   // (host-mapped: how far the host may run ahead)
     }
     if (ncand == 0) return;
     const int s_off = 2 * ncand;        // first counter-allocated slot of this sweep (candidate k owns slots 2k, 2k + 1)
@@ -337,8 +339,8 @@ __global__ __launch_bounds__(64 * CW_WPB) void k_clusters_wide(rs_args A_in_kern
         int4 c4b = make_int4(0, 0, -1, -1);
         unsigned long long mkb = 0;
         if (valid) {
-            c4 = (k == k_first) ? c4_first : W.cand4[k];
-            const unsigned long long mk = (k == k_first) ? mark_first : W.cand_mark[k];
+            c4 = (k == k_first) ? c4_first : amc_g_load(&W.cand4[k]);
+            const unsigned long long mk = (k == k_first) ? mark_first : amc_g(W.cand_mark)[k];
             const bool marked = (unsigned int)(mk >> 32) == A.sweep_epoch;
             // alone on both particles: nobody before it in either list, nobody displaced it from either head (the detect
             // kernel marks the displaced candidate) — decided from candidate-indexed words only
@@ -347,7 +349,7 @@ __global__ __launch_bounds__(64 * CW_WPB) void k_clusters_wide(rs_args A_in_kern
                 const unsigned int succ = (unsigned int)(mk & 0xffffffffULL);
                 if (succ != AMC_MARK_MULTI && (int)succ > k && (int)succ < ncand) k2 = (int)succ;
             }
-            if (k2 >= 0) { c4b = W.cand4[k2]; mkb = W.cand_mark[k2]; }
+            if (k2 >= 0) { c4b = amc_g_load(&W.cand4[k2]); mkb = amc_g(W.cand_mark)[k2]; }
             else if (!iso) {                // part of a larger component: the walk below starts at the particles' heads
                 head_i = cw_adj_head(W, A.sweep_epoch, c4.x);
                 head_j = cw_adj_head(W, A.sweep_epoch, c4.y);
@@ -382,19 +384,19 @@ __global__ __launch_bounds__(64 * CW_WPB) void k_clusters_wide(rs_args A_in_kern
                 int c = cur == 0 ? head_j : (cur == 1 ? head_i : cw_adj_head(W, A.sweep_epoch, p));
                 while (c >= 0) {
                     if (c < k) { owner = false; break; }            // the component belongs to a lower candidate's lane
-                    const int4 r = (c == k) ? c4 : W.cand4[c];
+                    const int4 r = (c == k) ? c4 : amc_g_load(&W.cand4[c]);
                     const int q = (r.x == p) ? r.y : r.x;
                     const int nx = (r.x == p) ? r.z : r.w;
                     bool seen = false;
                     for (int e = 0; e < nc; e++) seen |= cnd[e] == c;
                     if (!seen) {
-                        if (nc == CW_MAXC) { owner = false; wc->changed = 1; rs_raise(W); break; }       // too large for this kernel: left to the ordered workgroup
+                        if (nc == CW_MAXC) { owner = false; amc_g(wc)->changed = 1; rs_raise(W); break; }       // too large for this kernel: left to the ordered workgroup
                         cnd[nc++] = c;
                     }
                     seen = false;
                     for (int e = 0; e < nm; e++) seen |= mem[e] == q;
                     if (!seen) {
-                        if (nm == CW_MAXM) { owner = false; wc->changed = 1; rs_raise(W); break; }
+                        if (nm == CW_MAXM) { owner = false; amc_g(wc)->changed = 1; rs_raise(W); break; }
                         mem[nm++] = q;
                     }
                     c = nx;
@@ -421,7 +423,7 @@ __global__ __launch_bounds__(64 * CW_WPB) void k_clusters_wide(rs_args A_in_kern
         {
             // statistics: one counter per bank of waves (2000 waves adding to ONE word are a 24 us chain of same-address atomics)
             const int ncl = __popcll(__ballot(take));
-            if (lane == 0 && ncl) atomicAdd(&W.wctl[32 + (wave_id & 15)], ncl);
+            if (lane == 0 && ncl) amc_atomic_add(amc_g(W.wctl) + 32 + (wave_id & 15), ncl);
         }
         rs_wave_sync();
         CW_STAMP(2);
@@ -440,7 +442,7 @@ __global__ __launch_bounds__(64 * CW_WPB) void k_clusters_wide(rs_args A_in_kern
                     const int pj = mem[0], pi = mem[1], sj = L.msl[lane][0], si = L.msl[lane][1];
                     cw_init_slot(W, sj, pj, lab, g + 1, true);
                     cw_init_slot(W, si, pi, lab, g + 1, true);
-                    W.cand_s[k] = make_int4(si, sj, 1, 0);
+                    amc_g_store(&W.cand_s[k], make_int4(si, sj, 1, 0));
                     CW_STAMP(11);
                     amc_particle p1 = pre_j, p2 = pre_i;
                     const bool mv = rs_emulate_pair_io<GEOM>(A, wc, p1, p2, pj, pi, sj, si, &wd);
@@ -538,7 +540,7 @@ __global__ __launch_bounds__(64 * CW_WPB) void k_clusters_wide(rs_args A_in_kern
                     const cw_item it = L.item[t];
                     if (it.pad & 1) continue;
                     for (int c = sub; c < 8; c += lpi) {
-                        const int cell = amc_grid_box_cell(A.G, it.x, it.y, it.z, A.G.cr_probe, c);
+                        const int cell = amc_grid_box_cell<true>(A.G, it.x, it.y, it.z, A.G.cr_probe, c);
                         if (cell >= 0) cw_probe_grid(A, wc, L, it, cell, s_off);
                     }
                 }
@@ -572,13 +574,13 @@ __global__ __launch_bounds__(64 * CW_WPB) void k_clusters_wide(rs_args A_in_kern
                 if (!(it.pad & 1) && (it.pad >> 1) == L.gen[it.own]) {  // (an item of a dropped emulation is skipped)
                     int cx, cy, cz;
                     amc_grid_coords(A.G, it.x, it.y, it.z, cx, cy, cz);
-                    const int cell = amc_grid_cell(A.G, cx, cy, cz, nullptr);
+                    const int cell = amc_grid_cell<true>(A.G, cx, cy, cz, nullptr);
                     int expected = -1;                              // (the record was stored with next = -1)
                     for (;;) {
-                        const int old = atomicCAS(&W.ov_head[cell], expected, it.h);
+                        const int old = amc_atomic_cas(amc_g(W.ov_head) + cell, expected, it.h);
                         if (old == expected) break;
                         expected = old;
-                        __hip_atomic_store(&W.ov_next[it.h], old, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        __hip_atomic_store(amc_g(W.ov_next) + it.h, old, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                     }
                     L.next[t] = expected;
@@ -595,7 +597,7 @@ __global__ __launch_bounds__(64 * CW_WPB) void k_clusters_wide(rs_args A_in_kern
                 const cw_item it = L.item[t];
                 if ((it.pad & 1) || (it.pad >> 1) != L.gen[it.own]) continue;
                 for (int c = sub; c < 8; c += lpi) {
-                    const int cell = amc_grid_box_cell(A.G, it.x, it.y, it.z, A.G.cr_probe, c);
+                    const int cell = amc_grid_box_cell<true>(A.G, it.x, it.y, it.z, A.G.cr_probe, c);
                     if (cell >= 0) cw_probe_overlay(A, wc, L, it, cell, cr2i, h_off);
                 }
             }

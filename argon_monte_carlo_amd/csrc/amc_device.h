@@ -14,6 +14,40 @@
 
 #define AMC_DEV __device__ __forceinline__
 
+// ---- address spaces ------------------------------------------------------------------------------------------------------
+// A pointer that device code takes out of an argument block it reads from LDS (or through several levels of structures)
+// has no address space the compiler can prove, and every access through it becomes a FLAT instruction: one that counts
+// in vmcnt AND lgkmcnt — a wait for an LDS read behind it also waits for the memory round trip — and that carries its
+// whole 64-bit address in VGPRs.  amc_g(p) types a pointer to device (or host-mapped) memory at the point of use; the
+// access itself must be made through what it returns (`auto *`), a cast back to a generic pointer is FLAT again.
+// Pointers into LDS the compiler has so far traced by itself once everything is inlined.  The layouts of the argument
+// structures are untouched (the host fills them).
+#define AMC_AS_GLOBAL __attribute__((address_space(1)))
+template <class T> AMC_DEV AMC_AS_GLOBAL T *amc_g(T *p) { return (AMC_AS_GLOBAL T *)p; }
+// whole records (int4, double4, amc_rec, rs_event ..: class types have no assignment across address spaces): moved as
+// a vector of words with the record's own alignment
+template <class T> struct amc_words {
+    static_assert(sizeof(T) % 4 == 0 && (sizeof(T) / 4 & (sizeof(T) / 4 - 1)) == 0, "record of 1, 2, 4, 8, 16 words");
+    typedef unsigned int type __attribute__((ext_vector_type(sizeof(T) / 4), aligned(alignof(T))));
+};
+template <class T> AMC_DEV T amc_g_load(const T *p)
+{
+    return __builtin_bit_cast(T, *(const AMC_AS_GLOBAL typename amc_words<T>::type *)p);
+}
+template <class T> AMC_DEV void amc_g_store(T *p, const T &v)
+{
+    *(AMC_AS_GLOBAL typename amc_words<T>::type *)p = __builtin_bit_cast(typename amc_words<T>::type, v);
+}
+// HIP's atomicAdd / atomicAnd / atomicCAS take generic pointers; these are the same operations (relaxed, agent scope) on a
+// pointer of any address space
+template <class P, class V> AMC_DEV V amc_atomic_add(P p, V v) { return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+template <class P, class V> AMC_DEV V amc_atomic_and(P p, V v) { return __hip_atomic_fetch_and(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+template <class P, class V> AMC_DEV V amc_atomic_cas(P p, V compare, V v)
+{
+    __hip_atomic_compare_exchange_strong(p, &compare, v, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return compare;
+}
+
 // device-global work counters (one struct in device memory per ctx)
 struct amc_dev_counters {
     unsigned long long n_pp, n_wall, n_oob_walls, n_oob_pp, n_paths, n_candidates, n_clusters, n_rounds, n_fp_errors,

@@ -3,6 +3,11 @@
 #include "amc_internal.h"
 
 AMC_DEV int amc_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+template <bool GLOBAL> AMC_DEV auto amc_lay(const int *p)
+{
+    if constexpr (GLOBAL) return amc_g(p);
+    else return p;
+}
 
 AMC_DEV void amc_grid_coords(const amc_grid &G, double x, double y, double z, int &cx, int &cy, int &cz)
 {
@@ -13,17 +18,20 @@ AMC_DEV void amc_grid_coords(const amc_grid &G, double x, double y, double z, in
 
 // linear id of the cell that STORES a particle with coordinates (cx,cy,cz): coordinates outside the layer's window
 // are clamped into it (cannot happen for in-bounds particles; *outside is set so the caller can flag it)
+// LAY_GLOBAL: the caller knows the layer tables to be in device memory (amc_device.h, "address spaces") — not so in the
+// ordered workgroup, which points G at a copy in its LDS
+template <bool LAY_GLOBAL = false>
 AMC_DEV int amc_grid_cell(const amc_grid &G, int cx, int cy, int cz, bool *outside)
 {
     if (G.uniform) return (cz * G.gy + cy) * G.gx + cx;      // coordinates are already clamped into the full window
-    const int lo = G.lay_lo[cz], n = G.lay_n[cz];
+    const int lo = amc_lay<LAY_GLOBAL>(G.lay_lo)[cz], n = amc_lay<LAY_GLOBAL>(G.lay_n)[cz];
     int lx = cx - lo, ly = cy - lo;
     if (lx < 0 || lx >= n || ly < 0 || ly >= n) {
         if (outside) *outside = true;
         lx = amc_clampi(lx, 0, n - 1);
         ly = amc_clampi(ly, 0, n - 1);
     }
-    return G.lay_off[cz] + ly * n + lx;
+    return amc_lay<LAY_GLOBAL>(G.lay_off)[cz] + ly * n + lx;
 }
 
 // The stored cells that can hold a particle within distance r (<= h/2) of (x,y,z), as up to four runs of x-adjacent
@@ -60,6 +68,7 @@ AMC_DEV int amc_grid_box_ranges(const amc_grid &G, double x, double y, double z,
 
 // Cell number c (0..7) of the same enumeration: run c >> 1 (z-major, then y), end c & 1 (lower / upper x cell of the run);
 // -1 if there is none.  For probes that spread the cells of one box over several lanes.
+template <bool LAY_GLOBAL = false>
 AMC_DEV int amc_grid_box_cell(const amc_grid &G, double x, double y, double z, double r, int c)
 {
     const double ux = (x - G.x0) * G.inv_h, uy = (y - G.y0) * G.inv_h, uz = (z - G.z0) * G.inv_h;
@@ -75,7 +84,7 @@ AMC_DEV int amc_grid_box_cell(const amc_grid &G, double x, double y, double z, d
     for (int kz = z_lo; kz <= z_hi; kz++) {
         int lo = 0, nn = G.gx, off;
         if (G.uniform) off = kz * G.gy * G.gx;
-        else { lo = G.lay_lo[kz]; nn = G.lay_n[kz]; off = G.lay_off[kz]; }
+        else { lo = amc_lay<LAY_GLOBAL>(G.lay_lo)[kz]; nn = amc_lay<LAY_GLOBAL>(G.lay_n)[kz]; off = amc_lay<LAY_GLOBAL>(G.lay_off)[kz]; }
         const int a = amc_clampi(x_lo - lo, 0, nn - 1), b = amc_clampi(x_hi - lo, 0, nn - 1);
         const int ya = amc_clampi(y_lo - lo, 0, nn - 1), yb = amc_clampi(y_hi - lo, 0, nn - 1);
         const int ny = yb - ya + 1;
@@ -92,7 +101,7 @@ AMC_DEV int amc_grid_box_cell(const amc_grid &G, double x, double y, double z, d
 // ---- per-cell lists -----------------------------------------------------------------------------------------------------
 AMC_DEV int amc_rec_next(const amc_rec &r) { return r.next; }
 // the particle a list node stands for (amc_lists: nodes below n are the particles themselves)
-AMC_DEV int amc_node_particle(const amc_lists &B, int node) { return node < B.n ? node : B.extra[node - B.n]; }
+AMC_DEV int amc_node_particle(const amc_lists &B, int node) { return node < B.n ? node : amc_g(B.extra)[node - B.n]; }
 // position of a list record (absolute, double): what the particle was filed under, within the rounding of a float
 AMC_DEV void amc_rec_pos(const amc_grid &G, const amc_rec &r, double &x, double &y, double &z)
 {
@@ -101,7 +110,7 @@ AMC_DEV void amc_rec_pos(const amc_grid &G, const amc_rec &r, double &x, double 
 // first particle of cell c in the current epoch, or -1
 AMC_DEV int amc_list_head(const amc_lists &B, int c)
 {
-    const unsigned long long h = B.head[c];
+    const unsigned long long h = amc_g(B.head)[c];
     return ((unsigned int)(h >> 32) == B.epoch) ? (int)(unsigned int)(h & 0xffffffffULL) : -1;
 }
 // push particle p (position x,y,z) on the list of its cell; writes its record.  The cell is the one of the ROUNDED position

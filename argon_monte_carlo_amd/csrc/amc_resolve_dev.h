@@ -10,6 +10,16 @@
 #define RS_MAX_ROUNDS 256
 #define AMC_CR2_INFLATE (1.0 + 1.0e-9)
 
+// Where the sweep counters (rs_shared) of this file's shared device functions live is fixed per kernel, not per call
+// (amc_device.h, "address spaces"): device memory (W.wctl) in the wide cluster kernel, LDS in the ordered workgroup, where
+// the compiler sees it for itself — as it does for the wide kernel's working set, member lists and rs_wide hooks (LDS:
+// no FLAT access is left there, tests/test_isa_addressing.py).  Everything reached through rs_args is device memory.
+#ifdef RS_WAVE_SYNC_LDS_ONLY
+#define RS_CNT(p) amc_g(p)
+#else
+#define RS_CNT(p) (p)
+#endif
+
 // what the resolve kernels need of amc_params (the whole structure is 416 bytes, seven cache lines of kernel arguments that
 // a lone wave would fetch one dependent scalar load after the other)
 struct rs_geom {
@@ -67,7 +77,7 @@ struct rs_shared {
 // stores of the same value by the few waves that have something to report.
 AMC_DEV void rs_raise(const amc_resolve_ws &W)
 {
-    if (W.raise_dev) { *W.raise_dev = W.raise_tick; *W.raise_host = W.raise_tick; }
+    if (W.raise_dev) { *amc_g(W.raise_dev) = W.raise_tick; *amc_g(W.raise_host) = W.raise_tick; }
 }
 
 // working set of the multi-particle clusters (LDS pool or global fallback), indexed by sorted rank
@@ -80,20 +90,20 @@ struct rs_work {
 AMC_DEV amc_particle rs_load_particle(const amc_state &S, int p)
 {
     amc_particle q;
-    q.x = S.x[p]; q.y = S.y[p]; q.z = S.z[p]; q.vx = S.vx[p]; q.vy = S.vy[p]; q.vz = S.vz[p];
-    q.d = S.d[p]; q.dx = S.dx[p]; q.dy = S.dy[p]; q.dz = S.dz[p]; q.flag = S.flag[p] != 0;
+    q.x = amc_g(S.x)[p]; q.y = amc_g(S.y)[p]; q.z = amc_g(S.z)[p]; q.vx = amc_g(S.vx)[p]; q.vy = amc_g(S.vy)[p]; q.vz = amc_g(S.vz)[p];
+    q.d = amc_g(S.d)[p]; q.dx = amc_g(S.dx)[p]; q.dy = amc_g(S.dy)[p]; q.dz = amc_g(S.dz)[p]; q.flag = amc_g(S.flag)[p] != 0;
     return q;
 }
 AMC_DEV void rs_store_slot(const amc_resolve_ws &W, int s, const amc_particle &q)
 {
-    double *t = W.sl_state + (size_t)s * RS_SLOT_DOUBLES;          // one 96-byte record
+    auto *t = amc_g(W.sl_state) + (size_t)s * RS_SLOT_DOUBLES;     // one 96-byte record
     t[0] = q.x; t[1] = q.y; t[2] = q.z; t[3] = q.vx; t[4] = q.vy; t[5] = q.vz;
     t[6] = q.d; t[7] = q.dx; t[8] = q.dy; t[9] = q.dz; t[10] = q.flag ? 1.0 : 0.0;
-    W.sl_moved[s] = 1;
+    amc_g(W.sl_moved)[s] = 1;
 }
 AMC_DEV amc_particle rs_load_slot(const amc_resolve_ws &W, int s)
 {
-    const double *t = W.sl_state + (size_t)s * RS_SLOT_DOUBLES;
+    const auto *t = amc_g(W.sl_state) + (size_t)s * RS_SLOT_DOUBLES;
     amc_particle q;
     q.x = t[0]; q.y = t[1]; q.z = t[2]; q.vx = t[3]; q.vy = t[4]; q.vz = t[5];
     q.d = t[6]; q.dx = t[7]; q.dy = t[8]; q.dz = t[9]; q.flag = t[10] != 0.0;
@@ -102,9 +112,9 @@ AMC_DEV amc_particle rs_load_slot(const amc_resolve_ws &W, int s)
 // scratch state of a slot -> the particle arrays (commit)
 AMC_DEV void rs_apply_slot(const amc_resolve_ws &W, const amc_state &S, int s, int p)
 {
-    const double *t = W.sl_state + (size_t)s * RS_SLOT_DOUBLES;
-    S.x[p] = t[0]; S.y[p] = t[1]; S.z[p] = t[2]; S.vx[p] = t[3]; S.vy[p] = t[4]; S.vz[p] = t[5];
-    S.d[p] = t[6]; S.dx[p] = t[7]; S.dy[p] = t[8]; S.dz[p] = t[9]; S.flag[p] = t[10] != 0.0 ? 1 : 0;
+    const auto *t = amc_g(W.sl_state) + (size_t)s * RS_SLOT_DOUBLES;
+    amc_g(S.x)[p] = t[0]; amc_g(S.y)[p] = t[1]; amc_g(S.z)[p] = t[2]; amc_g(S.vx)[p] = t[3]; amc_g(S.vy)[p] = t[4]; amc_g(S.vz)[p] = t[5];
+    amc_g(S.d)[p] = t[6]; amc_g(S.dx)[p] = t[7]; amc_g(S.dy)[p] = t[8]; amc_g(S.dz)[p] = t[9]; amc_g(S.flag)[p] = t[10] != 0.0 ? 1 : 0;
 }
 AMC_DEV amc_particle rs_load_work(const rs_work &K, int w)
 {
@@ -132,16 +142,20 @@ AMC_DEV int rs_hist_gen(const double4 &r) { return (int)(__double_as_longlong(r.
 // counter += n for every lane that is here right now, with ONE atomic for the whole group (n in 0..2); returns the
 // lane's own first index.  The counters live in LDS for the ordered workgroup and in global memory for the wide pair
 // kernel, where a same-address atomic per hit would be a serial chain of ~12 ns each.
-AMC_DEV int rs_count_add(int *counter, int n)
+AMC_DEV int rs_count_add(AMC_AS_GLOBAL int *counter, int n)
 {
-    if (__builtin_amdgcn_is_shared((const __attribute__((address_space(0))) void *)counter)) return atomicAdd(counter, n);   // LDS: cheap as it is
     const unsigned long long act = __ballot(1), b1 = __ballot(n >= 1), b2 = __ballot(n >= 2);
     const int lane = (int)__lane_id(), leader = __ffsll((long long)act) - 1;
     const unsigned long long lt = (1ULL << lane) - 1ULL;
     const int before = __popcll(b1 & lt) + __popcll(b2 & lt), total = __popcll(b1) + __popcll(b2);
     int base = 0;
-    if (lane == leader && total) base = atomicAdd(counter, total);
+    if (lane == leader && total) base = amc_atomic_add(counter, total);
     return __shfl(base, leader, 64) + before;
+}
+AMC_DEV int rs_count_add(int *counter, int n)
+{
+    if (__builtin_amdgcn_is_shared((const __attribute__((address_space(0))) void *)counter)) return atomicAdd(counter, n);   // LDS: cheap as it is
+    return rs_count_add(amc_g(counter), n);
 }
 
 // What the wide cluster kernel (amc_clusters.hip) hands to rs_hit: its history pairs are reserved before the emulation
@@ -171,14 +185,14 @@ AMC_DEV void rs_store_hist(const amc_resolve_ws &W, int h, const double4 &r, boo
 {
     if (coherent) {
         // read by other workgroups of the same launch: write-through stores (agent scope), one per 8 bytes
-        double *d = (double *)&W.hist[h];
+        auto *d = amc_g((double *)&W.hist[h]);
         __hip_atomic_store(d + 0, r.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_store(d + 1, r.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_store(d + 2, r.z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_store(d + 3, r.w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&W.ov_next[h], -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(amc_g(W.ov_next) + h, -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     } else {
-        W.hist[h] = r;
+        amc_g_store(&W.hist[h], r);
     }
 }
 
@@ -203,29 +217,30 @@ AMC_DEV bool rs_hit(const rs_args &A, rs_shared *sh, amc_particle &p1, amc_parti
         const int q = (*wd.used)++;
         if (q < wd.ncnd) h = 4 * wd.cnd[q];
         else if (q < 2 * wd.ncnd) h = 4 * wd.cnd[q - wd.ncnd] + 2;
-        if (h < 0) { h = wd.h_off + rs_count_add(&sh->nhist, 2); *wd.unval = 1; }
+        if (h < 0) { h = wd.h_off + rs_count_add(&RS_CNT(sh)->nhist, 2); *wd.unval = 1; }
         unval = *wd.unval != 0;
     } else {
-        h = rs_count_add(&sh->nhist, 2);
+        h = rs_count_add(&RS_CNT(sh)->nhist, 2);
     }
     const bool room = h + 1 < W.max_hist;
-    if (!room) { sh->ovf = 1; rs_raise(W); }
+    if (!room) { RS_CNT(sh)->ovf = 1; rs_raise(W); }
     const int gen = wide ? wd.gen : sh->cur_round;
-    if (room) { W.ev_gen[h] = 0; W.ev_gen[h + 1] = 0; }
+    if (room) { amc_g(W.ev_gen)[h] = 0; amc_g(W.ev_gen)[h + 1] = 0; }
     auto emit = [&](int which, double tot, double px, double py, double pz) {
         if (!room) return;
         const int e = h + which;
-        rs_event ev;
-        ev.phase = phase; ev.i = pi; ev.j = pj; ev.which = which; ev.cell = cell; ev.slot = si; ev.pad = 0;
-        ev.val[0] = tot; ev.val[1] = px; ev.val[2] = py; ev.val[3] = pz;
-        W.ev[e] = ev;                   // one 64-byte record
-        W.ev_gen[e] = gen;
+        // one 64-byte record (field by field: assembled as one 16-word value first it cost the wide kernel's cube
+        // instantiation 20 VGPRs and 48 spilled SGPRs; the stores are merged either way)
+        auto *ev = amc_g(&W.ev[e]);
+        ev->phase = phase; ev->i = pi; ev->j = pj; ev->which = which; ev->cell = cell; ev->slot = si; ev->pad = 0;
+        ev->val[0] = tot; ev->val[1] = px; ev->val[2] = py; ev->val[3] = pz;
+        amc_g(W.ev_gen)[e] = gen;
     };
     const int fail = amc_collide(p1, p2, A.P.collision_range, A.P.argon_mass, emit);
     // counted on the slot — collisions in the low half, failed contact solves (the reference would raise
     // FloatingPointError there, Pore:11,185) in the high half — so that a cluster that is emulated again starts from zero
     // (no value needed back: the thread does not wait for the memory round trip)
-    atomicAdd(&W.sl_hits[si], fail ? 0x10000 : 1);
+    amc_atomic_add(amc_g(W.sl_hits) + si, fail ? 0x10000 : 1);
     if (room) {
         // (a failed hit moved nothing: its pair of entries stays empty — round 0 never matches a slot's round)
         rs_store_hist(W, h, rs_hist_make(p1.x, p1.y, p1.z, sj, fail ? 0 : gen), wide);
@@ -712,9 +727,9 @@ AMC_DEV void rs_union(int *M, int a, int b)
 // merge request found by validation: particles pa, pb must be in one cluster (slot ids are filled in next round)
 AMC_DEV void rs_add_edge(const amc_resolve_ws &W, rs_shared *sh, int pa, int pb)
 {
-    const int k = atomicAdd(&sh->nedges, 1);
-    if (k < W.max_edges) { W.edge_a[k] = pa; W.edge_b[k] = pb; } else sh->ovf = 1;
-    sh->dirty = 1;
+    const int k = amc_atomic_add(&RS_CNT(sh)->nedges, 1);
+    if (k < W.max_edges) { amc_g(W.edge_a)[k] = pa; amc_g(W.edge_b)[k] = pb; } else RS_CNT(sh)->ovf = 1;
+    RS_CNT(sh)->dirty = 1;
     rs_raise(W);                // (null in the ordered workgroup's own launches)
 }
 
