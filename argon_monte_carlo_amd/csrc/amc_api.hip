@@ -691,9 +691,9 @@ int amc_kernel_times(amc_ctx *c, double *total_ms, int64_t *launches)
         long long h[128];
         hipMemcpy(h, c->d_dbg, sizeof h, hipMemcpyDeviceToHost);
         const double n = h[11] > 0 ? (double)h[11] : 1.0;
-        fprintf(stderr, "[amc k_resolve phases, us/launch] count-left %.1f claim %.1f | rounds: collect %.1f pairs %.1f clusters>=3: sort+load %.1f emulate %.1f | overlay %.1f validate %.1f commit %.1f | rounds %.2f cand %.1f complex-members %.2f launches %lld (idle hand-over only %lld)\n",
+        fprintf(stderr, "[amc k_resolve phases, us/launch] count-left %.1f claim %.1f | rounds: collect %.1f pairs %.1f clusters>=3: sort+load %.1f emulate %.1f | overlay %.1f validate %.1f commit %.1f | rounds %.2f cand %.1f complex-members %.2f launches %lld (idle hand-over only %lld) | body: labels in the work space %lld moved there %lld layers in LDS %lld rounds split %lld heads shared %lld sorted %lld pool global %lld sort global %lld later %lld clusters by a wave %lld by one lane %lld most complex members %lld\n",
                 h[0] / n / 100.0, h[1] / n / 100.0, h[6] / n / 100.0, h[7] / n / 100.0, h[2] / n / 100.0, h[3] / n / 100.0, h[14] / n / 100.0, h[4] / n / 100.0, h[5] / n / 100.0,
-                h[8] / n, h[9] / n, h[10] / n, h[11], h[12]);
+                h[8] / n, h[9] / n, h[10] / n, h[11], h[12], h[32], h[33], h[34], h[35], h[36], h[37], h[38], h[39], h[40], h[41], h[42], h[43]);
         fprintf(stderr, "[amc host candidate count] %d (what the next launch plan is chosen from)\n", c->h_host_ncand ? (int)*c->h_host_ncand : -1);
         if (h[12] > 0)
             fprintf(stderr, "[amc k_resolve idle hand-over, us/launch] entry -> counts read %.2f, -> hand-over written %.2f, -> through the barrier %.2f (%lld launches)\n",

@@ -192,9 +192,15 @@ __global__ __launch_bounds__(RS_T) void k_resolve(rs_args A_in_kernarg)
     const double cr2i = A.P.collision_range * A.P.collision_range * AMC_CR2_INFLATE;
     rs_slots V;
     unsigned char *vdirty;
-    // (the slot arrays in global memory hold W.max_slots entries: labels in LDS must not let validation claim more)
-    if ((wide ? wide_ns : 0) + 2 * nleft + 256 <= RS_NS) { V.label = s_label; V.size = s_size; V.cap = RS_NS < W.max_slots ? RS_NS : W.max_slots; vdirty = s_dirty; }
-    else { V.label = W.sl_label; V.size = W.sl_tmp; V.cap = W.max_slots; vdirty = W.sl_dirty; }
+    // (the slot arrays in global memory hold W.max_slots entries, and that is what validation may claim up to — a claim
+    // writes no label: when the slots outgrow the LDS tables, the labels move to the work space at the next round's start)
+    if ((wide ? wide_ns : 0) + 2 * nleft + 256 <= RS_NS) { V.label = s_label; V.size = s_size; vdirty = s_dirty; }
+    else { V.label = W.sl_label; V.size = W.sl_tmp; vdirty = W.sl_dirty; }
+    V.cap = W.max_slots;
+    // (debug figures of the body, exact for a single launch: [32] launches that began with the tables in the work space,
+    // [33] that moved them there later, [34] layer tables in LDS, [35 ..] rounds by path, [41] / [42] clusters emulated by
+    // a wave / by one lane, [43] the largest count of complex members in a round)
+    if (A.dbg && tid == 0) { A.dbg[32] += V.label != s_label; A.dbg[34] += !resolved && !A.allpairs && 3 * A.G.gz <= RS_LAY; }
     amc_grid G = A.G;
     int rounds = 0;
     if (!resolved) {
@@ -228,6 +234,14 @@ __global__ __launch_bounds__(RS_T) void k_resolve(rs_args A_in_kernarg)
         const int ns = sh.nslots < V.cap ? sh.nslots : V.cap;
         const int nedges = sh.nedges < W.max_edges ? sh.nedges : W.max_edges;
         __syncthreads();
+        if (V.label == s_label && ns > RS_NS) {
+            // the previous validation claimed past the LDS tables: the labels of the rounds so far move to the work space
+            // (sizes and dirty flags are rebuilt below in every round)
+            for (int s = tid; s < ns_lab; s += RS_T) W.sl_label[s] = s_label[s];
+            V.label = W.sl_label; V.size = W.sl_tmp; vdirty = W.sl_dirty;
+            if (A.dbg && tid == 0) A.dbg[33] += 1;
+            __syncthreads();
+        }
         // ---- per-round reset; new merge edges: particle ids (or encoded slots) -> slot ids -----------------------------------
         const bool first = (rounds == 1);
         for (int s = tid; s < ns; s += RS_T) {
@@ -313,6 +327,11 @@ __global__ __launch_bounds__(RS_T) void k_resolve(rs_args A_in_kernarg)
         // emulation, write-back) with wave-level synchronisation while the other seven waves do the two-particle
         // clusters — the two kinds of cluster are disjoint, so the phases overlap instead of following each other.
         const bool split = nc > 0 && nc <= 64 && nc <= RS_POOL;
+        if (A.dbg && tid == 0) {
+            A.dbg[35] += split; A.dbg[37] += nc > 0 && !split; A.dbg[38] += nc > RS_POOL; A.dbg[39] += nc > RS_SORT_LDS;
+            A.dbg[40] += !first;
+            if (nc > A.dbg[43]) A.dbg[43] = nc;
+        }
         rs_work K;
         K.x = pool_d[0]; K.y = pool_d[1]; K.z = pool_d[2]; K.vx = pool_d[3]; K.vy = pool_d[4]; K.vz = pool_d[5];
         K.d = pool_d[6]; K.dx = pool_d[7]; K.dy = pool_d[8]; K.dz = pool_d[9];
@@ -353,6 +372,7 @@ __global__ __launch_bounds__(RS_T) void k_resolve(rs_args A_in_kernarg)
                     int e = w0 + 1;
                     while (e < nc && (unsigned)(sorted[e] >> 32) == lab) e++;
                     if (e - w0 >= 2) {
+                        if (A.dbg && w == 0) A.dbg[e - w0 <= RS_COOP_MAX ? 41 : 42] += 1;
                         if (e - w0 <= RS_COOP_MAX) rs_emulate_coop(A, &sh, K, w0, e);
                         else if (w == 0) rs_emulate_generic(A, &sh, K, w0, e);
                     }
@@ -363,6 +383,7 @@ __global__ __launch_bounds__(RS_T) void k_resolve(rs_args A_in_kernarg)
                 // (below) — each cluster by a whole wave again; this wave only publishes where the clusters start
                 if (is_head) s_heads[__popcll(__ballot(is_head) & ((1ULL << w) - 1ULL))] = w;
                 if (w == 0) s_nheads = nheads;
+                if (A.dbg && w == 0) A.dbg[36] += 1;
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
             __builtin_amdgcn_wave_barrier();
@@ -390,6 +411,7 @@ __global__ __launch_bounds__(RS_T) void k_resolve(rs_args A_in_kernarg)
                 int e = w0 + 1;
                 while (e < nc && (unsigned)(sorted[e] >> 32) == lab) e++;
                 if (e - w0 >= 2) {
+                    if (A.dbg && (tid & 63) == 0) atomicAdd((unsigned long long *)&A.dbg[e - w0 <= RS_COOP_MAX ? 41 : 42], 1ULL);
                     if (e - w0 <= RS_COOP_MAX) rs_emulate_coop(A, &sh, K, w0, e);
                     else if ((tid & 63) == 0) rs_emulate_generic(A, &sh, K, w0, e);
                 }
@@ -429,6 +451,7 @@ __global__ __launch_bounds__(RS_T) void k_resolve(rs_args A_in_kernarg)
                 if (w > 0 && (unsigned)(keys[w - 1] >> 32) == lab) continue;      // not a cluster head
                 int e = w + 1;
                 while (e < nc && (unsigned)(keys[e] >> 32) == lab) e++;
+                if (A.dbg && e - w >= 2) atomicAdd((unsigned long long *)&A.dbg[42], 1ULL);
                 if (e - w >= 2) rs_emulate_generic(A, &sh, K, w, e);
             }
             __syncthreads();

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Generate the golden vectors under tests/golden/ from the REFERENCE ITSELF (build container only).
 
-    MPLBACKEND=Agg PYTHONDONTWRITEBYTECODE=1 python3 oracle/gen_golden.py [--only func|edge|clusters|temp_edge|cube|pore|temp|consts|cube_natural|pore_natural]
+    MPLBACKEND=Agg PYTHONDONTWRITEBYTECODE=1 python3 oracle/gen_golden.py [--only func|edge|clusters|resolve|temp_edge|cube|pore|temp|consts|cube_natural|pore_natural]
 
 * function level: imports /root/reference/Open_Air_Pore_MC.py (its main loop is __main__-guarded) and calls
   pairwise_particles_in_cell / hit_vertical_wall / hit_cylinder_side_wall / num_out_of_bounds on seeded inputs
@@ -457,6 +457,53 @@ def gen_clusters():
     print("func_clusters.npz:", ncell, "cells,", int(ncoll.sum()), "collisions,", int(outcome.sum()), "cells the reference raised on")
 
 
+# ------------------------------------------------------------------------------------------------ ordered-workgroup cells
+def resolve_inputs():
+    """The inputs of --only resolve, built from tests/resolve_states.py: its family-A cells of up to a few hundred particles
+    (the split / pool fences, the head and coop cells, the merging clusters, short cascades), each as ONE cell."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    from tests import resolve_states as RS
+    cells = [RS.cell(name) for name in RS.SMALL]
+    out = {"rs_in_" + f: np.concatenate([np.asarray(c.arrays[f], dtype=np.float64) for c in cells]) for f in CLUSTER_FIELDS}
+    out["rs_off"] = np.cumsum([0] + [c.n for c in cells]).astype(np.int64)
+    out["rs_name"] = np.array(RS.SMALL, dtype="U40")
+    return out
+
+
+def gen_resolve():
+    """The reference's own pairwise_particles_in_cell on the crafted cells of tests/resolve_states.py."""
+    out = resolve_inputs()              # (before the import: the reference turns every floating-point warning into an error)
+    os.environ.setdefault("MPLBACKEND", "Agg")
+    sys.path.insert(0, REF)
+    import multiprocessing
+    import Open_Air_Pore_MC as P  # noqa
+    off = out["rs_off"]
+    ncell = len(off) - 1
+    res_all = {f: out["rs_in_" + f].copy() for f in CLUSTER_FIELDS}
+    paths, path_off = [], [0]
+    ncoll = np.zeros(ncell, dtype=np.int64)
+    for c in range(ncell):
+        sl = slice(int(off[c]), int(off[c + 1]))
+        counter = multiprocessing.Value('i', 0)
+        P.init_globals(counter)
+        args = [out["rs_in_" + f][sl].copy() for f in CLUSTER_FIELDS]
+        args[4] = args[4].astype(bool)
+        lists = [[], [], [], []]
+        res = P.pairwise_particles_in_cell(*lists, np.ones(sl.stop - sl.start, dtype=bool), *args)
+        for f, a in zip(CLUSTER_FIELDS, res[1:]):
+            res_all[f][sl] = np.asarray(a, dtype=np.float64)
+        paths.extend(zip(*lists))
+        path_off.append(len(paths))
+        ncoll[c] = counter.value
+    for f in CLUSTER_FIELDS:
+        out["rs_out_" + f] = res_all[f]
+    out["rs_paths"] = np.array(paths, dtype=np.float64).reshape(-1, 4)
+    out["rs_path_off"] = np.array(path_off, dtype=np.int64)
+    out["rs_ncoll"] = ncoll
+    save_npz_deterministic(os.path.join(OUT, "func_resolve.npz"), out)
+    print("func_resolve.npz:", ncell, "cells,", int(ncoll.sum()), "collisions")
+
+
 # ------------------------------------------------------------------------------------------------ constants
 def gen_consts():
     """Module constants of the three scripts, captured from the reference's own evaluation."""
@@ -847,6 +894,8 @@ def main():
         gen_edge()
     if a.only == "clusters":
         gen_clusters()
+    if a.only == "resolve":
+        gen_resolve()
     if a.only == "temp_edge":
         gen_temp_edge()
     if a.only == "cube_natural":

@@ -238,15 +238,16 @@ class Oracle:
         return r
 
 
-def pair_cell(params, cont, cx, cy, cz, flag, x, y, z, vx, vy, vz, mode="pow", with_records=False):
+def pair_cell(params, cont, cx, cy, cz, flag, x, y, z, vx, vy, vz, mode="pow", with_records=False, max_records=None):
     """pairwise_particles_in_cell (Pore:160-255) on one cell; returns (outputs dict, paths[k,4], ncoll, rc) and, with
-    with_records, the completed-path records themselves (i, j, which of every flagged partner of every hit, in order)."""
+    with_records, the completed-path records themselves (i, j, which of every flagged partner of every hit, in order).
+    max_records: room for that many records instead of 4 n^2 (cells of thousands of particles with a known hit count)."""
     L = lib()
     n = len(x)
     arrs = [np.array(a, dtype=np.float64, copy=True) for a in (cont, cx, cy, cz)]
     f = np.array(flag, copy=True).astype(np.uint8)
     parr = [np.array(a, dtype=np.float64, copy=True) for a in (x, y, z, vx, vy, vz)]
-    rec = np.zeros(max(16, 4 * n * n), dtype=path_record_dtype())
+    rec = np.zeros(max(16, 4 * n * n if max_records is None else max_records), dtype=path_record_dtype())
     sink = OrcSink(rec.ctypes.data_as(C.POINTER(AmcPathRecord)), len(rec), 0, 0)
     nc = C.c_int64(0)
     fn = getattr(L, f"orc_{mode}_pair_cell")
