@@ -113,6 +113,17 @@ class AmcFluxGrid(C.Structure):
     _fields_ = list(AmcFieldGrid._fields_)
 
 
+AMC_MFP_MAX_COLUMNS = 6144
+AMC_MFP_MAX_HIST_BINS = 64
+
+
+class AmcMfpGrid(C.Structure):
+    """amc_mfp_grid (include/argonmc_mfp.h): the bins of the sampled free paths, their histogram and what becomes of the records."""
+    _fields_ = [("struct_size", C.c_int32), ("kind", C.c_int32), ("n1", C.c_int32), ("n2", C.c_int32), ("n3", C.c_int32),
+                ("hist_bins", C.c_int32), ("keep_records", C.c_int32), ("reserved", C.c_int32),
+                ("lo", C.c_double * 3), ("hi", C.c_double * 3), ("hist_hi", C.c_double)]
+
+
 AMC_SURFACE_CASES = 7
 AMC_SURFACE_MAX_BINS = 256
 

@@ -8,7 +8,7 @@ import ctypes as C
 import os
 import subprocess
 
-from ._abi import (AMC_ABI_VERSION, AmcCorrGrid, AmcFieldGrid, AmcFluxGrid, AmcIcConfig, AmcParams, AmcPathRecord, AmcStepStats, AmcSurfaceGrid,
+from ._abi import (AMC_ABI_VERSION, AmcCorrGrid, AmcFieldGrid, AmcFluxGrid, AmcIcConfig, AmcMfpGrid, AmcParams, AmcPathRecord, AmcStepStats, AmcSurfaceGrid,
                    AmcTempRng)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -109,6 +109,14 @@ FLUX_SIGNATURES = {
     "amc_flux_reset": (C.c_int, [_ctx]),
 }
 
+# ... and every symbol include/argonmc_mfp.h declares (the sampled free paths; argonmc.h includes it)
+MFP_SIGNATURES = {
+    "amc_mfp_config": (C.c_int, [_ctx, C.POINTER(AmcMfpGrid)]),
+    "amc_mfp_read": (C.c_int, [_ctx, _i64p, _i64p, _i64p, _i64p, _i64p]),
+    "amc_mfp_load": (C.c_int, [_ctx, _i64p, _i64p, C.c_int64, C.c_int64, C.c_int64]),
+    "amc_mfp_reset": (C.c_int, [_ctx]),
+}
+
 # ... and every symbol include/argonmc_shard.h declares (the device-RNG energised pore over shards; argonmc.h includes it)
 SHARD_SIGNATURES = {
     "amc_mg_hits_view": (C.c_int, [_ctx, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
@@ -148,12 +156,13 @@ def _source_files():
     files.append(os.path.join(os.path.dirname(_HERE), "include", "argonmc_shard.h"))
     files.append(os.path.join(os.path.dirname(_HERE), "include", "argonmc_corr.h"))
     files.append(os.path.join(os.path.dirname(_HERE), "include", "argonmc_flux.h"))
+    files.append(os.path.join(os.path.dirname(_HERE), "include", "argonmc_mfp.h"))
     return files
 
 
 def source_digest():
-    """sha256 over the library's sources (csrc/*.hip, csrc/*.h, the Makefile, include/argonmc.h, argonmc_shard.h, argonmc_corr.h and
-    argonmc_flux.h)."""
+    """sha256 over the library's sources (csrc/*.hip, csrc/*.h, the Makefile, include/argonmc.h, argonmc_shard.h, argonmc_corr.h,
+    argonmc_flux.h and argonmc_mfp.h)."""
     import hashlib
     h = hashlib.sha256()
     for f in _source_files():
@@ -191,7 +200,7 @@ def load():
         raise ArgonMCError(-3, f"{LIB_PATH} does not match the sources {stale[0]}: rebuild it "
                                "(`python -c 'import __graft_entry__ as g; g.build()'`)")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(SHARD_SIGNATURES.items()) + list(CORR_SIGNATURES.items()) + list(FLUX_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(SHARD_SIGNATURES.items()) + list(CORR_SIGNATURES.items()) + list(FLUX_SIGNATURES.items()) + list(MFP_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError = missing export
         fn.restype = res
         fn.argtypes = args

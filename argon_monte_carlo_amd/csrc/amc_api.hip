@@ -531,6 +531,7 @@ int amc_drain_paths(amc_ctx *c, amc_path_record *out, size_t cap, size_t *n)
     if (pending) AMC_HIP(c, hipMemcpyAsync(out, c->d_rec, sizeof(amc_path_record) * pending, hipMemcpyDeviceToHost, c->stream));
     unsigned int zero = 0;
     AMC_HIP(c, hipMemcpyAsync(&c->d_cnt->path_count, &zero, sizeof zero, hipMemcpyHostToDevice, c->stream));
+    if (c->MF.on) { int rc_ = amc_mfp_rewind(c); if (rc_) return rc_; }     // (the sampled free paths' cursor with it)
     AMC_HIP(c, hipStreamSynchronize(c->stream));
     *n = pending;
     return AMC_OK;
@@ -574,6 +575,7 @@ int amc_reset_outputs(amc_ctx *c)
     if (c->d_hist) AMC_HIP(c, hipMemsetAsync(c->d_hist, 0, sizeof(uint64_t) * 4 * c->out.nbins * AMC_COUNTER_BANKS, c->stream));
     AMC_HIP(c, hipMemsetAsync(c->d_cnt, 0, sizeof(amc_dev_counters), c->stream));
     AMC_HIP(c, hipMemsetAsync(c->d_banks, 0, sizeof(amc_counter_bank) * AMC_COUNTER_BANKS, c->stream));
+    if (c->MF.on) { int rc_ = amc_mfp_rewind(c); if (rc_) return rc_; }     // (path_count is zero: the sampled free paths' cursor with it)
     AMC_HIP(c, hipStreamSynchronize(c->stream));
     memset(&c->h_prev, 0, sizeof c->h_prev);
     c->out.step = 0;

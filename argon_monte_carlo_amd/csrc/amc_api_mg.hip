@@ -314,7 +314,10 @@ int amc_mg_finish(amc_ctx *c, amc_step_stats *out)
     if (exchanged && c->SF.on) c->SF.n_steps++;
     { int rc_ = amc_samplers_step(c); if (rc_) return rc_; }
     if (!out) return AMC_OK;        // asynchronous: the caller reads the counters later
-    return amc_finish_stats(c, out);
+    const int rc = amc_finish_stats(c, out);
+    // an energised step whose work buffers overflowed: paths are missing from the sampled free paths (as after amc_temp_end)
+    if (rc == AMC_ERR_CAPACITY && c->P.geometry == AMC_GEOM_PORE_ENERGISED) c->MF.lost = c->MF.on;
+    return rc;
 }
 
 }  // extern "C"

@@ -498,6 +498,7 @@ int amc_temp_run_device(amc_ctx *c, double dt, int64_t nsteps, const amc_temp_rn
     int ovf[4] = {0, 0, 0, 0};
     AMC_HIP(c, hipMemcpy(ovf, D.ovf, sizeof ovf, hipMemcpyDeviceToHost));
     if (ovf[0] || rc == AMC_ERR_CAPACITY) c->SF.lost = c->SF.on;     // hits are missing from the sampled surfaces
+    if (ovf[0] || rc == AMC_ERR_CAPACITY) c->MF.lost = c->MF.on;     // ... and paths from the sampled free paths
     if (ovf[0]) {
         D.series_n = 0;
         return amc_fail(c, AMC_ERR_CAPACITY, "%d wall hits in case %d exceed the record capacity %d (step %d of the run)", ovf[2], ovf[0], D.seg.cap, ovf[1]);
@@ -539,6 +540,7 @@ int amc_temp_shard_run_end(amc_ctx *c, int64_t nsteps, amc_step_stats *sum)
     int ovf[4] = {0, 0, 0, 0};
     AMC_HIP(c, hipMemcpy(ovf, D.ovf, sizeof ovf, hipMemcpyDeviceToHost));
     if (ovf[0] || ovf[3] || rc == AMC_ERR_CAPACITY) c->SF.lost = c->SF.on;      // hits are missing from the sampled surfaces
+    if (ovf[0] || ovf[3] || rc == AMC_ERR_CAPACITY) c->MF.lost = c->MF.on;      // ... and paths from the sampled free paths
     if (ovf[0]) {
         D.series_n = 0;
         if (ovf[2] == 0x7fffffff)
@@ -602,6 +604,7 @@ int amc_temp_end(amc_ctx *c, amc_step_stats *out)
     if ((rc = amc_samplers_step(c))) return rc;
     rc = amc_finish_stats(c, out);
     if (rc == AMC_ERR_CAPACITY) c->SF.lost = c->SF.on;              // hits are missing from the sampled surfaces
+    if (rc == AMC_ERR_CAPACITY) c->MF.lost = c->MF.on;              // ... and paths from the sampled free paths
     return rc;
 }
 

@@ -255,6 +255,21 @@ struct amc_surface_ws {
     bool lost;                      // a step or run overflowed its records: hits are missing (amc_surface_read: AMC_ERR_STATE)
 };
 
+// sampled free paths (amc_mfp.hip): the grid, the 128-bit running totals per (bin, kind, quantity), the per-bin histograms and the
+// counters, the cursor among them
+struct amc_mfp_ws {
+    bool on;
+    amc_mfp_grid g;
+    amc_fields_grid_dev G;
+    double hist_w;                  // hist_hi / hist_bins, fp64 (1 when hist_bins == 0)
+    unsigned long long *tot;        // [bins][2][7][2] running totals, (low, high) words
+    unsigned long long *hist;       // [bins][2][hist_bins + 1] counts of `total` per column, the last one "beyond"
+    unsigned long long *meta;       // [0] lowest owner out of the quantisers' range (~0: none), [1] records binned, [2] owners outside,
+                                    // [3] the cursor: records of the buffer already seen, [4] != 0: records were lost
+    int64_t n_steps;                // steps completed with the grid on
+    bool lost;                      // an energised step or run overflowed a work buffer: paths are missing (amc_mfp_read: AMC_ERR_STATE)
+};
+
 // sampled correlations (amc_corr.hip): the group grid, the window position, the origin arrays, the per-workgroup slab rows of
 // one sample and the 128-bit running totals
 struct amc_corr_ws {
@@ -403,6 +418,7 @@ struct amc_ctx {
     amc_surface_ws SF;
     amc_corr_ws CR;
     amc_moments_ws FX;          // the sampled fluxes
+    amc_mfp_ws MF;              // the sampled free paths
     // outputs
     amc_out out;
     amc_path_record *d_rec;

@@ -327,6 +327,42 @@ class ShardedSimulation:
         g = self.engine.flux_grid
         return self._moments_summed(FX, "flux", g, None if g is None else FX.totals_shape(g), "fluxes_reset")
 
+    # ---- sampled free paths (free_paths.py): every rank bins the records it emitted — owners in its own range ---------------
+    def enable_free_paths(self, grid=None, keep_records=False):
+        from . import free_paths as FP
+        g = FP.default_grid(self.params) if grid is None else grid
+        self.engine.mfp_config(FP.copy_grid(g, keep_records=keep_records))
+
+    def disable_free_paths(self):
+        self.engine.mfp_config(None)
+
+    def free_paths_reset(self):
+        self.engine.mfp_reset()
+
+    def free_paths(self, dt=None):
+        """Simulation.free_paths() of the whole system (a collective: every rank calls it): the ranks' 128-bit totals, their
+        histogram counts (as words with a zero high half) and the two record counters summed in one ``totals.sum_over_ranks``
+        call, exactly as ``fields()`` does — a read that fails on one rank fails on every rank, from this same call.  The step
+        count is every rank's own: they step together.  ``dt``: the time step for the rates; None takes the simulation's own
+        where it has one (the energised driver) and raises ValueError where it has none: a rate needs a time."""
+        from . import free_paths as FP
+        g = self.engine.mfp_grid
+        if dt is None:
+            dt = getattr(self, "dt", None)
+        if dt is None:
+            raise ValueError("free_paths(dt=...): this driver has no time step of its own")
+
+        def read():
+            tot, hist, (nr, no, ns) = self.engine.mfp_read()
+            return [tot, np.stack([hist, np.zeros_like(hist)], axis=-1)], [nr, no], ns
+        (tot, hist), (nr, no), ns = self._read_summed(
+            read, None if g is None else [FP.totals_shape(g), FP.hist_shape(g) + (2,)], 2,
+            self._describe("mfp_read", "amc_mfp: a free path of particle {p} (rank {r}) is outside [0, 2^-16 m) (or NaN); "
+                                       "sampling stopped until free_paths_reset"))
+        if ns is None:                  # (unreachable: a failed read has raised above)
+            ns = 0
+        return FP.derive(g, tot, hist[..., 0], nr, no, ns, dt)
+
     def histograms(self):
         """Global free-path histograms = sum over ranks (every completed path is emitted by its particle's owner)."""
         counts, tot = self.engine.histograms()

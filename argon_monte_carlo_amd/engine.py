@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._abi import (AMC_K_NAMES, AmcCorrGrid, AmcFieldGrid, AmcFluxGrid, AmcParams, AmcPathRecord, AmcStepStats, AmcSurfaceGrid, path_record_dtype)
+from ._abi import (AMC_K_NAMES, AmcCorrGrid, AmcFieldGrid, AmcFluxGrid, AmcMfpGrid, AmcParams, AmcPathRecord, AmcStepStats, AmcSurfaceGrid, path_record_dtype)
 
 _dp = C.POINTER(C.c_double)
 _i64p = C.POINTER(C.c_int64)
@@ -34,6 +34,7 @@ class Engine:
         self.surface_grid = None
         self.corr_grid = None
         self.flux_grid = None
+        self.mfp_grid = None
         self._ctx = C.c_void_p()
         rc = self.lib.amc_create(C.byref(self._ctx), C.byref(params))
         if rc != 0:
@@ -139,6 +140,12 @@ class Engine:
             # inside a cell i ascending, j ascending, particle j before particle i (Pore:168-199)
             rec = rec[np.lexsort((rec["which"], rec["j"], rec["i"], rec["cell"], rec["phase"], rec["step"]))]
         return rec
+
+    def paths_pending(self):
+        """Path records waiting in the device buffer (at most its capacity)."""
+        pend = C.c_size_t(0)
+        self._ck(self.lib.amc_paths_pending(self._ctx, C.byref(pend)))
+        return int(pend.value)
 
     def histograms(self):
         nb = int(self.params.hist_bins)
@@ -252,6 +259,42 @@ class Engine:
 
     def corr_reset(self):
         self._ck(self.lib.amc_corr_reset(self._ctx))
+
+    # -- sampled free paths (free_paths.py) --------------------------------------------------------------
+    def mfp_config(self, grid):
+        """Sample on ``grid`` (an ``AmcMfpGrid``, free_paths.make_grid); None switches sampling off.  Starts from zero totals,
+        at the path records' current end."""
+        self._ck(self.lib.amc_mfp_config(self._ctx, None if grid is None else C.byref(grid)))
+        self.mfp_grid = None if grid is None else AmcMfpGrid.from_buffer_copy(grid)
+
+    def _mfp_shapes(self):
+        g = self.mfp_grid
+        if g is None:
+            raise _lib.ArgonMCError(-6, "mfp_read before mfp_config")
+        bins = int(g.n1) * int(g.n2) * int(g.n3)
+        return (bins, 2, 7, 2), (bins, 2, int(g.hist_bins) + 1)
+
+    def mfp_read(self):
+        """(int64[bins, 2, 7, 2] totals as (low, high) words, int64[bins, 2, hist_bins + 1] histogram counts, (records binned,
+        owners outside, steps)); synchronises."""
+        st, sh = self._mfp_shapes()
+        tot, hist = np.zeros(st, dtype=np.int64), np.zeros(sh, dtype=np.int64)
+        c = [C.c_int64(0) for _ in range(3)]
+        self._ck(self.lib.amc_mfp_read(self._ctx, tot.ctypes.data_as(_i64p), hist.ctypes.data_as(_i64p), *[C.byref(v) for v in c]))
+        return tot, hist, tuple(v.value for v in c)
+
+    def mfp_load(self, totals, hist, counters):
+        """The inverse of ``mfp_read``: totals, histogram counts and (records binned, owners outside, steps)."""
+        st, sh = self._mfp_shapes()
+        tot = np.ascontiguousarray(totals, dtype=np.int64)
+        h = np.ascontiguousarray(hist, dtype=np.int64)
+        if tot.size != int(np.prod(st)) or h.size != int(np.prod(sh)):
+            raise ValueError("totals do not match the configured grid")
+        nr, no, ns = (int(v) for v in counters)
+        self._ck(self.lib.amc_mfp_load(self._ctx, tot.ctypes.data_as(_i64p), h.ctypes.data_as(_i64p), nr, no, ns))
+
+    def mfp_reset(self):
+        self._ck(self.lib.amc_mfp_reset(self._ctx))
 
     # -- measurement -----------------------------------------------------------------------------------------------
     def set_stream(self, stream_ptr):

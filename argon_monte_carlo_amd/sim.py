@@ -271,23 +271,74 @@ class Simulation:
         """The dict of ``fluxes()`` as an .npz (edges as edges_1, edges_2[, edges_3])."""
         _write_npz(path, self.fluxes())
 
+    # ---- sampled free paths (free_paths.py, DESIGN.md 14; the reference has four global histograms) -----------------------
+    def enable_free_paths(self, grid=None, keep_records=False):
+        """Accumulate the completed free paths per bin of ``grid`` (free_paths.make_grid; None = the geometry's default,
+        free_paths.default_grid) and ending kind — a wall or another atom — after every step from now on, ``run(k)`` included.
+        Starts from zero.  With ``keep_records=False`` the sampler is the path records' reader and empties their buffer after
+        every step: the ``completed_*paths`` lists stop growing while the sampler is on (the device histograms are unaffected).
+        With ``keep_records=True`` the records stay for ``timestep(collect_paths=True)``; their buffer then has to be drained
+        as without the sampler — also before this call if a long ``run`` has filled it: with records missing the first step
+        marks the totals lost (``free_paths()`` raises until ``free_paths_reset()``).  Paths completed before the call are not
+        binned; a consuming sampler starts by emptying the buffer."""
+        from . import free_paths as FP
+        g = FP.default_grid(self.params) if grid is None else grid
+        self.engine.mfp_config(FP.copy_grid(g, keep_records=keep_records))
+
+    def disable_free_paths(self):
+        self.engine.mfp_config(None)
+
+    def free_paths_reset(self):
+        self.engine.mfp_reset()
+
+    def free_paths(self):
+        """dict (free_paths.derive): per bin and kind (wall, p-p, both) count, mean_free_path, mean_abs_x/y/z, var_free_path,
+        end_rate, hist and hist_density; per bin wall_fraction; hist_edges, edges, bin_volume, n_records, n_outside, n_steps
+        and the raw integer totals (int64[bins, 2, 7, 2], 128-bit (low, high) words; int64[bins, 2, hist_bins + 1])."""
+        from . import free_paths as FP
+        tot, hist, (nr, no, ns) = self.engine.mfp_read()
+        return FP.derive(self.engine.mfp_grid, tot, hist, nr, no, ns, self.dt)
+
+    def write_free_paths(self, path):
+        """The dict of ``free_paths()`` as an .npz (edges as edges_1, edges_2[, edges_3])."""
+        _write_npz(path, self.free_paths())
+
+    def _mfp_checkpoint(self):
+        if self.engine.mfp_grid is None:
+            return {}
+        from . import free_paths as FP
+        tot, hist, counters = self.engine.mfp_read()
+        return dict(mfp_grid=FP.grid_to_array(self.engine.mfp_grid), mfp_totals=tot, mfp_hist=hist,
+                    mfp_counters=np.array(counters, dtype=np.int64))
+
+    def _mfp_restore(self, z):
+        if "mfp_grid" in z:
+            from . import free_paths as FP
+            self.engine.mfp_config(FP.grid_from_array(z["mfp_grid"]))
+            self.engine.mfp_load(z["mfp_totals"], z["mfp_hist"], z["mfp_counters"])
+        else:                                           # a checkpoint without them: sampling is off in the resumed run
+            self.engine.mfp_config(None)
+
     # ---- checkpoint / resume (the reference has none: a 10^4-step run is one process lifetime there) ---------------
     def _checkpoint_extra(self):
-        """what a subclass adds to a checkpoint (it extends this dict) — here: grid, totals and counters of the sampled fluxes"""
+        """what a subclass adds to a checkpoint (it extends this dict) — here: grid, totals and counters of the sampled fluxes
+        and of the sampled free paths"""
         from . import fluxes as FX
-        return self._moments_checkpoint(FX, "flux", self.engine.flux_grid)
+        return dict(**self._moments_checkpoint(FX, "flux", self.engine.flux_grid), **self._mfp_checkpoint())
 
     def _restore_extra(self, z):
         """the inverse; a subclass calls it once ``_step_base`` is final (the cadence counts from the run's first step)"""
         from . import fluxes as FX
         if not self._moments_restore(FX, "flux", z):   # a checkpoint without them: sampling is off in the resumed run
             self.engine.flux_config(None)
+        self._mfp_restore(z)
 
     def save_checkpoint(self, path):
         """Everything a later ``load_checkpoint`` needs to continue bit-identically: the particle arrays, the
         completed-path lists, the device histograms and the counters (+ RNG streams and per-step lists for Temp, + the
         grid and the totals of the sampled fields when they are on, + the grid, totals, counters, window position and origin
-        arrays of the sampled correlations when they are on, + the grid, totals and counters of the sampled fluxes when they are on)."""
+        arrays of the sampled correlations when they are on, + the grid, totals and counters of the sampled fluxes and of the sampled
+        free paths when they are on)."""
         st = self.engine.download()
         self._collect()
         counts, _ = self.engine.histograms()

@@ -241,7 +241,7 @@ int amc_histograms(amc_ctx *ctx, uint64_t *counts, uint64_t *n_paths_total);
 /* Zero histograms, counters, the pending path records and the step index.  Whatever was enqueued before the call is
  * discarded from the outputs — the paths and collisions of a step that has returned without its statistics
  * (amc_mg_finish(ctx, NULL)) included — and its results still reach the particle arrays: the state is the one the steps so
- * far produce, and the next step's outputs and statistics hold that step alone.  Sampled fields, surfaces, correlations and fluxes are left alone. */
+ * far produce, and the next step's outputs and statistics hold that step alone.  Sampled fields, surfaces, correlations, fluxes and free paths are left alone. */
 int amc_reset_outputs(amc_ctx *ctx);
 
 /* Host-only helper of the hand-over above (no GPU, no context): the re-emission directions of one case's hits —
@@ -514,6 +514,9 @@ int amc_wall_contacts(amc_ctx *ctx, int case_id, double *contact_xyz, size_t cap
 
 /* ---- sampled fluxes: pressure tensor, energy flux and heat flux per spatial bin (opt-in) --------------------- */
 #include "argonmc_flux.h"
+
+/* ---- sampled free paths: completed free paths per spatial bin and ending kind (opt-in) ----------------------- */
+#include "argonmc_mfp.h"
 
 /* ---- the device-RNG energised pore over shards: the hits exchange and the host-free sharded run ---------------------------- */
 #include "argonmc_shard.h"
