@@ -124,6 +124,17 @@ class AmcMfpGrid(C.Structure):
                 ("lo", C.c_double * 3), ("hi", C.c_double * 3), ("hist_hi", C.c_double)]
 
 
+AMC_VDF_MAX_HIST_BINS = 256
+AMC_VDF_MAX_COLUMNS = 24576
+
+
+class AmcVdfGrid(C.Structure):
+    """amc_vdf_grid (include/argonmc_vdf.h): the regions of the sampled velocity distributions, their histograms and the cadence."""
+    _fields_ = [("struct_size", C.c_int32), ("kind", C.c_int32), ("n1", C.c_int32), ("n2", C.c_int32), ("n3", C.c_int32),
+                ("hist_bins", C.c_int32), ("every", C.c_int64), ("step_offset", C.c_int64),
+                ("lo", C.c_double * 3), ("hi", C.c_double * 3), ("v_max", C.c_double), ("reserved", C.c_int64 * 2)]
+
+
 AMC_SURFACE_CASES = 7
 AMC_SURFACE_MAX_BINS = 256
 

@@ -9,7 +9,7 @@ import os
 import subprocess
 
 from ._abi import (AMC_ABI_VERSION, AmcCorrGrid, AmcFieldGrid, AmcFluxGrid, AmcIcConfig, AmcMfpGrid, AmcParams, AmcPathRecord, AmcStepStats, AmcSurfaceGrid,
-                   AmcTempRng)
+                   AmcTempRng, AmcVdfGrid)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libargonmc.so")
@@ -117,6 +117,15 @@ MFP_SIGNATURES = {
     "amc_mfp_reset": (C.c_int, [_ctx]),
 }
 
+# ... and every symbol include/argonmc_vdf.h declares (the sampled velocity distributions; argonmc.h includes it)
+VDF_SIGNATURES = {
+    "amc_vdf_config": (C.c_int, [_ctx, C.POINTER(AmcVdfGrid)]),
+    "amc_vdf_sample": (C.c_int, [_ctx]),
+    "amc_vdf_read": (C.c_int, [_ctx, _i64p, _i64p, _i64p]),
+    "amc_vdf_load": (C.c_int, [_ctx, _i64p, C.c_int64, C.c_int64]),
+    "amc_vdf_reset": (C.c_int, [_ctx]),
+}
+
 # ... and every symbol include/argonmc_shard.h declares (the device-RNG energised pore over shards; argonmc.h includes it)
 SHARD_SIGNATURES = {
     "amc_mg_hits_view": (C.c_int, [_ctx, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
@@ -157,12 +166,13 @@ def _source_files():
     files.append(os.path.join(os.path.dirname(_HERE), "include", "argonmc_corr.h"))
     files.append(os.path.join(os.path.dirname(_HERE), "include", "argonmc_flux.h"))
     files.append(os.path.join(os.path.dirname(_HERE), "include", "argonmc_mfp.h"))
+    files.append(os.path.join(os.path.dirname(_HERE), "include", "argonmc_vdf.h"))
     return files
 
 
 def source_digest():
     """sha256 over the library's sources (csrc/*.hip, csrc/*.h, the Makefile, include/argonmc.h, argonmc_shard.h, argonmc_corr.h,
-    argonmc_flux.h and argonmc_mfp.h)."""
+    argonmc_flux.h, argonmc_mfp.h and argonmc_vdf.h)."""
     import hashlib
     h = hashlib.sha256()
     for f in _source_files():
@@ -200,7 +210,7 @@ def load():
         raise ArgonMCError(-3, f"{LIB_PATH} does not match the sources {stale[0]}: rebuild it "
                                "(`python -c 'import __graft_entry__ as g; g.build()'`)")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(SHARD_SIGNATURES.items()) + list(CORR_SIGNATURES.items()) + list(FLUX_SIGNATURES.items()) + list(MFP_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(SHARD_SIGNATURES.items()) + list(CORR_SIGNATURES.items()) + list(FLUX_SIGNATURES.items()) + list(MFP_SIGNATURES.items()) + list(VDF_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError = missing export
         fn.restype = res
         fn.argtypes = args

@@ -270,6 +270,20 @@ struct amc_mfp_ws {
     bool lost;                      // an energised step or run overflowed a work buffer: paths are missing (amc_mfp_read: AMC_ERR_STATE)
 };
 
+// sampled velocity distributions (amc_vdf.hip): the grid, the per-workgroup slab rows of one sample and the 64-bit running totals
+struct amc_vdf_ws {
+    bool on;
+    amc_vdf_grid g;
+    amc_fields_grid_dev G;          // the regions (bins: their number)
+    int C;                          // columns per region: 4 * hist_bins + 8
+    double wc, ws;                  // bin widths, fp64: 2 * v_max / hist_bins of a component, v_max / hist_bins of the speed
+    int max_blocks;                 // slab rows allocated (AMC_VDF_BLOCKS, else the number of CUs)
+    int blocks_env;                 // that knob at configuration (0: by particle count)
+    unsigned int *slab;             // [max_blocks][regions * C + 1] one sample's counts per workgroup (+ particles outside)
+    unsigned long long *tot;        // [regions][C] running totals
+    unsigned long long *meta;       // [0] unused, [1] samples, [2] particles outside, [3] lowest particle index out of range (~0: none)
+};
+
 // sampled correlations (amc_corr.hip): the group grid, the window position, the origin arrays, the per-workgroup slab rows of
 // one sample and the 128-bit running totals
 struct amc_corr_ws {
@@ -419,6 +433,7 @@ struct amc_ctx {
     amc_corr_ws CR;
     amc_moments_ws FX;          // the sampled fluxes
     amc_mfp_ws MF;              // the sampled free paths
+    amc_vdf_ws VD;              // the sampled velocity distributions
     // outputs
     amc_out out;
     amc_path_record *d_rec;

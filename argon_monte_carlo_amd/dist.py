@@ -363,6 +363,34 @@ class ShardedSimulation:
             ns = 0
         return FP.derive(g, tot, hist[..., 0], nr, no, ns, dt)
 
+    # ---- sampled velocity distributions (distributions.py): every rank samples its own index range, the counts are summed -----
+    def enable_distributions(self, grid=None, every=0):
+        from . import distributions as VD
+        g = VD.default_grid(self.params) if grid is None else grid
+        self.engine.vdf_config(VD.copy_grid(g, every=every))
+
+    def distributions_sample(self):
+        self.engine.vdf_sample()
+
+    def distributions_reset(self):
+        self.engine.vdf_reset()
+
+    def distributions(self):
+        """Simulation.distributions() of the whole system (a collective: every rank calls it): the ranks' 64-bit counts (as
+        words with a zero high half) and the outside counter summed in one ``totals.sum_over_ranks`` call, exactly as
+        ``fields()`` does — a read that fails on one rank fails on every rank, from this same call."""
+        from . import distributions as VD
+        g = self.engine.vdf_grid
+
+        def read():
+            tot, ns, no = self.engine.vdf_read()
+            return [np.stack([tot, np.zeros_like(tot)], axis=-1)], [no], ns
+        (tot,), (no,), ns = self._read_summed(
+            read, None if g is None else [VD.totals_shape(g) + (2,)], 1,
+            self._describe("vdf_read", "amc_vdf: particle {p} (rank {r}) has a velocity component outside |c| < 2^14 m/s (or NaN); "
+                                       "sampling stopped until distributions_reset"))
+        return VD.derive(g, tot[..., 0], ns, no, float(self.params.argon_mass), VD.boltzmann_constant(self.params))
+
     def histograms(self):
         """Global free-path histograms = sum over ranks (every completed path is emitted by its particle's owner)."""
         counts, tot = self.engine.histograms()

@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._abi import (AMC_K_NAMES, AmcCorrGrid, AmcFieldGrid, AmcFluxGrid, AmcMfpGrid, AmcParams, AmcPathRecord, AmcStepStats, AmcSurfaceGrid, path_record_dtype)
+from ._abi import (AMC_K_NAMES, AmcCorrGrid, AmcFieldGrid, AmcFluxGrid, AmcMfpGrid, AmcParams, AmcPathRecord, AmcStepStats, AmcSurfaceGrid, AmcVdfGrid, path_record_dtype)
 
 _dp = C.POINTER(C.c_double)
 _i64p = C.POINTER(C.c_int64)
@@ -35,6 +35,7 @@ class Engine:
         self.corr_grid = None
         self.flux_grid = None
         self.mfp_grid = None
+        self.vdf_grid = None
         self._ctx = C.c_void_p()
         rc = self.lib.amc_create(C.byref(self._ctx), C.byref(params))
         if rc != 0:
@@ -295,6 +296,39 @@ class Engine:
 
     def mfp_reset(self):
         self._ck(self.lib.amc_mfp_reset(self._ctx))
+
+    # -- sampled velocity distributions (distributions.py) -----------------------------------------------
+    def vdf_config(self, grid):
+        """Sample on ``grid`` (an ``AmcVdfGrid``, distributions.make_grid); None switches sampling off.  Starts from zero totals."""
+        self._ck(self.lib.amc_vdf_config(self._ctx, None if grid is None else C.byref(grid)))
+        self.vdf_grid = None if grid is None else AmcVdfGrid.from_buffer_copy(grid)
+
+    def _vdf_shape(self, what):
+        g = self.vdf_grid
+        if g is None:
+            raise _lib.ArgonMCError(-6, f"vdf_{what} before vdf_config")
+        return (int(g.n1) * int(g.n2) * int(g.n3), 4 * int(g.hist_bins) + 8)
+
+    def vdf_sample(self):
+        """One sample of the current state, enqueued on the context's stream."""
+        self._ck(self.lib.amc_vdf_sample(self._ctx))
+
+    def vdf_read(self):
+        """(int64[regions, 4 * hist_bins + 8] counts, samples, particles outside); synchronises."""
+        tot = np.zeros(self._vdf_shape("read"), dtype=np.int64)
+        ns, no = C.c_int64(0), C.c_int64(0)
+        self._ck(self.lib.amc_vdf_read(self._ctx, tot.ctypes.data_as(_i64p), C.byref(ns), C.byref(no)))
+        return tot, ns.value, no.value
+
+    def vdf_load(self, totals, n_samples, n_outside):
+        """The inverse of ``vdf_read``."""
+        tot = np.ascontiguousarray(totals, dtype=np.int64)
+        if self.vdf_grid is None or tot.size != int(np.prod(self._vdf_shape("load"))):
+            raise ValueError("totals do not match the configured grid")
+        self._ck(self.lib.amc_vdf_load(self._ctx, tot.ctypes.data_as(_i64p), int(n_samples), int(n_outside)))
+
+    def vdf_reset(self):
+        self._ck(self.lib.amc_vdf_reset(self._ctx))
 
     # -- measurement -----------------------------------------------------------------------------------------------
     def set_stream(self, stream_ptr):

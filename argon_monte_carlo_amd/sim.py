@@ -319,12 +319,61 @@ class Simulation:
         else:                                           # a checkpoint without them: sampling is off in the resumed run
             self.engine.mfp_config(None)
 
+    # ---- sampled velocity distributions (distributions.py; the reference has no such output) ----------------
+    def enable_distributions(self, grid=None, every=0):
+        """Sample histograms of the three velocity components and of the speed per region of ``grid``
+        (distributions.make_grid; None = the geometry's default, distributions.default_grid) after every ``every``-th step
+        (0: only on ``distributions_sample()``).  Starts from zero.  Independent of the other samplers."""
+        from . import distributions as VD
+        g = VD.default_grid(self.params) if grid is None else grid
+        # (the device's step counter restarts at a resumed checkpoint: the cadence counts from the run's first step)
+        self.engine.vdf_config(VD.copy_grid(g, every=every, step_offset=getattr(self, "_step_base", 0)))
+
+    def disable_distributions(self):
+        self.engine.vdf_config(None)
+
+    def distributions_sample(self):
+        """One sample of the current state now (asynchronous)."""
+        self.engine.vdf_sample()
+
+    def distributions_reset(self):
+        self.engine.vdf_reset()
+
+    def distributions(self):
+        """dict (distributions.derive): per region count, pdf (regions x 3 x hist_bins, per m/s — components x, y, z on a
+        Cartesian grid, r, theta, z on an axisymmetric one), pdf_speed (regions x hist_bins), the tail counts under, over and
+        over_speed, edges_v, edges_speed, the midpoint estimates mean, variance, T_est and mean_speed, n_samples, n_outside,
+        the raw counts (int64[regions, 4 * hist_bins + 8]), the spatial edges, kind and shape.  Regions in linear order
+        (i1 * n2 + i2) * n3 + i3."""
+        from . import distributions as VD
+        g = self.engine.vdf_grid
+        return VD.derive(g, *self.engine.vdf_read(), float(self.params.argon_mass), VD.boltzmann_constant(self.params))
+
+    def write_distributions(self, path):
+        """The dict of ``distributions()`` as an .npz (the spatial edges as edges_1, edges_2[, edges_3])."""
+        _write_npz(path, self.distributions())
+
+    def _vdf_checkpoint(self):
+        if self.engine.vdf_grid is None:
+            return {}
+        from . import distributions as VD
+        tot, ns, no = self.engine.vdf_read()
+        return dict(vdf_grid=VD.grid_to_array(self.engine.vdf_grid), vdf_totals=tot, vdf_counters=np.array([ns, no], dtype=np.int64))
+
+    def _vdf_restore(self, z):
+        if "vdf_grid" in z:
+            from . import distributions as VD
+            self.engine.vdf_config(VD.copy_grid(VD.grid_from_array(z["vdf_grid"]), step_offset=self._step_base))
+            self.engine.vdf_load(z["vdf_totals"], int(z["vdf_counters"][0]), int(z["vdf_counters"][1]))
+        else:                                           # a checkpoint without them: sampling is off in the resumed run
+            self.engine.vdf_config(None)
+
     # ---- checkpoint / resume (the reference has none: a 10^4-step run is one process lifetime there) ---------------
     def _checkpoint_extra(self):
-        """what a subclass adds to a checkpoint (it extends this dict) — here: grid, totals and counters of the sampled fluxes
-        and of the sampled free paths"""
+        """what a subclass adds to a checkpoint (it extends this dict) — here: grid, totals and counters of the sampled fluxes,
+        of the sampled free paths and of the sampled velocity distributions"""
         from . import fluxes as FX
-        return dict(**self._moments_checkpoint(FX, "flux", self.engine.flux_grid), **self._mfp_checkpoint())
+        return dict(**self._moments_checkpoint(FX, "flux", self.engine.flux_grid), **self._mfp_checkpoint(), **self._vdf_checkpoint())
 
     def _restore_extra(self, z):
         """the inverse; a subclass calls it once ``_step_base`` is final (the cadence counts from the run's first step)"""
@@ -332,13 +381,14 @@ class Simulation:
         if not self._moments_restore(FX, "flux", z):   # a checkpoint without them: sampling is off in the resumed run
             self.engine.flux_config(None)
         self._mfp_restore(z)
+        self._vdf_restore(z)
 
     def save_checkpoint(self, path):
         """Everything a later ``load_checkpoint`` needs to continue bit-identically: the particle arrays, the
         completed-path lists, the device histograms and the counters (+ RNG streams and per-step lists for Temp, + the
         grid and the totals of the sampled fields when they are on, + the grid, totals, counters, window position and origin
-        arrays of the sampled correlations when they are on, + the grid, totals and counters of the sampled fluxes and of the sampled
-        free paths when they are on)."""
+        arrays of the sampled correlations when they are on, + the grid, totals and counters of the sampled fluxes, of the sampled
+        free paths and of the sampled velocity distributions when they are on)."""
         st = self.engine.download()
         self._collect()
         counts, _ = self.engine.histograms()

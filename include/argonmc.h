@@ -518,6 +518,9 @@ int amc_wall_contacts(amc_ctx *ctx, int case_id, double *contact_xyz, size_t cap
 /* ---- sampled free paths: completed free paths per spatial bin and ending kind (opt-in) ----------------------- */
 #include "argonmc_mfp.h"
 
+/* ---- sampled velocity distributions: component and speed histograms per spatial region (opt-in) --------------- */
+#include "argonmc_vdf.h"
+
 /* ---- the device-RNG energised pore over shards: the hits exchange and the host-free sharded run ---------------------------- */
 #include "argonmc_shard.h"
 
