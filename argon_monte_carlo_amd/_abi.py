@@ -135,6 +135,20 @@ class AmcVdfGrid(C.Structure):
                 ("lo", C.c_double * 3), ("hi", C.c_double * 3), ("v_max", C.c_double), ("reserved", C.c_int64 * 2)]
 
 
+AMC_TRANSIT_MAX_ZONES = 8
+AMC_TRANSIT_HIST = 40
+AMC_TRANSIT_CLASS_COLUMNS = 43
+AMC_TRANSIT_COLUMNS = 263
+AMC_TRANSIT_MAX_SAMPLES = 2 ** 32 - 1
+
+
+class AmcTransitGrid(C.Structure):
+    """amc_transit_grid (include/argonmc_transit.h): the zones of the sampled transits and the cadence."""
+    _fields_ = [("struct_size", C.c_int32), ("n_zones", C.c_int32), ("every", C.c_int64), ("step_offset", C.c_int64),
+                ("axis", C.c_int32 * AMC_TRANSIT_MAX_ZONES), ("lo", C.c_double * AMC_TRANSIT_MAX_ZONES),
+                ("hi", C.c_double * AMC_TRANSIT_MAX_ZONES), ("reserved", C.c_int64 * 2)]
+
+
 AMC_SURFACE_CASES = 7
 AMC_SURFACE_MAX_BINS = 256
 

@@ -9,7 +9,7 @@ import os
 import subprocess
 
 from ._abi import (AMC_ABI_VERSION, AmcCorrGrid, AmcFieldGrid, AmcFluxGrid, AmcIcConfig, AmcMfpGrid, AmcParams, AmcPathRecord, AmcStepStats, AmcSurfaceGrid,
-                   AmcTempRng, AmcVdfGrid)
+                   AmcTempRng, AmcTransitGrid, AmcVdfGrid)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libargonmc.so")
@@ -126,6 +126,17 @@ VDF_SIGNATURES = {
     "amc_vdf_reset": (C.c_int, [_ctx]),
 }
 
+# ... and every symbol include/argonmc_transit.h declares (the sampled transits; argonmc.h includes it)
+_u32p = C.POINTER(C.c_uint32)
+TRANSIT_SIGNATURES = {
+    "amc_transit_config": (C.c_int, [_ctx, C.POINTER(AmcTransitGrid)]),
+    "amc_transit_sample": (C.c_int, [_ctx]),
+    "amc_transit_read": (C.c_int, [_ctx, _i64p, _i64p]),
+    "amc_transit_state": (C.c_int, [_ctx, _u32p, _u32p]),
+    "amc_transit_load": (C.c_int, [_ctx, _i64p, C.c_int64, _u32p, _u32p]),
+    "amc_transit_reset": (C.c_int, [_ctx]),
+}
+
 # ... and every symbol include/argonmc_shard.h declares (the device-RNG energised pore over shards; argonmc.h includes it)
 SHARD_SIGNATURES = {
     "amc_mg_hits_view": (C.c_int, [_ctx, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
@@ -167,12 +178,13 @@ def _source_files():
     files.append(os.path.join(os.path.dirname(_HERE), "include", "argonmc_flux.h"))
     files.append(os.path.join(os.path.dirname(_HERE), "include", "argonmc_mfp.h"))
     files.append(os.path.join(os.path.dirname(_HERE), "include", "argonmc_vdf.h"))
+    files.append(os.path.join(os.path.dirname(_HERE), "include", "argonmc_transit.h"))
     return files
 
 
 def source_digest():
     """sha256 over the library's sources (csrc/*.hip, csrc/*.h, the Makefile, include/argonmc.h, argonmc_shard.h, argonmc_corr.h,
-    argonmc_flux.h, argonmc_mfp.h and argonmc_vdf.h)."""
+    argonmc_flux.h, argonmc_mfp.h, argonmc_vdf.h and argonmc_transit.h)."""
     import hashlib
     h = hashlib.sha256()
     for f in _source_files():
@@ -210,7 +222,7 @@ def load():
         raise ArgonMCError(-3, f"{LIB_PATH} does not match the sources {stale[0]}: rebuild it "
                                "(`python -c 'import __graft_entry__ as g; g.build()'`)")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(SHARD_SIGNATURES.items()) + list(CORR_SIGNATURES.items()) + list(FLUX_SIGNATURES.items()) + list(MFP_SIGNATURES.items()) + list(VDF_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(SHARD_SIGNATURES.items()) + list(CORR_SIGNATURES.items()) + list(FLUX_SIGNATURES.items()) + list(MFP_SIGNATURES.items()) + list(VDF_SIGNATURES.items()) + list(TRANSIT_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError = missing export
         fn.restype = res
         fn.argtypes = args

@@ -103,6 +103,7 @@ AMC_INTERNAL int amc_corr_step(amc_ctx *c);                           // the cor
 AMC_INTERNAL int amc_flux_step(amc_ctx *c);                           // the fluxes' part (amc_fields.hip)
 AMC_INTERNAL int amc_mfp_step(amc_ctx *c);                            // the free paths' part: every completed step (amc_mfp.hip)
 AMC_INTERNAL int amc_vdf_step(amc_ctx *c);                            // the velocity distributions' part (amc_vdf.hip)
+AMC_INTERNAL int amc_transit_step(amc_ctx *c);                        // the transits' part (amc_transit.hip)
 AMC_INTERNAL int amc_mfp_rewind(amc_ctx *c);                          // the record buffer has been emptied: the cursor follows (no synchronisation)
 
 // amc_timestep, amc_run and the stage calls: not in the middle of a sharded step (the rule above amc_mg_step)
@@ -120,14 +121,16 @@ static inline bool amc_fields_due(const amc_ctx *c, int64_t step) { return amc_c
 static inline bool amc_corr_due(const amc_ctx *c, int64_t step) { return amc_cadence_due(c->CR.on, c->CR.g.every, c->CR.g.step_offset, step); }
 static inline bool amc_flux_due(const amc_ctx *c, int64_t step) { return amc_cadence_due(c->FX.on, c->FX.g.every, c->FX.g.step_offset, step); }
 static inline bool amc_vdf_due(const amc_ctx *c, int64_t step) { return amc_cadence_due(c->VD.on, c->VD.g.every, c->VD.g.step_offset, step); }
+static inline bool amc_transit_due(const amc_ctx *c, int64_t step) { return amc_cadence_due(c->TR.on, c->TR.g.every, c->TR.g.step_offset, step); }
 // ... for any sampler of the particle state: such a step ends with the state everybody reads (no deferred bounds pass)
 // (the sampled free paths bin by the owner's position at the end of the step: every step while they are on)
-static inline bool amc_samplers_due(const amc_ctx *c, int64_t step) { return c->MF.on || amc_fields_due(c, step) || amc_corr_due(c, step) || amc_flux_due(c, step) || amc_vdf_due(c, step); }
+static inline bool amc_samplers_due(const amc_ctx *c, int64_t step) { return c->MF.on || amc_fields_due(c, step) || amc_corr_due(c, step) || amc_flux_due(c, step) || amc_vdf_due(c, step) || amc_transit_due(c, step); }
 // a sampler runs on a cadence (every > 0: some step is due): amc_run takes its plain loop
 static inline bool amc_samplers_cadence(const amc_ctx *c)
 {
     return c->MF.on || amc_cadence_due(c->F.on, c->F.g.every, 0, 0) || amc_cadence_due(c->CR.on, c->CR.g.every, 0, 0) ||
-           amc_cadence_due(c->FX.on, c->FX.g.every, 0, 0) || amc_cadence_due(c->VD.on, c->VD.g.every, 0, 0);
+           amc_cadence_due(c->FX.on, c->FX.g.every, 0, 0) || amc_cadence_due(c->VD.on, c->VD.g.every, 0, 0) ||
+           amc_cadence_due(c->TR.on, c->TR.g.every, 0, 0);
 }
 // the cadence hook after a completed step
 static inline int amc_samplers_step(amc_ctx *c)
@@ -136,7 +139,8 @@ static inline int amc_samplers_step(amc_ctx *c)
     if (int rc = c->CR.on ? amc_corr_step(c) : AMC_OK) return rc;
     if (int rc = c->FX.on ? amc_flux_step(c) : AMC_OK) return rc;
     if (int rc = c->MF.on ? amc_mfp_step(c) : AMC_OK) return rc;
-    return c->VD.on ? amc_vdf_step(c) : AMC_OK;
+    if (int rc = c->VD.on ? amc_vdf_step(c) : AMC_OK) return rc;
+    return c->TR.on ? amc_transit_step(c) : AMC_OK;
 }
 
 // The grid fields amc_field_grid, amc_corr_grid, amc_flux_grid, amc_mfp_grid and amc_vdf_grid have in common, validated (`who`: the struct's name, `unit`: what it calls its

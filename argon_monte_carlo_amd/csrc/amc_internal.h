@@ -284,6 +284,21 @@ struct amc_vdf_ws {
     unsigned long long *meta;       // [0] unused, [1] samples, [2] particles outside, [3] lowest particle index out of range (~0: none)
 };
 
+// sampled transits (amc_transit.hip): the zones, the per-particle state, the per-workgroup slab rows of one sample and the
+// 128-bit running totals
+struct amc_transit_ws {
+    bool on;
+    amc_transit_grid g;
+    int max_blocks;                 // slab rows allocated (AMC_TRANSIT_BLOCKS, else the number of CUs)
+    int blocks_env;                 // that knob at configuration (0: by particle count)
+    int64_t stride;                 // elements per per-particle array: n rounded up to even
+    unsigned int *state;            // [stride] one word per particle, four bits per zone (argonmc_transit.h), by particle index
+    unsigned int *entry;            // [n_zones][stride] the sample index at which the particle was first seen inside
+    unsigned long long *slab;       // [max_blocks][n_zones * 269] one sample's sums per workgroup
+    unsigned long long *tot;        // [n_zones][AMC_TRANSIT_COLUMNS][2] running totals (low, high)
+    unsigned long long *meta;       // [0] unused, [1] samples, [2] != 0: a sample beyond the limit was asked for, [3] lowest particle with a NaN coordinate (~0: none)
+};
+
 // sampled correlations (amc_corr.hip): the group grid, the window position, the origin arrays, the per-workgroup slab rows of
 // one sample and the 128-bit running totals
 struct amc_corr_ws {
@@ -434,6 +449,7 @@ struct amc_ctx {
     amc_moments_ws FX;          // the sampled fluxes
     amc_mfp_ws MF;              // the sampled free paths
     amc_vdf_ws VD;              // the sampled velocity distributions
+    amc_transit_ws TR;          // the sampled transits
     // outputs
     amc_out out;
     amc_path_record *d_rec;

@@ -391,6 +391,42 @@ class ShardedSimulation:
                                        "sampling stopped until distributions_reset"))
         return VD.derive(g, tot[..., 0], ns, no, float(self.params.argon_mass), VD.boltzmann_constant(self.params))
 
+    # ---- sampled transits (transits.py): every rank tracks the particles of its own index range, the totals are summed -------
+    def enable_transits(self, grid=None, every=1):
+        from . import transits as TR
+        g = TR.default_grid(self.params) if grid is None else grid
+        self.engine.transit_config(TR.copy_grid(g, every=every))
+
+    def disable_transits(self):
+        self.engine.transit_config(None)
+
+    def transits_sample(self):
+        self.engine.transit_sample()
+
+    def transits_reset(self):
+        self.engine.transit_reset()
+
+    def transits(self, dt=None, every=None):
+        """Simulation.transits() of the whole system (a collective: every rank calls it): the ranks' 128-bit totals summed in
+        one ``totals.sum_over_ranks`` call, exactly as ``fields()`` does — a read that fails on one rank fails on every rank,
+        from this same call.  Every rank takes the same samples, so the sample counter is any rank's."""
+        from . import transits as TR
+        g = self.engine.transit_grid
+        if dt is None:
+            dt = getattr(self, "dt", None)
+        if dt is None:
+            raise ValueError("transits(dt=...): this driver has no time step of its own")
+
+        def read():
+            tot, ns = self.engine.transit_read()
+            return [tot], [], ns
+        (tot,), _, ns = self._read_summed(
+            read, None if g is None else [TR.totals_shape(g)], 0,
+            self._describe("transit_read", "amc_transit: particle {p} (rank {r}) has a NaN coordinate; sampling stopped until transits_reset"))
+        if ns is None:                  # (unreachable: a failed read has raised above)
+            ns = 0
+        return TR.derive(g, tot, ns, dt, every)
+
     def histograms(self):
         """Global free-path histograms = sum over ranks (every completed path is emitted by its particle's owner)."""
         counts, tot = self.engine.histograms()

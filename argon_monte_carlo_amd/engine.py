@@ -7,9 +7,11 @@ import numpy as np
 
 from . import _lib
 from ._abi import (AMC_K_NAMES, AmcCorrGrid, AmcFieldGrid, AmcFluxGrid, AmcMfpGrid, AmcParams, AmcPathRecord, AmcStepStats, AmcSurfaceGrid, AmcVdfGrid, path_record_dtype)
+from ._abi import AMC_TRANSIT_COLUMNS, AmcTransitGrid
 
 _dp = C.POINTER(C.c_double)
 _i64p = C.POINTER(C.c_int64)
+_u32p = C.POINTER(C.c_uint32)
 
 
 def _d(a):
@@ -36,6 +38,7 @@ class Engine:
         self.flux_grid = None
         self.mfp_grid = None
         self.vdf_grid = None
+        self.transit_grid = None
         self._ctx = C.c_void_p()
         rc = self.lib.amc_create(C.byref(self._ctx), C.byref(params))
         if rc != 0:
@@ -329,6 +332,60 @@ class Engine:
 
     def vdf_reset(self):
         self._ck(self.lib.amc_vdf_reset(self._ctx))
+
+    # -- sampled transits (transits.py) --------------------------------------------------------------------
+    def transit_config(self, grid):
+        """Sample on ``grid`` (an ``AmcTransitGrid``, transits.make_grid); None switches sampling off.  Starts from zero
+        totals and every particle unknown."""
+        self._ck(self.lib.amc_transit_config(self._ctx, None if grid is None else C.byref(grid)))
+        self.transit_grid = None if grid is None else AmcTransitGrid.from_buffer_copy(grid)
+
+    def _transit_zones(self, what):
+        g = self.transit_grid
+        if g is None:
+            raise _lib.ArgonMCError(-6, f"transit_{what} before transit_config")
+        return int(g.n_zones)
+
+    def transit_sample(self):
+        """One sample of the current state, enqueued on the context's stream."""
+        self._ck(self.lib.amc_transit_sample(self._ctx))
+
+    def transit_read(self):
+        """(int64[n_zones, 263, 2] totals as (low, high) words, samples); synchronises."""
+        tot = np.zeros((self._transit_zones("read"), AMC_TRANSIT_COLUMNS, 2), dtype=np.int64)
+        ns = C.c_int64(0)
+        self._ck(self.lib.amc_transit_read(self._ctx, tot.ctypes.data_as(_i64p), C.byref(ns)))
+        return tot, ns.value
+
+    def transit_state(self):
+        """The per-particle arrays of the context's index range: (uint32[count] state words, uint32[n_zones, count] entry indices)."""
+        cnt = self._corr_range()
+        state = np.zeros(cnt, dtype=np.uint32)
+        entry = np.zeros((self._transit_zones("state"), cnt), dtype=np.uint32)
+        self._ck(self.lib.amc_transit_state(self._ctx, state.ctypes.data_as(_u32p), entry.ctypes.data_as(_u32p)))
+        return state, entry
+
+    def transit_load(self, totals, n_samples, state=None, entry=None):
+        """The inverse of ``transit_read`` + ``transit_state`` (state None: every particle unknown; entry None: zeros)."""
+        zones = self._transit_zones("load")
+        tot = np.ascontiguousarray(totals, dtype=np.int64)
+        if tot.size != zones * AMC_TRANSIT_COLUMNS * 2:
+            raise ValueError("totals do not match the configured zones")
+        cnt = self._corr_range()
+        if state is not None:
+            state = np.ascontiguousarray(state, dtype=np.uint32)
+            if state.shape != (cnt,):
+                raise ValueError(f"expected uint32[{cnt}] state words, got {state.shape}")
+        if entry is not None:
+            entry = np.ascontiguousarray(entry, dtype=np.uint32)
+            if entry.shape != (zones, cnt):
+                raise ValueError(f"expected uint32[{zones}, {cnt}] entry indices, got {entry.shape}")
+        self._ck(self.lib.amc_transit_load(self._ctx, tot.ctypes.data_as(_i64p), int(n_samples),
+                                           None if state is None else state.ctypes.data_as(_u32p),
+                                           None if entry is None else entry.ctypes.data_as(_u32p)))
+
+    def transit_reset(self):
+        self._ck(self.lib.amc_transit_reset(self._ctx))
 
     # -- measurement -----------------------------------------------------------------------------------------------
     def set_stream(self, stream_ptr):

@@ -368,12 +368,65 @@ class Simulation:
         else:                                           # a checkpoint without them: sampling is off in the resumed run
             self.engine.vdf_config(None)
 
+    # ---- sampled transits (transits.py; the reference has no such output) -----------------------------------
+    def enable_transits(self, grid=None, every=1):
+        """Track, per zone of ``grid`` (transits.make_grid; None = the geometry's default, transits.default_grid), which side
+        every particle entered from and when, and count entries, exits by (entry side, exit side) and residence times, with
+        one sample after every ``every``-th step (0: only on ``transits_sample()``).  Starts from zero with every particle
+        unknown.  Independent of the other samplers."""
+        from . import transits as TR
+        g = TR.default_grid(self.params) if grid is None else grid
+        # (the device's step counter restarts at a resumed checkpoint: the cadence counts from the run's first step)
+        self.engine.transit_config(TR.copy_grid(g, every=every, step_offset=getattr(self, "_step_base", 0)))
+
+    def disable_transits(self):
+        self.engine.transit_config(None)
+
+    def transits_sample(self):
+        """One sample of the current state now (asynchronous)."""
+        self.engine.transit_sample()
+
+    def transits_reset(self):
+        self.engine.transit_reset()
+
+    def transits(self, every=None):
+        """dict (transits.derive): per zone transmission and return probabilities with their standard error, residence mean
+        and variance per (entry side, exit side) in seconds, entry and exit rates, occupancy, the Little's-law residence, the
+        number still inside, the residence histogram with its edges, and the raw integers (int64[n_zones, 263, 2], 128-bit
+        (low, high) words).  ``every``: steps per sample where the samples were taken by hand."""
+        from . import transits as TR
+        tot, ns = self.engine.transit_read()
+        return TR.derive(self.engine.transit_grid, tot, ns, self.dt, every)
+
+    def write_transits(self, path):
+        """The dict of ``transits()`` as an .npz."""
+        np.savez(path, **self.transits())
+
+    def _transit_checkpoint(self):
+        if self.engine.transit_grid is None:
+            return {}
+        from . import transits as TR
+        tot, ns = self.engine.transit_read()
+        state, entry = self.engine.transit_state()
+        return dict(transit_grid=TR.grid_to_array(self.engine.transit_grid), transit_totals=tot, transit_counters=np.array([ns], dtype=np.int64),
+                    transit_state=state, transit_entry=entry)
+
+    def _transit_restore(self, z):
+        if "transit_grid" in z:
+            from . import transits as TR
+            self.engine.transit_config(TR.copy_grid(TR.grid_from_array(z["transit_grid"]), step_offset=self._step_base))
+            self.engine.transit_load(z["transit_totals"], int(z["transit_counters"][0]), z["transit_state"], z["transit_entry"])
+        else:                                           # a checkpoint without them: sampling is off in the resumed run
+            self.engine.transit_config(None)
+
     # ---- checkpoint / resume (the reference has none: a 10^4-step run is one process lifetime there) ---------------
     def _checkpoint_extra(self):
         """what a subclass adds to a checkpoint (it extends this dict) — here: grid, totals and counters of the sampled fluxes,
-        of the sampled free paths and of the sampled velocity distributions"""
+        of the sampled free paths, of the sampled velocity distributions and of the sampled transits (these with their
+        per-particle arrays)"""
         from . import fluxes as FX
-        return dict(**self._moments_checkpoint(FX, "flux", self.engine.flux_grid), **self._mfp_checkpoint(), **self._vdf_checkpoint())
+        return dict(**self._moments_checkpoint(FX, "flux", self.engine.flux_grid), **self._mfp_checkpoint(), **self._vdf_checkpoint(),
+                    **self._transit_checkpoint())
 
     def _restore_extra(self, z):
         """the inverse; a subclass calls it once ``_step_base`` is final (the cadence counts from the run's first step)"""
@@ -382,6 +435,7 @@ class Simulation:
             self.engine.flux_config(None)
         self._mfp_restore(z)
         self._vdf_restore(z)
+        self._transit_restore(z)
 
     def save_checkpoint(self, path):
         """Everything a later ``load_checkpoint`` needs to continue bit-identically: the particle arrays, the
