@@ -149,6 +149,18 @@ class AmcTransitGrid(C.Structure):
                 ("hi", C.c_double * AMC_TRANSIT_MAX_ZONES), ("reserved", C.c_int64 * 2)]
 
 
+AMC_PAIR_MAX_HIST_BINS = 256
+AMC_PAIR_MAX_COLUMNS = 6144
+AMC_PAIR_MAX_CELLS_AXIS = 128
+
+
+class AmcPairGrid(C.Structure):
+    """amc_pair_grid (include/argonmc_pair.h): the regions of the sampled pair distribution, its histogram and the cadence."""
+    _fields_ = [("struct_size", C.c_int32), ("kind", C.c_int32), ("n1", C.c_int32), ("n2", C.c_int32), ("n3", C.c_int32),
+                ("hist_bins", C.c_int32), ("every", C.c_int64), ("step_offset", C.c_int64),
+                ("lo", C.c_double * 3), ("hi", C.c_double * 3), ("r_max", C.c_double), ("reserved", C.c_int64 * 2)]
+
+
 AMC_SURFACE_CASES = 7
 AMC_SURFACE_MAX_BINS = 256
 

@@ -9,7 +9,7 @@ import os
 import subprocess
 
 from ._abi import (AMC_ABI_VERSION, AmcCorrGrid, AmcFieldGrid, AmcFluxGrid, AmcIcConfig, AmcMfpGrid, AmcParams, AmcPathRecord, AmcStepStats, AmcSurfaceGrid,
-                   AmcTempRng, AmcTransitGrid, AmcVdfGrid)
+                   AmcPairGrid, AmcTempRng, AmcTransitGrid, AmcVdfGrid)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libargonmc.so")
@@ -137,6 +137,15 @@ TRANSIT_SIGNATURES = {
     "amc_transit_reset": (C.c_int, [_ctx]),
 }
 
+# ... and every symbol include/argonmc_pair.h declares (the sampled pair distribution; argonmc.h includes it)
+PAIR_SIGNATURES = {
+    "amc_pair_config": (C.c_int, [_ctx, C.POINTER(AmcPairGrid)]),
+    "amc_pair_sample": (C.c_int, [_ctx]),
+    "amc_pair_read": (C.c_int, [_ctx, _i64p, _i64p, _i64p, _i64p]),
+    "amc_pair_load": (C.c_int, [_ctx, _i64p, C.c_int64, C.c_int64, C.c_int64]),
+    "amc_pair_reset": (C.c_int, [_ctx]),
+}
+
 # ... and every symbol include/argonmc_shard.h declares (the device-RNG energised pore over shards; argonmc.h includes it)
 SHARD_SIGNATURES = {
     "amc_mg_hits_view": (C.c_int, [_ctx, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
@@ -179,12 +188,13 @@ def _source_files():
     files.append(os.path.join(os.path.dirname(_HERE), "include", "argonmc_mfp.h"))
     files.append(os.path.join(os.path.dirname(_HERE), "include", "argonmc_vdf.h"))
     files.append(os.path.join(os.path.dirname(_HERE), "include", "argonmc_transit.h"))
+    files.append(os.path.join(os.path.dirname(_HERE), "include", "argonmc_pair.h"))
     return files
 
 
 def source_digest():
     """sha256 over the library's sources (csrc/*.hip, csrc/*.h, the Makefile, include/argonmc.h, argonmc_shard.h, argonmc_corr.h,
-    argonmc_flux.h, argonmc_mfp.h, argonmc_vdf.h and argonmc_transit.h)."""
+    argonmc_flux.h, argonmc_mfp.h, argonmc_vdf.h, argonmc_transit.h and argonmc_pair.h)."""
     import hashlib
     h = hashlib.sha256()
     for f in _source_files():
@@ -222,7 +232,7 @@ def load():
         raise ArgonMCError(-3, f"{LIB_PATH} does not match the sources {stale[0]}: rebuild it "
                                "(`python -c 'import __graft_entry__ as g; g.build()'`)")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(SHARD_SIGNATURES.items()) + list(CORR_SIGNATURES.items()) + list(FLUX_SIGNATURES.items()) + list(MFP_SIGNATURES.items()) + list(VDF_SIGNATURES.items()) + list(TRANSIT_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(SHARD_SIGNATURES.items()) + list(CORR_SIGNATURES.items()) + list(FLUX_SIGNATURES.items()) + list(MFP_SIGNATURES.items()) + list(VDF_SIGNATURES.items()) + list(TRANSIT_SIGNATURES.items()) + list(PAIR_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError = missing export
         fn.restype = res
         fn.argtypes = args

@@ -104,6 +104,7 @@ AMC_INTERNAL int amc_flux_step(amc_ctx *c);                           // the flu
 AMC_INTERNAL int amc_mfp_step(amc_ctx *c);                            // the free paths' part: every completed step (amc_mfp.hip)
 AMC_INTERNAL int amc_vdf_step(amc_ctx *c);                            // the velocity distributions' part (amc_vdf.hip)
 AMC_INTERNAL int amc_transit_step(amc_ctx *c);                        // the transits' part (amc_transit.hip)
+AMC_INTERNAL int amc_pair_step(amc_ctx *c);                           // the pair distribution's part (amc_pair.hip)
 AMC_INTERNAL int amc_mfp_rewind(amc_ctx *c);                          // the record buffer has been emptied: the cursor follows (no synchronisation)
 
 // amc_timestep, amc_run and the stage calls: not in the middle of a sharded step (the rule above amc_mg_step)
@@ -122,15 +123,16 @@ static inline bool amc_corr_due(const amc_ctx *c, int64_t step) { return amc_cad
 static inline bool amc_flux_due(const amc_ctx *c, int64_t step) { return amc_cadence_due(c->FX.on, c->FX.g.every, c->FX.g.step_offset, step); }
 static inline bool amc_vdf_due(const amc_ctx *c, int64_t step) { return amc_cadence_due(c->VD.on, c->VD.g.every, c->VD.g.step_offset, step); }
 static inline bool amc_transit_due(const amc_ctx *c, int64_t step) { return amc_cadence_due(c->TR.on, c->TR.g.every, c->TR.g.step_offset, step); }
+static inline bool amc_pair_due(const amc_ctx *c, int64_t step) { return amc_cadence_due(c->PD.on, c->PD.g.every, c->PD.g.step_offset, step); }
 // ... for any sampler of the particle state: such a step ends with the state everybody reads (no deferred bounds pass)
 // (the sampled free paths bin by the owner's position at the end of the step: every step while they are on)
-static inline bool amc_samplers_due(const amc_ctx *c, int64_t step) { return c->MF.on || amc_fields_due(c, step) || amc_corr_due(c, step) || amc_flux_due(c, step) || amc_vdf_due(c, step) || amc_transit_due(c, step); }
+static inline bool amc_samplers_due(const amc_ctx *c, int64_t step) { return c->MF.on || amc_fields_due(c, step) || amc_corr_due(c, step) || amc_flux_due(c, step) || amc_vdf_due(c, step) || amc_transit_due(c, step) || amc_pair_due(c, step); }
 // a sampler runs on a cadence (every > 0: some step is due): amc_run takes its plain loop
 static inline bool amc_samplers_cadence(const amc_ctx *c)
 {
     return c->MF.on || amc_cadence_due(c->F.on, c->F.g.every, 0, 0) || amc_cadence_due(c->CR.on, c->CR.g.every, 0, 0) ||
            amc_cadence_due(c->FX.on, c->FX.g.every, 0, 0) || amc_cadence_due(c->VD.on, c->VD.g.every, 0, 0) ||
-           amc_cadence_due(c->TR.on, c->TR.g.every, 0, 0);
+           amc_cadence_due(c->TR.on, c->TR.g.every, 0, 0) || amc_cadence_due(c->PD.on, c->PD.g.every, 0, 0);
 }
 // the cadence hook after a completed step
 static inline int amc_samplers_step(amc_ctx *c)
@@ -140,10 +142,11 @@ static inline int amc_samplers_step(amc_ctx *c)
     if (int rc = c->FX.on ? amc_flux_step(c) : AMC_OK) return rc;
     if (int rc = c->MF.on ? amc_mfp_step(c) : AMC_OK) return rc;
     if (int rc = c->VD.on ? amc_vdf_step(c) : AMC_OK) return rc;
-    return c->TR.on ? amc_transit_step(c) : AMC_OK;
+    if (int rc = c->TR.on ? amc_transit_step(c) : AMC_OK) return rc;
+    return c->PD.on ? amc_pair_step(c) : AMC_OK;
 }
 
-// The grid fields amc_field_grid, amc_corr_grid, amc_flux_grid, amc_mfp_grid and amc_vdf_grid have in common, validated (`who`: the struct's name, `unit`: what it calls its
+// The grid fields amc_field_grid, amc_corr_grid, amc_flux_grid, amc_mfp_grid, amc_vdf_grid and amc_pair_grid have in common, validated (`who`: the struct's name, `unit`: what it calls its
 // bins; reserved0: its reserved fields are zero; own_fault: a fault in the struct's other fields, reported at its place in the
 // order, behind the bin count, or nullptr) and turned into the grid the kernels take, widths included.
 static inline int amc_sample_grid_check(amc_ctx *c, const char *who, const char *unit, int kind, int n1, int n2, int n3, int max_bins,

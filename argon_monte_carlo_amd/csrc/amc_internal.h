@@ -299,6 +299,31 @@ struct amc_transit_ws {
     unsigned long long *meta;       // [0] unused, [1] samples, [2] != 0: a sample beyond the limit was asked for, [3] lowest particle with a NaN coordinate (~0: none)
 };
 
+// sampled pair distribution (amc_pair.hip): the grid, the search cells, the records in cell order, the per-workgroup slab rows
+// of one sample and the 64-bit running totals
+struct amc_pair_ws {
+    bool on;
+    amc_pair_grid g;
+    amc_fields_grid_dev G;          // the regions (bins: their number)
+    amc_fields_grid_dev B;          // the search box as a Cartesian grid: lo, hi, w = the cell edges, n1 n2 n3 cells (bins: their number)
+    int C;                          // columns per region: 1 + 2 * hist_bins
+    double wr;                      // column width r_max / hist_bins, fp64
+    int max_blocks;                 // slab rows allocated (AMC_PAIR_BLOCKS, else the number of CUs)
+    int blocks_env;                 // that knob at configuration (0: one workgroup per CU)
+    bool dirty;                     // a sample's launches did not all go out: cell_count and side are cleared before the next one
+    unsigned int *cell_count;       // [cells] particles filed per cell; zero between samples (the scan leaves it so)
+    unsigned int *cell_off;         // [cells + 1] first record of every cell, the number of records behind them
+    unsigned int *wave_sum;         // [2048] the scan's sums per wave of its grid
+    int *cell_of, *rank_of;         // [n] the particle's cell (-1: unfiled) and its place among the cell's records
+    int2 *rec_ir;                   // [n] records in cell order: (particle index, region or -1)
+    double *rec_s;                  // [6][n] ... and x y z vx vy vz
+    unsigned long long *side;       // [3] one sample's particles outside and unfiled, folded into meta by the reduce (which zeroes them),
+                                    // and the pair pass's work cursor (zero between samples)
+    unsigned long long *slab;       // [max_blocks][regions * C] one sample's counts per workgroup
+    unsigned long long *tot;        // [regions][C] running totals
+    unsigned long long *meta;       // [0] the shared helpers' error word (never set: nothing is quantised), [1] samples, [2] particles outside, [3] unfiled
+};
+
 // sampled correlations (amc_corr.hip): the group grid, the window position, the origin arrays, the per-workgroup slab rows of
 // one sample and the 128-bit running totals
 struct amc_corr_ws {
@@ -450,6 +475,7 @@ struct amc_ctx {
     amc_mfp_ws MF;              // the sampled free paths
     amc_vdf_ws VD;              // the sampled velocity distributions
     amc_transit_ws TR;          // the sampled transits
+    amc_pair_ws PD;             // the sampled pair distribution
     // outputs
     amc_out out;
     amc_path_record *d_rec;

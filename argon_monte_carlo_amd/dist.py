@@ -427,6 +427,39 @@ class ShardedSimulation:
             ns = 0
         return TR.derive(g, tot, ns, dt, every)
 
+    # ---- sampled pair distribution (pairs.py): every rank counts the centres of its own index range against ALL particles ------
+    def enable_pairs(self, grid=None, every=0):
+        from . import pairs as PA
+        g = PA.default_grid(self.params) if grid is None else grid
+        self.engine.pair_config(PA.copy_grid(g, every=every))
+
+    def disable_pairs(self):
+        self.engine.pair_config(None)
+
+    def pairs_sample(self):
+        self.engine.pair_sample()
+
+    def pairs_reset(self):
+        self.engine.pair_reset()
+
+    def pairs(self):
+        """Simulation.pairs() of the whole system (a collective: every rank calls it): the ranks' 64-bit counts (as words with
+        a zero high half) and the outside counter summed in one ``totals.sum_over_ranks`` call, exactly as ``fields()`` does.
+        In the cube every rank holds the final state of every particle when a sample is taken (the sweep is replicated and
+        its results are still pending in every rank's slot arrays), so a rank's centres — its own index range — see all their
+        neighbours and the sum equals a single context's totals bit for bit.  On a shard of a pore geometry the library refuses
+        the sampler (``enable_pairs`` raises AMC_ERR_STATE): there the owner's bounds pass ends the step, and the other shards'
+        final state arrives with the next exchange only.
+        ``n_unfiled`` counts the particles of the WHOLE system on every rank alike: it is this rank's own value, not a sum."""
+        from . import pairs as PA
+        g = self.engine.pair_grid
+
+        def read():
+            tot, ns, no, nu = self.engine.pair_read()
+            return [np.stack([tot, np.zeros_like(tot)], axis=-1)], [no], (ns, nu)
+        (tot,), (no,), (ns, nu) = self._read_summed(read, None if g is None else [PA.totals_shape(g) + (2,)], 1, self._describe("pair_read"))
+        return PA.derive(g, tot[..., 0], ns, no, nu, float(self.params.collision_range))
+
     def histograms(self):
         """Global free-path histograms = sum over ranks (every completed path is emitted by its particle's owner)."""
         counts, tot = self.engine.histograms()

@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._abi import (AMC_K_NAMES, AmcCorrGrid, AmcFieldGrid, AmcFluxGrid, AmcMfpGrid, AmcParams, AmcPathRecord, AmcStepStats, AmcSurfaceGrid, AmcVdfGrid, path_record_dtype)
+from ._abi import (AMC_K_NAMES, AmcCorrGrid, AmcFieldGrid, AmcFluxGrid, AmcMfpGrid, AmcPairGrid, AmcParams, AmcPathRecord, AmcStepStats, AmcSurfaceGrid, AmcVdfGrid, path_record_dtype)
 from ._abi import AMC_TRANSIT_COLUMNS, AmcTransitGrid
 
 _dp = C.POINTER(C.c_double)
@@ -38,6 +38,7 @@ class Engine:
         self.flux_grid = None
         self.mfp_grid = None
         self.vdf_grid = None
+        self.pair_grid = None
         self.transit_grid = None
         self._ctx = C.c_void_p()
         rc = self.lib.amc_create(C.byref(self._ctx), C.byref(params))
@@ -386,6 +387,40 @@ class Engine:
 
     def transit_reset(self):
         self._ck(self.lib.amc_transit_reset(self._ctx))
+
+    # -- sampled pair distribution (pairs.py) --------------------------------------------------------------
+    def pair_config(self, grid):
+        """Sample on ``grid`` (an ``AmcPairGrid``, pairs.make_grid); None switches sampling off.  Starts from zero totals."""
+        self._ck(self.lib.amc_pair_config(self._ctx, None if grid is None else C.byref(grid)))
+        self.pair_grid = None if grid is None else AmcPairGrid.from_buffer_copy(grid)
+
+    def _pair_shape(self, what):
+        g = self.pair_grid
+        if g is None:
+            raise _lib.ArgonMCError(-6, f"pair_{what} before pair_config")
+        return (int(g.n1) * int(g.n2) * int(g.n3), 1 + 2 * int(g.hist_bins))
+
+    def pair_sample(self):
+        """One sample of the current state, enqueued on the context's stream."""
+        self._ck(self.lib.amc_pair_sample(self._ctx))
+
+    def pair_read(self):
+        """(int64[regions, 1 + 2 * hist_bins] counts, samples, particles of the range outside the grid, particles of the system
+        unfiled); synchronises."""
+        tot = np.zeros(self._pair_shape("read"), dtype=np.int64)
+        ns, no, nu = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._ck(self.lib.amc_pair_read(self._ctx, tot.ctypes.data_as(_i64p), C.byref(ns), C.byref(no), C.byref(nu)))
+        return tot, ns.value, no.value, nu.value
+
+    def pair_load(self, totals, n_samples, n_outside, n_unfiled):
+        """The inverse of ``pair_read``."""
+        tot = np.ascontiguousarray(totals, dtype=np.int64)
+        if self.pair_grid is None or tot.size != int(np.prod(self._pair_shape("load"))):
+            raise ValueError("totals do not match the configured grid")
+        self._ck(self.lib.amc_pair_load(self._ctx, tot.ctypes.data_as(_i64p), int(n_samples), int(n_outside), int(n_unfiled)))
+
+    def pair_reset(self):
+        self._ck(self.lib.amc_pair_reset(self._ctx))
 
     # -- measurement -----------------------------------------------------------------------------------------------
     def set_stream(self, stream_ptr):

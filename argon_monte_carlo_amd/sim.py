@@ -419,14 +419,62 @@ class Simulation:
         else:                                           # a checkpoint without them: sampling is off in the resumed run
             self.engine.transit_config(None)
 
+    # ---- sampled pair distribution (pairs.py; the reference has no such output) ----------------------------
+    def enable_pairs(self, grid=None, every=0):
+        """Sample, per region of ``grid`` (pairs.make_grid; None = the geometry's default, pairs.default_grid), the histogram of
+        the distances from every particle of the region to every other particle closer than r_max, and of those pairs that
+        still approach, after every ``every``-th step (0: only on ``pairs_sample()``).  A sample is a pair search — several
+        steps' worth of time — so ``every`` is meant to be large.  Starts from zero.  Independent of the other samplers."""
+        from . import pairs as PA
+        g = PA.default_grid(self.params) if grid is None else grid
+        # (the device's step counter restarts at a resumed checkpoint: the cadence counts from the run's first step)
+        self.engine.pair_config(PA.copy_grid(g, every=every, step_offset=getattr(self, "_step_base", 0)))
+
+    def disable_pairs(self):
+        self.engine.pair_config(None)
+
+    def pairs_sample(self):
+        """One sample of the current state now (asynchronous)."""
+        self.engine.pair_sample()
+
+    def pairs_reset(self):
+        self.engine.pair_reset()
+
+    def pairs(self):
+        """dict (pairs.derive): r_edges, r_mid, per region centres, pairs and approaching (the raw integers), g and g_err
+        (regions x hist_bins, no wall correction), coordination, overlap_per_centre, approach_fraction, n_samples, n_outside,
+        n_unfiled, the raw counts (int64[regions, 1 + 2 * hist_bins]), the spatial edges, kind and shape.  Regions in linear
+        order (i1 * n2 + i2) * n3 + i3."""
+        from . import pairs as PA
+        return PA.derive(self.engine.pair_grid, *self.engine.pair_read(), float(self.params.collision_range))
+
+    def write_pairs(self, path):
+        """The dict of ``pairs()`` as an .npz (the spatial edges as edges_1, edges_2[, edges_3])."""
+        _write_npz(path, self.pairs())
+
+    def _pair_checkpoint(self):
+        if self.engine.pair_grid is None:
+            return {}
+        from . import pairs as PA
+        tot, ns, no, nu = self.engine.pair_read()
+        return dict(pair_grid=PA.grid_to_array(self.engine.pair_grid), pair_totals=tot, pair_counters=np.array([ns, no, nu], dtype=np.int64))
+
+    def _pair_restore(self, z):
+        if "pair_grid" in z:
+            from . import pairs as PA
+            self.engine.pair_config(PA.copy_grid(PA.grid_from_array(z["pair_grid"]), step_offset=self._step_base))
+            self.engine.pair_load(z["pair_totals"], *(int(v) for v in z["pair_counters"]))
+        else:                                           # a checkpoint without them: sampling is off in the resumed run
+            self.engine.pair_config(None)
+
     # ---- checkpoint / resume (the reference has none: a 10^4-step run is one process lifetime there) ---------------
     def _checkpoint_extra(self):
         """what a subclass adds to a checkpoint (it extends this dict) — here: grid, totals and counters of the sampled fluxes,
-        of the sampled free paths, of the sampled velocity distributions and of the sampled transits (these with their
-        per-particle arrays)"""
+        of the sampled free paths, of the sampled velocity distributions, of the sampled transits (these with their
+        per-particle arrays) and of the sampled pair distribution"""
         from . import fluxes as FX
         return dict(**self._moments_checkpoint(FX, "flux", self.engine.flux_grid), **self._mfp_checkpoint(), **self._vdf_checkpoint(),
-                    **self._transit_checkpoint())
+                    **self._transit_checkpoint(), **self._pair_checkpoint())
 
     def _restore_extra(self, z):
         """the inverse; a subclass calls it once ``_step_base`` is final (the cadence counts from the run's first step)"""
@@ -436,6 +484,7 @@ class Simulation:
         self._mfp_restore(z)
         self._vdf_restore(z)
         self._transit_restore(z)
+        self._pair_restore(z)
 
     def save_checkpoint(self, path):
         """Everything a later ``load_checkpoint`` needs to continue bit-identically: the particle arrays, the

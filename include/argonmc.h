@@ -524,6 +524,9 @@ int amc_wall_contacts(amc_ctx *ctx, int case_id, double *contact_xyz, size_t cap
 /* ---- sampled transits: entries, exits and residence times per zone, with a memory per particle (opt-in) ------- */
 #include "argonmc_transit.h"
 
+/* ---- sampled pair distribution: pair distances and approaching pairs per spatial region (opt-in) -------------- */
+#include "argonmc_pair.h"
+
 /* ---- the device-RNG energised pore over shards: the hits exchange and the host-free sharded run ---------------------------- */
 #include "argonmc_shard.h"
 
