@@ -77,6 +77,7 @@ SIGNATURES = {
     "amc_kernel_name": (C.c_char_p, [C.c_int]),
     "amc_overlap_stats": (C.c_int, [_ctx, _i64p]),
     "amc_lists_stats": (C.c_int, [_ctx, _i64p]),
+    "amc_owned_count": (C.c_int, [_ctx, _i64p]),
     "amc_fields_config": (C.c_int, [_ctx, C.POINTER(AmcFieldGrid)]),
     "amc_fields_sample": (C.c_int, [_ctx]),
     "amc_fields_read": (C.c_int, [_ctx, _i64p, _i64p, _i64p]),

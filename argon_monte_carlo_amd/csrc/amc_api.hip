@@ -684,6 +684,14 @@ int amc_lists_stats(amc_ctx *c, int64_t *out)
     return AMC_OK;
 }
 
+// What the context owns right now (amc_ctx::owned, amc_host.h): a host value, nothing is synchronised or launched.
+int amc_owned_count(amc_ctx *c, int64_t *count)
+{
+    if (!c || !count) return AMC_ERR_INVALID;
+    *count = (int64_t)c->owned.size();
+    return AMC_OK;
+}
+
 int amc_kernel_times(amc_ctx *c, double *total_ms, int64_t *launches)
 {
     if (!c) return AMC_ERR_INVALID;

@@ -452,6 +452,12 @@ class Engine:
         return dict(keep_K=int(out[0]), wave_cap=int(out[1]), waves=int(out[2]), lists_age=int(out[3]), owner=int(out[4]),
                     count_sum=int(out[5]), count_max=int(out[6]), full_builds=int(out[7]))
 
+    def owned_count(self):
+        """The objects the context owns as it stands (amc_owned_count): allocations, streams and events.  Reads only."""
+        n = C.c_int64(0)
+        self._ck(self.lib.amc_owned_count(self._ctx, C.byref(n)))
+        return int(n.value)
+
     def profile(self, on=True):
         self._ck(self.lib.amc_profile(self._ctx, int(on)))
 

@@ -149,11 +149,21 @@ class Simulation:
         tot, ns, no = getattr(self.engine, name + "_read")()
         return {name + "_grid": mod.grid_to_array(g), name + "_totals": tot, name + "_n_samples": int(ns), name + "_n_outside": int(no)}
 
+    def _resumed_offset(self, g):
+        """The step_offset that continues the cadence of the checkpoint's grid ``g``.  A sample is due when the device's step
+        counter plus the offset is a multiple of ``every``: the counter stood at the checkpoint's ``device_step`` when the grid
+        was saved and stands at ``steps_done - _step_base`` now (0 after reset_outputs, the checkpoint's step in a device-RNG
+        run), so the offset moves by the difference — the grid's own offset is kept, not replaced."""
+        if self._saved_device_step is None:         # a checkpoint written before the key: cadences without an offset of their own
+            return self._step_base
+        return int(g.step_offset) + self._saved_device_step - (self.steps_done - self._step_base)
+
     def _moments_restore(self, mod, name, z):
         """grid, totals and counters from the checkpoint z; False if it has none of this sampler (nothing is changed then)"""
         if name + "_grid" not in z:
             return False
-        getattr(self.engine, name + "_config")(mod.copy_grid(mod.grid_from_array(z[name + "_grid"]), step_offset=self._step_base))
+        g = mod.grid_from_array(z[name + "_grid"])
+        getattr(self.engine, name + "_config")(mod.copy_grid(g, step_offset=self._resumed_offset(g)))
         getattr(self.engine, name + "_load")(z[name + "_totals"], int(z[name + "_n_samples"]), int(z[name + "_n_outside"]))
         return True
 
@@ -187,9 +197,8 @@ class Simulation:
         return self._moments_checkpoint(FL, "fields", self.engine.field_grid)
 
     def _fields_restore(self, z):
-        if not self._moments_restore(FL, "fields", z) and self.engine.field_grid is not None:
-            # fields on here, not in the checkpoint: they start with the resumed run
-            self.engine.fields_config(FL.copy_grid(self.engine.field_grid, step_offset=self._step_base))
+        if not self._moments_restore(FL, "fields", z):  # a checkpoint without them: sampling is off in the resumed run, as for the others
+            self.engine.fields_config(None)
 
     # ---- sampled correlations (correlations.py; the reference has no such output) ---------------------------
     def enable_correlations(self, grid=None, every=0, n_lags=None):
@@ -236,7 +245,8 @@ class Simulation:
     def _corr_restore(self, z):
         from . import correlations as CO
         if "corr_grid" in z:
-            self.engine.corr_config(CO.copy_grid(CO.grid_from_array(z["corr_grid"]), step_offset=self._step_base))
+            g = CO.grid_from_array(z["corr_grid"])
+            self.engine.corr_config(CO.copy_grid(g, step_offset=self._resumed_offset(g)))
             self.engine.corr_load(z["corr_totals"], z["corr_counters"], list(z["corr_origin"]))
         else:                                           # a checkpoint without them: sampling is off in the resumed run
             self.engine.corr_config(None)
@@ -363,7 +373,8 @@ class Simulation:
     def _vdf_restore(self, z):
         if "vdf_grid" in z:
             from . import distributions as VD
-            self.engine.vdf_config(VD.copy_grid(VD.grid_from_array(z["vdf_grid"]), step_offset=self._step_base))
+            g = VD.grid_from_array(z["vdf_grid"])
+            self.engine.vdf_config(VD.copy_grid(g, step_offset=self._resumed_offset(g)))
             self.engine.vdf_load(z["vdf_totals"], int(z["vdf_counters"][0]), int(z["vdf_counters"][1]))
         else:                                           # a checkpoint without them: sampling is off in the resumed run
             self.engine.vdf_config(None)
@@ -414,7 +425,8 @@ class Simulation:
     def _transit_restore(self, z):
         if "transit_grid" in z:
             from . import transits as TR
-            self.engine.transit_config(TR.copy_grid(TR.grid_from_array(z["transit_grid"]), step_offset=self._step_base))
+            g = TR.grid_from_array(z["transit_grid"])
+            self.engine.transit_config(TR.copy_grid(g, step_offset=self._resumed_offset(g)))
             self.engine.transit_load(z["transit_totals"], int(z["transit_counters"][0]), z["transit_state"], z["transit_entry"])
         else:                                           # a checkpoint without them: sampling is off in the resumed run
             self.engine.transit_config(None)
@@ -462,7 +474,8 @@ class Simulation:
     def _pair_restore(self, z):
         if "pair_grid" in z:
             from . import pairs as PA
-            self.engine.pair_config(PA.copy_grid(PA.grid_from_array(z["pair_grid"]), step_offset=self._step_base))
+            g = PA.grid_from_array(z["pair_grid"])
+            self.engine.pair_config(PA.copy_grid(g, step_offset=self._resumed_offset(g)))
             self.engine.pair_load(z["pair_totals"], *(int(v) for v in z["pair_counters"]))
         else:                                           # a checkpoint without them: sampling is off in the resumed run
             self.engine.pair_config(None)
@@ -504,6 +517,7 @@ class Simulation:
                  completed_y_paths=np.array(self.completed_y_paths, dtype=np.float64),
                  completed_z_paths=np.array(self.completed_z_paths, dtype=np.float64),
                  total_cols=int(self.total_cols), steps_done=int(self.steps_done),
+                 device_step=int(self.steps_done) - int(getattr(self, "_step_base", 0)),      # (what the saved grids' step_offset counts from)
                  **{f"state_{k}": v for k, v in st.items()}, **self._checkpoint_extra(), **self._fields_checkpoint(),
                  **self._corr_checkpoint())
 
@@ -522,6 +536,7 @@ class Simulation:
         self.completed_z_paths = z["completed_z_paths"].tolist()
         self.total_cols, self.steps_done = int(z["total_cols"]), int(z["steps_done"])
         self._step_base = self.steps_done           # (reset_outputs restarted the device's step counter)
+        self._saved_device_step = int(z["device_step"]) if "device_step" in z else None
         self._cache = None
         self._restore_extra(z)
         self._fields_restore(z)

@@ -424,6 +424,11 @@ int amc_overlap_stats(amc_ctx *ctx, int64_t *out /*[8]*/);
  * the owner's counters; launches nothing and changes nothing, whatever the last step left pending.  While out[3] is -1,
  * out[2], out[5] and out[6] are still those of whoever ran the cycle that ended.  Additive: AMC_ABI_VERSION stays 2. */
 int amc_lists_stats(amc_ctx *ctx, int64_t *out /*[8]*/);
+/* The number of objects the context owns as it stands (a diagnostic for tests): every device and pinned allocation, stream and
+ * event made for the context and not yet released.  A sampler's config(NULL), and a config that replaces a grid, release what
+ * the sampler allocated: the count is then back where it was, and a buffer that was not released shows as one more.  Reads one
+ * host value: no synchronisation, no launch, nothing settled or flushed.  Additive: AMC_ABI_VERSION stays 2. */
+int amc_owned_count(amc_ctx *ctx, int64_t *count);
 
 /* ---- sampled fields: number density, flow velocity, temperature per spatial bin (opt-in) -----------
  * The reference has no such output.  A sample bins every particle of the context's range [lo, hi) and adds, per bin,

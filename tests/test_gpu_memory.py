@@ -86,7 +86,29 @@ def test_contexts_of_every_kind_give_back_their_device_memory(monkeypatch):
         e.fields_sample()
         e.close()
 
-    kinds = [cube_context, pore_with_kept_lists, energised_pore, overlapped_pore, shard_views, fields_context]
+    from argon_monte_carlo_amd import correlations as CO, distributions as VD, fluxes as FX, free_paths as FP, pairs as PA, surface as SU, transits as TR
+    pa, ca = PR.pore_params(n=50_000, energised=True)         # (all eight samplers: the energised pore has the surfaces too)
+    pa.reserved0 |= 1
+    pa.E_cold, pa.E_hot = energies.cold, energies.hot
+    everything = IC.pore_ic(pa, ca, seed=9)
+    rng_all = device_rng_config(ca, 0x5EED)
+
+    def all_samplers():
+        e = EnergisedEngine(pa)
+        e.upload(*everything)
+        e.fields_config(FL.default_grid(pa, every=1))
+        e.corr_config(CO.default_grid(pa, every=1))
+        e.flux_config(FX.default_grid(pa, every=1))
+        e.mfp_config(FP.default_grid(pa))
+        e.vdf_config(VD.default_grid(pa, every=1))
+        e.transit_config(TR.default_grid(pa, every=1))
+        e.pair_config(PA.default_grid(pa, every=3))
+        e.surface_config(SU.default_grid(pa))
+        e.temp_run_device(ca["dt"], 3, rng_all)
+        assert e.pair_read()[1] == 1 and e.surface_read()[2] == 3 and e.mfp_read()[2][2] == 3
+        e.close()
+
+    kinds = [cube_context, pore_with_kept_lists, energised_pore, overlapped_pore, shard_views, fields_context, all_samplers]
     for _ in range(WARMUP_ROUNDS):
         for make in kinds:
             make()

@@ -178,6 +178,6 @@ def test_new_entry_points_are_declared_bound_and_exported_with_matching_argument
         assert res is C.c_int and len(args) == len(declared) == nargs, (name, declared, args)
         assert hasattr(lib, name), name
     assert _lib.SIGNATURES["amc_surface_config"][1][1] is C.POINTER(_abi.AmcSurfaceGrid)
-    assert len(_lib.SIGNATURES) == 57 + len(NEW)                   # new functions only (57: amc_lists_stats came after them)
+    assert len(_lib.SIGNATURES) == 58 + len(NEW)                   # new functions only (58: amc_lists_stats and amc_owned_count came after them)
     assert lib.amc_abi_version() == 2 and len(_abi.AMC_K_NAMES) == 13
     assert "#define AMC_K_COUNT 13" in hdr and "#define AMC_ABI_VERSION 2" in hdr
