@@ -157,6 +157,12 @@ SHARD_SIGNATURES = {
 }
 
 
+def all_signatures():
+    """every entry point of the library: the tables above, one per header, in one dict"""
+    return {**SIGNATURES, **SHARD_SIGNATURES, **CORR_SIGNATURES, **FLUX_SIGNATURES, **MFP_SIGNATURES, **VDF_SIGNATURES, **TRANSIT_SIGNATURES,
+            **PAIR_SIGNATURES}
+
+
 class ArgonMCError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libargonmc error {code}: {msg}")
@@ -233,7 +239,7 @@ def load():
         raise ArgonMCError(-3, f"{LIB_PATH} does not match the sources {stale[0]}: rebuild it "
                                "(`python -c 'import __graft_entry__ as g; g.build()'`)")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(SHARD_SIGNATURES.items()) + list(CORR_SIGNATURES.items()) + list(FLUX_SIGNATURES.items()) + list(MFP_SIGNATURES.items()) + list(VDF_SIGNATURES.items()) + list(TRANSIT_SIGNATURES.items()) + list(PAIR_SIGNATURES.items()):
+    for name, (res, args) in all_signatures().items():
         fn = getattr(lib, name)          # AttributeError = missing export
         fn.restype = res
         fn.argtypes = args

@@ -220,22 +220,12 @@ static void corr_free(amc_ctx *c)
 
 extern "C" {
 
-int amc_corr_step(amc_ctx *c)
-{
-    if (!amc_corr_due(c, c->out.step)) return AMC_OK;
-    return corr_enqueue(c);
-}
+int amc_corr_step(amc_ctx *c) { return corr_enqueue(c); }
 
 int amc_corr_config(amc_ctx *c, const amc_corr_grid *g)
 {
-    if (!c) return AMC_ERR_INVALID;
-    AMC_HIP(c, hipSetDevice(c->device));
-    AMC_HIP(c, hipStreamSynchronize(c->stream));        // (a sample in flight may still use the old buffers)
-    if (!g) {
-        corr_free(c);
-        return AMC_OK;
-    }
-    if (g->struct_size != (int32_t)sizeof(amc_corr_grid)) return amc_fail(c, AMC_ERR_INVALID, "amc_corr_grid.struct_size mismatch (ABI)");
+    bool done;
+    if (int rc = amc_sampler_config_begin(c, g, "amc_corr_grid", corr_free, &done); rc || done) return rc;
     char lags_fault[96] = "";           // (reported behind the group count, as before the grid check was shared)
     if (g->n_lags < 1 || (long long)g->n1 * g->n2 * g->n3 * ((long long)g->n_lags + 1) > AMC_CORR_MAX_CELLS)
         snprintf(lags_fault, sizeof lags_fault, "n_lags %d (>= 1, groups * (n_lags + 1) at most %d)", g->n_lags, AMC_CORR_MAX_CELLS);
@@ -266,17 +256,14 @@ int amc_corr_config(amc_ctx *c, const amc_corr_grid *g)
 int amc_corr_sample(amc_ctx *c)
 {
     if (!c) return AMC_ERR_INVALID;
-    if (!c->CR.on) return amc_fail(c, AMC_ERR_STATE, "amc_corr_sample before amc_corr_config");
-    if (!c->uploaded) return amc_fail(c, AMC_ERR_STATE, "amc_corr_sample before amc_upload");
-    AMC_HIP(c, hipSetDevice(c->device));
+    if (int rc = amc_sampler_sample_ready(c, c->CR.on, "amc_corr")) return rc;
     return corr_enqueue(c);
 }
 
 int amc_corr_read(amc_ctx *c, int64_t *totals, int64_t *n_origins, int64_t *n_samples, int64_t *n_outside, int64_t *window_pos)
 {
     if (!c) return AMC_ERR_INVALID;
-    if (!c->CR.on) return amc_fail(c, AMC_ERR_STATE, "amc_corr_read before amc_corr_config");
-    AMC_HIP(c, hipSetDevice(c->device));
+    if (int rc = amc_sampler_ready(c, c->CR.on, "amc_corr", "read")) return rc;
     amc_corr_ws &R = c->CR;
     unsigned long long meta[4], bad;
     if (int rc = amc_totals_get(c, corr_totals(R), totals, meta, &bad)) return rc;
@@ -293,8 +280,7 @@ int amc_corr_read(amc_ctx *c, int64_t *totals, int64_t *n_origins, int64_t *n_sa
 int amc_corr_origin(amc_ctx *c, double *x0, double *y0, double *z0, double *vx0, double *vy0, double *vz0)
 {
     if (!c) return AMC_ERR_INVALID;
-    if (!c->CR.on) return amc_fail(c, AMC_ERR_STATE, "amc_corr_origin before amc_corr_config");
-    AMC_HIP(c, hipSetDevice(c->device));
+    if (int rc = amc_sampler_ready(c, c->CR.on, "amc_corr", "origin")) return rc;
     amc_corr_ws &R = c->CR;
     double *dst[6] = {x0, y0, z0, vx0, vy0, vz0};
     const size_t bytes = sizeof(double) * (size_t)(c->hi - c->lo);
@@ -329,8 +315,7 @@ int amc_corr_load(amc_ctx *c, const int64_t *totals, int64_t n_origins, int64_t 
 int amc_corr_reset(amc_ctx *c)
 {
     if (!c) return AMC_ERR_INVALID;
-    if (!c->CR.on) return amc_fail(c, AMC_ERR_STATE, "amc_corr_reset before amc_corr_config");
-    AMC_HIP(c, hipSetDevice(c->device));
+    if (int rc = amc_sampler_ready(c, c->CR.on, "amc_corr", "reset")) return rc;
     const unsigned long long meta[4] = {0, 0, 0, 0};
     if (int rc = amc_totals_put(c, corr_totals(c->CR), nullptr, meta)) return rc;
     c->CR.pos = 0;

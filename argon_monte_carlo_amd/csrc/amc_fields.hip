@@ -222,18 +222,10 @@ static amc_totals moments_totals(const amc_moments_ws &W, const moments_desc &D)
     return amc_totals{W.tot, (size_t)2 * D.rows * AMC_MOMENTS_Q * (size_t)W.G.bins, W.meta, 4, 3};
 }
 
-// the checks every entry point on a configured sampler starts with (`what`: its name behind the sampler's); c is not null here
-// and below: the entry points have looked
-static int moments_ready(amc_ctx *c, const amc_moments_ws &W, const moments_desc &D, const char *what)
-{
-    if (!W.on) return amc_fail(c, AMC_ERR_STATE, "%s_%s before %s_config", D.name, what, D.name);
-    AMC_HIP(c, hipSetDevice(c->device));
-    return AMC_OK;
-}
-
+// (c is not null here and below: the entry points have looked)
 static int moments_reset(amc_ctx *c, amc_moments_ws &W, const moments_desc &D)
 {
-    if (int rc = moments_ready(c, W, D, "reset")) return rc;
+    if (int rc = amc_sampler_ready(c, W.on, D.name, "reset")) return rc;
     const unsigned long long meta[4] = {0, 0, 0, 0};
     return amc_totals_put(c, moments_totals(W, D), nullptr, meta);
 }
@@ -241,15 +233,11 @@ static int moments_reset(amc_ctx *c, amc_moments_ws &W, const moments_desc &D)
 // grid: the sampler's grid struct (the common layout, above), or nullptr
 static int moments_config(amc_ctx *c, amc_moments_ws &W, const moments_desc &D, const void *grid)
 {
-    AMC_HIP(c, hipSetDevice(c->device));
-    AMC_HIP(c, hipStreamSynchronize(c->stream));        // (a sample in flight may still use the old buffers)
-    if (!grid) {
-        moments_free(c, W);
-        return AMC_OK;
-    }
+    bool done;
+    if (int rc = amc_sampler_config_begin(c, (const amc_field_grid *)grid, D.grid, [&W](amc_ctx *ctx) { moments_free(ctx, W); }, &done); rc || done)
+        return rc;
     amc_field_grid g;
     memcpy(&g, grid, sizeof g);
-    if (g.struct_size != (int32_t)sizeof(amc_field_grid)) return amc_fail(c, AMC_ERR_INVALID, "%s.struct_size mismatch (ABI)", D.grid);
     amc_fields_grid_dev G;
     if (int rc = amc_sample_grid_check(c, D.grid, "bins", g.kind, g.n1, g.n2, g.n3, D.max_bins, g.lo, g.hi, g.every, g.step_offset,
                                        g.reserved == 0, nullptr, &G))
@@ -271,15 +259,13 @@ static int moments_config(amc_ctx *c, amc_moments_ws &W, const moments_desc &D, 
 
 static int moments_sample(amc_ctx *c, amc_moments_ws &W, const moments_desc &D)
 {
-    if (!W.on) return amc_fail(c, AMC_ERR_STATE, "%s_sample before %s_config", D.name, D.name);
-    if (!c->uploaded) return amc_fail(c, AMC_ERR_STATE, "%s_sample before amc_upload", D.name);
-    AMC_HIP(c, hipSetDevice(c->device));
+    if (int rc = amc_sampler_sample_ready(c, W.on, D.name)) return rc;
     return moments_enqueue(c, W, D);
 }
 
 static int moments_read(amc_ctx *c, amc_moments_ws &W, const moments_desc &D, int64_t *totals, int64_t *n_samples, int64_t *n_outside)
 {
-    if (int rc = moments_ready(c, W, D, "read")) return rc;
+    if (int rc = amc_sampler_ready(c, W.on, D.name, "read")) return rc;
     unsigned long long meta[4], bad;
     if (int rc = amc_totals_get(c, moments_totals(W, D), totals, meta, &bad)) return rc;
     if (bad != ~0ULL)
@@ -293,15 +279,15 @@ static int moments_read(amc_ctx *c, amc_moments_ws &W, const moments_desc &D, in
 static int moments_load(amc_ctx *c, amc_moments_ws &W, const moments_desc &D, const int64_t *totals, int64_t n_samples, int64_t n_outside)
 {
     if (!totals || n_samples < 0 || n_outside < 0) return AMC_ERR_INVALID;
-    if (int rc = moments_ready(c, W, D, "load")) return rc;
+    if (int rc = amc_sampler_ready(c, W.on, D.name, "load")) return rc;
     const unsigned long long meta[4] = {0, (unsigned long long)n_samples, (unsigned long long)n_outside, 0};
     return amc_totals_put(c, moments_totals(W, D), totals, meta);
 }
 
 extern "C" {
 
-int amc_fields_step(amc_ctx *c) { return amc_fields_due(c, c->out.step) ? moments_enqueue(c, c->F, FIELDS) : AMC_OK; }
-int amc_flux_step(amc_ctx *c) { return amc_flux_due(c, c->out.step) ? moments_enqueue(c, c->FX, FLUX) : AMC_OK; }
+int amc_fields_enqueue(amc_ctx *c) { return moments_enqueue(c, c->F, FIELDS); }
+int amc_flux_enqueue(amc_ctx *c) { return moments_enqueue(c, c->FX, FLUX); }
 
 int amc_fields_config(amc_ctx *c, const amc_field_grid *g) { return c ? moments_config(c, c->F, FIELDS, g) : AMC_ERR_INVALID; }
 int amc_flux_config(amc_ctx *c, const amc_flux_grid *g) { return c ? moments_config(c, c->FX, FLUX, g) : AMC_ERR_INVALID; }

@@ -98,13 +98,14 @@ AMC_INTERNAL int amc_finish_stats(amc_ctx *c, amc_step_stats *out);     // per-s
 AMC_INTERNAL int amc_publish_velocities(amc_ctx *c);                    // multi-GPU: vpub = current velocities (after an upload)
 AMC_INTERNAL int amc_flush(amc_ctx *c);                                 // write deferred sweep results to the particle arrays
 AMC_INTERNAL int amc_enqueue_sweep(amc_ctx *c, bool counted = false, bool defer_commit = false);   // bin (unless counted) + detect + resolve
-AMC_INTERNAL int amc_fields_step(amc_ctx *c);                         // the fields' part of the cadence hook (amc_fields.hip)
-AMC_INTERNAL int amc_corr_step(amc_ctx *c);                           // the correlations' part (amc_corr.hip)
-AMC_INTERNAL int amc_flux_step(amc_ctx *c);                           // the fluxes' part (amc_fields.hip)
-AMC_INTERNAL int amc_mfp_step(amc_ctx *c);                            // the free paths' part: every completed step (amc_mfp.hip)
-AMC_INTERNAL int amc_vdf_step(amc_ctx *c);                            // the velocity distributions' part (amc_vdf.hip)
-AMC_INTERNAL int amc_transit_step(amc_ctx *c);                        // the transits' part (amc_transit.hip)
-AMC_INTERNAL int amc_pair_step(amc_ctx *c);                           // the pair distribution's part (amc_pair.hip)
+// what the cadence hook calls for a sampler whose sample is due (AMC_SAMPLERS below): one sample of the current state, enqueued
+AMC_INTERNAL int amc_fields_enqueue(amc_ctx *c);                      // amc_fields.hip
+AMC_INTERNAL int amc_corr_step(amc_ctx *c);                           // amc_corr.hip: at the window position, which it advances
+AMC_INTERNAL int amc_flux_enqueue(amc_ctx *c);                        // amc_fields.hip
+AMC_INTERNAL int amc_mfp_step(amc_ctx *c);                            // amc_mfp.hip: the step's path records; every completed step
+AMC_INTERNAL int amc_vdf_enqueue(amc_ctx *c);                         // amc_vdf.hip
+AMC_INTERNAL int amc_transit_enqueue(amc_ctx *c);                     // amc_transit.hip
+AMC_INTERNAL int amc_pair_enqueue(amc_ctx *c);                        // amc_pair.hip
 AMC_INTERNAL int amc_mfp_rewind(amc_ctx *c);                          // the record buffer has been emptied: the cursor follows (no synchronisation)
 
 // amc_timestep, amc_run and the stage calls: not in the middle of a sharded step (the rule above amc_mg_step)
@@ -115,35 +116,99 @@ static inline int amc_mg_step_idle(amc_ctx *c, const char *who)
                                       "amc_mg_local / amc_upload", who);
 }
 
-// ---- what the samplers share on the host (amc_fields.hip, amc_corr.hip, amc_surface.hip) --------------------------------------------------
+// ---- what the samplers share on the host (every amc_<sampler>.hip, the step drivers) ---------------------------------------------------------
 // a sample is due after the step that leaves the step counter at `step`
 static inline bool amc_cadence_due(bool on, int64_t every, int64_t step_offset, int64_t step) { return on && every > 0 && (step + step_offset) % every == 0; }
-static inline bool amc_fields_due(const amc_ctx *c, int64_t step) { return amc_cadence_due(c->F.on, c->F.g.every, c->F.g.step_offset, step); }
-static inline bool amc_corr_due(const amc_ctx *c, int64_t step) { return amc_cadence_due(c->CR.on, c->CR.g.every, c->CR.g.step_offset, step); }
-static inline bool amc_flux_due(const amc_ctx *c, int64_t step) { return amc_cadence_due(c->FX.on, c->FX.g.every, c->FX.g.step_offset, step); }
-static inline bool amc_vdf_due(const amc_ctx *c, int64_t step) { return amc_cadence_due(c->VD.on, c->VD.g.every, c->VD.g.step_offset, step); }
-static inline bool amc_transit_due(const amc_ctx *c, int64_t step) { return amc_cadence_due(c->TR.on, c->TR.g.every, c->TR.g.step_offset, step); }
-static inline bool amc_pair_due(const amc_ctx *c, int64_t step) { return amc_cadence_due(c->PD.on, c->PD.g.every, c->PD.g.step_offset, step); }
-// ... for any sampler of the particle state: such a step ends with the state everybody reads (no deferred bounds pass)
-// (the sampled free paths bin by the owner's position at the end of the step: every step while they are on)
-static inline bool amc_samplers_due(const amc_ctx *c, int64_t step) { return c->MF.on || amc_fields_due(c, step) || amc_corr_due(c, step) || amc_flux_due(c, step) || amc_vdf_due(c, step) || amc_transit_due(c, step) || amc_pair_due(c, step); }
-// a sampler runs on a cadence (every > 0: some step is due): amc_run takes its plain loop
+
+// The samplers of the particle state, ONE entry each, in the order the hook runs them.  A new sampler is one more line here:
+// everything below is derived from the table.  cadence: the workspace's on, every and step_offset as they stand; step: what the hook
+// calls when a sample is due.
+#define AMC_EVERY_STEP (-1)     // amc_cadence::every of a sampler that is due after every step while it is on
+struct amc_cadence { bool on; int64_t every, step_offset; };
+struct amc_sampler { amc_cadence (*cadence)(const amc_ctx *c); int (*step)(amc_ctx *c); };
+template <class WS>
+static inline amc_cadence amc_cadence_of(const WS &W) { return amc_cadence{W.on, W.g.every, W.g.step_offset}; }
+static const amc_sampler AMC_SAMPLERS[] = {
+    {[](const amc_ctx *c) { return amc_cadence_of(c->F); }, amc_fields_enqueue},
+    {[](const amc_ctx *c) { return amc_cadence_of(c->CR); }, amc_corr_step},
+    {[](const amc_ctx *c) { return amc_cadence_of(c->FX); }, amc_flux_enqueue},
+    // (the sampled free paths bin by the owner's position at the end of the step)
+    {[](const amc_ctx *c) { return amc_cadence{c->MF.on, AMC_EVERY_STEP, 0}; }, amc_mfp_step},
+    {[](const amc_ctx *c) { return amc_cadence_of(c->VD); }, amc_vdf_enqueue},
+    {[](const amc_ctx *c) { return amc_cadence_of(c->TR); }, amc_transit_enqueue},
+    {[](const amc_ctx *c) { return amc_cadence_of(c->PD); }, amc_pair_enqueue},
+};
+static inline bool amc_sampler_due(const amc_cadence &k, int64_t step)
+{
+    return k.every == AMC_EVERY_STEP ? k.on : amc_cadence_due(k.on, k.every, k.step_offset, step);
+}
+// a sampler is configured, with a cadence or without (every == 0: manual samples)
+static inline bool amc_samplers_configured(const amc_ctx *c)
+{
+    for (const amc_sampler &s : AMC_SAMPLERS)
+        if (s.cadence(c).on) return true;
+    return false;
+}
+// a sample of some sampler is due after `step`: such a step ends with the state everybody reads (no deferred bounds pass)
+static inline bool amc_samplers_due(const amc_ctx *c, int64_t step)
+{
+    for (const amc_sampler &s : AMC_SAMPLERS)
+        if (amc_sampler_due(s.cadence(c), step)) return true;
+    return false;
+}
+// a sampler runs on a cadence (some step is due): amc_run takes its plain loop
 static inline bool amc_samplers_cadence(const amc_ctx *c)
 {
-    return c->MF.on || amc_cadence_due(c->F.on, c->F.g.every, 0, 0) || amc_cadence_due(c->CR.on, c->CR.g.every, 0, 0) ||
-           amc_cadence_due(c->FX.on, c->FX.g.every, 0, 0) || amc_cadence_due(c->VD.on, c->VD.g.every, 0, 0) ||
-           amc_cadence_due(c->TR.on, c->TR.g.every, 0, 0) || amc_cadence_due(c->PD.on, c->PD.g.every, 0, 0);
+    for (const amc_sampler &s : AMC_SAMPLERS) {
+        const amc_cadence k = s.cadence(c);
+        if (k.on && k.every != 0) return true;
+    }
+    return false;
 }
 // the cadence hook after a completed step
 static inline int amc_samplers_step(amc_ctx *c)
 {
-    if (int rc = amc_fields_step(c)) return rc;
-    if (int rc = c->CR.on ? amc_corr_step(c) : AMC_OK) return rc;
-    if (int rc = c->FX.on ? amc_flux_step(c) : AMC_OK) return rc;
-    if (int rc = c->MF.on ? amc_mfp_step(c) : AMC_OK) return rc;
-    if (int rc = c->VD.on ? amc_vdf_step(c) : AMC_OK) return rc;
-    if (int rc = c->TR.on ? amc_transit_step(c) : AMC_OK) return rc;
-    return c->PD.on ? amc_pair_step(c) : AMC_OK;
+    for (const amc_sampler &s : AMC_SAMPLERS)
+        if (amc_sampler_due(s.cadence(c), (int64_t)c->out.step))
+            if (int rc = s.step(c)) return rc;
+    return AMC_OK;
+}
+
+// The checks the samplers' entry points start with; `name`: the entry points' prefix ("amc_vdf").  c is not null: they have looked.
+// ... on a configured sampler (`what`: the entry point's name behind the prefix)
+static inline int amc_sampler_ready(amc_ctx *c, bool on, const char *name, const char *what)
+{
+    if (!on) return amc_fail(c, AMC_ERR_STATE, "%s_%s before %s_config", name, what, name);
+    AMC_HIP(c, hipSetDevice(c->device));
+    return AMC_OK;
+}
+// ... amc_<s>_sample: configured, a state uploaded
+static inline int amc_sampler_sample_ready(amc_ctx *c, bool on, const char *name)
+{
+    if (!on) return amc_fail(c, AMC_ERR_STATE, "%s_sample before %s_config", name, name);
+    if (!c->uploaded) return amc_fail(c, AMC_ERR_STATE, "%s_sample before amc_upload", name);
+    AMC_HIP(c, hipSetDevice(c->device));
+    return AMC_OK;
+}
+// ... amc_<s>_config, up to the struct's own fields: a null grid switches the sampler off (free_ws(c) gives its buffers back,
+// *done = true: the caller returns).  needs: what the sampler asks of the context, checked in front of the struct, or nullptr
+template <class Grid, class Free>
+static inline int amc_sampler_config_begin(amc_ctx *c, const Grid *g, const char *grid_name, Free free_ws, bool *done,
+                                           int (*needs)(amc_ctx *c) = nullptr)
+{
+    *done = false;
+    if (!c) return AMC_ERR_INVALID;
+    AMC_HIP(c, hipSetDevice(c->device));
+    AMC_HIP(c, hipStreamSynchronize(c->stream));        // (a sample or launch in flight may still use the old buffers)
+    if (!g) {
+        free_ws(c);
+        *done = true;
+        return AMC_OK;
+    }
+    if (needs)
+        if (int rc = needs(c)) return rc;
+    if (g->struct_size != (int32_t)sizeof(Grid)) return amc_fail(c, AMC_ERR_INVALID, "%s.struct_size mismatch (ABI)", grid_name);
+    return AMC_OK;
 }
 
 // The grid fields amc_field_grid, amc_corr_grid, amc_flux_grid, amc_mfp_grid, amc_vdf_grid and amc_pair_grid have in common, validated (`who`: the struct's name, `unit`: what it calls its

@@ -189,6 +189,15 @@ static int mfp_put(amc_ctx *c, const int64_t *totals, const int64_t *hist, int64
     return AMC_OK;
 }
 
+// what the sampler asks of the context
+static int mfp_needs(amc_ctx *c)
+{
+    if (!c->d_rec) return amc_fail(c, AMC_ERR_STATE, "amc_mfp_config needs path records (amc_params.max_paths >= 0)");
+    if (c->n > AMC_MFP_MAX_PARTICLES)
+        return amc_fail(c, AMC_ERR_CAPACITY, "amc_mfp_config: %lld particles (at most 2^24, as for the other samplers)", (long long)c->n);
+    return AMC_OK;
+}
+
 extern "C" {
 
 int amc_mfp_step(amc_ctx *c)
@@ -218,17 +227,8 @@ int amc_mfp_rewind(amc_ctx *c)
 
 int amc_mfp_config(amc_ctx *c, const amc_mfp_grid *g)
 {
-    if (!c) return AMC_ERR_INVALID;
-    AMC_HIP(c, hipSetDevice(c->device));
-    AMC_HIP(c, hipStreamSynchronize(c->stream));        // (a launch in flight may still use the old buffers)
-    if (!g) {
-        mfp_free(c);
-        return AMC_OK;
-    }
-    if (!c->d_rec) return amc_fail(c, AMC_ERR_STATE, "amc_mfp_config needs path records (amc_params.max_paths >= 0)");
-    if (c->n > AMC_MFP_MAX_PARTICLES)
-        return amc_fail(c, AMC_ERR_CAPACITY, "amc_mfp_config: %lld particles (at most 2^24, as for the other samplers)", (long long)c->n);
-    if (g->struct_size != (int32_t)sizeof(amc_mfp_grid)) return amc_fail(c, AMC_ERR_INVALID, "amc_mfp_grid.struct_size mismatch (ABI)");
+    bool done;
+    if (int rc = amc_sampler_config_begin(c, g, "amc_mfp_grid", mfp_free, &done, mfp_needs); rc || done) return rc;
     const char *fault = nullptr;
     if (g->hist_bins < 0 || g->hist_bins > AMC_MFP_MAX_HIST_BINS) fault = "hist_bins must be 0 .. 64";
     else if (g->keep_records != 0 && g->keep_records != 1) fault = "keep_records must be 0 or 1";
@@ -306,8 +306,7 @@ int amc_mfp_load(amc_ctx *c, const int64_t *totals, const int64_t *hist, int64_t
 int amc_mfp_reset(amc_ctx *c)
 {
     if (!c) return AMC_ERR_INVALID;
-    if (!c->MF.on) return amc_fail(c, AMC_ERR_STATE, "amc_mfp_reset before amc_mfp_config");
-    AMC_HIP(c, hipSetDevice(c->device));
+    if (int rc = amc_sampler_ready(c, c->MF.on, "amc_mfp", "reset")) return rc;
     if (int rc = mfp_put(c, nullptr, nullptr, 0, 0)) return rc;
     c->MF.n_steps = 0;
     return AMC_OK;

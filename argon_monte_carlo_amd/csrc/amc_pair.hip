@@ -313,7 +313,7 @@ static int pair_clear_scratch(amc_ctx *c)
 
 static int pair_launches(amc_ctx *c);
 
-static int pair_enqueue(amc_ctx *c)
+int amc_pair_enqueue(amc_ctx *c)       // (AMC_INTERNAL: the cadence hook's)
 {
     amc_pair_ws &F = c->PD;
     if (int rc = pair_shard_ok(c, "amc_pair")) return rc;
@@ -383,14 +383,6 @@ static void pair_free(amc_ctx *c)
 
 static amc_totals pair_totals(const amc_pair_ws &F) { return amc_totals{F.tot, (size_t)F.G.bins * (size_t)F.C, F.meta, 4, 0}; }
 
-// the checks every entry point on a configured sampler starts with (`what`: its name behind the sampler's)
-static int pair_ready(amc_ctx *c, const char *what)
-{
-    if (!c->PD.on) return amc_fail(c, AMC_ERR_STATE, "amc_pair_%s before amc_pair_config", what);
-    AMC_HIP(c, hipSetDevice(c->device));
-    return AMC_OK;
-}
-
 // The search box of grid G for r_max: the bounding box grown by r_max, min(floor(extent / (r_max * (1 + 2^-20))), 128) cells per
 // axis (at least 1).  false: the box is not finite or a cell edge is not positive.
 static bool pair_box(const amc_fields_grid_dev &G, double r_max, amc_fields_grid_dev *B)
@@ -418,26 +410,18 @@ static bool pair_box(const amc_fields_grid_dev &G, double r_max, amc_fields_grid
 
 extern "C" {
 
-int amc_pair_step(amc_ctx *c) { return amc_pair_due(c, c->out.step) ? pair_enqueue(c) : AMC_OK; }
-
 int amc_pair_reset(amc_ctx *c)
 {
     if (!c) return AMC_ERR_INVALID;
-    if (int rc = pair_ready(c, "reset")) return rc;
+    if (int rc = amc_sampler_ready(c, c->PD.on, "amc_pair", "reset")) return rc;
     const unsigned long long meta[4] = {0, 0, 0, 0};
     return amc_totals_put(c, pair_totals(c->PD), nullptr, meta);
 }
 
 int amc_pair_config(amc_ctx *c, const amc_pair_grid *g)
 {
-    if (!c) return AMC_ERR_INVALID;
-    AMC_HIP(c, hipSetDevice(c->device));
-    AMC_HIP(c, hipStreamSynchronize(c->stream));        // (a sample in flight may still use the old buffers)
-    if (!g) {
-        pair_free(c);
-        return AMC_OK;
-    }
-    if (g->struct_size != (int32_t)sizeof(amc_pair_grid)) return amc_fail(c, AMC_ERR_INVALID, "amc_pair_grid.struct_size mismatch (ABI)");
+    bool done;
+    if (int rc = amc_sampler_config_begin(c, g, "amc_pair_grid", pair_free, &done); rc || done) return rc;
     const char *fault = nullptr;
     if (g->hist_bins < 1 || g->hist_bins > AMC_PAIR_MAX_HIST_BINS) fault = "hist_bins must be 1 .. 256";
     else if (!(isfinite(g->r_max) && g->r_max > 0.0)) fault = "r_max must be finite and > 0";
@@ -478,16 +462,14 @@ int amc_pair_config(amc_ctx *c, const amc_pair_grid *g)
 int amc_pair_sample(amc_ctx *c)
 {
     if (!c) return AMC_ERR_INVALID;
-    if (!c->PD.on) return amc_fail(c, AMC_ERR_STATE, "amc_pair_sample before amc_pair_config");
-    if (!c->uploaded) return amc_fail(c, AMC_ERR_STATE, "amc_pair_sample before amc_upload");
-    AMC_HIP(c, hipSetDevice(c->device));
-    return pair_enqueue(c);
+    if (int rc = amc_sampler_sample_ready(c, c->PD.on, "amc_pair")) return rc;
+    return amc_pair_enqueue(c);
 }
 
 int amc_pair_read(amc_ctx *c, int64_t *totals, int64_t *n_samples, int64_t *n_outside, int64_t *n_unfiled)
 {
     if (!c) return AMC_ERR_INVALID;
-    if (int rc = pair_ready(c, "read")) return rc;
+    if (int rc = amc_sampler_ready(c, c->PD.on, "amc_pair", "read")) return rc;
     unsigned long long meta[4], bad;
     if (int rc = amc_totals_get(c, pair_totals(c->PD), totals, meta, &bad)) return rc;
     if (n_samples) *n_samples = (int64_t)meta[1];
@@ -499,7 +481,7 @@ int amc_pair_read(amc_ctx *c, int64_t *totals, int64_t *n_samples, int64_t *n_ou
 int amc_pair_load(amc_ctx *c, const int64_t *totals, int64_t n_samples, int64_t n_outside, int64_t n_unfiled)
 {
     if (!c || !totals || n_samples < 0 || n_outside < 0 || n_unfiled < 0) return AMC_ERR_INVALID;
-    if (int rc = pair_ready(c, "load")) return rc;
+    if (int rc = amc_sampler_ready(c, c->PD.on, "amc_pair", "load")) return rc;
     const unsigned long long meta[4] = {0, (unsigned long long)n_samples, (unsigned long long)n_outside, (unsigned long long)n_unfiled};
     return amc_totals_put(c, pair_totals(c->PD), totals, meta);
 }

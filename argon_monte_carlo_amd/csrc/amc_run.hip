@@ -347,7 +347,7 @@ int amc_run(amc_ctx *c, double dt, int64_t nsteps, amc_step_stats *sum)
     if (int rc = amc_mg_step_idle(c, "amc_run")) return rc;
     AMC_HIP(c, hipSetDevice(c->device));
     const bool whole = c->lo == 0 && c->hi == c->n && !c->allpairs;
-    // (sampled fields, correlations, fluxes, velocity distributions, transits or the pair distribution with a cadence, or sampled free paths: the plain loop, whose steps end with the state a sample reads)
+    // (a sampler with a cadence, or the sampled free paths: the plain loop, whose steps end with the state a sample reads)
     const bool sampling = amc_samplers_cadence(c);
     if (c->overlap_mode && whole && nsteps >= 2 && !c->keep_prior && !c->detect_ap && c->n > 0 && !sampling &&
         (c->P.geometry == AMC_GEOM_CUBE || c->P.geometry == AMC_GEOM_PORE)) {
@@ -357,7 +357,7 @@ int amc_run(amc_ctx *c, double dt, int64_t nsteps, amc_step_stats *sum)
     }
     // inside the run only the last step needs its own post-sweep bounds pass (needs the whole range in one context) — and
     // every step that is sampled: the sample sees the step's final state
-    if (!c->ordered_always && whole && nsteps >= AMC_OD_MIN_STEPS && nsteps < (1 << 30) && !c->F.on && !c->CR.on && !c->FX.on && !c->MF.on && !c->VD.on && !c->TR.on && !c->PD.on && !c->keep_prior && !c->detect_ap &&
+    if (!c->ordered_always && whole && nsteps >= AMC_OD_MIN_STEPS && nsteps < (1 << 30) && !amc_samplers_configured(c) && !c->keep_prior && !c->detect_ap &&
         !c->d_dbg && c->n > 0 && c->n <= c->od_max_n && c->h_od_stall && c->od_tick < (1 << 30) &&
         (c->P.geometry == AMC_GEOM_CUBE || c->P.geometry == AMC_GEOM_PORE)) {
         int rc = run_on_demand(c, dt, nsteps);

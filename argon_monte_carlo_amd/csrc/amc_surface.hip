@@ -222,21 +222,21 @@ static int surface_put(amc_ctx *c, const int64_t *totals, const int64_t *n_faile
     return AMC_OK;
 }
 
+// what the sampler asks of the context
+static int surface_needs(amc_ctx *c)
+{
+    if (c->P.geometry != AMC_GEOM_PORE_ENERGISED) return amc_fail(c, AMC_ERR_STATE, "amc_surface_config needs AMC_GEOM_PORE_ENERGISED");
+    if (c->n > AMC_SURFACE_MAX_PARTICLES)
+        return amc_fail(c, AMC_ERR_CAPACITY, "amc_surface_config: %lld particles (at most 2^24 keep a launch below 2^22 hit records and its sums exact)", (long long)c->n);
+    return AMC_OK;
+}
+
 extern "C" {
 
 int amc_surface_config(amc_ctx *c, const amc_surface_grid *g)
 {
-    if (!c) return AMC_ERR_INVALID;
-    AMC_HIP(c, hipSetDevice(c->device));
-    AMC_HIP(c, hipStreamSynchronize(c->stream));        // (a launch in flight may still use the old buffers)
-    if (!g) {
-        surface_free(c);
-        return AMC_OK;
-    }
-    if (c->P.geometry != AMC_GEOM_PORE_ENERGISED) return amc_fail(c, AMC_ERR_STATE, "amc_surface_config needs AMC_GEOM_PORE_ENERGISED");
-    if (c->n > AMC_SURFACE_MAX_PARTICLES)
-        return amc_fail(c, AMC_ERR_CAPACITY, "amc_surface_config: %lld particles (at most 2^24 keep a launch below 2^22 hit records and its sums exact)", (long long)c->n);
-    if (g->struct_size != (int32_t)sizeof(amc_surface_grid)) return amc_fail(c, AMC_ERR_INVALID, "amc_surface_grid.struct_size mismatch (ABI)");
+    bool done;
+    if (int rc = amc_sampler_config_begin(c, g, "amc_surface_grid", surface_free, &done, surface_needs); rc || done) return rc;
     if (g->nbins < 1 || g->nbins > AMC_SURFACE_MAX_BINS)
         return amc_fail(c, AMC_ERR_INVALID, "amc_surface_grid: %d bins (1 .. %d)", g->nbins, AMC_SURFACE_MAX_BINS);
     for (int s = 0; s < AMC_SURFACE_CASES; s++)
@@ -289,8 +289,7 @@ int amc_surface_load(amc_ctx *c, const int64_t *totals, const int64_t *n_failed,
 int amc_surface_reset(amc_ctx *c)
 {
     if (!c) return AMC_ERR_INVALID;
-    if (!c->SF.on) return amc_fail(c, AMC_ERR_STATE, "amc_surface_reset before amc_surface_config");
-    AMC_HIP(c, hipSetDevice(c->device));
+    if (int rc = amc_sampler_ready(c, c->SF.on, "amc_surface", "reset")) return rc;
     if (int rc = surface_put(c, nullptr, nullptr)) return rc;
     c->SF.n_steps = 0;
     return AMC_OK;

@@ -244,7 +244,7 @@ __global__ __launch_bounds__(AMC_TRANSIT_REDUCE_THREADS) void k_transit_reduce(c
 }
 
 // ---- the host side -------------------------------------------------------------------------------------------------------------
-static int transit_enqueue(amc_ctx *c)
+int amc_transit_enqueue(amc_ctx *c)    // (AMC_INTERNAL: the cadence hook's)
 {
     amc_transit_ws &F = c->TR;
     int blocks;
@@ -277,14 +277,6 @@ static void transit_free(amc_ctx *c)
 
 static amc_totals transit_totals(const amc_transit_ws &F) { return amc_totals{F.tot, (size_t)2 * AMC_TRANSIT_COLUMNS * (size_t)F.g.n_zones, F.meta, 4, 3}; }
 
-// the checks every entry point on a configured sampler starts with (`what`: its name behind the sampler's)
-static int transit_ready(amc_ctx *c, const char *what)
-{
-    if (!c->TR.on) return amc_fail(c, AMC_ERR_STATE, "amc_transit_%s before amc_transit_config", what);
-    AMC_HIP(c, hipSetDevice(c->device));
-    return AMC_OK;
-}
-
 // a state word as the kernel leaves it: per zone in use a position 0 .. 3 and, only while inside, an entry side 0 .. 2
 static bool transit_word_ok(uint32_t w, int n_zones)
 {
@@ -297,12 +289,10 @@ static bool transit_word_ok(uint32_t w, int n_zones)
 
 extern "C" {
 
-int amc_transit_step(amc_ctx *c) { return amc_transit_due(c, c->out.step) ? transit_enqueue(c) : AMC_OK; }
-
 int amc_transit_reset(amc_ctx *c)
 {
     if (!c) return AMC_ERR_INVALID;
-    if (int rc = transit_ready(c, "reset")) return rc;
+    if (int rc = amc_sampler_ready(c, c->TR.on, "amc_transit", "reset")) return rc;
     amc_transit_ws &F = c->TR;
     AMC_HIP(c, hipMemsetAsync(F.state, 0, sizeof(unsigned int) * (size_t)F.stride, c->stream));
     AMC_HIP(c, hipMemsetAsync(F.entry, 0, sizeof(unsigned int) * (size_t)F.stride * (size_t)F.g.n_zones, c->stream));
@@ -312,14 +302,8 @@ int amc_transit_reset(amc_ctx *c)
 
 int amc_transit_config(amc_ctx *c, const amc_transit_grid *g)
 {
-    if (!c) return AMC_ERR_INVALID;
-    AMC_HIP(c, hipSetDevice(c->device));
-    AMC_HIP(c, hipStreamSynchronize(c->stream));        // (a sample in flight may still use the old buffers)
-    if (!g) {
-        transit_free(c);
-        return AMC_OK;
-    }
-    if (g->struct_size != (int32_t)sizeof(amc_transit_grid)) return amc_fail(c, AMC_ERR_INVALID, "amc_transit_grid.struct_size mismatch (ABI)");
+    bool done;
+    if (int rc = amc_sampler_config_begin(c, g, "amc_transit_grid", transit_free, &done); rc || done) return rc;
     if (g->n_zones < 1 || g->n_zones > AMC_TRANSIT_MAX_ZONES)
         return amc_fail(c, AMC_ERR_INVALID, "amc_transit_grid: %d zones (1 .. %d)", g->n_zones, AMC_TRANSIT_MAX_ZONES);
     if (g->every < 0 || g->step_offset < 0 || g->reserved[0] != 0 || g->reserved[1] != 0)
@@ -353,16 +337,14 @@ int amc_transit_config(amc_ctx *c, const amc_transit_grid *g)
 int amc_transit_sample(amc_ctx *c)
 {
     if (!c) return AMC_ERR_INVALID;
-    if (!c->TR.on) return amc_fail(c, AMC_ERR_STATE, "amc_transit_sample before amc_transit_config");
-    if (!c->uploaded) return amc_fail(c, AMC_ERR_STATE, "amc_transit_sample before amc_upload");
-    AMC_HIP(c, hipSetDevice(c->device));
-    return transit_enqueue(c);
+    if (int rc = amc_sampler_sample_ready(c, c->TR.on, "amc_transit")) return rc;
+    return amc_transit_enqueue(c);
 }
 
 int amc_transit_read(amc_ctx *c, int64_t *totals, int64_t *n_samples)
 {
     if (!c) return AMC_ERR_INVALID;
-    if (int rc = transit_ready(c, "read")) return rc;
+    if (int rc = amc_sampler_ready(c, c->TR.on, "amc_transit", "read")) return rc;
     unsigned long long meta[4], bad;
     if (int rc = amc_totals_get(c, transit_totals(c->TR), totals, meta, &bad)) return rc;
     if (bad != ~0ULL)
@@ -377,7 +359,7 @@ int amc_transit_read(amc_ctx *c, int64_t *totals, int64_t *n_samples)
 int amc_transit_state(amc_ctx *c, uint32_t *state, uint32_t *entry)
 {
     if (!c) return AMC_ERR_INVALID;
-    if (int rc = transit_ready(c, "state")) return rc;
+    if (int rc = amc_sampler_ready(c, c->TR.on, "amc_transit", "state")) return rc;
     amc_transit_ws &F = c->TR;
     const size_t cnt = (size_t)(c->hi - c->lo), bytes = sizeof(uint32_t) * cnt;
     if (state && bytes) AMC_HIP(c, hipMemcpyAsync(state, F.state + c->lo, bytes, hipMemcpyDeviceToHost, c->stream));
@@ -390,7 +372,7 @@ int amc_transit_state(amc_ctx *c, uint32_t *state, uint32_t *entry)
 int amc_transit_load(amc_ctx *c, const int64_t *totals, int64_t n_samples, const uint32_t *state, const uint32_t *entry)
 {
     if (!c || !totals) return AMC_ERR_INVALID;
-    if (int rc = transit_ready(c, "load")) return rc;
+    if (int rc = amc_sampler_ready(c, c->TR.on, "amc_transit", "load")) return rc;
     amc_transit_ws &F = c->TR;
     if (n_samples < 0 || n_samples > AMC_TRANSIT_MAX_SAMPLES)
         return amc_fail(c, AMC_ERR_INVALID, "amc_transit_load: %lld samples (0 .. 2^32 - 1)", (long long)n_samples);

@@ -156,7 +156,7 @@ __global__ __launch_bounds__(AMC_VDF_REDUCE_THREADS) void k_vdf_reduce(const uns
 }
 
 // ---- the host side -------------------------------------------------------------------------------------------------------------
-static int vdf_enqueue(amc_ctx *c)
+int amc_vdf_enqueue(amc_ctx *c)        // (AMC_INTERNAL: the cadence hook's)
 {
     amc_vdf_ws &F = c->VD;
     int blocks;
@@ -184,36 +184,20 @@ static void vdf_free(amc_ctx *c)
 
 static amc_totals vdf_totals(const amc_vdf_ws &F) { return amc_totals{F.tot, (size_t)F.G.bins * (size_t)F.C, F.meta, 4, 3}; }
 
-// the checks every entry point on a configured sampler starts with (`what`: its name behind the sampler's)
-static int vdf_ready(amc_ctx *c, const char *what)
-{
-    if (!c->VD.on) return amc_fail(c, AMC_ERR_STATE, "amc_vdf_%s before amc_vdf_config", what);
-    AMC_HIP(c, hipSetDevice(c->device));
-    return AMC_OK;
-}
-
 extern "C" {
-
-int amc_vdf_step(amc_ctx *c) { return amc_vdf_due(c, c->out.step) ? vdf_enqueue(c) : AMC_OK; }
 
 int amc_vdf_reset(amc_ctx *c)
 {
     if (!c) return AMC_ERR_INVALID;
-    if (int rc = vdf_ready(c, "reset")) return rc;
+    if (int rc = amc_sampler_ready(c, c->VD.on, "amc_vdf", "reset")) return rc;
     const unsigned long long meta[4] = {0, 0, 0, 0};
     return amc_totals_put(c, vdf_totals(c->VD), nullptr, meta);
 }
 
 int amc_vdf_config(amc_ctx *c, const amc_vdf_grid *g)
 {
-    if (!c) return AMC_ERR_INVALID;
-    AMC_HIP(c, hipSetDevice(c->device));
-    AMC_HIP(c, hipStreamSynchronize(c->stream));        // (a sample in flight may still use the old buffers)
-    if (!g) {
-        vdf_free(c);
-        return AMC_OK;
-    }
-    if (g->struct_size != (int32_t)sizeof(amc_vdf_grid)) return amc_fail(c, AMC_ERR_INVALID, "amc_vdf_grid.struct_size mismatch (ABI)");
+    bool done;
+    if (int rc = amc_sampler_config_begin(c, g, "amc_vdf_grid", vdf_free, &done); rc || done) return rc;
     const char *fault = nullptr;
     if (g->hist_bins < 1 || g->hist_bins > AMC_VDF_MAX_HIST_BINS) fault = "hist_bins must be 1 .. 256";
     else if (!(isfinite(g->v_max) && g->v_max > 0.0 && g->v_max <= 16384.0)) fault = "v_max must be finite, > 0 and at most 16384 m/s";
@@ -244,16 +228,14 @@ int amc_vdf_config(amc_ctx *c, const amc_vdf_grid *g)
 int amc_vdf_sample(amc_ctx *c)
 {
     if (!c) return AMC_ERR_INVALID;
-    if (!c->VD.on) return amc_fail(c, AMC_ERR_STATE, "amc_vdf_sample before amc_vdf_config");
-    if (!c->uploaded) return amc_fail(c, AMC_ERR_STATE, "amc_vdf_sample before amc_upload");
-    AMC_HIP(c, hipSetDevice(c->device));
-    return vdf_enqueue(c);
+    if (int rc = amc_sampler_sample_ready(c, c->VD.on, "amc_vdf")) return rc;
+    return amc_vdf_enqueue(c);
 }
 
 int amc_vdf_read(amc_ctx *c, int64_t *totals, int64_t *n_samples, int64_t *n_outside)
 {
     if (!c) return AMC_ERR_INVALID;
-    if (int rc = vdf_ready(c, "read")) return rc;
+    if (int rc = amc_sampler_ready(c, c->VD.on, "amc_vdf", "read")) return rc;
     unsigned long long meta[4], bad;
     if (int rc = amc_totals_get(c, vdf_totals(c->VD), totals, meta, &bad)) return rc;
     if (bad != ~0ULL)
@@ -267,7 +249,7 @@ int amc_vdf_read(amc_ctx *c, int64_t *totals, int64_t *n_samples, int64_t *n_out
 int amc_vdf_load(amc_ctx *c, const int64_t *totals, int64_t n_samples, int64_t n_outside)
 {
     if (!c || !totals || n_samples < 0 || n_outside < 0) return AMC_ERR_INVALID;
-    if (int rc = vdf_ready(c, "load")) return rc;
+    if (int rc = amc_sampler_ready(c, c->VD.on, "amc_vdf", "load")) return rc;
     const unsigned long long meta[4] = {0, (unsigned long long)n_samples, (unsigned long long)n_outside, 0};
     return amc_totals_put(c, vdf_totals(c->VD), totals, meta);
 }

@@ -19,6 +19,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from . import samplers as S
+
 
 def shard_range(n, rank, world):
     """Contiguous index range [lo, hi) of ``rank``; equal shards when world divides n."""
@@ -92,7 +94,7 @@ class TorchComm:
         return [p.numpy().reshape(-1, width) for p in parts]
 
 
-class ShardedSimulation:
+class ShardedSimulation(S.Controls):
     SHARDED_DETECT_MIN_N = 1_500_000
     SUM_KEYS = ("n_pp", "n_wall", "n_oob_walls", "n_oob_pp", "n_paths", "n_fp_errors")
 
@@ -211,16 +213,18 @@ class ShardedSimulation:
         return out
 
     # ---- sampled fields (fields.py): every rank samples its own shard, the totals are summed exactly ---------------------
+    # (enable / disable / sample / reset are samplers.Controls', as in sim.Simulation; a cadence keeps the grid's own step_offset)
     def enable_fields(self, grid=None, every=0):
-        from . import fields as FL
-        g = FL.default_grid(self.params) if grid is None else grid
-        self.engine.fields_config(FL.copy_grid(g, every=every))
+        self._sampler_enable(S.FIELDS, grid, every=every)
+
+    def disable_fields(self):
+        self._sampler_disable(S.FIELDS)
 
     def fields_sample(self):
-        self.engine.fields_sample()
+        self._sampler_sample(S.FIELDS)
 
     def fields_reset(self):
-        self.engine.fields_reset()
+        self._sampler_reset(S.FIELDS)
 
     def _read_summed(self, read, shapes, n_counters, describe, own_if_all_failed=False):
         """``read()`` of this rank -> (its 128-bit word arrays, its counters to sum, whatever else the caller wants back), the
@@ -240,6 +244,11 @@ class ShardedSimulation:
         return arrays, counters, rest
 
     @staticmethod
+    def _as_words(counts):
+        """64-bit counts as (low, high) words with a zero high half: what ``totals.sum_over_ranks`` sums"""
+        return np.stack([counts, np.zeros_like(counts)], axis=-1)
+
+    @staticmethod
     def _describe(read, capacity=None):
         """the error for the first failing rank r: status s > 0 is particle s - 1 (named where ``capacity`` has the text), else the code"""
         from ._abi import AMC_ERR_CAPACITY
@@ -257,33 +266,33 @@ class ShardedSimulation:
         A read that fails on one rank (a particle out of the sampler's range lives on one shard) fails on every rank, from
         this same call: the failing rank still takes part in the all-reduce, whose first ``world`` entries carry each rank's
         status — 0, the bad particle's index + 1, or the (negative) error code of any other failure."""
-        from . import fields as FL
-        g = self.engine.field_grid
-        return self._moments_summed(FL, "fields", g, None if g is None else (FL.grid_bins(g), 7, 2), "fields_reset")
+        return self._moments_summed(S.FIELDS)
 
-    def _moments_summed(self, mod, name, g, shape, reset):
-        """``fields()`` / ``fluxes()``: the engine's ``<name>_read`` on grid ``g`` (None: not configured) summed over the ranks
-        and derived by ``mod``; ``shape``: the totals', ``reset``: the call the capacity text names."""
+    def _moments_summed(self, s):
+        """``fields()`` / ``fluxes()``: the engine's read of the sampler ``s`` summed over the ranks and derived by its module"""
+        g = getattr(self.engine, s.grid_attr)
+
         def read():
-            tot, ns, no = getattr(self.engine, name + "_read")()
+            tot, ns, no = getattr(self.engine, s.prefix + "_read")()
             return [tot], [no], ns
         (tot,), (no,), ns = self._read_summed(
-            read, None if g is None else [shape], 1,
-            self._describe(name + "_read", "amc_" + name + ": particle {p} (rank {r}) has a velocity component outside |c| < 2^14 m/s (or NaN); "
-                                           "sampling stopped until " + reset))
-        return mod.derive(g, tot, ns, no, float(self.params.argon_mass), mod.boltzmann_constant(self.params))
+            read, None if g is None else [s.totals_shape(g)], 1,
+            self._describe(s.prefix + "_read", "amc_" + s.prefix + ": particle {p} (rank {r}) has a velocity component outside |c| < 2^14 m/s (or NaN); "
+                                               "sampling stopped until " + s.name + "_reset"))
+        return s.module.derive(g, tot, ns, no, float(self.params.argon_mass), s.module.boltzmann_constant(self.params))
 
     # ---- sampled correlations (correlations.py): every rank samples its own index range, the totals are summed exactly ------
     def enable_correlations(self, grid=None, every=0, n_lags=None):
-        from . import correlations as CO
-        g = CO.default_grid(self.params) if grid is None else grid
-        self.engine.corr_config(CO.copy_grid(g, every=every, n_lags=n_lags))
+        self._sampler_enable(S.CORRELATIONS, grid, every=every, n_lags=n_lags)
+
+    def disable_correlations(self):
+        self._sampler_disable(S.CORRELATIONS)
 
     def correlations_sample(self):
-        self.engine.corr_sample()
+        self._sampler_sample(S.CORRELATIONS)
 
     def correlations_reset(self):
-        self.engine.corr_reset()
+        self._sampler_reset(S.CORRELATIONS)
 
     def correlations(self, dt=None, every=None):
         """Simulation.correlations() of the whole system (a collective: every rank calls it).  The ranks' 128-bit totals and
@@ -309,35 +318,32 @@ class ShardedSimulation:
 
     # ---- sampled fluxes (fluxes.py): every rank samples its own index range, the totals are summed exactly -------------------
     def enable_fluxes(self, grid=None, every=0):
-        from . import fluxes as FX
-        g = FX.default_grid(self.params) if grid is None else grid
-        self.engine.flux_config(FX.copy_grid(g, every=every))
+        self._sampler_enable(S.FLUXES, grid, every=every)
+
+    def disable_fluxes(self):
+        self._sampler_disable(S.FLUXES)
 
     def fluxes_sample(self):
-        self.engine.flux_sample()
+        self._sampler_sample(S.FLUXES)
 
     def fluxes_reset(self):
-        self.engine.flux_reset()
+        self._sampler_reset(S.FLUXES)
 
     def fluxes(self):
         """Simulation.fluxes() of the whole system (a collective: every rank calls it): the ranks' 128-bit totals and the
         outside counter summed as 32-bit limbs in one int64 all-reduce, exactly as ``fields()`` does — a read that fails on one
         rank fails on every rank, from this same call."""
-        from . import fluxes as FX
-        g = self.engine.flux_grid
-        return self._moments_summed(FX, "flux", g, None if g is None else FX.totals_shape(g), "fluxes_reset")
+        return self._moments_summed(S.FLUXES)
 
     # ---- sampled free paths (free_paths.py): every rank bins the records it emitted — owners in its own range ---------------
     def enable_free_paths(self, grid=None, keep_records=False):
-        from . import free_paths as FP
-        g = FP.default_grid(self.params) if grid is None else grid
-        self.engine.mfp_config(FP.copy_grid(g, keep_records=keep_records))
+        self._sampler_enable(S.FREE_PATHS, grid, keep_records=keep_records)
 
     def disable_free_paths(self):
-        self.engine.mfp_config(None)
+        self._sampler_disable(S.FREE_PATHS)
 
     def free_paths_reset(self):
-        self.engine.mfp_reset()
+        self._sampler_reset(S.FREE_PATHS)
 
     def free_paths(self, dt=None):
         """Simulation.free_paths() of the whole system (a collective: every rank calls it): the ranks' 128-bit totals, their
@@ -354,7 +360,7 @@ class ShardedSimulation:
 
         def read():
             tot, hist, (nr, no, ns) = self.engine.mfp_read()
-            return [tot, np.stack([hist, np.zeros_like(hist)], axis=-1)], [nr, no], ns
+            return [tot, self._as_words(hist)], [nr, no], ns
         (tot, hist), (nr, no), ns = self._read_summed(
             read, None if g is None else [FP.totals_shape(g), FP.hist_shape(g) + (2,)], 2,
             self._describe("mfp_read", "amc_mfp: a free path of particle {p} (rank {r}) is outside [0, 2^-16 m) (or NaN); "
@@ -365,15 +371,16 @@ class ShardedSimulation:
 
     # ---- sampled velocity distributions (distributions.py): every rank samples its own index range, the counts are summed -----
     def enable_distributions(self, grid=None, every=0):
-        from . import distributions as VD
-        g = VD.default_grid(self.params) if grid is None else grid
-        self.engine.vdf_config(VD.copy_grid(g, every=every))
+        self._sampler_enable(S.DISTRIBUTIONS, grid, every=every)
+
+    def disable_distributions(self):
+        self._sampler_disable(S.DISTRIBUTIONS)
 
     def distributions_sample(self):
-        self.engine.vdf_sample()
+        self._sampler_sample(S.DISTRIBUTIONS)
 
     def distributions_reset(self):
-        self.engine.vdf_reset()
+        self._sampler_reset(S.DISTRIBUTIONS)
 
     def distributions(self):
         """Simulation.distributions() of the whole system (a collective: every rank calls it): the ranks' 64-bit counts (as
@@ -384,7 +391,7 @@ class ShardedSimulation:
 
         def read():
             tot, ns, no = self.engine.vdf_read()
-            return [np.stack([tot, np.zeros_like(tot)], axis=-1)], [no], ns
+            return [self._as_words(tot)], [no], ns
         (tot,), (no,), ns = self._read_summed(
             read, None if g is None else [VD.totals_shape(g) + (2,)], 1,
             self._describe("vdf_read", "amc_vdf: particle {p} (rank {r}) has a velocity component outside |c| < 2^14 m/s (or NaN); "
@@ -393,18 +400,16 @@ class ShardedSimulation:
 
     # ---- sampled transits (transits.py): every rank tracks the particles of its own index range, the totals are summed -------
     def enable_transits(self, grid=None, every=1):
-        from . import transits as TR
-        g = TR.default_grid(self.params) if grid is None else grid
-        self.engine.transit_config(TR.copy_grid(g, every=every))
+        self._sampler_enable(S.TRANSITS, grid, every=every)
 
     def disable_transits(self):
-        self.engine.transit_config(None)
+        self._sampler_disable(S.TRANSITS)
 
     def transits_sample(self):
-        self.engine.transit_sample()
+        self._sampler_sample(S.TRANSITS)
 
     def transits_reset(self):
-        self.engine.transit_reset()
+        self._sampler_reset(S.TRANSITS)
 
     def transits(self, dt=None, every=None):
         """Simulation.transits() of the whole system (a collective: every rank calls it): the ranks' 128-bit totals summed in
@@ -429,18 +434,16 @@ class ShardedSimulation:
 
     # ---- sampled pair distribution (pairs.py): every rank counts the centres of its own index range against ALL particles ------
     def enable_pairs(self, grid=None, every=0):
-        from . import pairs as PA
-        g = PA.default_grid(self.params) if grid is None else grid
-        self.engine.pair_config(PA.copy_grid(g, every=every))
+        self._sampler_enable(S.PAIRS, grid, every=every)
 
     def disable_pairs(self):
-        self.engine.pair_config(None)
+        self._sampler_disable(S.PAIRS)
 
     def pairs_sample(self):
-        self.engine.pair_sample()
+        self._sampler_sample(S.PAIRS)
 
     def pairs_reset(self):
-        self.engine.pair_reset()
+        self._sampler_reset(S.PAIRS)
 
     def pairs(self):
         """Simulation.pairs() of the whole system (a collective: every rank calls it): the ranks' 64-bit counts (as words with
@@ -456,7 +459,7 @@ class ShardedSimulation:
 
         def read():
             tot, ns, no, nu = self.engine.pair_read()
-            return [np.stack([tot, np.zeros_like(tot)], axis=-1)], [no], (ns, nu)
+            return [self._as_words(tot)], [no], (ns, nu)
         (tot,), (no,), (ns, nu) = self._read_summed(read, None if g is None else [PA.totals_shape(g) + (2,)], 1, self._describe("pair_read"))
         return PA.derive(g, tot[..., 0], ns, no, nu, float(self.params.collision_range))
 
@@ -708,12 +711,11 @@ class ShardedTemperatureSimulation(ShardedSimulation):
 
     # ---- sampled surfaces over shards: every rank accumulates its own hits, the totals are summed exactly ----------------------
     def enable_surface(self, grid=None):
-        from . import surface as SU
         self._need_device_rng()
-        self.engine.surface_config(SU.default_grid(self.params) if grid is None else grid)
+        self._sampler_enable(S.SURFACES, grid)
 
     def surface_reset(self):
-        self.engine.surface_reset()
+        self._sampler_reset(S.SURFACES)
 
     def surface(self):
         """``TemperatureSimulation.surface()`` of the whole system (a collective: every rank calls it).  The ranks' 128-bit

@@ -6,8 +6,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._abi import (AMC_K_NAMES, AmcCorrGrid, AmcFieldGrid, AmcFluxGrid, AmcMfpGrid, AmcPairGrid, AmcParams, AmcPathRecord, AmcStepStats, AmcSurfaceGrid, AmcVdfGrid, path_record_dtype)
-from ._abi import AMC_TRANSIT_COLUMNS, AmcTransitGrid
+from . import samplers as S
+from ._abi import AMC_K_NAMES, AmcParams, AmcPathRecord, AmcStepStats, path_record_dtype
 
 _dp = C.POINTER(C.c_double)
 _i64p = C.POINTER(C.c_int64)
@@ -32,14 +32,8 @@ class Engine:
         self.lib = _lib.load()
         self.params = params
         self.n = int(params.n)
-        self.field_grid = None
-        self.surface_grid = None
-        self.corr_grid = None
-        self.flux_grid = None
-        self.mfp_grid = None
-        self.vdf_grid = None
-        self.pair_grid = None
-        self.transit_grid = None
+        for s in S.ALL:                 # the configured grids (None: off): field_grid, corr_grid, ... surface_grid
+            setattr(self, s.grid_attr, None)
         self._ctx = C.c_void_p()
         rc = self.lib.amc_create(C.byref(self._ctx), C.byref(params))
         if rc != 0:
@@ -162,265 +156,208 @@ class Engine:
     def reset_outputs(self):
         self._ck(self.lib.amc_reset_outputs(self._ctx))
 
-    # -- sampled fields (fields.py) and sampled fluxes (fluxes.py): one implementation.  name: the C prefix; attr, grid_type: where
-    # and as what the engine keeps the grid (g); rows: tables of seven totals per bin ---------------------------------------
-    def _moments_config(self, name, attr, grid_type, grid):
-        self._ck(getattr(self.lib, f"amc_{name}_config")(self._ctx, None if grid is None else C.byref(grid)))
-        setattr(self, attr, None if grid is None else grid_type.from_buffer_copy(grid))
+    # -- the samplers (samplers.py): one implementation over a sampler's record s; the public methods below name it -----------------
+    def _range_count(self):
+        """particles in the context's index range"""
+        return int(getattr(self, "hi", self.n)) - int(getattr(self, "lo", 0))
 
-    def _moments_read(self, name, g, rows):
+    def _sampler_config(self, s, grid):
+        self._ck(getattr(self.lib, f"amc_{s.prefix}_config")(self._ctx, None if grid is None else C.byref(grid)))
+        setattr(self, s.grid_attr, None if grid is None else s.grid_type.from_buffer_copy(grid))
+
+    def _sampler_sample(self, s):
+        self._ck(getattr(self.lib, f"amc_{s.prefix}_sample")(self._ctx))
+
+    def _sampler_reset(self, s):
+        self._ck(getattr(self.lib, f"amc_{s.prefix}_reset")(self._ctx))
+
+    def _sampler_grid(self, s, what):
+        g = getattr(self, s.grid_attr)
         if g is None:
-            raise _lib.ArgonMCError(-6, f"{name}_read before {name}_config")
-        tot = np.zeros((int(g.n1) * int(g.n2) * int(g.n3),) + (rows,) * (rows > 1) + (7, 2), dtype=np.int64)
-        ns, no = C.c_int64(0), C.c_int64(0)
-        self._ck(getattr(self.lib, f"amc_{name}_read")(self._ctx, tot.ctypes.data_as(_i64p), C.byref(ns), C.byref(no)))
-        return tot, ns.value, no.value
+            raise _lib.ArgonMCError(-6, f"{s.prefix}_{what} before {s.prefix}_config")
+        return g
 
-    def _moments_load(self, name, g, rows, totals, n_samples, n_outside):
-        tot = np.ascontiguousarray(totals, dtype=np.int64)
-        if g is None or tot.size != int(g.n1) * int(g.n2) * int(g.n3) * 14 * rows:
-            raise ValueError("totals do not match the configured grid")
-        self._ck(getattr(self.lib, f"amc_{name}_load")(self._ctx, tot.ctypes.data_as(_i64p), int(n_samples), int(n_outside)))
+    def _sampler_read(self, s):
+        g = self._sampler_grid(s, "read") if s.guarded else getattr(self, s.grid_attr)
+        tot = np.zeros(s.totals_shape(g), dtype=np.int64)
+        arrays = [np.zeros(shape(s.module, g), dtype=np.int64) for _, shape in s.arrays]
+        c = [C.c_int64(0) for _ in s.counters]
+        self._ck(getattr(self.lib, f"amc_{s.prefix}_read")(self._ctx, *[a.ctypes.data_as(_i64p) for a in [tot] + arrays], *[C.byref(v) for v in c]))
+        return s.join_read(tot, arrays, [v.value for v in c])
 
+    def _sampler_load(self, s, totals, arrays, counters, particles=(), unconfigured=None):
+        """totals and arrays checked against the configured grid (none — unconfigured None: the same ValueError; else the entry
+        point's name in the library's error), then the per-particle arrays: (array or None, dtype, shape, what the message calls it)"""
+        g = getattr(self, s.grid_attr) if unconfigured is None else self._sampler_grid(s, unconfigured)
+        arrs = [np.ascontiguousarray(a, dtype=np.int64) for a in (totals, *arrays)]
+        shapes = [] if g is None else [s.totals_shape(g)] + [shape(s.module, g) for _, shape in s.arrays]
+        if g is None or any(a.size != int(np.prod(sh)) for a, sh in zip(arrs, shapes)):
+            raise ValueError(f"totals do not match the configured {s.grid_word}")
+        per = [None if a is None else np.ascontiguousarray(a, dtype=dtype) for a, dtype, _, _ in particles]
+        for a, (_, dtype, shape, label) in zip(per, particles):
+            if a is not None and a.shape != shape:
+                raise ValueError(f"expected {np.dtype(dtype).name}[{', '.join(str(k) for k in shape)}]{label}, got {a.shape}")
+        ptrs = [None if a is None else a.ctypes.data_as(_u32p if a.dtype == np.uint32 else _dp) for a in per]
+        self._ck(getattr(self.lib, f"amc_{s.prefix}_load")(self._ctx, *[a.ctypes.data_as(_i64p) for a in arrs], *[int(v) for v in counters], *ptrs))
+
+    # -- sampled fields (fields.py) ------------------------------------------------------------------------------------------
     def fields_config(self, grid):
         """Sample on ``grid`` (an ``AmcFieldGrid``, fields.make_grid); None switches sampling off.  Starts from zero totals."""
-        self._moments_config("fields", "field_grid", AmcFieldGrid, grid)
+        self._sampler_config(S.FIELDS, grid)
 
     def fields_sample(self):
         """One sample of the current state, enqueued on the context's stream."""
-        self._ck(self.lib.amc_fields_sample(self._ctx))
+        self._sampler_sample(S.FIELDS)
 
     def fields_read(self):
         """(int64[bins, 7, 2] totals as (low, high) words, samples, particles outside); synchronises."""
-        return self._moments_read("fields", self.field_grid, 1)
+        return self._sampler_read(S.FIELDS)
 
     def fields_load(self, totals, n_samples, n_outside):
-        self._moments_load("fields", self.field_grid, 1, totals, n_samples, n_outside)
+        self._sampler_load(S.FIELDS, totals, (), (n_samples, n_outside))
 
     def fields_reset(self):
-        self._ck(self.lib.amc_fields_reset(self._ctx))
+        self._sampler_reset(S.FIELDS)
 
+    # -- sampled fluxes (fluxes.py) --------------------------------------------------------------------------------------------
     def flux_config(self, grid):
         """Sample on ``grid`` (an ``AmcFluxGrid``, fluxes.make_grid); None switches sampling off.  Starts from zero totals."""
-        self._moments_config("flux", "flux_grid", AmcFluxGrid, grid)
+        self._sampler_config(S.FLUXES, grid)
 
     def flux_sample(self):
         """One sample of the current state, enqueued on the context's stream."""
-        self._ck(self.lib.amc_flux_sample(self._ctx))
+        self._sampler_sample(S.FLUXES)
 
     def flux_read(self):
         """(int64[bins, 2, 7, 2] totals as (low, high) words, samples, particles outside); synchronises."""
-        return self._moments_read("flux", self.flux_grid, 2)
+        return self._sampler_read(S.FLUXES)
 
     def flux_load(self, totals, n_samples, n_outside):
-        self._moments_load("flux", self.flux_grid, 2, totals, n_samples, n_outside)
+        self._sampler_load(S.FLUXES, totals, (), (n_samples, n_outside))
 
     def flux_reset(self):
-        self._ck(self.lib.amc_flux_reset(self._ctx))
+        self._sampler_reset(S.FLUXES)
 
     # -- sampled correlations (correlations.py) ----------------------------------------------------------------------
     def corr_config(self, grid):
         """Sample on ``grid`` (an ``AmcCorrGrid``, correlations.make_grid); None switches sampling off.  Starts from zero
         totals; the first sample is a time origin."""
-        self._ck(self.lib.amc_corr_config(self._ctx, None if grid is None else C.byref(grid)))
-        self.corr_grid = None if grid is None else AmcCorrGrid.from_buffer_copy(grid)
-
-    def _corr_range(self):
-        return int(getattr(self, "hi", self.n)) - int(getattr(self, "lo", 0))
+        self._sampler_config(S.CORRELATIONS, grid)
 
     def corr_sample(self):
         """One sample of the current state at the window position, enqueued on the context's stream."""
-        self._ck(self.lib.amc_corr_sample(self._ctx))
+        self._sampler_sample(S.CORRELATIONS)
 
     def corr_read(self):
         """(int64[groups, n_lags + 1, 7, 2] totals as (low, high) words, (n_origins, n_samples, n_outside, window_pos));
         synchronises."""
-        g = self.corr_grid
-        if g is None:
-            raise _lib.ArgonMCError(-6, "corr_read before corr_config")
-        tot = np.zeros((int(g.n1) * int(g.n2) * int(g.n3), int(g.n_lags) + 1, 7, 2), dtype=np.int64)
-        c = [C.c_int64(0) for _ in range(4)]
-        self._ck(self.lib.amc_corr_read(self._ctx, tot.ctypes.data_as(_i64p), *[C.byref(v) for v in c]))
-        return tot, tuple(v.value for v in c)
+        return self._sampler_read(S.CORRELATIONS)
 
     def corr_origin(self):
         """The six origin arrays (x0, y0, z0, vx0, vy0, vz0) of the context's index range."""
-        if self.corr_grid is None:
-            raise _lib.ArgonMCError(-6, "corr_origin before corr_config")
-        arrs = [np.zeros(self._corr_range()) for _ in range(6)]
+        self._sampler_grid(S.CORRELATIONS, "origin")
+        arrs = [np.zeros(self._range_count()) for _ in range(6)]
         self._ck(self.lib.amc_corr_origin(self._ctx, *[_d(a) for a in arrs]))
         return arrs
 
     def corr_load(self, totals, counters, origin=None):
         """The inverse of ``corr_read`` + ``corr_origin``: totals, (n_origins, n_samples, n_outside, window_pos) and the six
         origin arrays (None only at window position 0)."""
-        tot = np.ascontiguousarray(totals, dtype=np.int64)
-        g = self.corr_grid
-        if g is None or tot.size != int(g.n1) * int(g.n2) * int(g.n3) * (int(g.n_lags) + 1) * 14:
-            raise ValueError("totals do not match the configured grid")
-        arrs = [None] * 6 if origin is None else [_f64(a, self._corr_range()) for a in origin]
-        no, ns, nout, pos = (int(v) for v in counters)
-        self._ck(self.lib.amc_corr_load(self._ctx, tot.ctypes.data_as(_i64p), no, ns, nout, pos, *[_d(a) for a in arrs]))
+        self._sampler_load(S.CORRELATIONS, totals, (), counters,
+                           [(a, np.float64, (self._range_count(),), "") for a in ([None] * 6 if origin is None else origin)])
 
     def corr_reset(self):
-        self._ck(self.lib.amc_corr_reset(self._ctx))
+        self._sampler_reset(S.CORRELATIONS)
 
     # -- sampled free paths (free_paths.py, DESIGN.md 14) --------------------------------------------------------------
     def mfp_config(self, grid):
         """Sample on ``grid`` (an ``AmcMfpGrid``, free_paths.make_grid); None switches sampling off.  Starts from zero totals,
         at the path records' current end."""
-        self._ck(self.lib.amc_mfp_config(self._ctx, None if grid is None else C.byref(grid)))
-        self.mfp_grid = None if grid is None else AmcMfpGrid.from_buffer_copy(grid)
-
-    def _mfp_shapes(self):
-        g = self.mfp_grid
-        if g is None:
-            raise _lib.ArgonMCError(-6, "mfp_read before mfp_config")
-        bins = int(g.n1) * int(g.n2) * int(g.n3)
-        return (bins, 2, 7, 2), (bins, 2, int(g.hist_bins) + 1)
+        self._sampler_config(S.FREE_PATHS, grid)
 
     def mfp_read(self):
         """(int64[bins, 2, 7, 2] totals as (low, high) words, int64[bins, 2, hist_bins + 1] histogram counts, (records binned,
         owners outside, steps)); synchronises."""
-        st, sh = self._mfp_shapes()
-        tot, hist = np.zeros(st, dtype=np.int64), np.zeros(sh, dtype=np.int64)
-        c = [C.c_int64(0) for _ in range(3)]
-        self._ck(self.lib.amc_mfp_read(self._ctx, tot.ctypes.data_as(_i64p), hist.ctypes.data_as(_i64p), *[C.byref(v) for v in c]))
-        return tot, hist, tuple(v.value for v in c)
+        return self._sampler_read(S.FREE_PATHS)
 
     def mfp_load(self, totals, hist, counters):
         """The inverse of ``mfp_read``: totals, histogram counts and (records binned, owners outside, steps)."""
-        st, sh = self._mfp_shapes()
-        tot = np.ascontiguousarray(totals, dtype=np.int64)
-        h = np.ascontiguousarray(hist, dtype=np.int64)
-        if tot.size != int(np.prod(st)) or h.size != int(np.prod(sh)):
-            raise ValueError("totals do not match the configured grid")
-        nr, no, ns = (int(v) for v in counters)
-        self._ck(self.lib.amc_mfp_load(self._ctx, tot.ctypes.data_as(_i64p), h.ctypes.data_as(_i64p), nr, no, ns))
+        self._sampler_load(S.FREE_PATHS, totals, (hist,), counters, unconfigured="read")
 
     def mfp_reset(self):
-        self._ck(self.lib.amc_mfp_reset(self._ctx))
+        self._sampler_reset(S.FREE_PATHS)
 
     # -- sampled velocity distributions (distributions.py, DESIGN.md 15) -----------------------------------------------
     def vdf_config(self, grid):
         """Sample on ``grid`` (an ``AmcVdfGrid``, distributions.make_grid); None switches sampling off.  Starts from zero totals."""
-        self._ck(self.lib.amc_vdf_config(self._ctx, None if grid is None else C.byref(grid)))
-        self.vdf_grid = None if grid is None else AmcVdfGrid.from_buffer_copy(grid)
-
-    def _vdf_shape(self, what):
-        g = self.vdf_grid
-        if g is None:
-            raise _lib.ArgonMCError(-6, f"vdf_{what} before vdf_config")
-        return (int(g.n1) * int(g.n2) * int(g.n3), 4 * int(g.hist_bins) + 8)
+        self._sampler_config(S.DISTRIBUTIONS, grid)
 
     def vdf_sample(self):
         """One sample of the current state, enqueued on the context's stream."""
-        self._ck(self.lib.amc_vdf_sample(self._ctx))
+        self._sampler_sample(S.DISTRIBUTIONS)
 
     def vdf_read(self):
         """(int64[regions, 4 * hist_bins + 8] counts, samples, particles outside); synchronises."""
-        tot = np.zeros(self._vdf_shape("read"), dtype=np.int64)
-        ns, no = C.c_int64(0), C.c_int64(0)
-        self._ck(self.lib.amc_vdf_read(self._ctx, tot.ctypes.data_as(_i64p), C.byref(ns), C.byref(no)))
-        return tot, ns.value, no.value
+        return self._sampler_read(S.DISTRIBUTIONS)
 
     def vdf_load(self, totals, n_samples, n_outside):
         """The inverse of ``vdf_read``."""
-        tot = np.ascontiguousarray(totals, dtype=np.int64)
-        if self.vdf_grid is None or tot.size != int(np.prod(self._vdf_shape("load"))):
-            raise ValueError("totals do not match the configured grid")
-        self._ck(self.lib.amc_vdf_load(self._ctx, tot.ctypes.data_as(_i64p), int(n_samples), int(n_outside)))
+        self._sampler_load(S.DISTRIBUTIONS, totals, (), (n_samples, n_outside))
 
     def vdf_reset(self):
-        self._ck(self.lib.amc_vdf_reset(self._ctx))
+        self._sampler_reset(S.DISTRIBUTIONS)
 
     # -- sampled transits (transits.py, DESIGN.md 16) --------------------------------------------------------------------
     def transit_config(self, grid):
         """Sample on ``grid`` (an ``AmcTransitGrid``, transits.make_grid); None switches sampling off.  Starts from zero
         totals and every particle unknown."""
-        self._ck(self.lib.amc_transit_config(self._ctx, None if grid is None else C.byref(grid)))
-        self.transit_grid = None if grid is None else AmcTransitGrid.from_buffer_copy(grid)
-
-    def _transit_zones(self, what):
-        g = self.transit_grid
-        if g is None:
-            raise _lib.ArgonMCError(-6, f"transit_{what} before transit_config")
-        return int(g.n_zones)
+        self._sampler_config(S.TRANSITS, grid)
 
     def transit_sample(self):
         """One sample of the current state, enqueued on the context's stream."""
-        self._ck(self.lib.amc_transit_sample(self._ctx))
+        self._sampler_sample(S.TRANSITS)
 
     def transit_read(self):
         """(int64[n_zones, 263, 2] totals as (low, high) words, samples); synchronises."""
-        tot = np.zeros((self._transit_zones("read"), AMC_TRANSIT_COLUMNS, 2), dtype=np.int64)
-        ns = C.c_int64(0)
-        self._ck(self.lib.amc_transit_read(self._ctx, tot.ctypes.data_as(_i64p), C.byref(ns)))
-        return tot, ns.value
+        return self._sampler_read(S.TRANSITS)
 
     def transit_state(self):
         """The per-particle arrays of the context's index range: (uint32[count] state words, uint32[n_zones, count] entry indices)."""
-        cnt = self._corr_range()
+        cnt = self._range_count()
         state = np.zeros(cnt, dtype=np.uint32)
-        entry = np.zeros((self._transit_zones("state"), cnt), dtype=np.uint32)
+        entry = np.zeros((int(self._sampler_grid(S.TRANSITS, "state").n_zones), cnt), dtype=np.uint32)
         self._ck(self.lib.amc_transit_state(self._ctx, state.ctypes.data_as(_u32p), entry.ctypes.data_as(_u32p)))
         return state, entry
 
     def transit_load(self, totals, n_samples, state=None, entry=None):
         """The inverse of ``transit_read`` + ``transit_state`` (state None: every particle unknown; entry None: zeros)."""
-        zones = self._transit_zones("load")
-        tot = np.ascontiguousarray(totals, dtype=np.int64)
-        if tot.size != zones * AMC_TRANSIT_COLUMNS * 2:
-            raise ValueError("totals do not match the configured zones")
-        cnt = self._corr_range()
-        if state is not None:
-            state = np.ascontiguousarray(state, dtype=np.uint32)
-            if state.shape != (cnt,):
-                raise ValueError(f"expected uint32[{cnt}] state words, got {state.shape}")
-        if entry is not None:
-            entry = np.ascontiguousarray(entry, dtype=np.uint32)
-            if entry.shape != (zones, cnt):
-                raise ValueError(f"expected uint32[{zones}, {cnt}] entry indices, got {entry.shape}")
-        self._ck(self.lib.amc_transit_load(self._ctx, tot.ctypes.data_as(_i64p), int(n_samples),
-                                           None if state is None else state.ctypes.data_as(_u32p),
-                                           None if entry is None else entry.ctypes.data_as(_u32p)))
+        zones, cnt = int(self._sampler_grid(S.TRANSITS, "load").n_zones), self._range_count()
+        self._sampler_load(S.TRANSITS, totals, (), (n_samples,), [(state, np.uint32, (cnt,), " state words"),
+                                                                  (entry, np.uint32, (zones, cnt), " entry indices")], unconfigured="load")
 
     def transit_reset(self):
-        self._ck(self.lib.amc_transit_reset(self._ctx))
+        self._sampler_reset(S.TRANSITS)
 
     # -- sampled pair distribution (pairs.py, DESIGN.md 17) --------------------------------------------------------------
     def pair_config(self, grid):
         """Sample on ``grid`` (an ``AmcPairGrid``, pairs.make_grid); None switches sampling off.  Starts from zero totals."""
-        self._ck(self.lib.amc_pair_config(self._ctx, None if grid is None else C.byref(grid)))
-        self.pair_grid = None if grid is None else AmcPairGrid.from_buffer_copy(grid)
-
-    def _pair_shape(self, what):
-        g = self.pair_grid
-        if g is None:
-            raise _lib.ArgonMCError(-6, f"pair_{what} before pair_config")
-        return (int(g.n1) * int(g.n2) * int(g.n3), 1 + 2 * int(g.hist_bins))
+        self._sampler_config(S.PAIRS, grid)
 
     def pair_sample(self):
         """One sample of the current state, enqueued on the context's stream."""
-        self._ck(self.lib.amc_pair_sample(self._ctx))
+        self._sampler_sample(S.PAIRS)
 
     def pair_read(self):
         """(int64[regions, 1 + 2 * hist_bins] counts, samples, particles of the range outside the grid, particles of the system
         unfiled); synchronises."""
-        tot = np.zeros(self._pair_shape("read"), dtype=np.int64)
-        ns, no, nu = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-        self._ck(self.lib.amc_pair_read(self._ctx, tot.ctypes.data_as(_i64p), C.byref(ns), C.byref(no), C.byref(nu)))
-        return tot, ns.value, no.value, nu.value
+        return self._sampler_read(S.PAIRS)
 
     def pair_load(self, totals, n_samples, n_outside, n_unfiled):
         """The inverse of ``pair_read``."""
-        tot = np.ascontiguousarray(totals, dtype=np.int64)
-        if self.pair_grid is None or tot.size != int(np.prod(self._pair_shape("load"))):
-            raise ValueError("totals do not match the configured grid")
-        self._ck(self.lib.amc_pair_load(self._ctx, tot.ctypes.data_as(_i64p), int(n_samples), int(n_outside), int(n_unfiled)))
+        self._sampler_load(S.PAIRS, totals, (), (n_samples, n_outside, n_unfiled))
 
     def pair_reset(self):
-        self._ck(self.lib.amc_pair_reset(self._ctx))
+        self._sampler_reset(S.PAIRS)
 
     # -- measurement -----------------------------------------------------------------------------------------------
     def set_stream(self, stream_ptr):
@@ -650,29 +587,17 @@ class EnergisedEngine(Engine):
     # ---- sampled surfaces (surface.py): hits, z-momentum and heat per wall bin -----------------------------
     def surface_config(self, grid):
         """Sample on ``grid`` (an ``AmcSurfaceGrid``, surface.make_grid); None switches sampling off.  Starts from zero."""
-        self._ck(self.lib.amc_surface_config(self._ctx, None if grid is None else C.byref(grid)))
-        self.surface_grid = None if grid is None else AmcSurfaceGrid.from_buffer_copy(grid)
+        self._sampler_config(S.SURFACES, grid)
 
     def surface_read(self):
         """(int64[7, nbins + 1, 3, 2] totals as (low, high) words, int64[7] failed contact solves, steps); synchronises."""
-        g = self.surface_grid
-        nb = 1 if g is None else int(g.nbins)       # (no grid: the library answers AMC_ERR_STATE)
-        tot = np.zeros((7, nb + 1, 3, 2), dtype=np.int64)
-        nf = np.zeros(7, dtype=np.int64)
-        ns = C.c_int64(0)
-        self._ck(self.lib.amc_surface_read(self._ctx, tot.ctypes.data_as(_i64p), nf.ctypes.data_as(_i64p), C.byref(ns)))
-        return tot, nf, ns.value
+        return self._sampler_read(S.SURFACES)
 
     def surface_load(self, totals, n_failed, n_steps):
-        tot = np.ascontiguousarray(totals, dtype=np.int64)
-        nf = np.ascontiguousarray(n_failed, dtype=np.int64)
-        g = self.surface_grid
-        if g is None or tot.size != 7 * (int(g.nbins) + 1) * 6 or nf.size != 7:
-            raise ValueError("totals do not match the configured surface grid")
-        self._ck(self.lib.amc_surface_load(self._ctx, tot.ctypes.data_as(_i64p), nf.ctypes.data_as(_i64p), int(n_steps)))
+        self._sampler_load(S.SURFACES, totals, (n_failed,), (n_steps,))
 
     def surface_reset(self):
-        self._ck(self.lib.amc_surface_reset(self._ctx))
+        self._sampler_reset(S.SURFACES)
 
     def set_step(self, step):
         """Index of the next step: the step word of the device draws (a resumed run continues the interrupted one's)."""

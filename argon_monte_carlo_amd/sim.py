@@ -10,10 +10,10 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import fields as FL
 from . import ic as IC
 from . import outputs as OUT
 from . import params as PR
+from . import samplers as S
 from .engine import Engine
 
 _NAMES = {"x_vals": "x", "y_vals": "y", "z_vals": "z", "x_velocities": "vx", "y_velocities": "vy",
@@ -27,7 +27,7 @@ def _write_npz(path, d):
     np.savez(path, **d, **{f"edges_{k + 1}": v for k, v in enumerate(e)})
 
 
-class Simulation:
+class Simulation(S.Controls):
     """``kind``: "cube" (Open_Air_Cube_MC.py), "pore" (Open_Air_Pore_MC.py) — see params.py for the constants."""
 
     def __init__(self, kind="pore", n=None, sigma=PR.SIGMA, device=0, keep_prior=False, tolerate_fp_errors=False,
@@ -133,21 +133,14 @@ class Simulation:
         dens, edges = self.histograms()
         OUT.write_histograms(directory, dens, edges)
 
-    # ---- what the sampled fields and the sampled fluxes share.  mod: the sampler's module (fields / fluxes); name: the prefix of
-    # its engine methods and checkpoint keys ("fields" / "flux"); g: the engine's grid of it (None: off)
-    def _moments_enable(self, mod, name, grid, every):
-        g = mod.default_grid(self.params) if grid is None else grid
+    # ---- what the samplers share (samplers.py: one record s per sampler; enable / disable / sample / reset are Controls') -------
+    def _cadence_offset(self):
         # (the device's step counter restarts at a resumed checkpoint: the cadence counts from the run's first step)
-        getattr(self.engine, name + "_config")(mod.copy_grid(g, every=every, step_offset=getattr(self, "_step_base", 0)))
+        return getattr(self, "_step_base", 0)
 
-    def _moments_derive(self, mod, name, g):
-        return mod.derive(g, *getattr(self.engine, name + "_read")(), float(self.params.argon_mass), mod.boltzmann_constant(self.params))
-
-    def _moments_checkpoint(self, mod, name, g):
-        if g is None:
-            return {}
-        tot, ns, no = getattr(self.engine, name + "_read")()
-        return {name + "_grid": mod.grid_to_array(g), name + "_totals": tot, name + "_n_samples": int(ns), name + "_n_outside": int(no)}
+    def _moments_derive(self, s):
+        g = getattr(self.engine, s.grid_attr)
+        return s.module.derive(g, *getattr(self.engine, s.prefix + "_read")(), float(self.params.argon_mass), s.module.boltzmann_constant(self.params))
 
     def _resumed_offset(self, g):
         """The step_offset that continues the cadence of the checkpoint's grid ``g``.  A sample is due when the device's step
@@ -158,66 +151,75 @@ class Simulation:
             return self._step_base
         return int(g.step_offset) + self._saved_device_step - (self.steps_done - self._step_base)
 
-    def _moments_restore(self, mod, name, z):
-        """grid, totals and counters from the checkpoint z; False if it has none of this sampler (nothing is changed then)"""
-        if name + "_grid" not in z:
-            return False
-        g = mod.grid_from_array(z[name + "_grid"])
-        getattr(self.engine, name + "_config")(mod.copy_grid(g, step_offset=self._resumed_offset(g)))
-        getattr(self.engine, name + "_load")(z[name + "_totals"], int(z[name + "_n_samples"]), int(z[name + "_n_outside"]))
-        return True
+    def _samplers(self):
+        """the records of the samplers this simulation can have"""
+        return S.CADENCE
+
+    def _samplers_checkpoint(self):
+        """every configured sampler's checkpoint entries (samplers.Sampler.keys): grid, totals, counters, per-particle arrays"""
+        out = {}
+        for s in self._samplers():
+            g = getattr(self.engine, s.grid_attr)
+            if g is not None:
+                tot, arrays, counters = s.split_read(getattr(self.engine, s.prefix + "_read")())
+                particles = getattr(self.engine, s.particle_read)() if s.particle_read else ()
+                out.update(s.to_checkpoint(g, tot, arrays, counters, particles))
+        return out
+
+    def _samplers_restore(self, z):
+        """the inverse, once ``_step_base`` is final (the cadence counts from the run's first step).  A checkpoint without a
+        sampler's grid switches that sampler off in the resumed run."""
+        for s in self._samplers():
+            saved = s.from_checkpoint(z)
+            if saved is None:
+                self._sampler_disable(s)
+                continue
+            g, args = saved
+            getattr(self.engine, s.prefix + "_config")(s.module.copy_grid(g, step_offset=self._resumed_offset(g)) if s.cadence else g)
+            getattr(self.engine, s.prefix + "_load")(*args)
 
     # ---- sampled fields (fields.py, DESIGN.md 10; the reference has no such output) ---------------------------------------
     def enable_fields(self, grid=None, every=0):
         """Sample number density, flow velocity and temperature per bin of ``grid`` (fields.make_grid; None = the geometry's
         default, fields.default_grid) after every ``every``-th step (0: only on ``fields_sample()``).  Starts from zero."""
-        self._moments_enable(FL, "fields", grid, every)
+        self._sampler_enable(S.FIELDS, grid, every=every)
 
     def disable_fields(self):
-        self.engine.fields_config(None)
+        self._sampler_disable(S.FIELDS)
 
     def fields_sample(self):
         """One sample of the current state now (asynchronous)."""
-        self.engine.fields_sample()
+        self._sampler_sample(S.FIELDS)
 
     def fields_reset(self):
-        self.engine.fields_reset()
+        self._sampler_reset(S.FIELDS)
 
     def fields(self):
         """dict: count, number_density (m^-3), velocity and temperature (bins x 3: x, y, z components on a Cartesian grid,
         r, theta, z on an axisymmetric one), T (mean of the three), edges, bin_volume, n_samples, n_outside and the raw
         integer totals (int64[bins, 7, 2], 128-bit (low, high) words).  Bins in linear order (i1 * n2 + i2) * n3 + i3."""
-        return self._moments_derive(FL, "fields", self.engine.field_grid)
+        return self._moments_derive(S.FIELDS)
 
     def write_fields(self, path):
         """The dict of ``fields()`` as an .npz (edges as edges_1, edges_2[, edges_3])."""
         _write_npz(path, self.fields())
-
-    def _fields_checkpoint(self):
-        return self._moments_checkpoint(FL, "fields", self.engine.field_grid)
-
-    def _fields_restore(self, z):
-        if not self._moments_restore(FL, "fields", z):  # a checkpoint without them: sampling is off in the resumed run, as for the others
-            self.engine.fields_config(None)
 
     # ---- sampled correlations (correlations.py, DESIGN.md 12; the reference has no such output) ---------------------------
     def enable_correlations(self, grid=None, every=0, n_lags=None):
         """Sample the mean-square displacement and the velocity autocorrelation per group of ``grid`` (correlations.make_grid;
         None = the geometry's default, correlations.default_grid) and lag 0 .. ``n_lags`` (None: the grid's), one sample after
         every ``every``-th step (0: only on ``correlations_sample()``).  Starts from zero; the first sample is a time origin."""
-        from . import correlations as CO
-        g = CO.default_grid(self.params) if grid is None else grid
-        self.engine.corr_config(CO.copy_grid(g, every=every, step_offset=getattr(self, "_step_base", 0), n_lags=n_lags))
+        self._sampler_enable(S.CORRELATIONS, grid, every=every, n_lags=n_lags)
 
     def disable_correlations(self):
-        self.engine.corr_config(None)
+        self._sampler_disable(S.CORRELATIONS)
 
     def correlations_sample(self):
         """One sample of the current state now (asynchronous): an origin, or the next lag of the window."""
-        self.engine.corr_sample()
+        self._sampler_sample(S.CORRELATIONS)
 
     def correlations_reset(self):
-        self.engine.corr_reset()
+        self._sampler_reset(S.CORRELATIONS)
 
     def correlations(self, every=None):
         """dict (correlations.derive): count, msd, vacf and D_msd per (group, lag, component), D_vacf per (group, component),
@@ -234,48 +236,29 @@ class Simulation:
         """The dict of ``correlations()`` as an .npz (edges as edges_1, edges_2[, edges_3])."""
         _write_npz(path, self.correlations())
 
-    def _corr_checkpoint(self):
-        if self.engine.corr_grid is None:
-            return {}
-        from . import correlations as CO
-        tot, counters = self.engine.corr_read()
-        return dict(corr_grid=CO.grid_to_array(self.engine.corr_grid), corr_totals=tot, corr_counters=np.array(counters, dtype=np.int64),
-                    corr_origin=np.stack(self.engine.corr_origin()))
-
-    def _corr_restore(self, z):
-        from . import correlations as CO
-        if "corr_grid" in z:
-            g = CO.grid_from_array(z["corr_grid"])
-            self.engine.corr_config(CO.copy_grid(g, step_offset=self._resumed_offset(g)))
-            self.engine.corr_load(z["corr_totals"], z["corr_counters"], list(z["corr_origin"]))
-        else:                                           # a checkpoint without them: sampling is off in the resumed run
-            self.engine.corr_config(None)
-
     # ---- sampled fluxes (fluxes.py, DESIGN.md 13; the reference has no such output) -----------------------------------------
     def enable_fluxes(self, grid=None, every=0):
         """Sample the velocity moments behind the pressure tensor, the energy flux and the heat flux per bin of ``grid``
         (fluxes.make_grid; None = the geometry's default, fluxes.default_grid) after every ``every``-th step (0: only on
         ``fluxes_sample()``).  Starts from zero.  Independent of ``enable_fields``."""
-        from . import fluxes as FX
-        self._moments_enable(FX, "flux", grid, every)
+        self._sampler_enable(S.FLUXES, grid, every=every)
 
     def disable_fluxes(self):
-        self.engine.flux_config(None)
+        self._sampler_disable(S.FLUXES)
 
     def fluxes_sample(self):
         """One sample of the current state now (asynchronous)."""
-        self.engine.flux_sample()
+        self._sampler_sample(S.FLUXES)
 
     def fluxes_reset(self):
-        self.engine.flux_reset()
+        self._sampler_reset(S.FLUXES)
 
     def fluxes(self):
         """dict (fluxes.derive): count, number_density (m^-3), velocity (bins x 3), pressure_tensor (bins x 3 x 3, Pa), pressure,
         T, energy_flux and heat_flux (bins x 3, W/m^2) — components x, y, z on a Cartesian grid, r, theta, z on an axisymmetric
         one — edges, bin_volume, n_samples, n_outside and the raw integer totals (int64[bins, 2, 7, 2], 128-bit (low, high)
         words).  Bins in linear order (i1 * n2 + i2) * n3 + i3."""
-        from . import fluxes as FX
-        return self._moments_derive(FX, "flux", self.engine.flux_grid)
+        return self._moments_derive(S.FLUXES)
 
     def write_fluxes(self, path):
         """The dict of ``fluxes()`` as an .npz (edges as edges_1, edges_2[, edges_3])."""
@@ -291,15 +274,13 @@ class Simulation:
         as without the sampler — also before this call if a long ``run`` has filled it: with records missing the first step
         marks the totals lost (``free_paths()`` raises until ``free_paths_reset()``).  Paths completed before the call are not
         binned; a consuming sampler starts by emptying the buffer."""
-        from . import free_paths as FP
-        g = FP.default_grid(self.params) if grid is None else grid
-        self.engine.mfp_config(FP.copy_grid(g, keep_records=keep_records))
+        self._sampler_enable(S.FREE_PATHS, grid, keep_records=keep_records)
 
     def disable_free_paths(self):
-        self.engine.mfp_config(None)
+        self._sampler_disable(S.FREE_PATHS)
 
     def free_paths_reset(self):
-        self.engine.mfp_reset()
+        self._sampler_reset(S.FREE_PATHS)
 
     def free_paths(self):
         """dict (free_paths.derive): per bin and kind (wall, p-p, both) count, mean_free_path, mean_abs_x/y/z, var_free_path,
@@ -313,41 +294,22 @@ class Simulation:
         """The dict of ``free_paths()`` as an .npz (edges as edges_1, edges_2[, edges_3])."""
         _write_npz(path, self.free_paths())
 
-    def _mfp_checkpoint(self):
-        if self.engine.mfp_grid is None:
-            return {}
-        from . import free_paths as FP
-        tot, hist, counters = self.engine.mfp_read()
-        return dict(mfp_grid=FP.grid_to_array(self.engine.mfp_grid), mfp_totals=tot, mfp_hist=hist,
-                    mfp_counters=np.array(counters, dtype=np.int64))
-
-    def _mfp_restore(self, z):
-        if "mfp_grid" in z:
-            from . import free_paths as FP
-            self.engine.mfp_config(FP.grid_from_array(z["mfp_grid"]))
-            self.engine.mfp_load(z["mfp_totals"], z["mfp_hist"], z["mfp_counters"])
-        else:                                           # a checkpoint without them: sampling is off in the resumed run
-            self.engine.mfp_config(None)
-
     # ---- sampled velocity distributions (distributions.py, DESIGN.md 15; the reference has no such output) ----------------
     def enable_distributions(self, grid=None, every=0):
         """Sample histograms of the three velocity components and of the speed per region of ``grid``
         (distributions.make_grid; None = the geometry's default, distributions.default_grid) after every ``every``-th step
         (0: only on ``distributions_sample()``).  Starts from zero.  Independent of the other samplers."""
-        from . import distributions as VD
-        g = VD.default_grid(self.params) if grid is None else grid
-        # (the device's step counter restarts at a resumed checkpoint: the cadence counts from the run's first step)
-        self.engine.vdf_config(VD.copy_grid(g, every=every, step_offset=getattr(self, "_step_base", 0)))
+        self._sampler_enable(S.DISTRIBUTIONS, grid, every=every)
 
     def disable_distributions(self):
-        self.engine.vdf_config(None)
+        self._sampler_disable(S.DISTRIBUTIONS)
 
     def distributions_sample(self):
         """One sample of the current state now (asynchronous)."""
-        self.engine.vdf_sample()
+        self._sampler_sample(S.DISTRIBUTIONS)
 
     def distributions_reset(self):
-        self.engine.vdf_reset()
+        self._sampler_reset(S.DISTRIBUTIONS)
 
     def distributions(self):
         """dict (distributions.derive): per region count, pdf (regions x 3 x hist_bins, per m/s — components x, y, z on a
@@ -363,42 +325,23 @@ class Simulation:
         """The dict of ``distributions()`` as an .npz (the spatial edges as edges_1, edges_2[, edges_3])."""
         _write_npz(path, self.distributions())
 
-    def _vdf_checkpoint(self):
-        if self.engine.vdf_grid is None:
-            return {}
-        from . import distributions as VD
-        tot, ns, no = self.engine.vdf_read()
-        return dict(vdf_grid=VD.grid_to_array(self.engine.vdf_grid), vdf_totals=tot, vdf_counters=np.array([ns, no], dtype=np.int64))
-
-    def _vdf_restore(self, z):
-        if "vdf_grid" in z:
-            from . import distributions as VD
-            g = VD.grid_from_array(z["vdf_grid"])
-            self.engine.vdf_config(VD.copy_grid(g, step_offset=self._resumed_offset(g)))
-            self.engine.vdf_load(z["vdf_totals"], int(z["vdf_counters"][0]), int(z["vdf_counters"][1]))
-        else:                                           # a checkpoint without them: sampling is off in the resumed run
-            self.engine.vdf_config(None)
-
     # ---- sampled transits (transits.py, DESIGN.md 16; the reference has no such output) -----------------------------------
     def enable_transits(self, grid=None, every=1):
         """Track, per zone of ``grid`` (transits.make_grid; None = the geometry's default, transits.default_grid), which side
         every particle entered from and when, and count entries, exits by (entry side, exit side) and residence times, with
         one sample after every ``every``-th step (0: only on ``transits_sample()``).  Starts from zero with every particle
         unknown.  Independent of the other samplers."""
-        from . import transits as TR
-        g = TR.default_grid(self.params) if grid is None else grid
-        # (the device's step counter restarts at a resumed checkpoint: the cadence counts from the run's first step)
-        self.engine.transit_config(TR.copy_grid(g, every=every, step_offset=getattr(self, "_step_base", 0)))
+        self._sampler_enable(S.TRANSITS, grid, every=every)
 
     def disable_transits(self):
-        self.engine.transit_config(None)
+        self._sampler_disable(S.TRANSITS)
 
     def transits_sample(self):
         """One sample of the current state now (asynchronous)."""
-        self.engine.transit_sample()
+        self._sampler_sample(S.TRANSITS)
 
     def transits_reset(self):
-        self.engine.transit_reset()
+        self._sampler_reset(S.TRANSITS)
 
     def transits(self, every=None):
         """dict (transits.derive): per zone transmission and return probabilities with their standard error, residence mean
@@ -413,44 +356,23 @@ class Simulation:
         """The dict of ``transits()`` as an .npz."""
         np.savez(path, **self.transits())
 
-    def _transit_checkpoint(self):
-        if self.engine.transit_grid is None:
-            return {}
-        from . import transits as TR
-        tot, ns = self.engine.transit_read()
-        state, entry = self.engine.transit_state()
-        return dict(transit_grid=TR.grid_to_array(self.engine.transit_grid), transit_totals=tot, transit_counters=np.array([ns], dtype=np.int64),
-                    transit_state=state, transit_entry=entry)
-
-    def _transit_restore(self, z):
-        if "transit_grid" in z:
-            from . import transits as TR
-            g = TR.grid_from_array(z["transit_grid"])
-            self.engine.transit_config(TR.copy_grid(g, step_offset=self._resumed_offset(g)))
-            self.engine.transit_load(z["transit_totals"], int(z["transit_counters"][0]), z["transit_state"], z["transit_entry"])
-        else:                                           # a checkpoint without them: sampling is off in the resumed run
-            self.engine.transit_config(None)
-
     # ---- sampled pair distribution (pairs.py, DESIGN.md 17; the reference has no such output) ----------------------------
     def enable_pairs(self, grid=None, every=0):
         """Sample, per region of ``grid`` (pairs.make_grid; None = the geometry's default, pairs.default_grid), the histogram of
         the distances from every particle of the region to every other particle closer than r_max, and of those pairs that
         still approach, after every ``every``-th step (0: only on ``pairs_sample()``).  A sample is a pair search — several
         steps' worth of time — so ``every`` is meant to be large.  Starts from zero.  Independent of the other samplers."""
-        from . import pairs as PA
-        g = PA.default_grid(self.params) if grid is None else grid
-        # (the device's step counter restarts at a resumed checkpoint: the cadence counts from the run's first step)
-        self.engine.pair_config(PA.copy_grid(g, every=every, step_offset=getattr(self, "_step_base", 0)))
+        self._sampler_enable(S.PAIRS, grid, every=every)
 
     def disable_pairs(self):
-        self.engine.pair_config(None)
+        self._sampler_disable(S.PAIRS)
 
     def pairs_sample(self):
         """One sample of the current state now (asynchronous)."""
-        self.engine.pair_sample()
+        self._sampler_sample(S.PAIRS)
 
     def pairs_reset(self):
-        self.engine.pair_reset()
+        self._sampler_reset(S.PAIRS)
 
     def pairs(self):
         """dict (pairs.derive): r_edges, r_mid, per region centres, pairs and approaching (the raw integers), g and g_err
@@ -464,47 +386,18 @@ class Simulation:
         """The dict of ``pairs()`` as an .npz (the spatial edges as edges_1, edges_2[, edges_3])."""
         _write_npz(path, self.pairs())
 
-    def _pair_checkpoint(self):
-        if self.engine.pair_grid is None:
-            return {}
-        from . import pairs as PA
-        tot, ns, no, nu = self.engine.pair_read()
-        return dict(pair_grid=PA.grid_to_array(self.engine.pair_grid), pair_totals=tot, pair_counters=np.array([ns, no, nu], dtype=np.int64))
-
-    def _pair_restore(self, z):
-        if "pair_grid" in z:
-            from . import pairs as PA
-            g = PA.grid_from_array(z["pair_grid"])
-            self.engine.pair_config(PA.copy_grid(g, step_offset=self._resumed_offset(g)))
-            self.engine.pair_load(z["pair_totals"], *(int(v) for v in z["pair_counters"]))
-        else:                                           # a checkpoint without them: sampling is off in the resumed run
-            self.engine.pair_config(None)
-
     # ---- checkpoint / resume (the reference has none: a 10^4-step run is one process lifetime there) ---------------
     def _checkpoint_extra(self):
-        """what a subclass adds to a checkpoint (it extends this dict) — here: grid, totals and counters of the sampled fluxes,
-        of the sampled free paths, of the sampled velocity distributions, of the sampled transits (these with their
-        per-particle arrays) and of the sampled pair distribution"""
-        from . import fluxes as FX
-        return dict(**self._moments_checkpoint(FX, "flux", self.engine.flux_grid), **self._mfp_checkpoint(), **self._vdf_checkpoint(),
-                    **self._transit_checkpoint(), **self._pair_checkpoint())
+        """what a subclass adds to a checkpoint (beside the samplers' entries, ``_samplers_checkpoint``)"""
+        return {}
 
     def _restore_extra(self, z):
-        """the inverse; a subclass calls it once ``_step_base`` is final (the cadence counts from the run's first step)"""
-        from . import fluxes as FX
-        if not self._moments_restore(FX, "flux", z):   # a checkpoint without them: sampling is off in the resumed run
-            self.engine.flux_config(None)
-        self._mfp_restore(z)
-        self._vdf_restore(z)
-        self._transit_restore(z)
-        self._pair_restore(z)
+        """the inverse; it leaves ``_step_base`` final: the samplers are restored behind it"""
 
     def save_checkpoint(self, path):
         """Everything a later ``load_checkpoint`` needs to continue bit-identically: the particle arrays, the
-        completed-path lists, the device histograms and the counters (+ RNG streams and per-step lists for Temp, + the
-        grid and the totals of the sampled fields when they are on, + the grid, totals, counters, window position and origin
-        arrays of the sampled correlations when they are on, + the grid, totals and counters of the sampled fluxes, of the sampled
-        free paths and of the sampled velocity distributions when they are on)."""
+        completed-path lists, the device histograms and the counters (+ RNG streams and per-step lists for Temp, + for every
+        sampler that is on the keys its record lists: ``samplers.Sampler.keys``)."""
         st = self.engine.download()
         self._collect()
         counts, _ = self.engine.histograms()
@@ -518,8 +411,7 @@ class Simulation:
                  completed_z_paths=np.array(self.completed_z_paths, dtype=np.float64),
                  total_cols=int(self.total_cols), steps_done=int(self.steps_done),
                  device_step=int(self.steps_done) - int(getattr(self, "_step_base", 0)),      # (what the saved grids' step_offset counts from)
-                 **{f"state_{k}": v for k, v in st.items()}, **self._checkpoint_extra(), **self._fields_checkpoint(),
-                 **self._corr_checkpoint())
+                 **{f"state_{k}": v for k, v in st.items()}, **self._checkpoint_extra(), **self._samplers_checkpoint())
 
     def load_checkpoint(self, path):
         z = np.load(path if str(path).endswith(".npz") else str(path) + ".npz", allow_pickle=False)
@@ -539,8 +431,7 @@ class Simulation:
         self._saved_device_step = int(z["device_step"]) if "device_step" in z else None
         self._cache = None
         self._restore_extra(z)
-        self._fields_restore(z)
-        self._corr_restore(z)
+        self._samplers_restore(z)
 
     def close(self):
         self.engine.close()
@@ -634,14 +525,16 @@ class TemperatureSimulation(Simulation):
         return st
 
     # ---- sampled surfaces (surface.py; the reference reports three sums per step) -------------------------
+    def _samplers(self):
+        return S.ALL
+
     def enable_surface(self, grid=None):
         """Accumulate hits, z-momentum and energy per wall bin of the seven energised surfaces in every step from now on
         (``grid``: surface.make_grid; None = surface.default_grid, 32 bins per surface).  Starts from zero."""
-        from . import surface as SU
-        self.engine.surface_config(SU.default_grid(self.params) if grid is None else grid)
+        self._sampler_enable(S.SURFACES, grid)
 
     def disable_surface(self):
-        self.engine.surface_config(None)
+        self._sampler_disable(S.SURFACES)
 
     def surface(self):
         """dict (surface.derive): per case and bin count, hit_rate, momentum_rate and energy_rate (gas side, per area), the
@@ -657,13 +550,7 @@ class TemperatureSimulation(Simulation):
     def _checkpoint_extra(self):
         np_state = self.sampler.np_rng.get_state()
         py_state = self.sampler.py_rng.getstate()
-        surf = {}
-        if self.engine.surface_grid is not None:
-            from . import surface as SU
-            tot, nf, ns = self.engine.surface_read()
-            surf = dict(surface_grid=SU.grid_to_array(self.engine.surface_grid), surface_totals=tot, surface_n_failed=nf,
-                        surface_n_steps=int(ns))
-        return dict(**super()._checkpoint_extra(), **surf, momentum=np.array([float(v) for v in self.momentum_z_change_per_step]),
+        return dict(momentum=np.array([float(v) for v in self.momentum_z_change_per_step]),
                     energy_cold=np.array([float(v) for v in self.energy_transfer_cold_per_step]),
                     energy_hot=np.array([float(v) for v in self.energy_transfer_hot_per_step]),
                     zero_flags=np.array(self._zero_flags, dtype=bool).reshape(-1, 3), total_errs=int(self.total_errs),
@@ -672,12 +559,6 @@ class TemperatureSimulation(Simulation):
                     py_rng_state=np.array(py_state[1], dtype=np.uint64), py_rng_version=int(py_state[0]))
 
     def _restore_extra(self, z):
-        if "surface_grid" in z:
-            from . import surface as SU
-            self.engine.surface_config(SU.grid_from_array(z["surface_grid"]))
-            self.engine.surface_load(z["surface_totals"], z["surface_n_failed"], int(z["surface_n_steps"]))
-        else:                                       # a checkpoint without surface data: sampling is off in the resumed run
-            self.engine.surface_config(None)
         self.momentum_z_change_per_step = z["momentum"].tolist()
         self.energy_transfer_cold_per_step = z["energy_cold"].tolist()
         self.energy_transfer_hot_per_step = z["energy_hot"].tolist()
@@ -691,7 +572,6 @@ class TemperatureSimulation(Simulation):
         self.sampler.np_rng.set_state(("MT19937", z["np_rng_keys"], int(z["np_rng_rest"][0]), int(z["np_rng_rest"][1]),
                                        float(z["np_rng_gauss"])))
         self.sampler.py_rng.setstate((int(z["py_rng_version"]), tuple(int(v) for v in z["py_rng_state"]), None))
-        super()._restore_extra(z)
 
     def write_outputs(self, directory="."):
         import os

@@ -400,6 +400,61 @@ def test_checkpoint_with_everything_on_resumes_to_the_uninterrupted_totals(geom,
     c.close()
 
 
+# ---- 4b. the checkpoint format: exactly these keys, dtypes and shapes ---------------------------------------------------------------------
+# what a checkpoint holds without any sampler: the cube / pores, and what the energised pore adds
+PLAIN_KEYS = {"kind", "n", "collision_range", "hist_counts", "completed_paths", "completed_x_paths", "completed_y_paths", "completed_z_paths",
+              "total_cols", "steps_done", "device_step"} | {"state_" + k for k in KEYS}
+TEMP_KEYS = {"momentum", "energy_cold", "energy_hot", "zero_flags", "total_errs", "np_rng_keys", "np_rng_rest", "np_rng_gauss", "py_rng_state",
+             "py_rng_version"}
+I8, U4, F8 = "int64", "uint32", "float64"
+
+
+def _sampler_keys(n, bins):
+    """key -> (dtype, shape) for the grids "A" of _grids: bins = (fields, correlation groups, fluxes, free paths) — the rest is the
+    same in the cube and the energised pore: n_lags 2, 8 free-path columns, 4 regions of 16 columns for the distributions and the
+    pairs, 3 zones"""
+    fl, co, fx, fp = bins
+    return {"fields_grid": (F8, (12,)), "fields_totals": (I8, (fl, 7, 2)), "fields_n_samples": (I8, ()), "fields_n_outside": (I8, ()),
+            "flux_grid": (F8, (12,)), "flux_totals": (I8, (fx, 2, 7, 2)), "flux_n_samples": (I8, ()), "flux_n_outside": (I8, ()),
+            "corr_grid": (F8, (13,)), "corr_totals": (I8, (co, 3, 7, 2)), "corr_counters": (I8, (4,)), "corr_origin": (F8, (6, n)),
+            "mfp_grid": (F8, (13,)), "mfp_totals": (I8, (fp, 2, 7, 2)), "mfp_hist": (I8, (fp, 2, 9)), "mfp_counters": (I8, (3,)),
+            "vdf_grid": (F8, (14,)), "vdf_totals": (I8, (4, 72)), "vdf_counters": (I8, (2,)),
+            "transit_grid": (F8, (27,)), "transit_totals": (I8, (3, 263, 2)), "transit_counters": (I8, (1,)), "transit_state": (U4, (n,)),
+            "transit_entry": (U4, (3, n)),
+            "pair_grid": (F8, (14,)), "pair_totals": (I8, (4, 33)), "pair_counters": (I8, (3,))}
+
+
+SURFACE_KEYS = {"surface_grid": (F8, (15,)), "surface_totals": (I8, (7, 9, 3, 2)), "surface_n_failed": (I8, (7,)), "surface_n_steps": (I8, ())}
+
+
+@pytest.mark.parametrize("geom", ["cube", "temp"])
+def test_a_checkpoint_holds_exactly_the_frozen_keys(geom, tmp_path):
+    """Two steps with every sampler on (the energised pore: the surfaces too), then the file's keys, dtypes and shapes; a simulation
+    with no sampler on writes none of the samplers' keys."""
+    temp = geom == "temp"
+    sim = _temp_new() if temp else _new(geom)
+    n = int(sim.params.n)
+    want = _sampler_keys(n, (10, 3, 8, 8) if temp else (12, 2, 6, 4))
+    if temp:
+        want.update(SURFACE_KEYS)
+    plain = PLAIN_KEYS | (TEMP_KEYS if temp else set())
+    assert n == (6_000 if temp else 3_000) and len(want) == (31 if temp else 27) and not set(want) & plain
+    off = str(tmp_path / "off.npz")
+    sim.save_checkpoint(off)
+    assert set(np.load(off).files) == plain
+    _configure(sim.engine, _grids(geom, sim.params), mix=EVERY_STEP, mfp=False, surfaces=temp)
+    sim.run(2)
+    on = str(tmp_path / "on.npz")
+    sim.save_checkpoint(on)
+    z = np.load(on)
+    assert set(z.files) == plain | set(want), (sorted(set(z.files) - plain - set(want)), sorted((plain | set(want)) - set(z.files)))
+    for k, (dtype, shape) in want.items():
+        assert z[k].dtype == np.dtype(dtype) and z[k].shape == shape, (k, z[k].dtype, z[k].shape)
+    assert int(z["fields_n_samples"]) == int(z["flux_n_samples"]) == 2 and z["vdf_counters"][0] == z["transit_counters"][0] == z["pair_counters"][0] == 2
+    assert z["corr_counters"][1] == 2 and z["mfp_counters"][2] == 2 and (not temp or int(z["surface_n_steps"]) == 2)
+    sim.close()
+
+
 # ---- 5. the energised pore, directions and gap energies drawn on the device ---------------------------------------------------------------
 _TEMP = {}
 
@@ -511,8 +566,9 @@ def _sum_over_ranks(name, reads):
 @pytest.mark.parametrize("geom", ["cube", "pore"])
 def test_three_ranks_sum_to_the_single_context(geom):
     """Cube (N = 3,001): all seven.  Pore (N = 8,000: fewer atoms complete no free path in 24 steps): all but the pair distribution,
-    which an index-range shard of a pore refuses."""
-    from argon_monte_carlo_amd.dist import LocalRanks, shard_range
+    which an index-range shard of a pore refuses.  Then one step more, around which the sharded driver switches four samplers
+    on and off: every rank's context owns what it owned before."""
+    from argon_monte_carlo_amd.dist import LocalRanks, ShardedSimulation, shard_range
     from argon_monte_carlo_amd.engine import Engine, ShardEngine
     if geom == "cube":
         n = 3001
@@ -557,6 +613,25 @@ def test_three_ranks_sum_to_the_single_context(geom):
         st = e.download()
         for k in ("x", "y", "z", "vx", "vy", "vz"):
             assert st[k][lo:hi].tobytes() == end[k][lo:hi].tobytes(), k
+    # the driver's disable_* (the engines are its; it needs no communicator for this)
+    four = ("fields", "correlations", "fluxes", "distributions")
+    drivers = [ShardedSimulation(p, r, 3, engine=e, comm=object()) for r, e in enumerate(engs)]
+
+    def switch_off(d):
+        d.disable_fields(), d.disable_correlations(), d.disable_fluxes(), d.disable_distributions()
+        assert all(getattr(d.engine, GRID_ATTR[name]) is None for name in four)
+        return d.engine.owned_count()
+    base = [switch_off(d) for d in drivers]
+    for d in drivers:
+        d.enable_fields(grids["fields"], every=1), d.enable_correlations(grids["correlations"], every=1)
+        d.enable_fluxes(grids["fluxes"], every=1), d.enable_distributions(grids["distributions"], every=1)
+        assert all(getattr(d.engine, GRID_ATTR[name]) is not None for name in four)
+    assert all(d.engine.owned_count() >= b + 4 for d, b in zip(drivers, base))
+    job.step(dt)
+    for d in drivers:
+        assert all(_read(d.engine, name, per_particle=False)["counters"][N_SAMPLES.get(name, 0)] == 1 for name in four)
+    assert [switch_off(d) for d in drivers] == base
+    for e in engs:
         e.close()
 
 
