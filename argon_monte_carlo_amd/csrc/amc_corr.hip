@@ -3,7 +3,7 @@
 // DESIGN.md 12).  The reference has no such output; the Python layer derives the mean-square displacement, the velocity
 // autocorrelation function and diffusion coefficients from the totals.
 //
-// One sample is two kernels, shaped like the sampled fields' (amc_fields.hip):
+// One sample is two kernels, the streaming samplers' pair (amc_sample_dev.h):
 //   k_corr_accum<MODE>  a persistent grid of at most one workgroup per CU, each over a contiguous index range, 16-byte loads
 //                       of particle pairs.  MODE origin: 48 B of state per particle in, 48 B of origin out, lag 0.  MODE lag:
 //                       state and origin in (96 B), the launch's lag.  MODE lag-and-origin: the last lag of the window against
@@ -12,9 +12,9 @@
 //                       (group, 7 sums) in registers and flushes it to LDS (64-bit integer LDS atomics) only when the group
 //                       changes and at the end: with one group every lane would otherwise hit the same seven words.  The
 //                       table leaves as one slab row with plain stores — no global atomics but the atomicMin on the error word.
-//   k_sample_reduce     (amc_fields.hip, the fields' own reduce) sums the slab rows per (group, quantity) into the 128-bit
-//                       totals at the launch's lag or lags, with carry, and bumps the counters.
-// The group rule (amc_sample_bin), the speed test and the lazy read are amc_sample_dev.h's.
+//   k_slab_reduce<unsigned long long, sample_sink>  (amc_fields.hip: the fields' sink) sums the slab rows per (group, quantity)
+//                       into the 128-bit totals at the launch's lag or lags, with carry, and bumps the counters.
+// The walk, the pair loads and stores, the group rule (amc_sample_bin), the speed test and the lazy read are amc_sample_dev.h's.
 #include "amc_host.h"
 #include "amc_sample_dev.h"
 
@@ -101,75 +101,43 @@ __global__ __launch_bounds__(AMC_CORR_THREADS) void k_corr_accum(amc_state S, am
     __shared__ unsigned long long tab[TABLES * AMC_CORR_MAX_GROUPS * AMC_CORR_Q];
     __shared__ unsigned int outside_sum;
     const int M = G.bins * AMC_CORR_Q;
-    for (int j = threadIdx.x; j < TABLES * M; j += blockDim.x) tab[j] = 0;
-    if (threadIdx.x == 0) outside_sum = 0;
-    __syncthreads();
+    amc_slab_begin(tab, TABLES * M, &outside_sum);
     unsigned long long *tab_lag = tab, *tab_org = tab + (TABLES - 1) * M;
-    // this workgroup's particles [b0, b1), walked as aligned pairs (2k, 2k + 1): one 16-byte access per array and pair
-    const long long cnt = hi - lo;
-    const long long per = (cnt + gridDim.x - 1) / gridDim.x;
-    const long long b0 = lo + per * blockIdx.x, b1 = b0 + per < hi ? b0 + per : hi;
     unsigned int outside = 0;
     long long first_bad = -1;
     corr_run rl, ro;
     rl.g = -1; ro.g = -1;
 #pragma unroll
     for (int q = 0; q < AMC_CORR_Q; q++) { rl.s[q] = 0; ro.s[q] = 0; }
-    if (b0 < b1) {
-        for (long long k = (b0 >> 1) + threadIdx.x; 2 * k < b1; k += blockDim.x) {
-            const long long p0 = 2 * k, p1 = p0 + 1;
-            const bool v0 = p0 >= b0, v1 = p1 < b1;
-            const bool pair = v0 && v1;
-            double x[2], y[2], z[2], vx[2], vy[2], vz[2];
-            double x0[2], y0[2], z0[2], vx0[2], vy0[2], vz0[2];
-            if (pair) {
-                const double2 ax = *(const double2 *)(S.x + p0), ay = *(const double2 *)(S.y + p0), az = *(const double2 *)(S.z + p0);
-                const double2 bx = *(const double2 *)(S.vx + p0), by = *(const double2 *)(S.vy + p0), bz = *(const double2 *)(S.vz + p0);
-                x[0] = ax.x; x[1] = ax.y; y[0] = ay.x; y[1] = ay.y; z[0] = az.x; z[1] = az.y;
-                vx[0] = bx.x; vx[1] = bx.y; vy[0] = by.x; vy[1] = by.y; vz[0] = bz.x; vz[1] = bz.y;
-                if (LAG) {
-                    const double2 cx = *(const double2 *)(O.x + p0), cy = *(const double2 *)(O.y + p0), cz = *(const double2 *)(O.z + p0);
-                    const double2 dx = *(const double2 *)(O.vx + p0), dy = *(const double2 *)(O.vy + p0), dz = *(const double2 *)(O.vz + p0);
-                    x0[0] = cx.x; x0[1] = cx.y; y0[0] = cy.x; y0[1] = cy.y; z0[0] = cz.x; z0[1] = cz.y;
-                    vx0[0] = dx.x; vx0[1] = dx.y; vy0[0] = dy.x; vy0[1] = dy.y; vz0[0] = dz.x; vz0[1] = dz.y;
-                }
-            } else {
-                const long long p = v0 ? p0 : p1;
-                const int e = v0 ? 0 : 1;
-                x[e] = S.x[p]; y[e] = S.y[p]; z[e] = S.z[p]; vx[e] = S.vx[p]; vy[e] = S.vy[p]; vz[e] = S.vz[p];
-                if (LAG) { x0[e] = O.x[p]; y0[e] = O.y[p]; z0[e] = O.z[p]; vx0[e] = O.vx[p]; vy0[e] = O.vy[p]; vz0[e] = O.vz[p]; }
-            }
-#pragma unroll
-            for (int e = 0; e < 2; e++) {
-                if (!(e == 0 ? v0 : v1)) continue;
-                const long long p = p0 + e;
-                amc_fields_lazy(S, L, p, x[e], y[e], z[e], vx[e], vy[e], vz[e]);
-                bool ok = true;
-                if (LAG) ok = corr_lag_particle(G, tab_lag, rl, x[e], y[e], z[e], vx[e], vy[e], vz[e], x0[e], y0[e], z0[e], vx0[e], vy0[e], vz0[e]);
-                if (ORIGIN) ok = corr_origin_particle(G, tab_org, ro, outside, x[e], y[e], z[e], vx[e], vy[e], vz[e]) && ok;
-                if (!ok && first_bad < 0) first_bad = p;
-            }
-            if (ORIGIN) {
-                if (pair) {
-                    *(double2 *)(O.x + p0) = make_double2(x[0], x[1]); *(double2 *)(O.y + p0) = make_double2(y[0], y[1]);
-                    *(double2 *)(O.z + p0) = make_double2(z[0], z[1]); *(double2 *)(O.vx + p0) = make_double2(vx[0], vx[1]);
-                    *(double2 *)(O.vy + p0) = make_double2(vy[0], vy[1]); *(double2 *)(O.vz + p0) = make_double2(vz[0], vz[1]);
-                } else {
-                    const long long p = v0 ? p0 : p1;
-                    const int e = v0 ? 0 : 1;
-                    O.x[p] = x[e]; O.y[p] = y[e]; O.z[p] = z[e]; O.vx[p] = vx[e]; O.vy[p] = vy[e]; O.vz[p] = vz[e];
-                }
-            }
+    for (amc_sample_walk w(lo, hi); w.more(); w.next()) {
+        const long long p0 = w.p0();
+        const bool v0 = w.v0(), v1 = w.v1();
+        double x[2], y[2], z[2], vx[2], vy[2], vz[2];
+        double x0[2], y0[2], z0[2], vx0[2], vy0[2], vz0[2];
+        if (v0 && v1) {                 // (the state's loads and the origins' under one branch: amc_sample_dev.h)
+            amc_sample_load_both(S, p0, x, y, z, vx, vy, vz);
+            if (LAG) amc_sample_load_both(O, p0, x0, y0, z0, vx0, vy0, vz0);
+        } else {
+            amc_sample_load_one(S, v0 ? p0 : p0 + 1, v0 ? 0 : 1, x, y, z, vx, vy, vz);
+            if (LAG) amc_sample_load_one(O, v0 ? p0 : p0 + 1, v0 ? 0 : 1, x0, y0, z0, vx0, vy0, vz0);
         }
+#pragma unroll
+        for (int e = 0; e < 2; e++) {
+            if (!(e == 0 ? v0 : v1)) continue;
+            const long long p = p0 + e;
+            amc_fields_lazy(L, p, x[e], y[e], z[e], vx[e], vy[e], vz[e]);
+            bool ok = true;
+            if (LAG) ok = corr_lag_particle(G, tab_lag, rl, x[e], y[e], z[e], vx[e], vy[e], vz[e], x0[e], y0[e], z0[e], vx0[e], vy0[e], vz0[e]);
+            if (ORIGIN) ok = corr_origin_particle(G, tab_org, ro, outside, x[e], y[e], z[e], vx[e], vy[e], vz[e]) && ok;
+            if (!ok && first_bad < 0) first_bad = p;
+        }
+        if (ORIGIN) amc_sample_store_pair(O, p0, v0, v1, x, y, z, vx, vy, vz);
     }
     if (LAG) corr_flush(tab_lag, rl);
     if (ORIGIN) corr_flush(tab_org, ro);
     if (outside) atomicAdd(&outside_sum, outside);
     if (first_bad >= 0) atomicMin(bad, (unsigned long long)first_bad);
-    __syncthreads();
-    unsigned long long *row = slab + (size_t)blockIdx.x * (size_t)(TABLES * M + 1);
-    for (int j = threadIdx.x; j < TABLES * M; j += blockDim.x) row[j] = tab[j];
-    if (threadIdx.x == 0) row[TABLES * M] = outside_sum;
+    amc_slab_store(slab, tab, TABLES * M, &outside_sum);
 }
 
 static amc_corr_arrays corr_arrays(const amc_corr_ws &R)

@@ -11,9 +11,10 @@
 //                    them into ROWS tables in LDS (64-bit integer LDS atomics: exact and order-free).  It stores the tables
 //                    as one slab row [ROWS][bins * 7][outside] with plain stores — no global atomics but the atomicMin on
 //                    the error word.
-//   k_sample_reduce  sums the slab rows per (bin, quantity) and adds the result into the 128-bit running totals, with carry
-//                    (the fluxes: row A at "lag" 0 and row B at "lag" 1 of two, totals[bins][2][7][2]); it serves the sampled
-//                    correlations too (amc_launch_sample_reduce) and adds nothing once the error word is set.
+//   k_slab_reduce<unsigned long long, sample_sink>  (amc_sample_dev.h) sums the slab rows per (bin, quantity); the sink adds the
+//                    result into the 128-bit running totals, with carry (the fluxes: row A at "lag" 0 and row B at "lag" 1 of
+//                    two, totals[bins][2][7][2]); it serves the sampled correlations too (amc_launch_sample_reduce) and adds
+//                    nothing once the error word is set.
 // Integer sums do not depend on the order of the adds, so the totals are bitwise the same for any number of workgroups.
 #include "amc_host.h"
 #include "amc_sample_dev.h"
@@ -21,7 +22,6 @@
 
 #define AMC_MOMENTS_Q AMC_SAMPLE_Q       // per row — A: count, q1(c1..c3), q2(c1..c3); B: 0, q2(c1c2, c1c3, c2c3), q3(c1..c3)
 #define AMC_MOMENTS_THREADS 1024        // the 112 KiB of tables leave room for one workgroup per CU: 16 waves
-#define AMC_SAMPLE_REDUCE_THREADS 1024
 static_assert(2 * AMC_FLUX_MAX_BINS == AMC_FIELDS_MAX_BINS, "both instances of k_moments_accum fill the one LDS table");
 
 AMC_DEV unsigned long long moments_q1(double c) { return (unsigned long long)(long long)rint(c * 16777216.0); }
@@ -29,35 +29,17 @@ AMC_DEV unsigned long long moments_q2(double a, double b) { return (unsigned lon
 AMC_DEV unsigned long long moments_q3(double e, double c) { return (unsigned long long)(long long)rint(ldexp(e * c, -6)); }
 
 // one particle into the workgroup's tables (tab: row A; ROWS == 2: tab + M is row B); returns false if a component is out of
-// the quantisation range.  (The bin is amc_sample_bin's rule written out: calling it here measured + 0.5 us on the cube's
-// 16 us sample)
+// the quantisation range
 template <int ROWS>
 AMC_DEV bool amc_moments_particle(const amc_fields_grid_dev &G, unsigned long long *tab, int M, unsigned int &outside, double x, double y,
                                   double z, double vx, double vy, double vz)
 {
-    int i1, i2, i3;
-    double c1, c2, c3;
-    if (G.kind == AMC_FIELDS_CARTESIAN) {
-        i1 = amc_fields_axis(x, G.lo[0], G.hi[0], G.w[0], G.n1);
-        i2 = amc_fields_axis(y, G.lo[1], G.hi[1], G.w[1], G.n2);
-        i3 = amc_fields_axis(z, G.lo[2], G.hi[2], G.w[2], G.n3);
-        c1 = vx; c2 = vy; c3 = vz;
-    } else {
-        const double r = sqrt(x * x + y * y);
-        i1 = amc_fields_axis(r, G.lo[0], G.hi[0], G.w[0], G.n1);
-        i2 = amc_fields_axis(z, G.lo[1], G.hi[1], G.w[1], G.n2);
-        i3 = 0;
-        if (r > 0.0) {
-            c1 = (x * vx + y * vy) / r;
-            c2 = (x * vy - y * vx) / r;
-        } else {
-            c1 = vx; c2 = vy;
-        }
-        c3 = vz;
-    }
-    if (i1 < 0 || i2 < 0 || i3 < 0) { outside++; return true; }
+    int bin;
+    double c[3];
+    if (!amc_sample_frame(G, x, y, z, vx, vy, vz, bin, c)) { outside++; return true; }
+    const double c1 = c[0], c2 = c[1], c3 = c[2];
     if (!amc_sample_speed_ok(c1, c2, c3)) return false;
-    unsigned long long *a = tab + (size_t)((i1 * G.n2 + i2) * G.n3 + i3) * AMC_MOMENTS_Q;
+    unsigned long long *a = tab + (size_t)bin * AMC_MOMENTS_Q;
     const double s1 = c1 * c1, s2 = c2 * c2, s3 = c3 * c3;
     atomicAdd(a + 0, 1ULL);
     atomicAdd(a + 1, moments_q1(c1));
@@ -87,92 +69,56 @@ __global__ __launch_bounds__(AMC_MOMENTS_THREADS) void k_moments_accum(amc_state
     __shared__ unsigned long long tab[AMC_FIELDS_MAX_BINS * AMC_MOMENTS_Q];     // ROWS tables of G.bins * 7 (the sampler's bin limit)
     __shared__ unsigned int outside_sum;
     const int M = G.bins * AMC_MOMENTS_Q;
-    for (int j = threadIdx.x; j < ROWS * M; j += blockDim.x) tab[j] = 0;
-    if (threadIdx.x == 0) outside_sum = 0;
-    __syncthreads();
-    // this workgroup's particles [b0, b1), walked as aligned pairs (2k, 2k + 1): one 16-byte load per array and pair
-    const long long cnt = hi - lo;
-    const long long per = (cnt + gridDim.x - 1) / gridDim.x;
-    const long long b0 = lo + per * blockIdx.x, b1 = b0 + per < hi ? b0 + per : hi;
+    amc_slab_begin(tab, ROWS * M, &outside_sum);
     unsigned int outside = 0;
     long long first_bad = -1;
-    if (b0 < b1) {
-        for (long long k = (b0 >> 1) + threadIdx.x; 2 * k < b1; k += blockDim.x) {
-            const long long p0 = 2 * k, p1 = p0 + 1;
-            const bool v0 = p0 >= b0, v1 = p1 < b1;
-            double x[2], y[2], z[2], vx[2], vy[2], vz[2];
-            if (v0 && v1) {
-                const double2 ax = *(const double2 *)(S.x + p0), ay = *(const double2 *)(S.y + p0), az = *(const double2 *)(S.z + p0);
-                const double2 bx = *(const double2 *)(S.vx + p0), by = *(const double2 *)(S.vy + p0), bz = *(const double2 *)(S.vz + p0);
-                x[0] = ax.x; x[1] = ax.y; y[0] = ay.x; y[1] = ay.y; z[0] = az.x; z[1] = az.y;
-                vx[0] = bx.x; vx[1] = bx.y; vy[0] = by.x; vy[1] = by.y; vz[0] = bz.x; vz[1] = bz.y;
-            } else {
-                const long long p = v0 ? p0 : p1;
-                const int e = v0 ? 0 : 1;
-                x[e] = S.x[p]; y[e] = S.y[p]; z[e] = S.z[p]; vx[e] = S.vx[p]; vy[e] = S.vy[p]; vz[e] = S.vz[p];
-            }
-            for (int e = 0; e < 2; e++) {
-                if (!(e == 0 ? v0 : v1)) continue;
-                const long long p = p0 + e;
-                amc_fields_lazy(S, L, p, x[e], y[e], z[e], vx[e], vy[e], vz[e]);
-                if (!amc_moments_particle<ROWS>(G, tab, M, outside, x[e], y[e], z[e], vx[e], vy[e], vz[e]) && first_bad < 0) first_bad = p;
-            }
+    for (amc_sample_walk w(lo, hi); w.more(); w.next()) {
+        const long long p0 = w.p0();
+        const bool v0 = w.v0(), v1 = w.v1();
+        double x[2], y[2], z[2], vx[2], vy[2], vz[2];
+        amc_sample_load_pair(S, p0, v0, v1, x, y, z, vx, vy, vz);
+        for (int e = 0; e < 2; e++) {
+            if (!(e == 0 ? v0 : v1)) continue;
+            const long long p = p0 + e;
+            amc_fields_lazy(L, p, x[e], y[e], z[e], vx[e], vy[e], vz[e]);
+            if (!amc_moments_particle<ROWS>(G, tab, M, outside, x[e], y[e], z[e], vx[e], vy[e], vz[e]) && first_bad < 0) first_bad = p;
         }
     }
     if (outside) atomicAdd(&outside_sum, outside);
     if (first_bad >= 0) atomicMin(bad, (unsigned long long)first_bad);
-    __syncthreads();
-    unsigned long long *row = slab + (size_t)blockIdx.x * (size_t)(ROWS * M + 1);
-    for (int j = threadIdx.x; j < ROWS * M; j += blockDim.x) row[j] = tab[j];
-    if (threadIdx.x == 0) row[ROWS * M] = outside_sum;
+    amc_slab_store(slab, tab, ROWS * M, &outside_sum);
 }
 
-// column j of the slab (j < tables * M: table j / M, (bin, quantity) j % M; j == tables * M: particles outside) summed over
-// the rows -> running totals at lag_a (table 0) or lag_b (table 1).  64 columns per workgroup, its sixteen waves take every
-// sixteenth row, four loads in flight each: the rows are a chain of memory round trips otherwise (measured: 10 us for 123 rows
-// with four waves).
+// The moment samplers' and the correlations' end of k_slab_reduce: column j of the slab is table j / M, (bin, quantity) j % M, and
+// goes with carry into the 128-bit running totals at lag_a (table 0) or lag_b (table 1) of lags1.
 // meta: [0] origins, [1] samples, [2] particles outside, [3] lowest particle out of range (~0: none)
-__global__ __launch_bounds__(AMC_SAMPLE_REDUCE_THREADS) void k_sample_reduce(const unsigned long long *slab, int rows, int M, int tables, int lag_a,
-                                                                             int lag_b, int lags1, int origin, unsigned long long *tot,
-                                                                             unsigned long long *meta)
-{
-    if (meta[3] != ~0ULL) return;       // a sample with a particle out of range adds nothing, nor does a later one (the read reports it)
-    constexpr int WAVES = AMC_SAMPLE_REDUCE_THREADS / 64;
-    __shared__ unsigned long long part[WAVES][64];
-    const int W = tables * M;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int j = blockIdx.x * 64 + lane;
-    unsigned long long s = 0;           // (wraps modulo 2^64; the true sum of one sample is below 2^62 in magnitude)
-    if (j <= W) {
-#pragma unroll 4
-        for (int b = wave; b < rows; b += WAVES) s += slab[(size_t)b * (size_t)(W + 1) + j];
+struct sample_sink {
+    static constexpr bool companion = false;
+    int M, lag_a, lag_b, lags1, origin;
+    unsigned long long *tot, *meta;
+    AMC_DEV bool stopped() const { return amc_g(meta)[3] != ~0ULL; }    // a sample with a particle out of range adds nothing, nor does a later one
+    AMC_DEV int stride(int W) const { return W + 1; }
+    AMC_DEV void column(int j, unsigned long long s) const       // (the true sum of one sample is below 2^62 in magnitude)
+    {
+        const int t = j / M, jj = j - t * M;
+        const int g = jj / AMC_SAMPLE_Q, q = jj - g * AMC_SAMPLE_Q;
+        auto *at = amc_g(tot) + 2 * (((size_t)g * (size_t)lags1 + (size_t)(t == 0 ? lag_a : lag_b)) * AMC_SAMPLE_Q + (size_t)q);
+        unsigned long long tl = at[0], th = at[1];
+        amc_add128(tl, th, s);
+        at[0] = tl; at[1] = th;
     }
-    part[wave][lane] = s;
-    __syncthreads();
-    if (wave != 0 || j > W) return;
-    s = 0;
-#pragma unroll
-    for (int k = 0; k < WAVES; k++) s += part[k][lane];
-    if (j == W) {
-        meta[0] += (unsigned long long)origin;
-        meta[1] += 1;
-        meta[2] += s;
-        return;
+    AMC_DEV void counters(unsigned long long s) const
+    {
+        amc_g(meta)[0] += (unsigned long long)origin;
+        amc_g(meta)[1] += 1;
+        amc_g(meta)[2] += s;
     }
-    const int t = j / M, jj = j - t * M;
-    const int g = jj / AMC_SAMPLE_Q, q = jj - g * AMC_SAMPLE_Q;
-    const size_t at = ((size_t)g * (size_t)lags1 + (size_t)(t == 0 ? lag_a : lag_b)) * AMC_SAMPLE_Q + (size_t)q;
-    amc_add128(tot[2 * at], tot[2 * at + 1], s);
-}
+};
 
 hipError_t amc_launch_sample_reduce(amc_ctx *c, const unsigned long long *slab, int rows, int M, int tables, int lag_a, int lag_b,
                                     int lags1, int origin, unsigned long long *tot, unsigned long long *meta)
 {
-    amc_prof_begin(c, AMC_K_FIELDS);
-    AMC_LAUNCH(c, k_sample_reduce, dim3((tables * M + 1 + 63) / 64), dim3(AMC_SAMPLE_REDUCE_THREADS), slab, rows, M, tables, lag_a, lag_b,
-               lags1, origin, tot, meta);
-    amc_prof_end(c);
-    return hipGetLastError();
+    return amc_launch_slab_reduce(c, slab, rows, tables * M, sample_sink{M, lag_a, lag_b, lags1, origin, tot, meta});
 }
 
 // ---- the host side: one implementation over a workspace (c->F, c->FX) and its sampler's descriptor -------------------------------------------
@@ -216,20 +162,13 @@ static void moments_free(amc_ctx *c, amc_moments_ws &W)
     W = amc_moments_ws();
 }
 
-// meta: [0] unused, [1] samples, [2] particles outside, [3] the error word (the layout k_sample_reduce writes)
+// meta: [0] unused, [1] samples, [2] particles outside, [3] the error word (the layout amc_sampler_read reads)
 static amc_totals moments_totals(const amc_moments_ws &W, const moments_desc &D)
 {
     return amc_totals{W.tot, (size_t)2 * D.rows * AMC_MOMENTS_Q * (size_t)W.G.bins, W.meta, 4, 3};
 }
 
-// (c is not null here and below: the entry points have looked)
-static int moments_reset(amc_ctx *c, amc_moments_ws &W, const moments_desc &D)
-{
-    if (int rc = amc_sampler_ready(c, W.on, D.name, "reset")) return rc;
-    const unsigned long long meta[4] = {0, 0, 0, 0};
-    return amc_totals_put(c, moments_totals(W, D), nullptr, meta);
-}
-
+// (c is not null here: the entry points have looked)
 // grid: the sampler's grid struct (the common layout, above), or nullptr
 static int moments_config(amc_ctx *c, amc_moments_ws &W, const moments_desc &D, const void *grid)
 {
@@ -253,35 +192,8 @@ static int moments_config(amc_ctx *c, amc_moments_ws &W, const moments_desc &D, 
         return amc_fail(c, AMC_ERR_HIP, "%s_config: device allocation failed", D.name);
     }
     W.on = true;
-    if (int rc = moments_reset(c, W, D)) { moments_free(c, W); return rc; }
+    if (int rc = amc_sampler_reset(c, W.on, D.name, moments_totals(W, D))) { moments_free(c, W); return rc; }
     return AMC_OK;
-}
-
-static int moments_sample(amc_ctx *c, amc_moments_ws &W, const moments_desc &D)
-{
-    if (int rc = amc_sampler_sample_ready(c, W.on, D.name)) return rc;
-    return moments_enqueue(c, W, D);
-}
-
-static int moments_read(amc_ctx *c, amc_moments_ws &W, const moments_desc &D, int64_t *totals, int64_t *n_samples, int64_t *n_outside)
-{
-    if (int rc = amc_sampler_ready(c, W.on, D.name, "read")) return rc;
-    unsigned long long meta[4], bad;
-    if (int rc = amc_totals_get(c, moments_totals(W, D), totals, meta, &bad)) return rc;
-    if (bad != ~0ULL)
-        return amc_fail(c, AMC_ERR_CAPACITY, "%s: particle %llu has a velocity component outside |c| < 2^14 m/s (or NaN); "
-                        "sampling stopped until %s_reset", D.name, bad, D.name);
-    if (n_samples) *n_samples = (int64_t)meta[1];
-    if (n_outside) *n_outside = (int64_t)meta[2];
-    return AMC_OK;
-}
-
-static int moments_load(amc_ctx *c, amc_moments_ws &W, const moments_desc &D, const int64_t *totals, int64_t n_samples, int64_t n_outside)
-{
-    if (!totals || n_samples < 0 || n_outside < 0) return AMC_ERR_INVALID;
-    if (int rc = amc_sampler_ready(c, W.on, D.name, "load")) return rc;
-    const unsigned long long meta[4] = {0, (unsigned long long)n_samples, (unsigned long long)n_outside, 0};
-    return amc_totals_put(c, moments_totals(W, D), totals, meta);
 }
 
 extern "C" {
@@ -292,20 +204,20 @@ int amc_flux_enqueue(amc_ctx *c) { return moments_enqueue(c, c->FX, FLUX); }
 int amc_fields_config(amc_ctx *c, const amc_field_grid *g) { return c ? moments_config(c, c->F, FIELDS, g) : AMC_ERR_INVALID; }
 int amc_flux_config(amc_ctx *c, const amc_flux_grid *g) { return c ? moments_config(c, c->FX, FLUX, g) : AMC_ERR_INVALID; }
 
-int amc_fields_sample(amc_ctx *c) { return c ? moments_sample(c, c->F, FIELDS) : AMC_ERR_INVALID; }
-int amc_flux_sample(amc_ctx *c) { return c ? moments_sample(c, c->FX, FLUX) : AMC_ERR_INVALID; }
+int amc_fields_sample(amc_ctx *c) { return c ? amc_sampler_sample(c, c->F.on, FIELDS.name, amc_fields_enqueue) : AMC_ERR_INVALID; }
+int amc_flux_sample(amc_ctx *c) { return c ? amc_sampler_sample(c, c->FX.on, FLUX.name, amc_flux_enqueue) : AMC_ERR_INVALID; }
 
 int amc_fields_read(amc_ctx *c, int64_t *totals, int64_t *n_samples, int64_t *n_outside)
-{ return c ? moments_read(c, c->F, FIELDS, totals, n_samples, n_outside) : AMC_ERR_INVALID; }
+{ return c ? amc_sampler_read(c, c->F.on, FIELDS.name, moments_totals(c->F, FIELDS), totals, n_samples, n_outside) : AMC_ERR_INVALID; }
 int amc_flux_read(amc_ctx *c, int64_t *totals, int64_t *n_samples, int64_t *n_outside)
-{ return c ? moments_read(c, c->FX, FLUX, totals, n_samples, n_outside) : AMC_ERR_INVALID; }
+{ return c ? amc_sampler_read(c, c->FX.on, FLUX.name, moments_totals(c->FX, FLUX), totals, n_samples, n_outside) : AMC_ERR_INVALID; }
 
 int amc_fields_load(amc_ctx *c, const int64_t *totals, int64_t n_samples, int64_t n_outside)
-{ return c ? moments_load(c, c->F, FIELDS, totals, n_samples, n_outside) : AMC_ERR_INVALID; }
+{ return c ? amc_sampler_load(c, c->F.on, FIELDS.name, moments_totals(c->F, FIELDS), totals, n_samples, n_outside) : AMC_ERR_INVALID; }
 int amc_flux_load(amc_ctx *c, const int64_t *totals, int64_t n_samples, int64_t n_outside)
-{ return c ? moments_load(c, c->FX, FLUX, totals, n_samples, n_outside) : AMC_ERR_INVALID; }
+{ return c ? amc_sampler_load(c, c->FX.on, FLUX.name, moments_totals(c->FX, FLUX), totals, n_samples, n_outside) : AMC_ERR_INVALID; }
 
-int amc_fields_reset(amc_ctx *c) { return c ? moments_reset(c, c->F, FIELDS) : AMC_ERR_INVALID; }
-int amc_flux_reset(amc_ctx *c) { return c ? moments_reset(c, c->FX, FLUX) : AMC_ERR_INVALID; }
+int amc_fields_reset(amc_ctx *c) { return c ? amc_sampler_reset(c, c->F.on, FIELDS.name, moments_totals(c->F, FIELDS)) : AMC_ERR_INVALID; }
+int amc_flux_reset(amc_ctx *c) { return c ? amc_sampler_reset(c, c->FX.on, FLUX.name, moments_totals(c->FX, FLUX)) : AMC_ERR_INVALID; }
 
 }  // extern "C"

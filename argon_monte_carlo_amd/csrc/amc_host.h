@@ -297,3 +297,36 @@ static inline int amc_totals_get(amc_ctx *c, const amc_totals &T, int64_t *total
     *bad = meta_out[T.bad_slot];
     return AMC_OK;
 }
+
+// The entry points of a sampler whose counters are [unused, samples, particles outside, the error word] and whose range is the
+// velocity quantisers' (the fields, the fluxes, the distributions) over its totals T; c is not null: they have looked.
+static inline int amc_sampler_reset(amc_ctx *c, bool on, const char *name, const amc_totals &T)
+{
+    if (int rc = amc_sampler_ready(c, on, name, "reset")) return rc;
+    const unsigned long long meta[4] = {0, 0, 0, 0};
+    return amc_totals_put(c, T, nullptr, meta);
+}
+static inline int amc_sampler_sample(amc_ctx *c, bool on, const char *name, int (*enqueue)(amc_ctx *c))
+{
+    if (int rc = amc_sampler_sample_ready(c, on, name)) return rc;
+    return enqueue(c);
+}
+static inline int amc_sampler_read(amc_ctx *c, bool on, const char *name, const amc_totals &T, int64_t *totals, int64_t *n_samples, int64_t *n_outside)
+{
+    if (int rc = amc_sampler_ready(c, on, name, "read")) return rc;
+    unsigned long long meta[4], bad;
+    if (int rc = amc_totals_get(c, T, totals, meta, &bad)) return rc;
+    if (bad != ~0ULL)
+        return amc_fail(c, AMC_ERR_CAPACITY, "%s: particle %llu has a velocity component outside |c| < 2^14 m/s (or NaN); "
+                        "sampling stopped until %s_reset", name, bad, name);
+    if (n_samples) *n_samples = (int64_t)meta[1];
+    if (n_outside) *n_outside = (int64_t)meta[2];
+    return AMC_OK;
+}
+static inline int amc_sampler_load(amc_ctx *c, bool on, const char *name, const amc_totals &T, const int64_t *totals, int64_t n_samples, int64_t n_outside)
+{
+    if (!totals || n_samples < 0 || n_outside < 0) return AMC_ERR_INVALID;
+    if (int rc = amc_sampler_ready(c, on, name, "load")) return rc;
+    const unsigned long long meta[4] = {0, (unsigned long long)n_samples, (unsigned long long)n_outside, 0};
+    return amc_totals_put(c, T, totals, meta);
+}

@@ -108,13 +108,8 @@ __global__ __launch_bounds__(AMC_MFP_THREADS) void k_mfp_accum(amc_mfp_args A)
         const int owner = pp ? (which ? ri : rj) : ri;
         if (owner < 0 || (long long)owner >= A.n) { atomicMin(&s_bad, owner < 0 ? 0xfffffffeu : (unsigned int)owner); continue; }
         double x = amc_g(A.x)[owner], y = amc_g(A.y)[owner], z = amc_g(A.z)[owner];
-        if (A.L.enabled) {              // (amc_fields_lazy, through global addresses)
-            const int sl = amc_g(A.L.slot_of)[owner];
-            if (sl >= 0 && amc_g(A.L.moved)[sl]) {
-                const auto *t = amc_g(A.L.state) + (size_t)sl * RS_SLOT_DOUBLES;
-                x = t[0]; y = t[1]; z = t[2];
-            }
-        }
+        double vx, vy, vz;              // (not looked at: their loads fall away)
+        amc_fields_lazy(A.L, owner, x, y, z, vx, vy, vz);
         const int bin = amc_sample_bin(A.G, x, y, z);
         if (bin < 0) { outside++; continue; }
         bool ok = true;

@@ -20,8 +20,8 @@
 //                   the centre is broadcast with v_readlane, the distance is tested in registers, a hit adds into the
 //                   workgroup's table of 64-bit counters in LDS (LDS atomics whose result nobody reads: exact and order-free).
 //                   One slab row per workgroup, plain stores.
-//   k_pair_reduce   sums the slab rows per column and adds the result into the 64-bit running totals (k_vdf_reduce's geometry);
-//                   one thread folds the two side counters in.  No global atomic touches the totals.
+//   k_slab_reduce<unsigned long long, pair_sink>  (amc_sample_dev.h) sums the slab rows per column; the sink adds the result into
+//                   the 64-bit running totals, and one thread folds the two side counters in.  No global atomic touches the totals.
 // Integer sums do not depend on the order of the adds, so the totals are bitwise the same for any number of workgroups, any
 // order within a cell and any split of the index range.
 #include <float.h>
@@ -33,7 +33,6 @@
 #define AMC_PAIR_WAVES (AMC_PAIR_THREADS / 64)
 #define AMC_PAIR_FILE_THREADS 256
 #define AMC_PAIR_SCAN_THREADS 1024
-#define AMC_PAIR_REDUCE_THREADS 1024
 // Why the table's counters are 64-bit: a centre adds one per neighbour within r_max, and nothing bounds how many particles a
 // crafted state puts into one ball — 2^17 particles in one cell are 2^34 ordered pairs in one column of one workgroup.
 static_assert(AMC_PAIR_MAX_COLUMNS * sizeof(unsigned long long) == 48 * 1024, "the table is 48 KiB of LDS");
@@ -65,7 +64,7 @@ __global__ __launch_bounds__(AMC_PAIR_FILE_THREADS) void k_pair_file(amc_state S
     const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (p < n) {
         double x = amc_g(S.x)[p], y = amc_g(S.y)[p], z = amc_g(S.z)[p], vx = 0.0, vy = 0.0, vz = 0.0;
-        amc_fields_lazy(S, L, p, x, y, z, vx, vy, vz);
+        amc_fields_lazy(L, p, x, y, z, vx, vy, vz);
         const int cell = amc_sample_bin(V.B, x, y, z);
         int rank = 0;
         if (cell >= 0) {
@@ -154,7 +153,7 @@ __global__ __launch_bounds__(AMC_PAIR_FILE_THREADS) void k_pair_scatter(amc_stat
     if (cell < 0) return;
     const size_t dst = (size_t)amc_g(cell_off)[cell] + (size_t)amc_g(rank_of)[p];     // (below the number of filed particles <= n)
     double x = amc_g(S.x)[p], y = amc_g(S.y)[p], z = amc_g(S.z)[p], vx = amc_g(S.vx)[p], vy = amc_g(S.vy)[p], vz = amc_g(S.vz)[p];
-    amc_fields_lazy(S, L, p, x, y, z, vx, vy, vz);
+    amc_fields_lazy(L, p, x, y, z, vx, vy, vz);
     int2 ir;
     ir.x = (int)p;
     ir.y = amc_sample_bin(V.G, x, y, z);
@@ -224,7 +223,7 @@ AMC_DEV void pair_home(const amc_pair_dev &V, unsigned long long *tab, int lane,
 }
 
 // chunk: consecutive cells a wave takes at a time (1 .. 64: lane b < chunk reads cell b's bounds; pair_enqueue chooses it).
-// cursor: the next chunk nobody has taken yet, zero at the launch (k_pair_reduce puts it back); who takes which chunk changes
+// cursor: the next chunk nobody has taken yet, zero at the launch (pair_sink puts it back); who takes which chunk changes
 // from launch to launch, the sums do not.
 __global__ __launch_bounds__(AMC_PAIR_THREADS) void k_pair_count(amc_pair_dev V, long long n, int lo, int hi, int chunk, const unsigned int *cell_off,
                                                                  const int2 *rec_ir, const double *rec_s, unsigned long long *slab,
@@ -232,8 +231,7 @@ __global__ __launch_bounds__(AMC_PAIR_THREADS) void k_pair_count(amc_pair_dev V,
 {
     __shared__ unsigned long long tab[AMC_PAIR_MAX_COLUMNS];    // G.bins * C counters (the sampler's column limit)
     const int M = V.G.bins * V.C;
-    for (int j = threadIdx.x; j < M; j += blockDim.x) tab[j] = 0;
-    __syncthreads();
+    amc_slab_begin(tab, M);
     const int lane = threadIdx.x & 63;
     const int ncells = V.B.bins;
     for (;;) {
@@ -250,44 +248,28 @@ __global__ __launch_bounds__(AMC_PAIR_THREADS) void k_pair_count(amc_pair_dev V,
                       rec_s);
         }
     }
-    __syncthreads();
-    auto *row = amc_g(slab) + (size_t)blockIdx.x * (size_t)M;
-    for (int j = threadIdx.x; j < M; j += blockDim.x) row[j] = tab[j];
+    amc_slab_store(slab, tab, M);
 }
 
-// column j < W of the slab summed over the rows -> running totals; the thread of j == W counts the sample and folds the side
-// counters in (and zeroes them for the next sample).  The geometry of k_vdf_reduce.
+// the pair distribution's end of k_slab_reduce: column j is the totals' (region, column) j; the counters' thread counts the sample
+// and folds the side counters in (and zeroes them, and k_pair_count's cursor, for the next sample).  It never stops.
 // meta: [0] unused, [1] samples, [2] particles outside, [3] particles unfiled
-__global__ __launch_bounds__(AMC_PAIR_REDUCE_THREADS) void k_pair_reduce(const unsigned long long *slab, int rows, int W, unsigned long long *tot,
-                                                                         unsigned long long *meta, unsigned long long *side)
-{
-    constexpr int WAVES = AMC_PAIR_REDUCE_THREADS / 64;
-    __shared__ unsigned long long part[WAVES][64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int j = blockIdx.x * 64 + lane;
-    unsigned long long s = 0;
-    if (j < W) {
-        const auto *col = amc_g(slab) + j;
-#pragma unroll 4
-        for (int b = wave; b < rows; b += WAVES) s += col[(size_t)b * (size_t)W];
-    }
-    part[wave][lane] = s;
-    __syncthreads();
-    if (wave != 0 || j > W) return;
-    if (j == W) {
+struct pair_sink {
+    static constexpr bool companion = false;
+    unsigned long long *tot, *meta, *side;
+    AMC_DEV bool stopped() const { return false; }
+    AMC_DEV int stride(int W) const { return W; }
+    AMC_DEV void column(int j, unsigned long long s) const { amc_g(tot)[j] += s; }
+    AMC_DEV void counters(unsigned long long) const
+    {
         amc_g(meta)[1] += 1;
         amc_g(meta)[2] += amc_g(side)[0];
         amc_g(meta)[3] += amc_g(side)[1];
         amc_g(side)[0] = 0;
         amc_g(side)[1] = 0;
         amc_g(side)[2] = 0;             // k_pair_count's cursor
-        return;
     }
-    s = 0;
-#pragma unroll
-    for (int k = 0; k < WAVES; k++) s += part[k][lane];
-    amc_g(tot)[j] += s;
-}
+};
 
 // ---- the host side -------------------------------------------------------------------------------------------------------------
 // A shard of a pore geometry cannot sample: its step ends with the owner's bounds pass over [lo, hi) (amc_mg_finish), which
@@ -366,11 +348,7 @@ static int pair_launches(amc_ctx *c)
                (const unsigned int *)F.cell_off, (const int2 *)F.rec_ir, (const double *)F.rec_s, F.slab, F.side + 2);
     amc_prof_end(c);
     AMC_HIP(c, hipGetLastError());
-    amc_prof_begin(c, AMC_K_FIELDS);
-    AMC_LAUNCH(c, k_pair_reduce, dim3((W + 1 + 63) / 64), dim3(AMC_PAIR_REDUCE_THREADS), (const unsigned long long *)F.slab, blocks, W, F.tot,
-               F.meta, F.side);
-    amc_prof_end(c);
-    AMC_HIP(c, hipGetLastError());
+    AMC_HIP(c, amc_launch_slab_reduce(c, (const unsigned long long *)F.slab, blocks, W, pair_sink{F.tot, F.meta, F.side}));
     return AMC_OK;
 }
 

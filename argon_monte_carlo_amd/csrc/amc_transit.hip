@@ -2,7 +2,7 @@
 // particle (include/argonmc_transit.h).  The reference has no such output; the Python layer derives transmission
 // probabilities, residence times, rates and occupancies from the totals.
 //
-// One sample is two kernels, the shape of the sampled velocity distributions' (amc_vdf.hip):
+// One sample is two kernels, the streaming samplers' pair (amc_sample_dev.h):
 //   k_transit_accum   a persistent grid of at most one workgroup per CU.  Each workgroup streams a contiguous index range: the
 //                     coordinate arrays of the axes in use (8 B each, 16-B loads of particle pairs) and the particles' state
 //                     words (4 B, 8-B loads).  A particle's new position word is built from compares alone; where it equals
@@ -14,14 +14,14 @@
 //                     the first sample after a reset, when everybody is seen for the first time — handles the event in
 //                     place.)  The table leaves as one slab row with plain stores — no global atomics but the atomicMin on
 //                     the error word.
-//   k_transit_reduce  sums the slab rows per column and adds the result into the 128-bit running totals, the two limbs of
-//                     sum_tau2 into one total; it adds nothing once the error word or the sample limit's flag is set.
+//   k_slab_reduce<unsigned long long, transit_sink>  sums the slab rows per column; the sink adds the result into the 128-bit
+//                     running totals, the two limbs of sum_tau2 into one total (the reduce's companion column), and nothing
+//                     once the error word or the sample limit's flag is set.
 // Integer sums do not depend on the order of the adds, so the totals are bitwise the same for any number of workgroups.
 #include "amc_host.h"
 #include "amc_sample_dev.h"
 
 #define AMC_TRANSIT_THREADS 512
-#define AMC_TRANSIT_REDUCE_THREADS 1024
 #define TR_QUEUE 4096                   // events a workgroup defers to the end of its walk: 32 KiB of LDS
 // a slab row's columns per zone: the totals' (argonmc_transit.h) with sum_tau2 as two columns, the sums of tau * tau's low and
 // high 32-bit limbs
@@ -110,10 +110,9 @@ __global__ __launch_bounds__(AMC_TRANSIT_THREADS) void k_transit_accum(amc_state
     __shared__ uint2 queue[TR_QUEUE];   // (particle index - lo, new position word) of the particles with an event
     __shared__ unsigned int queued;
     const int M = T.n_zones * TR_COLUMNS;
-    for (int j = threadIdx.x; j < M; j += blockDim.x) tab[j] = 0;
     // (one read per workgroup: another workgroup of this sample may set the error word meanwhile, and all threads must agree)
     if (threadIdx.x == 0) { head[0] = amc_g(meta)[1]; head[1] = amc_g(meta)[3]; queued = 0; }
-    __syncthreads();
+    amc_slab_begin(tab, M);
     // a stopped sampler changes nothing, the particles' state included
     const unsigned long long ns = head[0];
     if (head[1] != ~0ULL) return;
@@ -124,55 +123,50 @@ __global__ __launch_bounds__(AMC_TRANSIT_THREADS) void k_transit_accum(amc_state
     const unsigned int s = (unsigned int)ns;
     const auto *gx = amc_g(S.x), *gy = amc_g(S.y), *gz = amc_g(S.z);
     auto *gs = amc_g(state);
-    // this workgroup's particles [b0, b1), walked as aligned pairs (2k, 2k + 1): one 16-byte load per coordinate array and pair
-    const long long cnt = hi - lo;
-    const long long per = (cnt + gridDim.x - 1) / gridDim.x;
-    const long long b0 = lo + per * blockIdx.x, b1 = b0 + per < hi ? b0 + per : hi;
     unsigned int inside[AMC_TRANSIT_MAX_ZONES];
 #pragma unroll
     for (int k = 0; k < AMC_TRANSIT_MAX_ZONES; k++) inside[k] = 0;
     long long first_bad = -1;
-    if (b0 < b1) {
-        for (long long k = (b0 >> 1) + threadIdx.x; 2 * k < b1; k += blockDim.x) {
-            const long long p0 = 2 * k, p1 = p0 + 1;
-            const bool v0 = p0 >= b0, v1 = p1 < b1;
-            double x[2] = {0.0, 0.0}, y[2] = {0.0, 0.0}, z[2] = {0.0, 0.0};
-            unsigned int ow[2];
-            if (v0 && v1) {
-                if (T.used & 1) { const double2 a = amc_g_load((const double2 *)(S.x + p0)); x[0] = a.x; x[1] = a.y; }
-                if (T.used & 2) { const double2 a = amc_g_load((const double2 *)(S.y + p0)); y[0] = a.x; y[1] = a.y; }
-                if (T.used & 4) { const double2 a = amc_g_load((const double2 *)(S.z + p0)); z[0] = a.x; z[1] = a.y; }
-                const uint2 o = amc_g_load((const uint2 *)(state + p0));
-                ow[0] = o.x; ow[1] = o.y;
-            } else {
-                const long long p = v0 ? p0 : p1;
-                const int e = v0 ? 0 : 1;
-                if (T.used & 1) x[e] = gx[p];
-                if (T.used & 2) y[e] = gy[p];
-                if (T.used & 4) z[e] = gz[p];
-                ow[e] = gs[p];
-                ow[1 - e] = 0;
+    // per pair one 16-byte load per coordinate array in use and one 8-byte load of the state words
+    for (amc_sample_walk w(lo, hi); w.more(); w.next()) {
+        const long long p0 = w.p0();
+        const bool v0 = w.v0(), v1 = w.v1();
+        double x[2] = {0.0, 0.0}, y[2] = {0.0, 0.0}, z[2] = {0.0, 0.0};
+        unsigned int ow[2];
+        if (v0 && v1) {
+            if (T.used & 1) { const double2 a = amc_g_load((const double2 *)(S.x + p0)); x[0] = a.x; x[1] = a.y; }
+            if (T.used & 2) { const double2 a = amc_g_load((const double2 *)(S.y + p0)); y[0] = a.x; y[1] = a.y; }
+            if (T.used & 4) { const double2 a = amc_g_load((const double2 *)(S.z + p0)); z[0] = a.x; z[1] = a.y; }
+            const uint2 o = amc_g_load((const uint2 *)(state + p0));
+            ow[0] = o.x; ow[1] = o.y;
+        } else {
+            const long long p = v0 ? p0 : p0 + 1;
+            const int e = v0 ? 0 : 1;
+            if (T.used & 1) x[e] = gx[p];
+            if (T.used & 2) y[e] = gy[p];
+            if (T.used & 4) z[e] = gz[p];
+            ow[e] = gs[p];
+            ow[1 - e] = 0;
+        }
+#pragma unroll
+        for (int e = 0; e < 2; e++) {
+            if (!(e == 0 ? v0 : v1)) continue;
+            const long long p = p0 + e;
+            double vx, vy, vz;          // (not looked at: their loads fall away)
+            amc_fields_lazy(L, p, x[e], y[e], z[e], vx, vy, vz);
+            bool nan;
+            const unsigned int nw = tr_positions(T, x[e], y[e], z[e], &nan);
+            if (nan) {
+                if (first_bad < 0) first_bad = p;
+                continue;
             }
+            const unsigned int in = (nw >> 1) & ~nw & 0x11111111u;      // one bit per zone the particle is inside
 #pragma unroll
-            for (int e = 0; e < 2; e++) {
-                if (!(e == 0 ? v0 : v1)) continue;
-                const long long p = p0 + e;
-                double vx, vy, vz;          // (not looked at: their loads fall away)
-                amc_fields_lazy(S, L, p, x[e], y[e], z[e], vx, vy, vz);
-                bool nan;
-                const unsigned int nw = tr_positions(T, x[e], y[e], z[e], &nan);
-                if (nan) {
-                    if (first_bad < 0) first_bad = p;
-                    continue;
-                }
-                const unsigned int in = (nw >> 1) & ~nw & 0x11111111u;      // one bit per zone the particle is inside
-#pragma unroll
-                for (int q = 0; q < AMC_TRANSIT_MAX_ZONES; q++) inside[q] += (in >> (4 * q)) & 1u;
-                if ((ow[e] ^ nw) & 0x33333333u) {
-                    const unsigned int slot = atomicAdd(&queued, 1u);
-                    if (slot < TR_QUEUE) queue[slot] = make_uint2((unsigned int)(p - lo), nw);
-                    else gs[p] = tr_events(tab, entry, stride, p, s, ow[e], nw);
-                }
+            for (int q = 0; q < AMC_TRANSIT_MAX_ZONES; q++) inside[q] += (in >> (4 * q)) & 1u;
+            if ((ow[e] ^ nw) & 0x33333333u) {
+                const unsigned int slot = atomicAdd(&queued, 1u);
+                if (slot < TR_QUEUE) queue[slot] = make_uint2((unsigned int)(p - lo), nw);
+                else gs[p] = tr_events(tab, entry, stride, p, s, ow[e], nw);
             }
         }
     }
@@ -189,9 +183,7 @@ __global__ __launch_bounds__(AMC_TRANSIT_THREADS) void k_transit_accum(amc_state
     for (int q = 0; q < AMC_TRANSIT_MAX_ZONES; q++)
         if (q < T.n_zones && inside[q]) tr_add(tab + q * TR_COLUMNS + 4, inside[q]);
     if (first_bad >= 0) (void)__hip_atomic_fetch_min(amc_g(meta) + 3, (unsigned long long)first_bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    auto *row = amc_g(slab) + (size_t)blockIdx.x * (size_t)M;
-    for (int j = threadIdx.x; j < M; j += blockDim.x) row[j] = tab[j];
+    amc_slab_store(slab, tab, M);
 }
 
 // (lo, hi) += v * 2^32 for a non-negative v below 2^64: the high limb of sum_tau2
@@ -202,46 +194,30 @@ AMC_DEV void tr_add128_limb1(unsigned long long &lo, unsigned long long &hi, uns
     lo = now;
 }
 
-// column j of the slab (j < W: (zone, slab column); j == W: the sample counter) summed over the rows -> the 128-bit totals.
-// The geometry of k_vdf_reduce: 64 columns per workgroup, its sixteen waves take every sixteenth row.  The thread of a
-// sum_tau2 low-limb column also sums the high limb's, the column beside it, and adds both into the one total.
-__global__ __launch_bounds__(AMC_TRANSIT_REDUCE_THREADS) void k_transit_reduce(const unsigned long long *slab, int rows, int W,
-                                                                               unsigned long long *tot, unsigned long long *meta)
-{
-    if (amc_g(meta)[3] != ~0ULL || amc_g(meta)[2] != 0ULL) return;     // a stopped sampler adds nothing (the read reports it)
-    constexpr int WAVES = AMC_TRANSIT_REDUCE_THREADS / 64;
-    __shared__ unsigned long long part[2][WAVES][64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int j = blockIdx.x * 64 + lane;
-    const int zone = j / TR_COLUMNS, c = j % TR_COLUMNS;
-    const int k = c < 5 ? 0 : (c - 5) / TR_CLASS, q = c < 5 ? -1 : (c - 5) % TR_CLASS;     // exit class, column of the class
-    unsigned long long s = 0, s1 = 0;   // (each below 2^56: above)
-    if (j < W) {
-        const auto *col = amc_g(slab) + j;
-#pragma unroll 4
-        for (int b = wave; b < rows; b += WAVES) {
-            s += col[(size_t)b * (size_t)W];
-            if (q == 2) s1 += col[(size_t)b * (size_t)W + 1];
-        }
+// The transits' end of k_slab_reduce: column j of the slab is (zone, slab column) and goes with carry into the 128-bit totals.  The
+// thread of a sum_tau2 low-limb column has the high limb's sum, the column beside it, as its companion and adds both into the one
+// total; the high limb's own thread does nothing (two threads must not add into the same total).  Sums stay below 2^56: above.
+struct transit_sink {
+    static constexpr bool companion = true;
+    unsigned long long *tot, *meta;
+    // the column of its exit class that slab column j is (2: sum_tau2's low limb, 3: its high limb), -1: one of the zone's first five
+    AMC_DEV static int class_column(int j) { const int c = j % TR_COLUMNS; return c < 5 ? -1 : (c - 5) % TR_CLASS; }
+    AMC_DEV bool stopped() const { return amc_g(meta)[3] != ~0ULL || amc_g(meta)[2] != 0ULL; }     // (the read reports it)
+    AMC_DEV int stride(int W) const { return W; }
+    AMC_DEV int mate(int j) const { const int q = class_column(j); return q == 2 ? 1 : q == 3 ? -1 : 0; }
+    template <class Mate>
+    AMC_DEV void column(int j, unsigned long long s, Mate mate_sum) const
+    {
+        const int zone = j / TR_COLUMNS, c = j % TR_COLUMNS, q = class_column(j);
+        const int k = c < 5 ? 0 : (c - 5) / TR_CLASS;       // the exit class
+        auto *t = amc_g(tot) + 2 * ((size_t)zone * AMC_TRANSIT_COLUMNS + (c < 5 ? c : 5 + k * AMC_TRANSIT_CLASS_COLUMNS + (q < 3 ? q : q - 1)));
+        unsigned long long tl = t[0], th = t[1];
+        amc_add128(tl, th, s);
+        if (q == 2) tr_add128_limb1(tl, th, mate_sum());
+        t[0] = tl; t[1] = th;
     }
-    part[0][wave][lane] = s;
-    part[1][wave][lane] = s1;
-    __syncthreads();
-    if (wave != 0 || j > W) return;
-    if (j == W) {
-        amc_g(meta)[1] += 1;
-        return;
-    }
-    if (q == 3) return;                 // (the high limb: added by the thread of the low limb)
-    s = 0; s1 = 0;
-#pragma unroll
-    for (int w = 0; w < WAVES; w++) { s += part[0][w][lane]; s1 += part[1][w][lane]; }
-    auto *t = amc_g(tot) + 2 * ((size_t)zone * AMC_TRANSIT_COLUMNS + (c < 5 ? c : 5 + k * AMC_TRANSIT_CLASS_COLUMNS + (q < 3 ? q : q - 1)));
-    unsigned long long tl = t[0], th = t[1];
-    amc_add128(tl, th, s);
-    if (q == 2) tr_add128_limb1(tl, th, s1);
-    t[0] = tl; t[1] = th;
-}
+    AMC_DEV void counters(unsigned long long) const { amc_g(meta)[1] += 1; }
+};
 
 // ---- the host side -------------------------------------------------------------------------------------------------------------
 int amc_transit_enqueue(amc_ctx *c)    // (AMC_INTERNAL: the cadence hook's)
@@ -261,11 +237,7 @@ int amc_transit_enqueue(amc_ctx *c)    // (AMC_INTERNAL: the cadence hook's)
                F.entry, (long long)F.stride, F.slab, F.meta);
     amc_prof_end(c);
     AMC_HIP(c, hipGetLastError());
-    amc_prof_begin(c, AMC_K_FIELDS);
-    AMC_LAUNCH(c, k_transit_reduce, dim3((W + 1 + 63) / 64), dim3(AMC_TRANSIT_REDUCE_THREADS), (const unsigned long long *)F.slab, blocks, W, F.tot,
-               F.meta);
-    amc_prof_end(c);
-    AMC_HIP(c, hipGetLastError());
+    AMC_HIP(c, amc_launch_slab_reduce(c, (const unsigned long long *)F.slab, blocks, W, transit_sink{F.tot, F.meta}));
     return AMC_OK;
 }
 

@@ -2,20 +2,19 @@
 // of the speed, accumulated as exact integer counts (include/argonmc_vdf.h).  The reference has no such output; the
 // Python layer derives probability densities and the Maxwell comparison from the totals.
 //
-// One sample is two kernels, the shape of the moment samplers' (amc_fields.hip):
+// One sample is two kernels, the streaming samplers' pair (amc_sample_dev.h):
 //   k_vdf_accum    a persistent grid of at most one workgroup per CU.  Each workgroup streams a contiguous index range (x, y, z,
 //                  vx, vy, vz: 48 B per particle, 16-B loads of particle pairs), computes the region, the components and the
 //                  speed of each particle and adds one into five columns of a table of 32-bit counters in LDS (LDS atomics whose
 //                  result nobody reads: exact and order-free).  It stores the table as one slab row [regions * C][outside] with
 //                  plain stores — no global atomics but the atomicMin on the error word.
-//   k_vdf_reduce   sums the slab rows per column and adds the result into the 64-bit running totals; it adds nothing once the
-//                  error word is set.
+//   k_slab_reduce<unsigned int, vdf_sink>  sums the slab rows per column; the sink adds the result into the 64-bit running
+//                  totals, and nothing once the error word is set.
 // Integer sums do not depend on the order of the adds, so the totals are bitwise the same for any number of workgroups.
 #include "amc_host.h"
 #include "amc_sample_dev.h"
 
 #define AMC_VDF_THREADS 1024            // the 96 KiB table leaves room for one workgroup per CU: 16 waves
-#define AMC_VDF_REDUCE_THREADS 1024
 // Why 32-bit counters are exact: amc_sample_blocks refuses a sample of more than AMC_SAMPLE_MAX_PARTICLES = 2^24 particles, a
 // workgroup sees a part of them, and a particle adds 1 to any one column at most once (count, one column of each component's
 // histogram, one of the speed's: five different columns).  So no counter of a table, nor a workgroup's count of particles
@@ -31,39 +30,17 @@ struct amc_vdf_dev {
     double v_max, wc, ws;               // wc = 2 * v_max / H, ws = v_max / H
 };
 
-// an aligned pair of particles' values: one 16-byte load from device memory
-AMC_DEV double2 vdf_pair(const double *p) { return amc_g_load((const double2 *)p); }
 AMC_DEV void vdf_count(unsigned int *p) { (void)__hip_atomic_fetch_add(p, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 
-// one particle into the workgroup's table; returns false if a component is out of the samplers' range.  (Region and components
-// are amc_sample_bin's and the fields' rule written out, as in amc_moments_particle.)
+// one particle into the workgroup's table; returns false if a component is out of the samplers' range
 AMC_DEV bool vdf_particle(const amc_vdf_dev &V, unsigned int *tab, unsigned int &outside, double x, double y, double z, double vx,
                           double vy, double vz)
 {
-    const amc_fields_grid_dev &G = V.G;
-    int i1, i2, i3;
+    int bin;
     double c[3];
-    if (G.kind == AMC_FIELDS_CARTESIAN) {
-        i1 = amc_fields_axis(x, G.lo[0], G.hi[0], G.w[0], G.n1);
-        i2 = amc_fields_axis(y, G.lo[1], G.hi[1], G.w[1], G.n2);
-        i3 = amc_fields_axis(z, G.lo[2], G.hi[2], G.w[2], G.n3);
-        c[0] = vx; c[1] = vy; c[2] = vz;
-    } else {
-        const double r = sqrt(x * x + y * y);
-        i1 = amc_fields_axis(r, G.lo[0], G.hi[0], G.w[0], G.n1);
-        i2 = amc_fields_axis(z, G.lo[1], G.hi[1], G.w[1], G.n2);
-        i3 = 0;
-        if (r > 0.0) {
-            c[0] = (x * vx + y * vy) / r;
-            c[1] = (x * vy - y * vx) / r;
-        } else {
-            c[0] = vx; c[1] = vy;
-        }
-        c[2] = vz;
-    }
-    if (i1 < 0 || i2 < 0 || i3 < 0) { outside++; return true; }
+    if (!amc_sample_frame(V.G, x, y, z, vx, vy, vz, bin, c)) { outside++; return true; }
     if (!amc_sample_speed_ok(c[0], c[1], c[2])) return false;
-    unsigned int *a = tab + ((i1 * G.n2 + i2) * G.n3 + i3) * V.C;
+    unsigned int *a = tab + bin * V.C;
     const int H = V.H;
     vdf_count(a);
 #pragma unroll
@@ -83,77 +60,36 @@ __global__ __launch_bounds__(AMC_VDF_THREADS) void k_vdf_accum(amc_state S, amc_
     __shared__ unsigned int tab[AMC_VDF_MAX_COLUMNS];   // G.bins * C counters (the sampler's column limit)
     __shared__ unsigned int outside_sum;
     const int M = V.G.bins * V.C;
-    for (int j = threadIdx.x; j < M; j += blockDim.x) tab[j] = 0;
-    if (threadIdx.x == 0) outside_sum = 0;
-    __syncthreads();
-    const auto *gx = amc_g(S.x), *gy = amc_g(S.y), *gz = amc_g(S.z), *gvx = amc_g(S.vx), *gvy = amc_g(S.vy), *gvz = amc_g(S.vz);
-    // this workgroup's particles [b0, b1), walked as aligned pairs (2k, 2k + 1): one 16-byte load per array and pair
-    const long long cnt = hi - lo;
-    const long long per = (cnt + gridDim.x - 1) / gridDim.x;
-    const long long b0 = lo + per * blockIdx.x, b1 = b0 + per < hi ? b0 + per : hi;
+    amc_slab_begin(tab, M, &outside_sum);
     unsigned int outside = 0;
     long long first_bad = -1;
-    if (b0 < b1) {
-        for (long long k = (b0 >> 1) + threadIdx.x; 2 * k < b1; k += blockDim.x) {
-            const long long p0 = 2 * k, p1 = p0 + 1;
-            const bool v0 = p0 >= b0, v1 = p1 < b1;
-            double x[2], y[2], z[2], vx[2], vy[2], vz[2];
-            if (v0 && v1) {
-                const double2 ax = vdf_pair(S.x + p0), ay = vdf_pair(S.y + p0), az = vdf_pair(S.z + p0);
-                const double2 bx = vdf_pair(S.vx + p0), by = vdf_pair(S.vy + p0), bz = vdf_pair(S.vz + p0);
-                x[0] = ax.x; x[1] = ax.y; y[0] = ay.x; y[1] = ay.y; z[0] = az.x; z[1] = az.y;
-                vx[0] = bx.x; vx[1] = bx.y; vy[0] = by.x; vy[1] = by.y; vz[0] = bz.x; vz[1] = bz.y;
-            } else {
-                const long long p = v0 ? p0 : p1;
-                const int e = v0 ? 0 : 1;
-                x[e] = gx[p]; y[e] = gy[p]; z[e] = gz[p]; vx[e] = gvx[p]; vy[e] = gvy[p]; vz[e] = gvz[p];
-            }
-            for (int e = 0; e < 2; e++) {
-                if (!(e == 0 ? v0 : v1)) continue;
-                const long long p = p0 + e;
-                amc_fields_lazy(S, L, p, x[e], y[e], z[e], vx[e], vy[e], vz[e]);
-                if (!vdf_particle(V, tab, outside, x[e], y[e], z[e], vx[e], vy[e], vz[e]) && first_bad < 0) first_bad = p;
-            }
+    for (amc_sample_walk w(lo, hi); w.more(); w.next()) {
+        const long long p0 = w.p0();
+        const bool v0 = w.v0(), v1 = w.v1();
+        double x[2], y[2], z[2], vx[2], vy[2], vz[2];
+        amc_sample_load_pair(S, p0, v0, v1, x, y, z, vx, vy, vz);
+        for (int e = 0; e < 2; e++) {
+            if (!(e == 0 ? v0 : v1)) continue;
+            const long long p = p0 + e;
+            amc_fields_lazy(L, p, x[e], y[e], z[e], vx[e], vy[e], vz[e]);
+            if (!vdf_particle(V, tab, outside, x[e], y[e], z[e], vx[e], vy[e], vz[e]) && first_bad < 0) first_bad = p;
         }
     }
     if (outside) atomicAdd(&outside_sum, outside);
     if (first_bad >= 0) atomicMin(bad, (unsigned long long)first_bad);
-    __syncthreads();
-    auto *row = amc_g(slab) + (size_t)blockIdx.x * (size_t)(M + 1);
-    for (int j = threadIdx.x; j < M; j += blockDim.x) row[j] = tab[j];
-    if (threadIdx.x == 0) row[M] = outside_sum;
+    amc_slab_store(slab, tab, M, &outside_sum);
 }
 
-// column j of the slab (j < W: (region, column) of the totals; j == W: particles outside) summed over the rows -> running totals.
-// The geometry of k_sample_reduce: 64 columns per workgroup, its sixteen waves take every sixteenth row.
+// the distributions' end of k_slab_reduce: column j is the totals' (region, column) j; a sum is at most 2^24, one sample's particles
 // meta: [0] unused, [1] samples, [2] particles outside, [3] lowest particle out of range (~0: none)
-__global__ __launch_bounds__(AMC_VDF_REDUCE_THREADS) void k_vdf_reduce(const unsigned int *slab, int rows, int W, unsigned long long *tot,
-                                                                       unsigned long long *meta)
-{
-    if (*amc_g(meta + 3) != ~0ULL) return;      // a sample with a particle out of range adds nothing, nor does a later one (the read reports it)
-    constexpr int WAVES = AMC_VDF_REDUCE_THREADS / 64;
-    __shared__ unsigned long long part[WAVES][64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int j = blockIdx.x * 64 + lane;
-    unsigned long long s = 0;           // (at most 2^24: one sample's particles)
-    if (j <= W) {
-        const auto *col = amc_g(slab) + j;
-#pragma unroll 4
-        for (int b = wave; b < rows; b += WAVES) s += col[(size_t)b * (size_t)(W + 1)];
-    }
-    part[wave][lane] = s;
-    __syncthreads();
-    if (wave != 0 || j > W) return;
-    s = 0;
-#pragma unroll
-    for (int k = 0; k < WAVES; k++) s += part[k][lane];
-    if (j == W) {
-        amc_g(meta)[1] += 1;
-        amc_g(meta)[2] += s;
-        return;
-    }
-    amc_g(tot)[j] += s;
-}
+struct vdf_sink {
+    static constexpr bool companion = false;
+    unsigned long long *tot, *meta;
+    AMC_DEV bool stopped() const { return amc_g(meta)[3] != ~0ULL; }    // a sample with a particle out of range adds nothing, nor does a later one
+    AMC_DEV int stride(int W) const { return W + 1; }
+    AMC_DEV void column(int j, unsigned long long s) const { amc_g(tot)[j] += s; }
+    AMC_DEV void counters(unsigned long long s) const { amc_g(meta)[1] += 1; amc_g(meta)[2] += s; }
+};
 
 // ---- the host side -------------------------------------------------------------------------------------------------------------
 int amc_vdf_enqueue(amc_ctx *c)        // (AMC_INTERNAL: the cadence hook's)
@@ -169,10 +105,7 @@ int amc_vdf_enqueue(amc_ctx *c)        // (AMC_INTERNAL: the cadence hook's)
                F.meta + 3);
     amc_prof_end(c);
     AMC_HIP(c, hipGetLastError());
-    amc_prof_begin(c, AMC_K_FIELDS);
-    AMC_LAUNCH(c, k_vdf_reduce, dim3((W + 1 + 63) / 64), dim3(AMC_VDF_REDUCE_THREADS), (const unsigned int *)F.slab, blocks, W, F.tot, F.meta);
-    amc_prof_end(c);
-    AMC_HIP(c, hipGetLastError());
+    AMC_HIP(c, amc_launch_slab_reduce(c, (const unsigned int *)F.slab, blocks, W, vdf_sink{F.tot, F.meta}));
     return AMC_OK;
 }
 
@@ -186,13 +119,7 @@ static amc_totals vdf_totals(const amc_vdf_ws &F) { return amc_totals{F.tot, (si
 
 extern "C" {
 
-int amc_vdf_reset(amc_ctx *c)
-{
-    if (!c) return AMC_ERR_INVALID;
-    if (int rc = amc_sampler_ready(c, c->VD.on, "amc_vdf", "reset")) return rc;
-    const unsigned long long meta[4] = {0, 0, 0, 0};
-    return amc_totals_put(c, vdf_totals(c->VD), nullptr, meta);
-}
+int amc_vdf_reset(amc_ctx *c) { return c ? amc_sampler_reset(c, c->VD.on, "amc_vdf", vdf_totals(c->VD)) : AMC_ERR_INVALID; }
 
 int amc_vdf_config(amc_ctx *c, const amc_vdf_grid *g)
 {
@@ -225,33 +152,12 @@ int amc_vdf_config(amc_ctx *c, const amc_vdf_grid *g)
     return AMC_OK;
 }
 
-int amc_vdf_sample(amc_ctx *c)
-{
-    if (!c) return AMC_ERR_INVALID;
-    if (int rc = amc_sampler_sample_ready(c, c->VD.on, "amc_vdf")) return rc;
-    return amc_vdf_enqueue(c);
-}
+int amc_vdf_sample(amc_ctx *c) { return c ? amc_sampler_sample(c, c->VD.on, "amc_vdf", amc_vdf_enqueue) : AMC_ERR_INVALID; }
 
 int amc_vdf_read(amc_ctx *c, int64_t *totals, int64_t *n_samples, int64_t *n_outside)
-{
-    if (!c) return AMC_ERR_INVALID;
-    if (int rc = amc_sampler_ready(c, c->VD.on, "amc_vdf", "read")) return rc;
-    unsigned long long meta[4], bad;
-    if (int rc = amc_totals_get(c, vdf_totals(c->VD), totals, meta, &bad)) return rc;
-    if (bad != ~0ULL)
-        return amc_fail(c, AMC_ERR_CAPACITY, "amc_vdf: particle %llu has a velocity component outside |c| < 2^14 m/s (or NaN); "
-                        "sampling stopped until amc_vdf_reset", bad);
-    if (n_samples) *n_samples = (int64_t)meta[1];
-    if (n_outside) *n_outside = (int64_t)meta[2];
-    return AMC_OK;
-}
+{ return c ? amc_sampler_read(c, c->VD.on, "amc_vdf", vdf_totals(c->VD), totals, n_samples, n_outside) : AMC_ERR_INVALID; }
 
 int amc_vdf_load(amc_ctx *c, const int64_t *totals, int64_t n_samples, int64_t n_outside)
-{
-    if (!c || !totals || n_samples < 0 || n_outside < 0) return AMC_ERR_INVALID;
-    if (int rc = amc_sampler_ready(c, c->VD.on, "amc_vdf", "load")) return rc;
-    const unsigned long long meta[4] = {0, (unsigned long long)n_samples, (unsigned long long)n_outside, 0};
-    return amc_totals_put(c, vdf_totals(c->VD), totals, meta);
-}
+{ return c ? amc_sampler_load(c, c->VD.on, "amc_vdf", vdf_totals(c->VD), totals, n_samples, n_outside) : AMC_ERR_INVALID; }
 
 }  // extern "C"

@@ -610,3 +610,40 @@ def test_pore_shard_is_refused_with_a_clear_error():
     whole.close()
     for e in engs:
         e.close()
+
+
+# ---- 12. the reduce at its shapes -------------------------------------------------------------------------------------------------
+_REDUCE_REF = {}
+
+
+def _reduce_case(regions):
+    """(params, grid of ``regions`` regions over the lower half of the pore's box, state, the mirror's sample), computed once"""
+    from tests.sampler_states import ODD_N, drifting_states
+    if regions not in _REDUCE_REF:
+        p, (st,) = drifting_states(ODD_N, 1, seed=29)
+        g = PA.make_grid("cartesian", (regions, 1, 1), (-p.R_oa, -p.R_oa, 0.0), (p.R_oa, p.R_oa, 0.5 * p.H), 2.0e-8,
+                         hist_bins={21: 1, 13: 2}[regions])
+        _REDUCE_REF[regions] = (p, g, st) + REF.sample(g, *st)
+    return _REDUCE_REF[regions]
+
+
+@pytest.mark.parametrize("blocks", ["1", "17", "33"])
+@pytest.mark.parametrize("regions", [21, 13])
+def test_reduce_shapes_equal_reference(regions, blocks, monkeypatch):
+    """21 regions of H = 1: W = 21 * 3 = 63 totals columns, the counters' thread is lane 63 of the reduce's only workgroup; 13
+    regions of H = 2: W = 13 * 5 = 65, the counters' thread is lane 1 of a second one.  1, 17 and 33 slab rows: below, one above and
+    two above a multiple of the reduce's sixteen waves.  The counters' thread folds the side words in and leaves them and the cell
+    cursor at zero: a sample that found them otherwise would count twice, or no cell at all."""
+    from argon_monte_carlo_amd.engine import Engine
+    p, g, st, sums, outside, unfiled = _reduce_case(regions)
+    assert sums.size == {21: 63, 13: 65}[regions] and outside > 0 and unfiled > 0 and (sums[:, 0] > 0).all() and (sums[:, 1:].sum(axis=0) > 0).all()
+    monkeypatch.setenv("AMC_PAIR_BLOCKS", blocks)
+    eng = Engine(p)
+    eng.upload(*st)
+    eng.pair_config(g)
+    for k in (1, 2, 3):                 # (the later samples add onto non-zero totals)
+        eng.pair_sample()
+        tot, ns, no, nu = eng.pair_read()
+        assert (ns, no, nu) == (k, k * outside, k * unfiled)
+        assert np.array_equal(tot, k * sums), np.argwhere(tot != k * sums)[:5]
+    eng.close()

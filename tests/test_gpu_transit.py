@@ -551,3 +551,79 @@ def test_two_ranks_on_one_gpu_equal_single_engine(kind, n):
     assert ns == ref_ns == steps
     t = words_to_ints(ref_tot)
     assert np.array_equal(tot, ref_tot) and int(t[:, 0:3].sum()) > 0 and int(t[:, 4].sum()) > 0
+
+
+# ---- 12. the reduce at its shapes -------------------------------------------------------------------------------------------------
+# a slab row's columns per zone (amc_transit.hip): the totals' with sum_tau2 as two columns, its low and its high 32-bit limb
+TR_CLASS = REF.CLASS_COLUMNS + 1
+TR_COLUMNS = 5 + 6 * TR_CLASS
+_REDUCE_REF = {}
+
+
+def _reduce_case(n_zones):
+    """(params, zones, two states ten steps apart, the mirror after both), computed once"""
+    if n_zones not in _REDUCE_REF:
+        p, states = drifting_states(ODD_N, 11)
+        zones = (_thin_zones(p) + [(0, -2e-9, 2e-9), (1, 0.0, 5e-9), (2, p.h_oa + 2e-9, p.h_oa + 4e-9), (0, 0.0, p.R_oa), (1, -p.R_oa, 0.0)])[:n_zones]
+        m = REF.Mirror(zones, ODD_N)
+        for st in (states[0], states[10]):
+            m.sample(*st[:3])
+        _REDUCE_REF[n_zones] = (p, zones, (states[0], states[10]), m)
+    return _REDUCE_REF[n_zones]
+
+
+@pytest.mark.parametrize("blocks", ["1", "17", "33"])
+@pytest.mark.parametrize("n_zones", [1, 8])
+def test_reduce_shapes_equal_mirror(n_zones, blocks, monkeypatch):
+    """One zone: W = 269 slab columns, five workgroups of the reduce; eight: W = 2,152.  1, 17 and 33 slab rows: below, one above
+    and two above a multiple of the reduce's sixteen waves.  The second sample adds onto non-zero totals."""
+    from argon_monte_carlo_amd.engine import Engine
+    p, zones, states, m = _reduce_case(n_zones)
+    assert n_zones * TR_COLUMNS == {1: 269, 8: 2152}[n_zones]
+    monkeypatch.setenv("AMC_TRANSIT_BLOCKS", blocks)
+    eng = Engine(p)
+    eng.transit_config(TR.make_grid(zones, every=0))
+    for st in states:
+        eng.upload(*st)
+        eng.transit_sample()
+    t = _check(eng, m)
+    assert all(int(t[k, 0:3].sum()) > 0 for k in range(n_zones)) and sum(sum(_classes(t, k)) for k in range(n_zones)) > 0
+    eng.close()
+
+
+def test_reduce_adds_a_limb_pair_split_over_two_workgroups():
+    """The reduce takes 64 slab columns per workgroup, and the thread of a sum_tau2 low-limb column adds the high limb's sum, the
+    column beside it, into the same total.  Zone 4, exit class (entered from above, left above): the low limb is slab column 1215,
+    lane 63 of workgroup 18, the high limb lane 0 of workgroup 19.  tau = 2^17 gives tau^2 = 2^34: a low limb of 0, a high limb of 4."""
+    import re
+    from argon_monte_carlo_amd import _lib
+    from argon_monte_carlo_amd.sim import Simulation
+    src = open(os.path.join(os.path.dirname(_lib.__file__), "csrc", "amc_transit.hip")).read()
+    assert re.search(r"#define TR_CLASS \(AMC_TRANSIT_CLASS_COLUMNS \+ 1\)", src) and re.search(r"#define TR_COLUMNS \(5 \+ 6 \* TR_CLASS\)", src)
+    zone, cls = 4, 2 * 1 + 1
+    low = zone * TR_COLUMNS + 5 + cls * TR_CLASS + 2
+    assert (TR_COLUMNS, TR_CLASS, low) == (269, 44, 1215) and low % 64 == 63
+    n, who = 10, 3
+    sim = Simulation("cube", n=n)
+    L = float(sim.params.cube_x)
+    zones = [(1, (0.1 + 0.1 * k) * L, (0.15 + 0.1 * k) * L) for k in range(8)]      # disjoint, in ascending order along y
+    sim.enable_transits(TR.make_grid(zones), every=0)
+    m = REF.Mirror(zones, n)
+    # everybody below every zone, but `who`: inside zone 4 since sample 0, entered from above — above zones 0 .. 3, below 5 .. 7
+    state = np.full(n, 0x11111111, dtype=np.uint32)
+    state[who] = 0x11100000 | (2 | 1 << 2) << 16 | 0x3333
+    entry = np.zeros((8, n), dtype=np.uint32)
+    zero = ints_to_words(np.zeros((8, REF.COLUMNS), dtype=object))
+    ns = 2 ** 17
+    sim.engine.transit_load(zero, ns, state, entry)
+    m.load(zero, ns, state, entry)
+    y = np.full(n, 0.05 * L)
+    y[who] = 0.57 * L                   # above zone 4, still below zone 5: nobody else's position word changes
+    m.sample(*_set_y(sim, n, L, y))
+    sim.transits_sample()
+    t = _check(sim.engine, m)
+    c = COL(1, 1)
+    want = np.zeros((8, REF.COLUMNS), dtype=object)
+    want[zone, c], want[zone, c + 1], want[zone, c + 2], want[zone, c + 3 + 17] = 1, 2 ** 17, 2 ** 34, 1
+    assert np.array_equal(t, want), np.argwhere(t != want)
+    sim.close()

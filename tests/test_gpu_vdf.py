@@ -535,3 +535,37 @@ def test_maxwell_start_gives_maxwellian_histograms_and_its_temperature():
     print("T_est", d["T_est"][0], "T0", T0, "bound", bound)
     assert abs(d["T_est"][0] - T0) < bound
     sim.close()
+
+
+# ---- 13. the reduce at its shapes -------------------------------------------------------------------------------------------------
+_REDUCE_REF = {}
+
+
+def _reduce_case(regions):
+    """(params, grid of ``regions`` regions over the lower half of the pore's box, state, reference sums, outside), computed once"""
+    if regions not in _REDUCE_REF:
+        p, (st,) = drifting_states(ODD_N, 1, seed=29)
+        g = VD.make_grid("cartesian", (regions, 1, 1), (-p.R_oa, -p.R_oa, 0.0), (p.R_oa, p.R_oa, 0.5 * p.H), hist_bins={4: 2, 5: 1}[regions])
+        _REDUCE_REF[regions] = (p, g, st) + REF.sample(g, *st)
+    return _REDUCE_REF[regions]
+
+
+@pytest.mark.parametrize("blocks", ["1", "17", "33"])
+@pytest.mark.parametrize("regions", [4, 5])
+def test_reduce_shapes_equal_reference(regions, blocks, monkeypatch):
+    """4 regions of H = 2: W = 4 * 16 = 64 totals columns, the last one lane 63 of the reduce's first workgroup, the outside column
+    lane 0 of a second one; 5 regions of H = 1: W = 60, one partial workgroup.  1, 17 and 33 slab rows: below, one above and two
+    above a multiple of the reduce's sixteen waves."""
+    from argon_monte_carlo_amd.engine import Engine
+    p, g, st, sums, outside = _reduce_case(regions)
+    assert _slab_columns(g) - 1 == {4: 64, 5: 60}[regions] and outside > 0 and (sums[:, 0] > 0).all()
+    monkeypatch.setenv("AMC_VDF_BLOCKS", blocks)
+    eng = Engine(p)
+    eng.upload(*st)
+    eng.vdf_config(g)
+    for k in (1, 2):                    # (the second sample adds onto non-zero totals)
+        eng.vdf_sample()
+        tot, ns, no = eng.vdf_read()
+        assert ns == k and no == k * outside
+        assert np.array_equal(tot, k * sums), np.argwhere(tot != k * sums)[:5]
+    eng.close()

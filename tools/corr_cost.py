@@ -1,5 +1,5 @@
 """Cost of the sampled correlations on one GPU: the per-sample kernel time of a lag sample and of an origin
-sample (kernel class "fields": k_corr_accum<MODE> + k_sample_reduce, timed on the dispatch like every other class), the traffic
+sample (kernel class "fields": k_corr_accum<MODE> + k_slab_reduce<unsigned long long, sample_sink>, timed on the dispatch like every other class), the traffic
 floor beside them, and the overhead of run(100) with a sample every 10 steps and 8 lags against run(100) without sampling.
 Prints one JSON line per workload.
 

@@ -1,5 +1,5 @@
 """Cost of the sampled fields on one GPU: the per-sample kernel time (kernel class "fields": k_moments_accum<1> +
-k_sample_reduce, timed on the dispatch like every other class) and the overhead of run(100) with a sample every 10 steps
+k_slab_reduce<unsigned long long, sample_sink>, timed on the dispatch like every other class) and the overhead of run(100) with a sample every 10 steps
 against run(100) without sampling.  Prints one JSON line per workload.
 
     python tools/fields_cost.py [--reps 5]

@@ -1,5 +1,5 @@
 """Cost of the sampled fluxes on one GPU: the per-sample kernel time (kernel class "fields": k_moments_accum<2> +
-k_sample_reduce, timed on the dispatch like every other class) beside a sample of the fields on the same grid in the same
+k_slab_reduce<unsigned long long, sample_sink>, timed on the dispatch like every other class) beside a sample of the fields on the same grid in the same
 process, and the overhead of run(100) with a flux sample every 10 steps against run(100) without sampling.  Prints one JSON
 line per workload.
 

@@ -1,5 +1,5 @@
 """Cost of the sampled pair distribution on one GPU: the kernel time of one sample (kernel class "fields": the six
-kernels k_pair_file, k_pair_scan_sums, k_pair_scan, k_pair_scatter, k_pair_count, k_pair_reduce, timed on the dispatch like every other class) on
+kernels k_pair_file, k_pair_scan_sums, k_pair_scan, k_pair_scatter, k_pair_count, k_slab_reduce<unsigned long long, pair_sink>, timed on the dispatch like every other class) on
 the default grid, on a standing state, beside the time of a step at the same size (run(200) without a sampler) and the pair tests
 a sample makes (from its totals); and the time of a sample on a grid at the cap of 128 cells per axis that holds few particles
 (what the cells cost, not the pairs).  Prints one JSON line per workload.

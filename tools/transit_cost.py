@@ -1,5 +1,5 @@
 """Cost of the sampled transits on one GPU: the per-sample kernel time (kernel class "fields": k_transit_accum +
-k_transit_reduce, timed on the dispatch like every other class) on the default zones beside a sample of the velocity
+k_slab_reduce<unsigned long long, transit_sink>, timed on the dispatch like every other class) on the default zones beside a sample of the velocity
 distributions and one of the fields on THEIR default grids, on the same state in the same process, alternated; and run(200)
 with the transits at every = 1, with the fields at every = 1 (both force the same plain loop) and with no sampler, alternated.
 Five takes of everything: median, minimum and maximum.  Prints one JSON line per workload.

@@ -1,5 +1,5 @@
 """Cost of the sampled velocity distributions on one GPU: the per-sample kernel time (kernel class "fields":
-k_vdf_accum + k_vdf_reduce, timed on the dispatch like every other class) on the default grid beside a sample of the fields and
+k_vdf_accum + k_slab_reduce<unsigned int, vdf_sink>, timed on the dispatch like every other class) on the default grid beside a sample of the fields and
 one of the fluxes on THEIR default grids, on the same state in the same process, and the overhead of run(100) with a sample of
 the distributions every 10 steps against run(100) without sampling.  Prints one JSON line per workload.
 
