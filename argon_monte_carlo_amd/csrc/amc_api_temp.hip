@@ -1,5 +1,6 @@
 // amc_api_temp.hip — C ABI of the energised-wall path (Temperature_Pore_MC.py, Temp:662-853): the per-case hand-over to
 // the host's random draws (amc_wall_hits / amc_wall_apply) and the opt-in device-side sampling (amc_temp_cases_device).
+#include "amc_case_sums_dev.h"
 #include "amc_host.h"
 
 extern "C" {
@@ -317,29 +318,21 @@ int amc_temp_device_sums(amc_ctx *c, double *sums, int32_t *had)
     int rc = temp_dev_fetch(c);
     if (rc) return rc;
     amc_temp_dev_ws &D = c->TD;
-    sums[0] = sums[1] = sums[2] = 0.0;
-    had[0] = had[1] = had[2] = 0;
+    // k_case_sums's order (amc_case_sums_dev.h) on the host's copies of the records
+    double m[7], e[7];
+    int any[7], present[7];
     std::vector<int> perm;
     for (int s = 0; s < 7; s++) {
-        const int case_id = 3 + s;
-        const size_t k = (size_t)std::max(D.h_count[s], 0);
-        if (!k) continue;
+        const size_t k = (size_t)amc_clamp_count(D.h_count[s], D.seg.cap);
+        m[s] = e[s] = 0.0; any[s] = 0; present[s] = k != 0;
         temp_order(D.h_idx[s].data(), k, perm);
-        double m_case = 0.0, e_case = 0.0;
-        bool any = false;
         for (size_t u = 0; u < k; u++) {
             const int r = perm[u];
-            if (!D.h_ok[s][r]) continue;
-            m_case = m_case + D.h_dpz[s][r];
-            e_case = e_case + D.h_dE[s][r];
-            any = true;
+            if (D.h_ok[s][r]) { m[s] = m[s] + D.h_dpz[s][r]; e[s] = e[s] + D.h_dE[s][r]; any[s] = 1; }
         }
-        sums[0] = sums[0] + m_case;
-        had[0] |= any ? 1 : 0;
-        const bool cold = (case_id == 3 || case_id == 7 || case_id == 9), hot = (case_id == 4 || case_id == 6 || case_id == 8);
-        if (cold) { sums[1] = sums[1] + e_case; had[1] |= any ? 1 : 0; }
-        if (hot) { sums[2] = sums[2] + e_case; had[2] |= any ? 1 : 0; }
     }
+    const amc_temp_row row = amc_fold_cases(m, e, any, present);
+    for (int k = 0; k < 3; k++) { sums[k] = row.sums[k]; had[k] = (row.had >> k) & 1; }
     return AMC_OK;
 }
 

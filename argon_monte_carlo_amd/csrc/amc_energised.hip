@@ -191,109 +191,35 @@ hipError_t amc_launch_temp_cases_device(amc_ctx *c, const amc_temp_rng *cfg)
 }
 
 // ---- the step's sums on the device (a host-free run, amc_temp_run_device) ------------------------------------------------
-// What amc_temp_device_sums does on the host, addition for addition: per case the hits in ASCENDING PARTICLE INDEX, failed
-// contact solves skipped, m_case = m_case + dpz and e_case = e_case + dE left to right from 0.0; then the cases folded in
-// order 3..9.  The records of a segment stand in the order their atomics happened to run, so the kernel orders them first:
-// a particle hits a case at most once per step, hence the RANK of a record — the records of its case with a smaller
-// particle index — is its place.  Counting ranks is quadratic in a case's hits but needs no exchange between threads: with
-// ~90 hits per case (N = 1e6) it is a few hundred LDS reads per thread.  One workgroup; lanes 0..6 then add one case each.
-// A step with more hits than the tile takes the same steps through global memory (perm): slow, and as exact.
+// One context's seven record segments as k_case_sums's source (amc_case_sums_dev.h): segment q is case 3 + q.  With ~90 hits
+// per case (N = 1e6) ranking is a few hundred LDS reads per thread; a step with more hits than the tile goes through TD.perm.
 #define AMC_TEMP_SUMS_TILE 2048
 #define AMC_TEMP_SUMS_THREADS 256
-__global__ __launch_bounds__(AMC_TEMP_SUMS_THREADS) void k_temp_sums(temp_dev_segments D, int *__restrict__ perm, amc_temp_row *__restrict__ row,
-                                                                     int row_index, int *__restrict__ ovf)
-{
-    __shared__ int s_idx[AMC_TEMP_SUMS_TILE];
-    __shared__ double s_dpz[AMC_TEMP_SUMS_TILE], s_dE[AMC_TEMP_SUMS_TILE];
-    __shared__ unsigned char s_ok[AMC_TEMP_SUMS_TILE];
-    __shared__ int s_n[7], s_off[8];
-    __shared__ double s_m[7], s_e[7];
-    __shared__ int s_any[7];
-    const int tid = threadIdx.x;
-    if (tid == 0) {
-        int off = 0;
-        for (int s = 0; s < 7; s++) {
-            const int cnt = D.count[s];
-            if (cnt > D.cap && ovf[0] == 0) { ovf[1] = row_index; ovf[2] = cnt; ovf[0] = 3 + s; }   // (the run fails: AMC_ERR_CAPACITY)
-            const int k = cnt < 0 ? 0 : (cnt < D.cap ? cnt : D.cap);
-            s_n[s] = k; s_off[s] = off;
-            off += k;
-        }
-        s_off[7] = off;
+struct temp_segments {
+    static constexpr int MAX_WORLD = 1;
+    temp_dev_segments D;
+    struct view {
+        const int *idx;
+        const unsigned char *okv;
+        const double *dpzv, *dEv;
+        __device__ int key(int k) const { return idx[k]; }
+        __device__ bool ok(int k) const { return okv[k] != 0; }
+        __device__ double dpz(int k) const { return dpzv[k]; }
+        __device__ double dE(int k) const { return dEv[k]; }
+    };
+    __device__ int nseg() const { return 7; }
+    __device__ int cap() const { return D.cap; }
+    __device__ long long count(int q) const { return D.count[q]; }
+    __device__ view segment(int q) const
+    {
+        const size_t o = (size_t)q * (size_t)D.cap;
+        return view{D.idx + o, D.ok + o, D.dpz + o, D.dE + o};
     }
-    __syncthreads();
-    const int total = s_off[7];
-    const bool tiled = total <= AMC_TEMP_SUMS_TILE;
-    if (tiled) {
-        for (int i = tid; i < total; i += AMC_TEMP_SUMS_THREADS) {
-            int s = 0;
-            while (i >= s_off[s + 1]) s++;
-            s_idx[i] = D.idx[(size_t)s * (size_t)D.cap + (size_t)(i - s_off[s])];
-        }
-        __syncthreads();
-    }
-    for (int i = tid; i < total; i += AMC_TEMP_SUMS_THREADS) {
-        int s = 0;
-        while (i >= s_off[s + 1]) s++;
-        const size_t seg = (size_t)s * (size_t)D.cap;
-        const int k = i - s_off[s], n = s_n[s];
-        int rank = 0;
-        if (tiled) {
-            const int mine = s_idx[i];
-            const int *v = s_idx + s_off[s];
-            for (int j = 0; j < n; j++) rank += v[j] < mine ? 1 : 0;
-            const int at = s_off[s] + rank;
-            s_dpz[at] = D.dpz[seg + k]; s_dE[at] = D.dE[seg + k]; s_ok[at] = D.ok[seg + k];
-        } else {
-            const int mine = D.idx[seg + k];
-            const int *v = D.idx + seg;
-            for (int j = 0; j < n; j++) rank += v[j] < mine ? 1 : 0;
-            perm[seg + rank] = k;
-        }
-    }
-    __syncthreads();
-    if (tid < 7) {
-        const int s = tid, n = s_n[s];
-        const size_t seg = (size_t)s * (size_t)D.cap;
-        double m_case = 0.0, e_case = 0.0;
-        int any = 0;
-        for (int u = 0; u < n; u++) {
-            double a, b;
-            unsigned char ok;
-            if (tiled) {
-                a = s_dpz[s_off[s] + u]; b = s_dE[s_off[s] + u]; ok = s_ok[s_off[s] + u];
-            } else {
-                const int r = perm[seg + u];
-                a = D.dpz[seg + r]; b = D.dE[seg + r]; ok = D.ok[seg + r];
-            }
-            if (!ok) continue;
-            m_case = m_case + a;
-            e_case = e_case + b;
-            any = 1;
-        }
-        s_m[s] = m_case; s_e[s] = e_case; s_any[s] = any;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        double sums[3] = {0.0, 0.0, 0.0};
-        unsigned int had = 0;
-        for (int s = 0; s < 7; s++) {
-            if (!s_n[s]) continue;
-            const int case_id = 3 + s;
-            sums[0] = sums[0] + s_m[s];
-            if (s_any[s]) had |= 1u;
-            const bool cold = (case_id == 3 || case_id == 7 || case_id == 9), hot = (case_id == 4 || case_id == 6 || case_id == 8);
-            if (cold) { sums[1] = sums[1] + s_e[s]; if (s_any[s]) had |= 2u; }
-            if (hot) { sums[2] = sums[2] + s_e[s]; if (s_any[s]) had |= 4u; }
-        }
-        amc_temp_row r;
-        r.sums[0] = sums[0]; r.sums[1] = sums[1]; r.sums[2] = sums[2]; r.had = had; r.pad = 0;
-        row[row_index] = r;
-    }
-}
+};
 
 hipError_t amc_launch_temp_sums(amc_ctx *c, int64_t row)
 {
-    AMC_LAUNCH(c, k_temp_sums, dim3(1), dim3(AMC_TEMP_SUMS_THREADS), c->TD.seg, c->TD.perm, c->TD.series, (int)row, c->TD.ovf);
+    AMC_LAUNCH(c, (k_case_sums<temp_segments, AMC_TEMP_SUMS_THREADS, AMC_TEMP_SUMS_TILE>), dim3(1), dim3(AMC_TEMP_SUMS_THREADS),
+               temp_segments{c->TD.seg}, c->TD.perm, c->TD.series, (int)row, c->TD.ovf, AMC_TEMP_SUMS_TILE);
     return hipGetLastError();
 }

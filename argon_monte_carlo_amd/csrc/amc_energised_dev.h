@@ -3,7 +3,7 @@
 // masks (Temp:708-751), the contact solve, the energy accommodation, the device-side draws (amc_temp_rng) and the
 // sequence of all seven cases.
 #pragma once
-#include "amc_internal.h"
+#include "amc_case_sums_dev.h"
 #include "amc_philox.h"
 
 __device__ inline bool temp_mask(const amc_params &P, int case_id, double x, double y, double z, double px, double py,
@@ -121,7 +121,7 @@ __device__ inline void temp_draw(const amc_params &P, const amc_temp_rng &g, int
         break;
     }
     Es = (case_id == 5) ? temp_gap_energy(g, contact_z)
-                        : ((case_id == 3 || case_id == 7 || case_id == 9) ? P.E_cold : P.E_hot);
+                        : (amc_case_cold(case_id) ? P.E_cold : P.E_hot);
 }
 
 // ---- all seven cases of one particle (device-RNG mode) -----------------------------------------------------------------

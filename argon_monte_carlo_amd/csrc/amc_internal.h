@@ -371,7 +371,7 @@ struct amc_corr_ws {
 // amc_mg_step_fresh abandons a pending hits exchange with everything else: amc_temp_begin, amc_upload, amc_set_shard.
 enum amc_mg_phase { AMC_MG_IDLE = 0, AMC_MG_PACKED, AMC_MG_DETECTED, AMC_MG_SWEPT };
 enum amc_mg_hits_phase { AMC_MG_HITS_NONE = 0, AMC_MG_HITS_LAUNCHED, AMC_MG_HITS_PACKED, AMC_MG_HITS_SUMMED };
-#define AMC_MG_HITS_MAX_WORLD 64   // ranks whose segment offsets fit k_hits_sums's LDS table
+#define AMC_MG_HITS_MAX_WORLD 64   // ranks whose segment offsets fit the LDS table of k_case_sums over the blocks (amc_hits.hip)
 struct amc_mg_step {
     amc_mg_phase phase;            // (zero: idle)
     amc_mg_hits_phase hits;        // (zero: none)
@@ -402,7 +402,7 @@ struct amc_mg_ws {
     long long *hits_send, *hits_recv;
     int *hits_perm;                // [7 * world * hits_cap]
     int hits_cap, hits_view_world;
-    int hits_tile;                 // records up to which k_hits_sums orders a step in LDS (AMC_MG_HITS_TILE, else its whole tile)
+    int hits_tile;                 // records up to which the sums kernel orders a step in LDS (AMC_MG_HITS_TILE, else its whole tile)
     int64_t hits_rows;             // rows of the series the run in progress may write (amc_temp_shard_run_begin; 0: none)
     amc_mg_step step;
 };

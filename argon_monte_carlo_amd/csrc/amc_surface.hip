@@ -9,6 +9,7 @@
 // adds it into the 128-bit running totals with carry.  A single workgroup owns the totals: no global atomics.  None of the
 // step's own kernels is involved: the launch sits behind the kernel that completes the records and in front of whatever
 // clears or overwrites them (stream order).
+#include "amc_case_sums_dev.h"
 #include "amc_host.h"
 #include "amc_sample_dev.h"
 
@@ -74,9 +75,9 @@ __global__ __launch_bounds__(AMC_SURFACE_THREADS) void k_surface_accum(amc_surfa
         t0[i] = j < M ? ((const ulonglong2 *)tot)[j] : make_ulonglong2(0, 0);
     }
     for (int j = tid; j < M; j += AMC_SURFACE_THREADS) tab[j] = 0;
-    if (tid < AMC_SURFACE_CASES) {      // (clamped as k_temp_sums clamps: nothing beyond min(count, cap) is read)
+    if (tid < AMC_SURFACE_CASES) {
         s_failed[tid] = 0;
-        s_n[tid] = cnt < 0 ? 0 : (cnt < R.cap ? cnt : R.cap);
+        s_n[tid] = amc_clamp_count(cnt, R.cap);
     }
     if (tid == 0) s_bad = ~0u;
     __syncthreads();

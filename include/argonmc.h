@@ -391,7 +391,7 @@ int amc_mg_finish(amc_ctx *ctx, amc_step_stats *out);      /* out == NULL: no ho
 #define AMC_K_DRIFT_WALLS 0
 #define AMC_K_BIN_COUNT 1        /* k_bin_lists (stand-alone list build; the step driver fuses it into k_stream) and the multi-GPU pack / unpack kernels, which build the lists too */
 #define AMC_K_BIN_SCAN 2         /* (the lists need neither scan nor scatter: the class now times k_hits_pack, the hits exchange of a sharded device-RNG step, argonmc_shard.h) */
-#define AMC_K_BIN_SCATTER 3      /* (likewise: k_hits_sums, that step's sums from the blocks of all ranks) */
+#define AMC_K_BIN_SCATTER 3      /* (likewise: k_case_sums on the blocks of all ranks, that step's sums) */
 #define AMC_K_DETECT 4
 #define AMC_K_RESOLVE 5          /* k_resolve: the ordered workgroup (entangled remainder, later rounds; no-grid mode: everything) */
 #define AMC_K_BOUNDS 6

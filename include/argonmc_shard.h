@@ -19,7 +19,8 @@
  * even if one shard owns them all; AMC_MG_HITS_CAP=k lowers it, AMC_MG_HITS_TILE=k the records a step is ordered in LDS, for tests).  send holds this rank's block, recv the blocks of all
  * ranks in rank order.  The pointers stay valid until the context is destroyed or the call is made with another world size.
  * amc_mg_hits_pack(world): behind amc_temp_cases_device — the rank's seven segments into its send block.
- * amc_mg_hits_sums(world, row): behind the all-gather — one workgroup adds, per case, left to right from 0.0 in ascending
+ * amc_mg_hits_sums(world, row): behind the all-gather — one workgroup of the kernel that also writes a single context's rows
+ * (k_case_sums, here reading the blocks of all ranks) adds, per case, left to right from 0.0 in ascending
  * particle index over all ranks (ok == 0 skipped), folds the cases in order 3..9 and writes row `row` of the series that
  * amc_temp_series_read reads: what amc_temp_device_sums returns for the whole system.
  * A block over capacity is flagged by its owner's pack and by every rank's sums call; every rank's amc_temp_shard_run_end then

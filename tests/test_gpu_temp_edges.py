@@ -487,7 +487,7 @@ def python_sums(records):
 
 
 def test_sums_past_the_tile(steps_many, tmp_path):
-    """temp_many_hits(): more than 2048 hits in one step, so k_temp_sums ranks and permutes through global memory; some of
+    """temp_many_hits(): more than 2048 hits in one step, so k_case_sums ranks and permutes through global memory; some of
     case 8's solves fail and are skipped.  The single step's sums, the run's series row and amc_temp_device_sums equal the
     left-to-right Python sum of the oracle's per-hit values; unchanged with AMC_STREAM_BS=64 (another atomic order)."""
     s = build("many")[0]
