@@ -321,7 +321,8 @@ static int pair_launches(amc_ctx *c)
     // cells a wave takes at a time: one, unless that made more than 16 takes per wave — every take is an atomic on ONE word, and
     // a grid at the cap of 128 cells per axis, mostly empty, would spend its time there
     const int chunk = (int)std::max<long long>(1, std::min<long long>(64, ncells / ((long long)blocks * AMC_PAIR_WAVES * 16)));
-    const unsigned int pblocks = (unsigned int)((c->n + AMC_PAIR_FILE_THREADS - 1) / AMC_PAIR_FILE_THREADS);
+    // (an empty system still launches one workgroup, which finds no particle: a grid of zero workgroups is an invalid launch)
+    const unsigned int pblocks = (unsigned int)std::max<long long>(1, (c->n + AMC_PAIR_FILE_THREADS - 1) / AMC_PAIR_FILE_THREADS);
     const amc_lazy L = amc_sample_lazy(c);
     int sblocks, seg;
     pair_scan_geometry(ncells, &sblocks, &seg);

@@ -28,6 +28,8 @@
  * Limits: groups = n1 * n2 * n3 <= AMC_CORR_MAX_GROUPS, groups * (n_lags + 1) <= AMC_CORR_MAX_CELLS.  A context's range is
  * fixed (amc_set_shard) before amc_corr_config.  Without a grid every call but amc_corr_config returns AMC_ERR_STATE, and
  * nothing is allocated or launched. */
+#ifndef ARGONMC_CORR_H
+#define ARGONMC_CORR_H
 #define AMC_CORR_MAX_GROUPS 256
 #define AMC_CORR_MAX_CELLS 65536
 typedef struct amc_corr_grid {
@@ -56,3 +58,4 @@ int amc_corr_load(amc_ctx *ctx, const int64_t *totals, int64_t n_origins, int64_
                   const double *vy0, const double *vz0);
 /* zero totals and counters, clear a pending error; the next sample is an origin */
 int amc_corr_reset(amc_ctx *ctx);
+#endif /* ARGONMC_CORR_H */

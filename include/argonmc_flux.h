@@ -21,6 +21,8 @@
  * Samples come from the cadence (`every`: the hooks of the sampled fields, a sample sees the step's final state) or from
  * amc_flux_sample.  The sampler is self-contained: it does not need the fields switched on.  amc_reset_outputs leaves it
  * alone.  Without a grid every call but amc_flux_config returns AMC_ERR_STATE, and nothing is allocated or launched. */
+#ifndef ARGONMC_FLUX_H
+#define ARGONMC_FLUX_H
 #define AMC_FLUX_MAX_BINS 1024
 typedef struct amc_flux_grid {
     int32_t struct_size;          /* sizeof(amc_flux_grid)                                                       */
@@ -43,3 +45,4 @@ int amc_flux_read(amc_ctx *ctx, int64_t *totals, int64_t *n_samples, int64_t *n_
 int amc_flux_load(amc_ctx *ctx, const int64_t *totals, int64_t n_samples, int64_t n_outside);
 /* zero totals and counters, clear a pending error */
 int amc_flux_reset(amc_ctx *ctx);
+#endif /* ARGONMC_FLUX_H */

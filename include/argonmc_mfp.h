@@ -39,6 +39,8 @@
  * energised step or run that returned AMC_ERR_CAPACITY.  While lost, amc_mfp_read returns AMC_ERR_STATE until reset, load or
  * config.  amc_reset_outputs leaves totals and counters alone.  A sharded context bins the records it emitted: owners in its
  * own index range.  Without a grid every call but amc_mfp_config returns AMC_ERR_STATE, and nothing is allocated or launched. */
+#ifndef ARGONMC_MFP_H
+#define ARGONMC_MFP_H
 #define AMC_MFP_MAX_COLUMNS 6144   /* n1 * n2 * n3 * 2 * (7 + hist_bins + 1): 48 KiB of 64-bit words, one launch's table in LDS */
 #define AMC_MFP_MAX_HIST_BINS 64
 typedef struct amc_mfp_grid {
@@ -63,3 +65,4 @@ int amc_mfp_read(amc_ctx *ctx, int64_t *totals, int64_t *hist, int64_t *n_record
 int amc_mfp_load(amc_ctx *ctx, const int64_t *totals, const int64_t *hist, int64_t n_records, int64_t n_outside, int64_t n_steps);
 /* zero totals and counters, clear a pending error or loss */
 int amc_mfp_reset(amc_ctx *ctx);
+#endif /* ARGONMC_MFP_H */

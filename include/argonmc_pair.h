@@ -34,6 +34,8 @@
  * Samples come from the cadence (`every`: the hooks of the sampled fields, a sample sees the step's final state) or from
  * amc_pair_sample.  The sampler is self-contained.  amc_reset_outputs leaves it alone.  Without a grid every call but
  * amc_pair_config returns AMC_ERR_STATE, and nothing is allocated or launched. */
+#ifndef ARGONMC_PAIR_H
+#define ARGONMC_PAIR_H
 #define AMC_PAIR_MAX_HIST_BINS 256
 #define AMC_PAIR_MAX_COLUMNS 6144   /* n1 * n2 * n3 * (1 + 2 * hist_bins): one workgroup's table of 64-bit counters, 48 KiB of LDS */
 #define AMC_PAIR_MAX_CELLS_AXIS 128 /* cells of the search box per axis                                                          */
@@ -60,3 +62,4 @@ int amc_pair_read(amc_ctx *ctx, int64_t *totals, int64_t *n_samples, int64_t *n_
 int amc_pair_load(amc_ctx *ctx, const int64_t *totals, int64_t n_samples, int64_t n_outside, int64_t n_unfiled);
 /* zero totals and counters */
 int amc_pair_reset(amc_ctx *ctx);
+#endif /* ARGONMC_PAIR_H */

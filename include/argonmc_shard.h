@@ -30,6 +30,8 @@
  *   amc_mg_hits_pack(world)        amc_temp_cases_device since amc_temp_begin, the hits view of `world`, no pack yet
  *   amc_mg_hits_sums(world, row)   amc_mg_hits_pack(world) of this step, no sums yet, row inside the run that was begun
  * amc_temp_begin, amc_upload, amc_init_synthetic and amc_set_shard abandon a pending hits exchange. */
+#ifndef ARGONMC_SHARD_H
+#define ARGONMC_SHARD_H
 int amc_mg_hits_view(amc_ctx *ctx, int world, void **send, void **recv, int64_t *block_words);
 int amc_mg_hits_pack(amc_ctx *ctx, int world);
 int amc_mg_hits_sums(amc_ctx *ctx, int world, int64_t row);
@@ -40,3 +42,4 @@ int amc_mg_hits_sums(amc_ctx *ctx, int world, int64_t row);
  * and counts n_steps; a run that lost hits marks the surfaces as amc_temp_run_device does. */
 int amc_temp_shard_run_begin(amc_ctx *ctx, int64_t nsteps);
 int amc_temp_shard_run_end(amc_ctx *ctx, int64_t nsteps, amc_step_stats *sum);
+#endif /* ARGONMC_SHARD_H */

@@ -46,6 +46,8 @@
  * Samples come from the cadence (`every`: the hooks of the sampled fields, a sample sees the step's final state) or from
  * amc_transit_sample.  Without a grid every call but amc_transit_config returns AMC_ERR_STATE, and nothing is allocated or
  * launched. */
+#ifndef ARGONMC_TRANSIT_H
+#define ARGONMC_TRANSIT_H
 #define AMC_TRANSIT_MAX_ZONES 8
 #define AMC_TRANSIT_HIST 40             /* histogram columns per exit class                                   */
 #define AMC_TRANSIT_CLASS_COLUMNS 43    /* count, sum_tau, sum_tau2, the histogram                            */
@@ -75,3 +77,4 @@ int amc_transit_state(amc_ctx *ctx, uint32_t *state, uint32_t *entry);
 int amc_transit_load(amc_ctx *ctx, const int64_t *totals, int64_t n_samples, const uint32_t *state, const uint32_t *entry);
 /* zero totals and n_samples, every particle unknown, clear a pending error */
 int amc_transit_reset(amc_ctx *ctx);
+#endif /* ARGONMC_TRANSIT_H */

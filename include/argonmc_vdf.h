@@ -26,6 +26,8 @@
  * Samples come from the cadence (`every`: the hooks of the sampled fields, a sample sees the step's final state) or from
  * amc_vdf_sample.  The sampler is self-contained.  amc_reset_outputs leaves it alone.  Without a grid every call but
  * amc_vdf_config returns AMC_ERR_STATE, and nothing is allocated or launched. */
+#ifndef ARGONMC_VDF_H
+#define ARGONMC_VDF_H
 #define AMC_VDF_MAX_HIST_BINS 256
 #define AMC_VDF_MAX_COLUMNS 24576   /* n1 * n2 * n3 * (4 * hist_bins + 8): one workgroup's table of 32-bit counters, 96 KiB of LDS */
 typedef struct amc_vdf_grid {
@@ -50,3 +52,4 @@ int amc_vdf_read(amc_ctx *ctx, int64_t *totals, int64_t *n_samples, int64_t *n_o
 int amc_vdf_load(amc_ctx *ctx, const int64_t *totals, int64_t n_samples, int64_t n_outside);
 /* zero totals and counters, clear a pending error */
 int amc_vdf_reset(amc_ctx *ctx);
+#endif /* ARGONMC_VDF_H */

@@ -220,3 +220,23 @@ def test_header_with_the_shard_entry_points_compiles_as_c_and_cxx(tmp_path, lang
     r = subprocess.run([cc, "-x", lang, std, "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(src), "-o",
                         str(tmp_path / "t.o")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
     assert r.returncode == 0, r.stdout.decode()
+
+
+PART_HEADERS = ["corr", "flux", "mfp", "vdf", "transit", "pair", "shard"]
+
+
+@pytest.mark.parametrize("lang,std", [("c", "-std=c99"), ("c++", "-std=c++11")])
+def test_every_part_header_may_follow_the_main_header(tmp_path, lang, std):
+    """argonmc.h includes its seven part headers; a caller who names one of them as well must not meet redefinitions."""
+    cc = shutil.which("cc" if lang == "c" else "c++")
+    if cc is None:
+        pytest.skip("no host compiler")
+    parts = sorted(f[len("argonmc_"):-2] for f in os.listdir(os.path.join(ROOT, "include")) if f.startswith("argonmc_") and f.endswith(".h"))
+    assert parts == sorted(PART_HEADERS), parts
+    for part in PART_HEADERS:
+        src = tmp_path / ("t_%s.%s" % (part, "c" if lang == "c" else "cpp"))
+        src.write_text('#include "argonmc.h"\n#include "argonmc_%s.h"\n#include "argonmc_%s.h"\n#include "argonmc.h"\n'
+                       "int version_(void) { return AMC_ABI_VERSION; }\n" % (part, part))
+        r = subprocess.run([cc, "-x", lang, std, "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(src), "-o",
+                            str(tmp_path / ("t_%s.o" % part))], stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+        assert r.returncode == 0, (part, r.stdout.decode())
