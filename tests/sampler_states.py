@@ -1,4 +1,4 @@
-"""States for the samplers' GPU tests (tests/test_gpu_fields.py, tests/test_gpu_corr.py): a few thousand pore particles drifting
+"""States for the samplers' GPU tests (tests/test_gpu_sampler_protocol.py, tests/sampler_protocol.py): a few thousand pore particles drifting
 freely, and index ranges that begin or end inside an aligned pair of particles."""
 from argon_monte_carlo_amd import ic as IC
 from argon_monte_carlo_amd import params as PR

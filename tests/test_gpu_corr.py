@@ -1,9 +1,8 @@
 """GPU (-m gpu): sampled correlations (include/argonmc.h "sampled correlations").  The device's integer totals must equal the
-Python-int reference (tests/corr_ref.py) on the downloaded states bit for bit, whatever the launch configuration or the way
-the steps were driven, and sampling must change nothing else."""
-import os
-import random
-
+Python-int reference (tests/corr_ref.py) on the downloaded states bit for bit, whatever the launch configuration or the way the
+steps were driven, and sampling must change nothing else.  What the correlations share with the other streaming samplers — two
+ranks, odd index ranges, sampling changes nothing else — is in tests/test_gpu_sampler_protocol.py, and the body of run(k)
+against k timesteps in tests/sampler_protocol.py."""
 import numpy as np
 import pytest
 
@@ -12,40 +11,14 @@ from argon_monte_carlo_amd import fields as FL
 from argon_monte_carlo_amd import ic as IC
 from argon_monte_carlo_amd import params as PR
 from tests import corr_ref as REF
-from tests.sampler_states import ODD_N, ODD_SHARDS, drifting_states
+from tests import sampler_protocol as SP
+from tests.sampler_protocol import KEYS, N
+from tests.sampler_protocol import CorrMirror as Window
+from tests.sampler_protocol import make_sim as _sim
 
 pytestmark = pytest.mark.gpu
 
-KEYS = ["x", "y", "z", "vx", "vy", "vz", "d", "dx", "dy", "dz", "flag"]
-N = 20_011                              # odd: the unpaired tail; three workgroups
-
-
-def _sim(kind, n, seed=11):
-    from argon_monte_carlo_amd.sim import Simulation
-    sim = Simulation(kind, n=n)
-    gen = IC.cube_ic if kind == "cube" else IC.pore_ic
-    sim.set_state(*gen(sim.params, sim.consts, seed))
-    return sim
-
-
-def _grid(kind, params, which, n_lags):
-    if which == "default":
-        return CO.default_grid(params, n_lags=n_lags)
-    if which == "one":
-        if kind == "cube":
-            return CO.make_grid("cartesian", (1, 1, 1), (0, 0, 0), (params.cube_x, params.cube_y, params.cube_z), n_lags=n_lags)
-        return CO.make_grid("axisymmetric", (1, 1), (0, 0), (params.R_oa, params.H), n_lags=n_lags)
-    assert which == "444" and kind == "cube"
-    return CO.make_grid("cartesian", (4, 4, 4), (0, 0, 0), (params.cube_x, params.cube_y, params.cube_z), n_lags=n_lags)
-
-
-def _check(engine, win):
-    """The engine's totals and counters equal the reference window's; returns the totals."""
-    tot, counters = engine.corr_read()
-    assert counters == win.counters(), (counters, win.counters())
-    ref = win.words()
-    assert np.array_equal(tot, ref), np.argwhere(tot != ref)[:5]
-    return tot
+_grid = SP.CORRELATIONS.grids
 
 
 # ---- 1. the totals equal the reference on the downloaded states ----------------------------------------------------------
@@ -56,14 +29,14 @@ def test_totals_equal_reference_after_timesteps(kind, which, n, blocks, monkeypa
         monkeypatch.setenv("AMC_CORR_BLOCKS", blocks)
     sim = _sim(kind, n)
     sim.enable_correlations(_grid(kind, sim.params, which, 3))
-    win = REF.Window(sim.engine.corr_grid)
+    win = Window(sim.engine.corr_grid)
     sim.correlations_sample()           # straight after the upload: the first origin
-    win.add(REF.state6(sim.engine.download()))
+    win.add_state(sim.engine.download())
     for _ in range(7):                  # lags 1, 2, 3 + origin, 1, 2, 3 + origin, 1: two turnovers, the end mid-window
         sim.timestep()
         sim.correlations_sample()       # the cube's sweep results are still deferred here: read through the slot arrays
-        win.add(REF.state6(sim.engine.download()))
-    tot = CO.words_to_ints(_check(sim.engine, win))
+        win.add_state(sim.engine.download())
+    tot = CO.words_to_ints(win.check(sim.engine))
     assert win.counters()[0] == 3 and win.counters()[3] == 2
     assert sum(int(v) for v in tot[:, 0, 0]) + win.n_outside == 3 * n           # counts plus outside, per origin
     assert any(int(v) != 0 for v in tot[:, 3, 1]) and any(int(v) != 0 for v in tot[:, 1, 4])
@@ -74,56 +47,7 @@ def test_totals_equal_reference_after_timesteps(kind, which, n, blocks, monkeypa
 @pytest.mark.parametrize("kind,overlap,blocks", [("cube", None, None), ("pore", None, None), ("cube", "1", None), ("pore", "1", None),
                                                  ("cube", None, "1"), ("pore", None, "1"), ("cube", None, "7"), ("pore", None, "7")])
 def test_run_equals_timesteps_and_reference(kind, overlap, blocks, monkeypatch):
-    steps, every = 7, 2
-    ref_sim = _sim(kind, N)
-    ref_sim.enable_correlations(every=every, n_lags=2)
-    win = REF.Window(ref_sim.engine.corr_grid)
-    for s in range(1, steps + 1):
-        ref_sim.timestep()
-        if s % every == 0:              # steps 2 (origin), 4 (lag 1), 6 (lag 2 + origin)
-            win.add(REF.state6(ref_sim.engine.download()))
-    ref_tot = _check(ref_sim.engine, win)
-    ref_state = ref_sim.engine.download()
-    ref_sim.close()
-    if overlap is not None:
-        monkeypatch.setenv("AMC_OVERLAP", overlap)
-    if blocks is not None:
-        monkeypatch.setenv("AMC_CORR_BLOCKS", blocks)
-    sim = _sim(kind, N)
-    sim.enable_correlations(every=every, n_lags=2)
-    sim.run(steps)
-    tot, counters = sim.engine.corr_read()
-    assert counters == win.counters() == (2, 3, win.n_outside, 1)
-    assert np.array_equal(tot, ref_tot)
-    st = sim.engine.download()
-    for k in KEYS:
-        assert np.array_equal(st[k], ref_state[k]), k
-    sim.close()
-
-
-# ---- 3. sampling changes nothing else -----------------------------------------------------------------------------------
-def test_sampling_leaves_state_counters_histograms_and_paths_unchanged():
-    out = []
-    for on in (False, True):
-        sim = _sim("pore", N, seed=5)
-        if on:
-            sim.enable_correlations(every=2, n_lags=3)
-        stats = [sim.run(10)]
-        sim._collect()
-        for _ in range(10):
-            stats.append(sim.timestep())
-        st = sim.engine.download()
-        counts, npaths = sim.engine.histograms()
-        out.append((st, stats, counts, npaths, list(sim.completed_paths), list(sim.completed_x_paths)))
-        if on:
-            assert sim.engine.corr_read()[1][:2] == (4, 10)         # steps 2, 4, ... 20: origins at 2, 8, 14, 20
-        sim.close()
-    (a, sa, ca, na, pa, pxa), (b, sb, cb, nb, pb, pxb) = out
-    for k in KEYS:
-        assert np.array_equal(a[k], b[k]), k
-    assert sa == sb
-    assert na == nb and np.array_equal(ca, cb)
-    assert len(pa) > 0 and pa == pb and pxa == pxb
+    SP.check_run(SP.CORRELATIONS, monkeypatch, kind, None, overlap, blocks)
 
 
 # ---- 4. together with the fields: one "any sampler due" predicate ------------------------------------------------------------
@@ -279,81 +203,16 @@ def test_checkpoint_without_correlations_loads_with_sampling_off(tmp_path):
 
 
 # ---- 9. energised pore: host-RNG and device-RNG steps --------------------------------------------------------------------------
-def _temp_sim(device_rng):
-    from argon_monte_carlo_amd.sim import TemperatureSimulation
-    p, c = PR.pore_params(n=20_000, energised=True)
-    sim = TemperatureSimulation(params=p, consts=c, np_rng=np.random.RandomState(3), py_rng=random.Random(3),
-                                device_rng_seed=(7 if device_rng else None))
-    sim.set_state(*IC.pore_ic(p, c, 13))
-    sim.enable_correlations(every=1, n_lags=2)
-    return sim
-
-
 @pytest.mark.parametrize("device_rng", [False, True])
 def test_energised_pore_totals_equal_reference(device_rng):
-    sim = _temp_sim(device_rng)
-    win = REF.Window(sim.engine.corr_grid)
-    for _ in range(4):                  # origin, lag 1, lag 2 + origin, lag 1
-        sim.timestep()
-        win.add(REF.state6(sim.engine.download()))
-    tot = _check(sim.engine, win)
+    sim, win, tot = SP.energised_totals(SP.CORRELATIONS, device_rng, every=1, n_lags=2)     # origin, lag 1, lag 2 + origin, lag 1
     assert win.counters()[:2] == (2, 4) and tot[:, 1:, 1:4].any()
     f = sim.correlations()
     assert np.isfinite(f["msd"][f["count"] > 0]).all()
-    state = sim.engine.download()
+    read, state = sim.engine.corr_read(), sim.engine.download()
     sim.close()
     if device_rng:                      # the host-free run takes the same samples as four single steps
-        run = _temp_sim(True)
-        run.run(4)
-        tot_run, cnt_run = run.engine.corr_read()
-        assert cnt_run == win.counters() and np.array_equal(tot_run, tot)
-        st = run.engine.download()
-        for k in KEYS:
-            assert np.array_equal(st[k], state[k]), k
-        run.close()
-
-
-# ---- 10. two ranks on one GPU ---------------------------------------------------------------------------------------------------
-def _corr_worker(rank, world, port, kind, n, steps, every, q):
-    import torch.distributed as dist
-    try:
-        os.environ["MASTER_ADDR"] = "127.0.0.1"
-        os.environ["MASTER_PORT"] = str(port)
-        dist.init_process_group("gloo", rank=rank, world_size=world)
-        try:
-            from argon_monte_carlo_amd.dist import ShardedSimulation
-            from tests.test_gpu_dist import _case
-            p, c, init = _case(kind, n)
-            sim = ShardedSimulation(p, rank, world, backend="gloo")
-            sim.upload(*init)
-            sim.enable_correlations(every=every, n_lags=2)
-            sim.run(c["dt"], steps)
-            f = sim.correlations(dt=c["dt"])
-            if rank == 0:
-                q.put(("ok", (f["totals"], (f["n_origins"], f["n_samples"], f["n_outside"], f["window_pos"]))))
-        finally:
-            dist.destroy_process_group()
-    except BaseException as e:
-        import traceback
-        q.put(("error", f"rank {rank}: {e!r}\n{traceback.format_exc()}"))
-        raise
-
-
-@pytest.mark.parametrize("kind,n", [("cube", 30_000), ("pore", 60_001)])
-def test_two_ranks_on_one_gpu_equal_single_engine(kind, n):
-    from argon_monte_carlo_amd.engine import Engine
-    from tests.test_gpu_dist import _case, _run_ranks
-    steps, every = 6, 2
-    p, c, init = _case(kind, n)
-    eng = Engine(p)
-    eng.upload(*init)
-    eng.corr_config(CO.default_grid(p, every=every, n_lags=2))
-    eng.run(c["dt"], steps)
-    ref_tot, ref_cnt = eng.corr_read()
-    eng.close()
-    tot, cnt = _run_ranks(2, (kind, n, steps, every), target=_corr_worker)
-    assert tuple(cnt) == ref_cnt and ref_cnt[:2] == (2, 3) and ref_cnt[3] == 1
-    assert np.array_equal(tot, ref_tot) and ref_tot[:, 2].any()
+        SP.host_free_run(SP.CORRELATIONS, read, state, every=1, n_lags=2)
 
 
 # ---- 11. physics, derivable ------------------------------------------------------------------------------------------------------
@@ -370,28 +229,6 @@ def test_maxwell_initial_condition_reads_back_the_velocity_variance():
         assert abs(f["vacf"][0, 0, k] - a2) < 4 * sigma, (k, f["vacf"][0, 0, k], a2, sigma)
         assert f["msd"][0, 0, k] == 0.0
     sim.close()
-
-
-# ---- 12. the walk's odd ends, in all three modes of the accumulate kernel --------------------------------------------------------
-@pytest.mark.parametrize("lo,hi", ODD_SHARDS)
-def test_index_range_with_odd_ends_equals_reference(lo, hi):
-    """An index range that begins or ends inside an aligned pair (lo odd / hi odd: the first / the last particle has no partner),
-    n_lags = 2 and four samples: an origin, a lag, the lag-and-origin pass, a lag.  The origin arrays outside [lo, hi) stay zero."""
-    from argon_monte_carlo_amd.engine import ShardEngine
-    p, states = drifting_states(ODD_N, 4)
-    eng = ShardEngine(p, lo, hi)
-    eng.corr_config(CO.default_grid(p, n_lags=2))
-    win = REF.Window(eng.corr_grid)
-    for st in states:
-        eng.upload(*st)
-        eng.corr_sample()
-        win.add(tuple(a[lo:hi].copy() for a in st))
-    tot = CO.words_to_ints(_check(eng, win))
-    assert win.counters() == (2, 4, win.n_outside, 2)
-    assert all(any(int(v) != 0 for v in tot[:, lag, 1]) for lag in (1, 2))           # both lags saw displacements
-    origin = eng.corr_origin()
-    assert all(np.array_equal(o, a[lo:hi]) for o, a in zip(origin, states[2]))      # the origin stored by the third sample
-    eng.close()
 
 
 # ---- 13. the carry-add through the correlations' loads ------------------------------------------------------------------------------

@@ -1,61 +1,21 @@
 """GPU (-m gpu): sampled fields (include/argonmc.h "sampled fields").  The device's integer totals must equal the NumPy
 reference (tests/fields_ref.py) on the downloaded state bit for bit, whatever the launch configuration or the way the steps
-were driven, and sampling must change nothing else."""
-import os
-import random
-
+were driven, and sampling must change nothing else.  What the fields share with the other streaming samplers — run against
+timesteps (the body), two ranks, odd index ranges, the reduce's shapes — is in tests/sampler_protocol.py and
+tests/test_gpu_sampler_protocol.py."""
 import numpy as np
 import pytest
 
 from argon_monte_carlo_amd import fields as FL
 from argon_monte_carlo_amd import ic as IC
 from argon_monte_carlo_amd import params as PR
-from tests import fields_ref as REF
-from tests.sampler_states import ODD_N, ODD_SHARDS, drifting_states
+from tests import sampler_protocol as SP
+from tests.sampler_protocol import FieldsMirror as _Acc
+from tests.sampler_protocol import make_sim as _sim
 
 pytestmark = pytest.mark.gpu
 
-KEYS = ["x", "y", "z", "vx", "vy", "vz", "d", "dx", "dy", "dz", "flag"]
-
-
-def _sim(kind, n, seed=11):
-    from argon_monte_carlo_amd.sim import Simulation
-    sim = Simulation(kind, n=n)
-    gen = IC.cube_ic if kind == "cube" else IC.pore_ic
-    sim.set_state(*gen(sim.params, sim.consts, seed))
-    return sim
-
-
-def _grid(kind, params, which):
-    if which == "default":
-        return FL.default_grid(params)
-    if which == "one":
-        if kind == "cube":
-            return FL.make_grid("cartesian", (1, 1, 1), (0, 0, 0), (params.cube_x, params.cube_y, params.cube_z))
-        return FL.make_grid("axisymmetric", (1, 1), (0, 0), (params.R_oa, params.H))
-    assert which == "cart"          # a Cartesian grid in the pore, over its bounding box
-    return FL.make_grid("cartesian", (6, 6, 40), (-params.R_oa, -params.R_oa, 0.0), (params.R_oa, params.R_oa, params.H))
-
-
-class _Acc:
-    """Reference totals accumulated sample by sample (exact Python ints)."""
-
-    def __init__(self, g):
-        self.g, self.sums, self.outside, self.samples = g, np.zeros((FL.grid_bins(g), 7), dtype=object), 0, 0
-        self.sums[:] = 0
-
-    def add(self, st, lo=0, hi=None):
-        s, o = REF.sample_state(self.g, st, lo, hi)
-        self.sums = self.sums + s
-        self.outside += o
-        self.samples += 1
-
-    def check(self, engine):
-        tot, ns, no = engine.fields_read()
-        assert ns == self.samples and no == self.outside, (ns, self.samples, no, self.outside)
-        ref = FL.ints_to_words(self.sums)
-        assert np.array_equal(tot, ref), np.argwhere(tot != ref)[:5]
-        return tot
+_grid = SP.FIELDS.grids
 
 
 # ---- 1. the totals equal the reference on the downloaded state -----------------------------------------------------------
@@ -66,74 +26,24 @@ def test_totals_equal_reference_after_timesteps(kind, which):
     sim.enable_fields(g)
     acc = _Acc(sim.engine.field_grid)
     sim.fields_sample()                  # straight after the upload
-    acc.add(sim.engine.download())
+    acc.add_state(sim.engine.download())
     for _ in range(3):
         sim.timestep()
         sim.fields_sample()              # the cube's sweep results are still deferred here: read through the slot arrays
-        acc.add(sim.engine.download())
+        acc.add_state(sim.engine.download())
     acc.check(sim.engine)
     assert acc.sums[:, 0].sum() + acc.outside == 4 * 100_003
     sim.close()
 
 
-# ---- 2. sampling changes nothing else -------------------------------------------------------------------------------------
-def test_sampling_leaves_state_counters_histograms_and_paths_unchanged():
-    out = []
-    for on in (False, True):
-        sim = _sim("pore", 50_000, seed=5)
-        if on:
-            sim.enable_fields(every=3)
-        stats = [sim.run(10)]
-        sim._collect()
-        for _ in range(10):
-            stats.append(sim.timestep())
-        st = sim.engine.download()
-        counts, npaths = sim.engine.histograms()
-        out.append((st, stats, counts, npaths, list(sim.completed_paths), list(sim.completed_x_paths)))
-        if on:
-            assert sim.engine.fields_read()[1] == 6           # steps 3, 6, 9 (inside run) and 12, 15, 18
-        sim.close()
-    (a, sa, ca, na, pa, pxa), (b, sb, cb, nb, pb, pxb) = out
-    for k in KEYS:
-        assert np.array_equal(a[k], b[k]), k
-    assert sa == sb
-    assert na == nb and np.array_equal(ca, cb)
-    assert len(pa) > 0 and pa == pb and pxa == pxb
-
-
-# ---- 3. run vs timestep, overlapped runs, any number of workgroups -----------------------------------------------------------
+# ---- 2. run vs timestep, overlapped runs, any number of workgroups -----------------------------------------------------------
 @pytest.mark.parametrize("kind,overlap,blocks", [("cube", None, None), ("pore", None, None), ("cube", "1", None), ("pore", "1", None),
                                                  ("pore", None, "1"), ("cube", None, "7"), ("pore", None, "7")])
 def test_run_equals_timesteps_and_reference(kind, overlap, blocks, monkeypatch):
-    n, steps, every = 100_003, 7, 2
-    # stepwise, with the reference on the downloaded state of every sampled step
-    ref_sim = _sim(kind, n)
-    ref_sim.enable_fields(every=every)
-    acc = _Acc(ref_sim.engine.field_grid)
-    for s in range(1, steps + 1):
-        ref_sim.timestep()
-        if s % every == 0:
-            acc.add(ref_sim.engine.download())
-    ref_tot = acc.check(ref_sim.engine)
-    ref_state = ref_sim.engine.download()
-    ref_sim.close()
-    if overlap is not None:
-        monkeypatch.setenv("AMC_OVERLAP", overlap)
-    if blocks is not None:
-        monkeypatch.setenv("AMC_FIELDS_BLOCKS", blocks)
-    sim = _sim(kind, n)
-    sim.enable_fields(every=every)
-    sim.run(steps)
-    tot, ns, no = sim.engine.fields_read()
-    assert ns == steps // every and no == acc.outside
-    assert np.array_equal(tot, ref_tot)
-    st = sim.engine.download()
-    for k in KEYS:
-        assert np.array_equal(st[k], ref_state[k]), k
-    sim.close()
+    SP.check_run(SP.FIELDS, monkeypatch, kind, None, overlap, blocks)
 
 
-# ---- 4. physics ---------------------------------------------------------------------------------------------------------------
+# ---- 3. physics ---------------------------------------------------------------------------------------------------------------
 def test_maxwell_initial_condition_reads_back_ambient_temperature():
     n = 100_000
     sim = _sim("cube", n, seed=3)
@@ -174,7 +84,7 @@ def test_specular_cube_conserves_the_sampled_kinetic_energy():
     sim.close()
 
 
-# ---- 5. the quantisation range is checked, not wrapped ------------------------------------------------------------------------
+# ---- 4. the quantisation range is checked, not wrapped ------------------------------------------------------------------------
 def test_velocity_out_of_range_is_reported_not_summed():
     from argon_monte_carlo_amd._lib import ArgonMCError
     from argon_monte_carlo_amd.sim import Simulation
@@ -195,139 +105,18 @@ def test_velocity_out_of_range_is_reported_not_summed():
     sim.close()
 
 
-# ---- 6. checkpoints ------------------------------------------------------------------------------------------------------------
+# ---- 5. checkpoints ------------------------------------------------------------------------------------------------------------
 def test_checkpoint_resume_gives_the_same_totals(tmp_path):
-    from argon_monte_carlo_amd.sim import Simulation
-    ref = _sim("pore", 50_000, seed=4)
-    ref.enable_fields(every=3)
-    ref.run(7)
-    ref.run(8)
-    ref_tot = ref.engine.fields_read()
-    ref.close()
-    a = _sim("pore", 50_000, seed=4)
-    a.enable_fields(every=3)
-    a.run(7)
     ck = str(tmp_path / "ck.npz")
-    a.save_checkpoint(ck)
-    a.close()
-    b = Simulation("pore", n=50_000)
-    b.load_checkpoint(ck)               # restores the grid, the totals and the cadence (steps 9, 12, 15 still to come)
-    b.run(8)
-    tot = b.engine.fields_read()
-    assert tot[1] == ref_tot[1] == 5 and tot[2] == ref_tot[2]
-    assert np.array_equal(tot[0], ref_tot[0])
-    b.close()
+    ref_tot = SP.uninterrupted(SP.FIELDS, 50_000)
+    SP.checkpointed(SP.FIELDS, 50_000, ck).close()
+    SP.resumed(SP.FIELDS, 50_000, ck, ref_tot)
 
 
-# ---- 7. energised pore: host-RNG and device-RNG steps --------------------------------------------------------------------------
+# ---- 6. energised pore: host-RNG and device-RNG steps --------------------------------------------------------------------------
 @pytest.mark.parametrize("device_rng", [False, True])
 def test_energised_pore_totals_equal_reference(device_rng):
-    from argon_monte_carlo_amd.sim import TemperatureSimulation
-    p, c = PR.pore_params(n=20_000, energised=True)
-    sim = TemperatureSimulation(params=p, consts=c, np_rng=np.random.RandomState(3), py_rng=random.Random(3),
-                                device_rng_seed=(7 if device_rng else None))
-    sim.set_state(*IC.pore_ic(p, c, 13))
-    sim.enable_fields(every=2)
-    acc = _Acc(sim.engine.field_grid)
-    for s in range(1, 5):
-        sim.timestep()
-        if s % 2 == 0:
-            acc.add(sim.engine.download())
-    acc.check(sim.engine)
+    sim, acc, tot = SP.energised_totals(SP.FIELDS, device_rng, every=2)
     f = sim.fields()
     assert np.isfinite(f["T"][f["count"] >= 2]).all()
     sim.close()
-
-
-# ---- 8. two ranks on one GPU ----------------------------------------------------------------------------------------------------
-def _fields_worker(rank, world, port, kind, n, steps, every, q):
-    import torch.distributed as dist
-    try:
-        os.environ["MASTER_ADDR"] = "127.0.0.1"
-        os.environ["MASTER_PORT"] = str(port)
-        dist.init_process_group("gloo", rank=rank, world_size=world)
-        try:
-            from argon_monte_carlo_amd.dist import ShardedSimulation
-            from tests.test_gpu_dist import _case
-            p, c, init = _case(kind, n)
-            sim = ShardedSimulation(p, rank, world, backend="gloo")
-            sim.upload(*init)
-            sim.enable_fields(every=every)
-            sim.run(c["dt"], steps)
-            f = sim.fields()
-            if rank == 0:
-                q.put(("ok", (f["totals"], f["n_samples"], f["n_outside"])))
-        finally:
-            dist.destroy_process_group()
-    except BaseException as e:
-        import traceback
-        q.put(("error", f"rank {rank}: {e!r}\n{traceback.format_exc()}"))
-        raise
-
-
-@pytest.mark.parametrize("kind,n", [("cube", 30_000), ("pore", 60_001)])
-def test_two_ranks_on_one_gpu_equal_single_engine(kind, n):
-    from argon_monte_carlo_amd.engine import Engine
-    from tests.test_gpu_dist import _case, _run_ranks
-    steps, every = 6, 2
-    p, c, init = _case(kind, n)
-    eng = Engine(p)
-    eng.upload(*init)
-    eng.fields_config(FL.default_grid(p, every=every))
-    eng.run(c["dt"], steps)
-    ref = eng.fields_read()
-    eng.close()
-    tot, ns, no = _run_ranks(2, (kind, n, steps, every), target=_fields_worker)
-    assert ns == ref[1] == steps // every and no == ref[2]
-    assert np.array_equal(tot, ref[0])
-
-
-# ---- 9. the walk's odd ends: an index range that begins or ends inside an aligned pair ------------------------------------------
-@pytest.mark.parametrize("lo,hi", ODD_SHARDS)
-def test_index_range_with_odd_ends_equals_reference(lo, hi):
-    from argon_monte_carlo_amd.engine import ShardEngine
-    p, states = drifting_states(ODD_N, 4)
-    eng = ShardEngine(p, lo, hi)
-    eng.fields_config(FL.default_grid(p))
-    acc = _Acc(eng.field_grid)
-    for st in states:
-        eng.upload(*st)
-        eng.fields_sample()
-        acc.add(dict(zip(("x", "y", "z", "vx", "vy", "vz"), st)), lo, hi)
-    acc.check(eng)
-    assert acc.sums[:, 0].sum() + acc.outside == 4 * (hi - lo)
-    eng.close()
-
-
-# ---- 10. the shape of the shared reduce: exactly one workgroup of 64 columns and a little more, rows around its sixteen waves ----
-_REDUCE_REF = {}
-
-
-def _reduce_case(bins):
-    """(params, grid of ``bins`` bins over the lower half of the pore's box, state, reference sums, outside), computed once"""
-    if bins not in _REDUCE_REF:
-        p, (st,) = drifting_states(ODD_N, 1, seed=29)
-        n3 = {9: (3, 3, 1), 10: (5, 2, 1)}[bins]
-        g = FL.make_grid("cartesian", n3, (-p.R_oa, -p.R_oa, 0.0), (p.R_oa, p.R_oa, 0.5 * p.H))
-        _REDUCE_REF[bins] = (p, g, st) + REF.sample(g, *st)
-    return _REDUCE_REF[bins]
-
-
-@pytest.mark.parametrize("blocks", ["1", "17", "33"])
-@pytest.mark.parametrize("bins", [9, 10])
-def test_reduce_shapes_equal_reference(bins, blocks, monkeypatch):
-    """9 bins: 9 * 7 sums + the outside column = 64 columns, one full workgroup of the reduce; 10 bins: 71, a second one with
-    seven live lanes.  1, 17 and 33 slab rows: below, one above and two above a multiple of the reduce's sixteen waves."""
-    from argon_monte_carlo_amd.engine import Engine
-    p, g, st, sums, outside = _reduce_case(bins)
-    assert FL.grid_bins(g) == bins and outside > 0 and (sums[:, 0] > 0).all()
-    monkeypatch.setenv("AMC_FIELDS_BLOCKS", blocks)
-    eng = Engine(p)
-    eng.upload(*st)
-    eng.fields_config(g)
-    for k in (1, 2):                    # (the second sample adds onto non-zero totals)
-        eng.fields_sample()
-        tot, ns, no = eng.fields_read()
-        assert ns == k and no == k * outside
-        assert np.array_equal(tot, FL.ints_to_words(k * sums)), np.argwhere(tot != FL.ints_to_words(k * sums))[:5]
-    eng.close()

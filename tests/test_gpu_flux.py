@@ -1,8 +1,8 @@
 """GPU (-m gpu): sampled fluxes (include/argonmc_flux.h).  The device's integer totals must equal the NumPy + Python-int
 reference (tests/flux_ref.py) on the downloaded states bit for bit, whatever the launch configuration or the way the steps were
-driven, and sampling must change nothing else."""
-import os
-import random
+driven, and sampling must change nothing else.  What the fluxes share with the other streaming samplers — two ranks, odd index
+ranges, sampling changes nothing else — is in tests/test_gpu_sampler_protocol.py, and the body of run(k) against k timesteps in
+tests/sampler_protocol.py."""
 from fractions import Fraction
 
 import numpy as np
@@ -13,41 +13,14 @@ from argon_monte_carlo_amd import fluxes as FX
 from argon_monte_carlo_amd import ic as IC
 from argon_monte_carlo_amd import params as PR
 from tests import fields_ref as FREF
-from tests import flux_ref as REF
-from tests.sampler_states import ODD_N, ODD_SHARDS, drifting_states
+from tests import sampler_protocol as SP
+from tests.sampler_protocol import N
+from tests.sampler_protocol import FluxMirror as Totals
+from tests.sampler_protocol import make_sim as _sim
 
 pytestmark = pytest.mark.gpu
 
-KEYS = ["x", "y", "z", "vx", "vy", "vz", "d", "dx", "dy", "dz", "flag"]
-N = 20_011                              # odd: the unpaired tail; three workgroups
-
-
-def _sim(kind, n, seed=11):
-    from argon_monte_carlo_amd.sim import Simulation
-    sim = Simulation(kind, n=n)
-    gen = IC.cube_ic if kind == "cube" else IC.pore_ic
-    sim.set_state(*gen(sim.params, sim.consts, seed))
-    return sim
-
-
-def _grid(kind, p, which):
-    if which == "default":
-        return FX.default_grid(p)
-    if which == "cart":                 # a Cartesian grid in the pore, over its bounding box
-        return FX.make_grid("cartesian", (5, 5, 40), (-p.R_oa, -p.R_oa, 0.0), (p.R_oa, p.R_oa, p.H))
-    n3 = {"one": (1, 1, 1), "1024": (16, 8, 8), "9": (9, 1, 1), "10": (5, 2, 1)}[which]
-    if kind == "cube":
-        return FX.make_grid("cartesian", n3, (0, 0, 0), (p.cube_x, p.cube_y, p.cube_z))
-    return FX.make_grid("axisymmetric", (n3[1] * n3[2], n3[0]), (0, 0), (p.R_oa, p.H))
-
-
-def _check(engine, ref):
-    """The engine's totals and counters equal the reference's; returns the totals."""
-    tot, ns, no = engine.flux_read()
-    assert (ns, no) == (ref.n_samples, ref.n_outside), (ns, no, ref.n_samples, ref.n_outside)
-    want = ref.words()
-    assert tot.shape == want.shape and np.array_equal(tot, want), np.argwhere(tot != want)[:5]
-    return tot
+_grid = SP.FLUXES.grids
 
 
 # ---- 1. the totals equal the reference on the downloaded states -----------------------------------------------------------
@@ -59,14 +32,14 @@ def test_totals_equal_reference_after_timesteps(kind, n, which):
     g = sim.engine.flux_grid
     if which == "1024" or (kind, which) == ("pore", "default"):
         assert FX.grid_bins(g) == 1024  # the whole table in LDS
-    ref = REF.Totals(g)
+    ref = Totals(g)
     sim.fluxes_sample()                 # straight after the upload
     ref.add_state(sim.engine.download())
     for _ in range(3):
         sim.timestep()
         sim.fluxes_sample()             # the cube's sweep results are still deferred here: read through the slot arrays
         ref.add_state(sim.engine.download())
-    tot = FX.words_to_ints(_check(sim.engine, ref))
+    tot = FX.words_to_ints(ref.check(sim.engine))
     assert sum(int(v) for v in tot[:, 0, 0]) + ref.n_outside == 4 * n
     assert not any(int(v) for v in tot[:, 1, 0])                            # the reserved slot is never added to
     assert any(int(v) for v in tot[:, 1, 1]) and any(int(v) for v in tot[:, 1, 6])
@@ -77,27 +50,6 @@ def test_totals_equal_reference_after_timesteps(kind, n, which):
 
 
 # ---- 2. run(k) equals k timesteps, for any number of workgroups and in an overlapped run -----------------------------------
-_RUN_REF = {}
-STEPS, EVERY = 7, 2
-
-
-def _run_reference(kind, which):
-    """timesteps + fluxes_sample against the reference, once per (geometry, grid): (totals, counters, final state)"""
-    if (kind, which) not in _RUN_REF:
-        sim = _sim(kind, N)
-        sim.enable_fluxes(_grid(kind, sim.params, which))
-        ref = REF.Totals(sim.engine.flux_grid)
-        for s in range(1, STEPS + 1):
-            sim.timestep()
-            if s % EVERY == 0:
-                sim.fluxes_sample()
-                ref.add_state(sim.engine.download())
-        tot = _check(sim.engine, ref)
-        _RUN_REF[(kind, which)] = (tot, (ref.n_samples, ref.n_outside), sim.engine.download())
-        sim.close()
-    return _RUN_REF[(kind, which)]
-
-
 @pytest.mark.parametrize("kind,which,overlap,blocks", [
     ("cube", "default", None, None), ("pore", "default", None, None), ("cube", "default", "1", None), ("pore", "default", "1", None),
     ("cube", "9", None, "1"), ("pore", "9", None, "17"), ("cube", "9", None, "33"),
@@ -105,21 +57,7 @@ def _run_reference(kind, which):
 def test_run_equals_timesteps_and_reference(kind, which, overlap, blocks, monkeypatch):
     """9 bins: 2 * 63 sums + the outside column = 127 columns, one lane short of two workgroups of the reduce; 10 bins: 141, a
     third one with thirteen live lanes.  1, 17 and 33 slab rows: below, one above and two above a multiple of its sixteen waves."""
-    ref_tot, ref_cnt, ref_state = _run_reference(kind, which)
-    if overlap is not None:
-        monkeypatch.setenv("AMC_OVERLAP", overlap)
-    if blocks is not None:
-        monkeypatch.setenv("AMC_FLUX_BLOCKS", blocks)
-    sim = _sim(kind, N)
-    sim.enable_fluxes(_grid(kind, sim.params, which), every=EVERY)
-    sim.run(STEPS)
-    tot, ns, no = sim.engine.flux_read()
-    assert (ns, no) == ref_cnt and ns == STEPS // EVERY
-    assert np.array_equal(tot, ref_tot), np.argwhere(tot != ref_tot)[:5]
-    st = sim.engine.download()
-    for k in KEYS:
-        assert np.array_equal(st[k], ref_state[k]), k
-    sim.close()
+    SP.check_run(SP.FLUXES, monkeypatch, kind, which, overlap, blocks)
 
 
 # ---- 3. row A against the fields ---------------------------------------------------------------------------------------------
@@ -135,23 +73,6 @@ def test_row_a_equals_the_fields_totals(kind):
     assert (ns, no) == (f_ns, f_no) and ns == 3
     assert np.array_equal(tot[:, 0], f_tot) and f_tot.any() and tot[:, 1, 1:].any() and not tot[:, 1, 0].any()
     sim.close()
-
-
-# ---- 4. the walk's odd ends: an index range that begins or ends inside an aligned pair ------------------------------------------
-@pytest.mark.parametrize("lo,hi", ODD_SHARDS)
-def test_index_range_with_odd_ends_equals_reference(lo, hi):
-    from argon_monte_carlo_amd.engine import ShardEngine
-    p, states = drifting_states(ODD_N, 3)
-    eng = ShardEngine(p, lo, hi)
-    eng.flux_config(FX.default_grid(p))
-    ref = REF.Totals(eng.flux_grid)
-    for st in states:
-        eng.upload(*st)
-        eng.flux_sample()
-        ref.add(*(a[lo:hi] for a in st))
-    tot = FX.words_to_ints(_check(eng, ref))
-    assert sum(int(v) for v in tot[:, 0, 0]) + ref.n_outside == 3 * (hi - lo)
-    eng.close()
 
 
 # ---- 5. a crafted state with a closed form -------------------------------------------------------------------------------------
@@ -211,9 +132,9 @@ def test_range_edge_is_reported_with_its_index_and_the_value_below_is_summed():
     vx[601] = vy[601] = top
     sim.set_state(x, y, z, vx, vy, vz)
     sim.fluxes_sample()
-    ref = REF.Totals(sim.engine.flux_grid)
+    ref = Totals(sim.engine.flux_grid)
     ref.add(x, y, z, vx, vy, vz)
-    tot = FX.words_to_ints(_check(sim.engine, ref))
+    tot = FX.words_to_ints(ref.check(sim.engine))
     assert max(abs(int(v)) for v in tot[:, 1, 4:].ravel()) >= 2 ** 37
     sim.close()
 
@@ -241,56 +162,17 @@ def test_calls_before_a_config_return_state_errors():
     sim.close()
 
 
-# ---- 7. sampling changes nothing else ------------------------------------------------------------------------------------------
-def test_sampling_leaves_state_counters_histograms_and_paths_unchanged():
-    out = []
-    for on in (False, True):
-        sim = _sim("pore", N, seed=5)
-        if on:
-            sim.enable_fluxes(every=2)
-        stats = [sim.run(10)]
-        sim._collect()
-        for _ in range(10):
-            stats.append(sim.timestep())
-        st = sim.engine.download()
-        counts, npaths = sim.engine.histograms()
-        out.append((st, stats, counts, npaths, list(sim.completed_paths), list(sim.completed_x_paths)))
-        if on:
-            assert sim.engine.flux_read()[1] == 10
-        sim.close()
-    (a, sa, ca, na, pa, pxa), (b, sb, cb, nb, pb, pxb) = out
-    for k in KEYS:
-        assert np.array_equal(a[k], b[k]), k
-    assert sa == sb
-    assert na == nb and np.array_equal(ca, cb)
-    assert len(pa) > 0 and pa == pb and pxa == pxb
-
-
 # ---- 8. checkpoints ------------------------------------------------------------------------------------------------------------
 def test_checkpoint_resume_gives_the_same_totals(tmp_path):
-    from argon_monte_carlo_amd.sim import Simulation
-    ref = _sim("pore", 20_000, seed=4)
-    ref.enable_fluxes(every=3)
-    ref.run(7)
-    ref.run(8)
-    ref_tot = ref.engine.flux_read()
-    ref.close()
-    a = _sim("pore", 20_000, seed=4)
-    a.enable_fluxes(every=3)
-    a.run(7)
     ck = str(tmp_path / "ck.npz")
-    a.save_checkpoint(ck)
+    ref_tot = SP.uninterrupted(SP.FLUXES, 20_000)
+    a = SP.checkpointed(SP.FLUXES, 20_000, ck)
     a.write_fluxes(str(tmp_path / "fluxes.npz"))
     a.close()
     z = np.load(str(tmp_path / "fluxes.npz"))
     assert z["totals"].shape == (1024, 2, 7, 2) and z["heat_flux"].shape == (1024, 3) and "edges_2" in z and int(z["n_samples"]) == 2
-    b = Simulation("pore", n=20_000)
-    b.load_checkpoint(ck)               # restores the grid, the totals and the cadence (steps 9, 12, 15 still to come)
-    b.run(8)
-    tot = b.engine.flux_read()
-    assert tot[1] == ref_tot[1] == 5 and tot[2] == ref_tot[2]
-    assert np.array_equal(tot[0], ref_tot[0]) and tot[0][:, 1].any()
-    b.close()
+    tot = SP.resumed(SP.FLUXES, 20_000, ck, ref_tot)
+    assert tot[0][:, 1].any()
     c = _sim("pore", 20_000)            # a checkpoint without fluxes: sampling is off in the resumed run
     c.run(1)
     c.save_checkpoint(str(tmp_path / "plain.npz"))
@@ -310,7 +192,7 @@ def test_flux_load_carry_and_borrow():
     g = FX.make_grid("cartesian", (2, 1, 1), (-1.0e-7, -1.0e-7, 0.0), (1.0e-7, 1.0e-7, 1.0e-6))
     x, y, z = np.where(k % 2 == 0, -5.0e-8, 5.0e-8), np.zeros(n), np.full(n, 5.0e-7)
     state = (x, y, z, 300.0 + k, -(120.5 + 0.25 * k), -(77.0 + k))
-    ref = REF.Totals(g)
+    ref = Totals(g)
     ref.add(*state)
     sums = ref.sums
     assert ref.n_outside == 0 and (sums[:, 1, 1:] != 0).all() and (sums[:, 0] > 0)[:, [0, 1, 4, 5, 6]].all()
@@ -335,85 +217,19 @@ def test_flux_load_carry_and_borrow():
 
 
 # ---- 10. energised pore: host-RNG and device-RNG steps, and the host-free run ---------------------------------------------------
-def _temp_sim(device_rng):
-    from argon_monte_carlo_amd.sim import TemperatureSimulation
-    p, c = PR.pore_params(n=20_000, energised=True)
-    sim = TemperatureSimulation(params=p, consts=c, np_rng=np.random.RandomState(3), py_rng=random.Random(3),
-                                device_rng_seed=(7 if device_rng else None))
-    sim.set_state(*IC.pore_ic(p, c, 13))
-    sim.enable_fluxes(every=2)
-    return sim
-
-
 @pytest.mark.parametrize("device_rng", [False, True])
 def test_energised_pore_totals_equal_reference(device_rng, tmp_path):
-    sim = _temp_sim(device_rng)
-    ref = REF.Totals(sim.engine.flux_grid)
-    for s in range(1, 5):
-        sim.timestep()
-        if s % 2 == 0:
-            ref.add_state(sim.engine.download())
-    tot = _check(sim.engine, ref)
+    sim, ref, tot = SP.energised_totals(SP.FLUXES, device_rng, every=2)
     assert ref.n_samples == 2 and tot[:, 1, 1:].any()
     f = sim.fluxes()
     assert np.isfinite(f["heat_flux"][f["count"] >= 2]).all()
-    state = sim.engine.download()
+    read, state = sim.engine.flux_read(), sim.engine.download()
     ck = str(tmp_path / "ck.npz")
     sim.save_checkpoint(ck)             # the energised class extends the base class's checkpoint: the fluxes travel with it
     sim.close()
     assert np.array_equal(np.load(ck)["flux_totals"], tot)
     if device_rng:                      # the host-free run takes the same samples as four single steps
-        run = _temp_sim(True)
-        run.run(4)
-        tot_run, ns, no = run.engine.flux_read()
-        assert (ns, no) == (2, ref.n_outside) and np.array_equal(tot_run, tot)
-        st = run.engine.download()
-        for k in KEYS:
-            assert np.array_equal(st[k], state[k]), k
-        run.close()
-
-
-# ---- 11. two ranks on one GPU ---------------------------------------------------------------------------------------------------
-def _flux_worker(rank, world, port, kind, n, steps, every, q):
-    import torch.distributed as dist
-    try:
-        os.environ["MASTER_ADDR"] = "127.0.0.1"
-        os.environ["MASTER_PORT"] = str(port)
-        dist.init_process_group("gloo", rank=rank, world_size=world)
-        try:
-            from argon_monte_carlo_amd.dist import ShardedSimulation
-            from tests.test_gpu_dist import _case
-            p, c, init = _case(kind, n)
-            sim = ShardedSimulation(p, rank, world, backend="gloo")
-            sim.upload(*init)
-            sim.enable_fluxes(every=every)
-            sim.run(c["dt"], steps)
-            f = sim.fluxes()
-            if rank == 0:
-                q.put(("ok", (f["totals"], f["n_samples"], f["n_outside"])))
-        finally:
-            dist.destroy_process_group()
-    except BaseException as e:
-        import traceback
-        q.put(("error", f"rank {rank}: {e!r}\n{traceback.format_exc()}"))
-        raise
-
-
-@pytest.mark.parametrize("kind,n", [("cube", 30_000), ("pore", 60_001)])
-def test_two_ranks_on_one_gpu_equal_single_engine(kind, n):
-    from argon_monte_carlo_amd.engine import Engine
-    from tests.test_gpu_dist import _case, _run_ranks
-    steps, every = 6, 2
-    p, c, init = _case(kind, n)
-    eng = Engine(p)
-    eng.upload(*init)
-    eng.flux_config(FX.default_grid(p, every=every))
-    eng.run(c["dt"], steps)
-    ref = eng.flux_read()
-    eng.close()
-    tot, ns, no = _run_ranks(2, (kind, n, steps, every), target=_flux_worker)
-    assert ns == ref[1] == steps // every and no == ref[2]
-    assert np.array_equal(tot, ref[0]) and ref[0][:, 1].any()
+        SP.host_free_run(SP.FLUXES, read, state, every=2)
 
 
 # ---- 12. physics on a Maxwell start ---------------------------------------------------------------------------------------------

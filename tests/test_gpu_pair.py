@@ -2,7 +2,6 @@
 brute-force NumPy mirror (tests/pair_ref.py) on the state download() returns after the sample: crafted edges, the cell structure
 at its limits, deferred sweep results, any launch geometry, the life cycle, the energised run and index-range shards."""
 import math
-import random
 
 import numpy as np
 import pytest
@@ -13,19 +12,12 @@ from argon_monte_carlo_amd import pairs as PA
 from argon_monte_carlo_amd import params as PR
 from tests import fields_ref as FREF
 from tests import pair_ref as REF
+from tests.sampler_protocol import KEYS, make_temp_sim
+from tests.sampler_protocol import PairMirror as Totals
 
 pytestmark = pytest.mark.gpu
 
-KEYS = ["x", "y", "z", "vx", "vy", "vz", "d", "dx", "dy", "dz", "flag"]
 U = 2.0 ** -26                          # 14.9 nm: the crafted states' unit, exact in fp64 (the default cube is 100 nm = 6.71 U wide)
-
-
-def _check(engine, ref):
-    """The engine's totals and counters equal the reference's; returns the totals."""
-    tot, ns, no, nu = engine.pair_read()
-    assert (ns, no, nu) == (ref.n_samples, ref.n_outside, ref.n_unfiled), ((ns, no, nu), ref.read()[1:])
-    assert tot.shape == ref.sums.shape and tot.dtype == np.int64 and np.array_equal(tot, ref.sums), np.argwhere(tot != ref.sums)[:5]
-    return tot
 
 
 def _crafted(points, grid_of, lo=None, hi=None):
@@ -39,7 +31,7 @@ def _crafted(points, grid_of, lo=None, hi=None):
     eng.upload(*state)
     eng.pair_config(grid_of(p))
     eng.pair_sample()
-    ref = REF.Totals(eng.pair_grid)
+    ref = Totals(eng.pair_grid)
     ref.add_state(eng.download(), 0 if lo is None else lo, hi)
     return eng, eng.pair_grid, state, ref
 
@@ -80,7 +72,7 @@ def test_crafted_pairs_land_in_the_documented_columns():
     for col, approaching in ((7, 0), (3, 0), (0, 0), (4, 0), (4, 0), (2, 2), (2, 0)):
         want[0, 1 + col] += 2
         want[0, 9 + col] += approaching
-    tot = _check(eng, ref)
+    tot = ref.check(eng)
     assert np.array_equal(tot, want), np.argwhere(tot != want)
     assert (ref.n_outside, ref.n_unfiled) == (0, 0)
     eng.close()
@@ -97,7 +89,7 @@ def test_box_edge_outside_and_unfiled():
            (U / 4, math.nan, z, 0, 0, 0),       # 4: unfiled, although x and z sit next to the centre
            (5 * U, y, z, 0, 0, 0)]              # 5: a centre without a neighbour
     eng, g, state, ref = _crafted(pts, _cube_grid(U, 8))
-    tot = _check(eng, ref)
+    tot = ref.check(eng)
     want = np.zeros((1, 17), dtype=np.int64)
     want[0, 0], want[0, 1 + 4], want[0, 9 + 4] = 2, 1, 1
     assert np.array_equal(tot, want) and (ref.n_outside, ref.n_unfiled) == (1, 3)
@@ -127,11 +119,11 @@ def test_corner_one_partner_in_each_of_the_26_neighbouring_cells():
     assert all(np.abs(np.array(np.unravel_index(k, cells)) - home).max() == 1 for k in cell[1:27])
     assert np.abs(np.array(np.unravel_index(cell[27], cells)) - home).max() == 2
     eng, g, state, ref = _crafted(pts, _cube_grid(U, 8), lo=0, hi=1)
-    tot = _check(eng, ref)
+    tot = ref.check(eng)
     assert tot[0, 0] == 1 and tot[0, 1:9].sum() == 26 and tot[0, 9:].sum() == 0
     eng.close()
     eng, g, state, ref = _crafted(pts, _cube_grid(U, 8))          # ... and everybody as a centre
-    tot = _check(eng, ref)
+    tot = ref.check(eng)
     assert tot[0, 0] == 28 and tot[0, 1:9].sum() > 52
     eng.close()
 
@@ -152,7 +144,7 @@ def test_full_cells_more_particles_than_a_tile():
     cell = _cells(g, pos[:, 0], pos[:, 1], pos[:, 2])
     assert len(set(cell[:300].tolist())) == 1 and len(set(cell[300:].tolist())) == 1 and cell[300] == cell[0] + 1
     eng, g, state, ref = _crafted(pts, _cube_grid(U, 16))
-    tot = _check(eng, ref)
+    tot = ref.check(eng)
     assert tot[0, 0] == 600 and tot[0, 1:17].sum() > 2 * 300 * 299 and not (tot[0, 1:] % 2).any()
     assert tot[0, 1:9].sum() == 2 * 300 * 299           # within r_max / 2: the pairs inside either ball and no others
     eng.close()
@@ -174,7 +166,7 @@ def test_one_and_two_cells_on_an_axis_are_clipped_not_visited_twice():
         return PA.make_grid("cartesian", (3, 1, 1), (0.0, 2.0 * U, 3.0 * U), (p.cube_x, 2.5 * U, 3.0 * U * (1.0 + 2.0 ** -30)), U, hist_bins=8)
     assert PA.search_box(grid(p))[2] == [8, 2, 1]
     eng, g, state, ref = _crafted(np.stack([x, y, z, v[0], v[1], v[2]], axis=1), grid)
-    tot = _check(eng, ref)
+    tot = ref.check(eng)
     assert tot[:, 0].sum() > 10 and tot[:, 1:9].sum() > 20 and ref.n_outside > 100 and ref.n_unfiled > 20
     eng.close()
     # one cell on every axis (a grid of 2^-30 r_max: the box is 2 r_max and a little): the home cell is its own only neighbour
@@ -182,7 +174,7 @@ def test_one_and_two_cells_on_an_axis_are_clipped_not_visited_twice():
     eng, g, state, ref = _crafted(np.stack([x, y, z, v[0], v[1], v[2]], axis=1),
                                   lambda p: PA.make_grid("cartesian", (1, 1, 1), (3 * U, 2 * U, 3 * U), (3 * U * eps, 2 * U * eps, 3 * U * eps), U, hist_bins=4))
     assert PA.search_box(g)[2] == [1, 1, 1]
-    tot = _check(eng, ref)
+    tot = ref.check(eng)
     assert tot[0, 0] == 3 and tot[0, 1] >= 6 and tot[0, 1:5].sum() > 30
     eng.close()
 
@@ -200,7 +192,7 @@ def test_cap_of_128_cells_per_axis():
     eng, g, state, ref = _crafted(pts, _cube_grid(r_max, 32, n=(2, 2, 2)))
     lo, hi, cells, edge = PA.search_box(g)
     assert cells == [128, 128, 128] and edge[0] > 1.5 * r_max
-    tot = _check(eng, ref)
+    tot = ref.check(eng)
     assert tot[:, 0].sum() == n and tot[:, 1:33].sum() > 4 * 2000 and (ref.n_outside, ref.n_unfiled) == (0, 0)
     eng.close()
 
@@ -217,13 +209,13 @@ def test_axisymmetric_grid_in_the_pore(wide):
     r_max = 1.0e-7 if wide else 32.0 * float(p.collision_range)
     sim.enable_pairs(PA.make_grid("axisymmetric", (2, 4), (0.0, 0.0), (p.R_oa, p.H), r_max, hist_bins=16))
     assert (r_max > 0.5 * p.R_oa) == wide
-    ref = REF.Totals(sim.engine.pair_grid)
+    ref = Totals(sim.engine.pair_grid)
     sim.pairs_sample()
     ref.add_state(sim.engine.download())
     sim.timestep()
     sim.pairs_sample()
     ref.add_state(sim.engine.download())
-    tot = _check(sim.engine, ref)
+    tot = ref.check(sim.engine)
     assert int(tot[:, 0].sum()) + ref.n_outside == 2 * 4096 and ref.n_unfiled == 0
     assert tot[:, 1:17].sum() > (100_000 if wide else 100)
     d = sim.pairs()
@@ -250,13 +242,13 @@ def test_sample_reads_through_the_deferred_results_of_the_last_sweep():
     """Straight after a timestep() whose collisions are still pending in the slot arrays, and again after the next step."""
     sim = _dense_cube()
     sim.enable_pairs(_small_grid(sim.params, (2, 1, 2)))
-    ref = REF.Totals(sim.engine.pair_grid)
+    ref = Totals(sim.engine.pair_grid)
     for _ in range(2):
         st = sim.timestep()
         assert st["n_pp"] >= 1                  # the sweep moved particles: their final state is in the slot arrays
         sim.pairs_sample()
         ref.add_state(sim.engine.download())
-    tot = _check(sim.engine, ref)
+    tot = ref.check(sim.engine)
     d = sim.pairs()
     assert tot[:, 0].sum() + ref.n_outside == 6000 and tot[:, 1:17].sum() > 1000      # (a few particles have left the cube)
     # d = 2 columns of d / 2: the overlap count is exact here, and the scheme does leave pairs closer than d
@@ -278,7 +270,7 @@ def test_totals_do_not_depend_on_the_number_of_workgroups(blocks, monkeypatch):
     sim.run(4)
     got = sim.engine.pair_read()
     if "ref" not in _GEOMETRY:
-        ref = REF.Totals(sim.engine.pair_grid)
+        ref = Totals(sim.engine.pair_grid)
         one = _dense_cube(n=5000, seed=2)
         for s in range(4):
             one.timestep()
@@ -298,7 +290,7 @@ def test_cadence_with_step_offset_reset_and_load():
     sim.engine.pair_config(PA.copy_grid(g, every=3, step_offset=1))        # after the steps s with (s + 1) % 3 == 0: 2, 5, 8
     sim.run(10)
     end = sim.engine.download()
-    ref = REF.Totals(g)
+    ref = Totals(g)
     one = _dense_cube()
     for s in range(1, 11):
         one.timestep()
@@ -308,7 +300,7 @@ def test_cadence_with_step_offset_reset_and_load():
     one.close()
     for k in KEYS:
         assert np.array_equal(end[k], last[k]), k
-    tot = _check(sim.engine, ref)
+    tot = ref.check(sim.engine)
     assert ref.n_samples == 3 and tot[0, 0] + ref.n_outside == 9000
     # load: the inverse of read; a sample adds exactly to what was loaded
     big = (1 << 62) - 3
@@ -317,7 +309,7 @@ def test_cadence_with_step_offset_reset_and_load():
     got = sim.engine.pair_read()
     assert got[1:] == (7, 5, 2) and np.array_equal(got[0], loaded)
     sim.pairs_sample()
-    one_more = REF.Totals(g)
+    one_more = Totals(g)
     one_more.add_state(sim.engine.download())
     got = sim.engine.pair_read()
     assert got[1:] == (8, 5, 2) and np.array_equal(got[0], loaded + one_more.sums)
@@ -421,10 +413,8 @@ def test_sampling_leaves_step_statistics_and_state_unchanged():
 
 # ---- 7. the energised pore's host-free run ------------------------------------------------------------------------------------------
 def _temp_sim(every):
-    from argon_monte_carlo_amd.sim import TemperatureSimulation
-    p, c = PR.pore_params(n=6_000, energised=True)
-    sim = TemperatureSimulation(params=p, consts=c, np_rng=np.random.RandomState(3), py_rng=random.Random(3), device_rng_seed=7)
-    sim.set_state(*IC.pore_ic(p, c, 13))
+    sim = make_temp_sim(True, n=6_000)
+    p = sim.params
     sim.enable_pairs(PA.make_grid("axisymmetric", (1, 4), (0.0, 0.0), (p.R_oa, p.H), 32.0 * float(p.collision_range), hist_bins=8), every=every)
     return sim
 
@@ -436,7 +426,7 @@ def test_device_rng_run_samples_like_three_manual_samples():
     end = run.engine.download()
     run.close()
     one = _temp_sim(0)
-    ref = REF.Totals(one.engine.pair_grid)
+    ref = Totals(one.engine.pair_grid)
     for s in range(1, 7):
         one.timestep()
         if s % 2 == 0:
@@ -512,12 +502,12 @@ def test_three_ranks_sum_to_the_single_context():
     eng = Engine(p)
     eng.upload(*init)
     eng.pair_config(g)
-    ref = REF.Totals(g)
+    ref = Totals(g)
     for s in range(1, steps + 1):
         assert eng.timestep(c["dt"])["n_pp"] >= 1
         if s % every == 0:
             ref.add_state(eng.download())
-    want = _check(eng, ref)
+    want = ref.check(eng)
     eng.close()
     assert ref.n_outside > 0 and ref.n_unfiled > 0 and want[:, 1:17].sum() > 100
     ranges = [shard_range(n, r, 3) for r in range(3)]
@@ -566,7 +556,7 @@ def test_pore_one_rank_over_the_whole_range_through_the_sharded_step():
     eng.upload(*init)
     eng.pair_config(g)
     job = LocalRanks([eng])
-    ref = REF.Totals(g)
+    ref = Totals(g)
     n_pp = 0
     for s in range(1, 7):
         n_pp += job.step(c["dt"], want_stats=True)[0]["n_pp"]
@@ -574,7 +564,7 @@ def test_pore_one_rank_over_the_whole_range_through_the_sharded_step():
             ref.add_state(eng.download())
     print("p-p collisions in six steps:", n_pp)
     assert n_pp >= 1
-    tot = _check(eng, ref)
+    tot = ref.check(eng)
     assert ref.n_samples == 3 and tot[:, 1:17].sum() > 0
     eng.close()
 

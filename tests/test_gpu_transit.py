@@ -1,65 +1,30 @@
 """GPU (-m gpu): sampled transits (include/argonmc_transit.h).  The device's integer totals must equal the mirror
-(tests/transit_ref.py) on the downloaded states bit for bit, whatever the launch configuration or the way the steps were
-driven, and sampling must change nothing else."""
+(tests/transit_ref.py) on the downloaded states bit for bit, whatever the launch configuration or the way the steps were driven,
+and sampling must change nothing else.  What the transits share with the other streaming samplers — two ranks, odd index ranges,
+sampling changes nothing else — is in tests/test_gpu_sampler_protocol.py, and the body of run(k) against k timesteps in
+tests/sampler_protocol.py."""
 import math
 import os
-import random
 
 import numpy as np
 import pytest
 
-from argon_monte_carlo_amd import ic as IC
 from argon_monte_carlo_amd import params as PR
 from argon_monte_carlo_amd import transits as TR
 from argon_monte_carlo_amd.totals import ints_to_words, words_to_ints
+from tests import sampler_protocol as SP
 from tests import transit_ref as REF
-from tests.sampler_states import ODD_N, ODD_SHARDS, drifting_states
+from tests.sampler_protocol import KEYS
+from tests.sampler_protocol import TransitMirror as Mirror
+from tests.sampler_protocol import make_sim as _sim
+from tests.sampler_protocol import thin_zones as _thin_zones
+from tests.sampler_protocol import transit_classes as _classes
+from tests.sampler_protocol import transit_zones as _zones
+from tests.sampler_states import ODD_N, drifting_states
 
 pytestmark = pytest.mark.gpu
 
-KEYS = ["x", "y", "z", "vx", "vy", "vz", "d", "dx", "dy", "dz", "flag"]
-N = 20_011                              # odd: the unpaired tail; three workgroups
 COL = TR.class_column
-
-
-def _sim(kind, n, seed=11):
-    from argon_monte_carlo_amd.sim import Simulation
-    sim = Simulation(kind, n=n)
-    gen = IC.cube_ic if kind == "cube" else IC.pore_ic
-    sim.set_state(*gen(sim.params, sim.consts, seed))
-    return sim
-
-
-def _thin_zones(p):
-    """The pore moves an atom about 0.07 nm per step: zones thin enough for whole residences within a test — 0.5 nm and 2 nm
-    at the lower mouth of the coated section, nested, and one abutting the floor z = 0."""
-    return [(2, p.h_oa, p.h_oa + 0.5e-9), (2, p.h_oa, p.h_oa + 2e-9), (2, 0.0, 1e-9)]
-
-
-def _zones(kind, p):
-    return TR.zones(TR.default_grid(p)) if kind == "cube" else _thin_zones(p)
-
-
-def _mirror_sample(m, st):
-    m.sample(st["x"], st["y"], st["z"])
-
-
-def _check(engine, m):
-    """The engine's totals, counter and per-particle arrays equal the mirror's; returns the totals as Python ints."""
-    tot, ns = engine.transit_read()
-    want = m.words()
-    assert ns == m.n_samples, (ns, m.n_samples)
-    assert tot.shape == want.shape and tot.dtype == np.int64 and np.array_equal(tot, want), np.argwhere(tot != want)[:5]
-    state, entry = engine.transit_state()
-    assert np.array_equal(state, m.state), np.flatnonzero(state != m.state)[:5]
-    for k in range(len(m.zones)):
-        inside = ((m.state >> np.uint32(4 * k)) & np.uint32(3)) == 2
-        assert np.array_equal(entry[k][inside], m.entry[k][inside]), k
-    return words_to_ints(tot)
-
-
-def _classes(t, k):
-    return [int(t[k, COL(e, x)]) for e in range(3) for x in range(2)]
 
 
 # ---- 1. the totals equal the mirror on the downloaded states ------------------------------------------------------------------
@@ -68,13 +33,13 @@ def test_totals_equal_mirror_after_timesteps(kind, n, steps, every, offset):
     sim = _sim(kind, n)
     zones = _zones(kind, sim.params)
     sim.engine.transit_config(TR.make_grid(zones, every=every, step_offset=offset))
-    m = REF.Mirror(zones, n)
+    m = Mirror(zones, n)
     for s in range(1, steps + 1):
         sim.timestep()
         st = sim.engine.download()
         if (s + offset) % every == 0:
-            _mirror_sample(m, st)
-    t = _check(sim.engine, m)
+            m.add_state(st)
+    t = m.check(sim.engine)
     assert m.n_samples == (steps + offset) // every
     hit = [any(_classes(t, k)[c] > 0 for k in range(len(zones))) for c in range(6)]
     print("exits per zone and class:", [_classes(t, k) for k in range(len(zones))], "skipped", [int(t[k, 3]) for k in range(len(zones))])
@@ -90,71 +55,12 @@ def test_totals_equal_mirror_after_timesteps(kind, n, steps, every, offset):
 
 
 # ---- 2. run(k) equals k timesteps equals the mirror, for any number of workgroups, overlapped, beside another sampler ------------
-_RUN_REF = {}
-STEPS = 12
-
-
-def _run_reference(kind):
-    """timesteps with the cadence against the mirror, once per geometry: (totals, samples, state words, final particle state)"""
-    if kind not in _RUN_REF:
-        sim = _sim(kind, N)
-        zones = _zones(kind, sim.params)
-        sim.enable_transits(TR.make_grid(zones))
-        m = REF.Mirror(zones, N)
-        for _ in range(STEPS):
-            sim.timestep()
-            _mirror_sample(m, sim.engine.download())
-        t = _check(sim.engine, m)
-        assert sum(sum(_classes(t, k)) for k in range(len(zones))) > 0
-        _RUN_REF[kind] = (sim.engine.transit_read(), sim.engine.transit_state()[0], sim.engine.download())
-        sim.close()
-    return _RUN_REF[kind]
-
-
 @pytest.mark.parametrize("kind,overlap,blocks,mfp", [
     ("cube", None, None, False), ("pore", None, None, False), ("cube", None, "1", False), ("pore", None, "1", False),
     ("cube", None, "3", False), ("pore", None, "3", False), ("cube", "1", None, False), ("pore", "1", None, False),
     ("cube", None, None, True), ("pore", None, None, True)])
 def test_run_equals_timesteps_and_mirror(kind, overlap, blocks, mfp, monkeypatch):
-    (ref_tot, ref_ns), ref_words, ref_state = _run_reference(kind)
-    if overlap is not None:
-        monkeypatch.setenv("AMC_OVERLAP", overlap)
-    if blocks is not None:
-        monkeypatch.setenv("AMC_TRANSIT_BLOCKS", blocks)
-    sim = _sim(kind, N)
-    if mfp:
-        sim.enable_free_paths()
-    sim.enable_transits(TR.make_grid(_zones(kind, sim.params)))
-    sim.run(STEPS)
-    tot, ns = sim.engine.transit_read()
-    assert ns == ref_ns == STEPS
-    assert np.array_equal(tot, ref_tot), np.argwhere(tot != ref_tot)[:5]
-    assert np.array_equal(sim.engine.transit_state()[0], ref_words)
-    st = sim.engine.download()
-    for k in KEYS:
-        assert np.array_equal(st[k], ref_state[k]), k
-    sim.close()
-
-
-# ---- 3. the walk's odd ends: an index range that begins or ends inside an aligned pair ------------------------------------------
-@pytest.mark.parametrize("lo,hi", ODD_SHARDS)
-def test_index_range_with_odd_ends_equals_mirror(lo, hi):
-    """(Uploads do not restart tracking: every sample follows an upload.)"""
-    from argon_monte_carlo_amd.engine import ShardEngine
-    p, states = drifting_states(ODD_N, 24)
-    zones = _thin_zones(p) + [(0, -2e-9, 2e-9), (1, 0.0, 5e-9)]
-    eng = ShardEngine(p, lo, hi)
-    eng.transit_config(TR.make_grid(zones, every=0))
-    m = REF.Mirror(zones, hi - lo)
-    for st in states:
-        eng.upload(*st)
-        eng.transit_sample()
-        m.sample(*(a[lo:hi] for a in st[:3]))
-    t = _check(eng, m)
-    assert all(int(t[k, 0:3].sum()) > 0 for k in range(len(zones))) and int(t[:, 0:2].sum()) > 0 and sum(sum(_classes(t, k)) for k in range(len(zones))) > 0
-    state, entry = eng.transit_state()
-    assert state.shape == (hi - lo,) and entry.shape == (len(zones), hi - lo)
-    eng.close()
+    SP.check_run(SP.TRANSITS, monkeypatch, kind, None, overlap, blocks, mfp)
 
 
 # ---- 4. crafted edges -----------------------------------------------------------------------------------------------------------------
@@ -183,12 +89,12 @@ def test_crafted_edges_land_in_the_documented_columns():
     half = np.full(n, 0.5 * L)
     zero = np.zeros(n)
     sim.enable_transits(TR.make_grid(zones), every=0)
-    m = REF.Mirror(zones, n)
+    m = Mirror(zones, n)
     for f in range(frames):
         sim.set_state(X[f].copy(), half, half, zero, zero, zero)
         sim.transits_sample()
         m.sample(X[f], half, half)
-    t = _check(sim.engine, m)
+    t = m.check(sim.engine)
     a = np.zeros(263, dtype=object)
     a[0], a[1], a[2], a[3] = 2, 5, 2, 1                         # entries from below (4, 10), above (5 .. 9), already inside (0, 11); skipped (3)
     a[4] = frames + 1 + (2 + 3 + 4 + 7 + 8) + 5 + 1             # inside_sum: particle 0 always, 4 once, the five residences, 10 five times, 11 once
@@ -229,7 +135,7 @@ def _set_y(sim, n, L, y):
 def test_long_residences_are_exact_and_the_sample_limit_stops_the_sampler():
     from argon_monte_carlo_amd._lib import ArgonMCError
     sim, n, L, zones = _tiny()
-    m = REF.Mirror(zones, n)
+    m = Mirror(zones, n)
     inside, below, above = 0.3 * L, 0.1 * L, 0.9 * L
     # particles 3 and 6 are inside, entered from below at sample 3 and from above at sample 0; everybody else below
     state = np.full(n, 1, dtype=np.uint32)
@@ -249,7 +155,7 @@ def test_long_residences_are_exact_and_the_sample_limit_stops_the_sampler():
     y[3], y[6] = above, inside
     m.sample(*_set_y(sim, n, L, y))
     sim.transits_sample()
-    t = _check(sim.engine, m)
+    t = m.check(sim.engine)
     tau = 2 ** 31 + 2
     c = COL(0, 1)
     assert [int(v) for v in t[0, c:c + 3]] == [1, tau, tau * tau] and int(t[0, c + 3 + 31]) == 1 and tau * tau > 2 ** 62
@@ -263,7 +169,7 @@ def test_long_residences_are_exact_and_the_sample_limit_stops_the_sampler():
     y[6] = below
     m.sample(*_set_y(sim, n, L, y))
     sim.transits_sample()
-    t = _check(sim.engine, m)
+    t = m.check(sim.engine)
     tau = 2 ** 32 - 2
     c = COL(1, 0)
     assert [int(v) for v in t[0, c:c + 3]] == [1, tau, tau * tau] and int(t[0, c + 3 + 31]) == 1 and m.n_samples == 2 ** 32 - 1
@@ -302,14 +208,14 @@ def test_long_residences_are_exact_and_the_sample_limit_stops_the_sampler():
 def test_nan_is_reported_with_its_index_and_the_sample_before_it_counted():
     from argon_monte_carlo_amd._lib import ArgonMCError
     sim, n, L, zones = _tiny()
-    m = REF.Mirror(zones, n)
+    m = Mirror(zones, n)
     y = np.linspace(0.05, 0.95, n) * L
     half = np.full(n, 0.5 * L)
     nan = np.full(n, math.nan)
     sim.set_state(nan, y, nan, np.zeros(n), np.zeros(n), np.zeros(n))      # (axes no zone looks at are not examined)
     sim.transits_sample()
     m.sample(nan, y, nan)
-    t = _check(sim.engine, m)
+    t = m.check(sim.engine)
     assert int(t[0, 2]) == int(((y >= 0.25 * L) & (y < 0.5 * L)).sum()) > 0
     y2 = y.copy()
     y2[7] = y2[9] = math.nan
@@ -374,30 +280,6 @@ def test_calls_before_a_config_return_state_errors():
     sim.close()
 
 
-def test_sampling_leaves_state_counters_histograms_and_paths_unchanged():
-    out = []
-    for on in (False, True):
-        sim = _sim("pore", N, seed=5)
-        if on:
-            sim.enable_transits(every=2)
-        stats = [sim.run(10)]
-        sim._collect()
-        for _ in range(10):
-            stats.append(sim.timestep())
-        st = sim.engine.download()
-        counts, npaths = sim.engine.histograms()
-        out.append((st, stats, counts, npaths, list(sim.completed_paths), list(sim.completed_x_paths)))
-        if on:
-            assert sim.engine.transit_read()[1] == 10
-        sim.close()
-    (a, sa, ca, na, pa, pxa), (b, sb, cb, nb, pb, pxb) = out
-    for k in KEYS:
-        assert np.array_equal(a[k], b[k]), k
-    assert sa == sb
-    assert na == nb and np.array_equal(ca, cb)
-    assert len(pa) > 0 and pa == pb and pxa == pxb
-
-
 def test_checkpoint_mid_residence_resumes_to_the_same_totals(tmp_path):
     from argon_monte_carlo_amd.sim import Simulation
     n = 20_000
@@ -459,12 +341,12 @@ def test_load_read_round_trip_and_a_sample_adds_exactly():
     eng.transit_load(ints_to_words(t0), 9, state, None)
     tot, ns = eng.transit_read()
     assert ns == 9 and np.array_equal(tot, ints_to_words(t0))
-    m = REF.Mirror(zones, n)
+    m = Mirror(zones, n)
     m.load(ints_to_words(t0), 9, state)
     eng.upload(x, np.zeros(n), z, np.zeros(n), np.zeros(n), np.zeros(n))
     eng.transit_sample()
     m.sample(x, np.zeros(n), z)
-    t = _check(eng, m)
+    t = m.check(eng)
     assert int(t[0, 0]) == 2 ** 64 - 1 + 20 and int(t[1, 4]) == 2 ** 64 - 3 + 20 and int(t[1, 0]) == int(t0[1, 0]) + 20
     with pytest.raises(ValueError):
         eng.transit_load(ints_to_words(t0)[:1], 0)
@@ -474,17 +356,6 @@ def test_load_read_round_trip_and_a_sample_adds_exactly():
 
 
 # ---- 7. energised pore: host-RNG and device-RNG steps, and the host-free run ---------------------------------------------------
-def _temp_sim(device_rng, zones):
-    from argon_monte_carlo_amd.sim import TemperatureSimulation
-    p, c = PR.pore_params(n=20_000, energised=True)
-    sim = TemperatureSimulation(params=p, consts=c, np_rng=np.random.RandomState(3), py_rng=random.Random(3),
-                                device_rng_seed=(7 if device_rng else None))
-    sim.set_state(*IC.pore_ic(p, c, 13))
-    if zones is not None:
-        sim.enable_transits(TR.make_grid(zones(p)))
-    return sim
-
-
 @pytest.mark.parametrize("device_rng", [False, True])
 def test_energised_pore_run_equals_mirror_on_a_twin(device_rng):
     """Thin zones at the hot coating's lower edge, z = h_oa, on both sides of it.  run(k) samples after every step; the twin takes
@@ -492,65 +363,22 @@ def test_energised_pore_run_equals_mirror_on_a_twin(device_rng):
     def zones(p):
         return [(2, p.h_oa, p.h_oa + 0.5e-9), (2, p.h_oa - 1e-9, p.h_oa + 1e-9), (2, p.h_oa, p.z_gap_bottom)]
     steps = 10
-    twin = _temp_sim(device_rng, None)
-    m = REF.Mirror(zones(twin.params), 20_000)
+    twin = SP.make_temp_sim(device_rng)
+    m = Mirror(zones(twin.params), 20_000)
     for _ in range(steps):
         twin.timestep()
-        _mirror_sample(m, twin.engine.download())
+        m.add_state(twin.engine.download())
     state = twin.engine.download()
     twin.close()
-    sim = _temp_sim(device_rng, zones)
+    sim = SP.make_temp_sim(device_rng)
+    sim.enable_transits(TR.make_grid(zones(sim.params)))
     sim.run(steps)
-    t = _check(sim.engine, m)
+    t = m.check(sim.engine)
     assert m.n_samples == steps and sum(sum(_classes(t, k)) for k in range(3)) > 0 and all(int(t[k, 0:3].sum()) > 0 for k in range(3))
     st = sim.engine.download()
     for k in KEYS:
         assert np.array_equal(st[k], state[k]), k
     sim.close()
-
-
-# ---- 8. two ranks on one GPU ---------------------------------------------------------------------------------------------------
-def _transit_worker(rank, world, port, kind, n, steps, q):
-    import torch.distributed as dist
-    try:
-        os.environ["MASTER_ADDR"] = "127.0.0.1"
-        os.environ["MASTER_PORT"] = str(port)
-        dist.init_process_group("gloo", rank=rank, world_size=world)
-        try:
-            from argon_monte_carlo_amd.dist import ShardedSimulation
-            from tests.test_gpu_dist import _case
-            p, c, init = _case(kind, n)
-            sim = ShardedSimulation(p, rank, world, backend="gloo")
-            sim.upload(*init)
-            sim.enable_transits(TR.make_grid(_zones(kind, p)))
-            sim.run(c["dt"], steps)
-            d = sim.transits(dt=c["dt"])
-            if rank == 0:
-                q.put(("ok", (d["totals"], d["n_samples"])))
-        finally:
-            dist.destroy_process_group()
-    except BaseException as e:
-        import traceback
-        q.put(("error", f"rank {rank}: {e!r}\n{traceback.format_exc()}"))
-        raise
-
-
-@pytest.mark.parametrize("kind,n", [("cube", 30_000), ("pore", 60_001)])
-def test_two_ranks_on_one_gpu_equal_single_engine(kind, n):
-    from argon_monte_carlo_amd.engine import Engine
-    from tests.test_gpu_dist import _case, _run_ranks
-    steps = 6
-    p, c, init = _case(kind, n)
-    eng = Engine(p)
-    eng.upload(*init)
-    eng.transit_config(TR.make_grid(_zones(kind, p)))
-    eng.run(c["dt"], steps)
-    ref_tot, ref_ns = eng.transit_read()
-    eng.close()
-    tot, ns = _run_ranks(2, (kind, n, steps), target=_transit_worker)
-    assert ns == ref_ns == steps
-    t = words_to_ints(ref_tot)
-    assert np.array_equal(tot, ref_tot) and int(t[:, 0:3].sum()) > 0 and int(t[:, 4].sum()) > 0
 
 
 # ---- 12. the reduce at its shapes -------------------------------------------------------------------------------------------------
@@ -565,7 +393,7 @@ def _reduce_case(n_zones):
     if n_zones not in _REDUCE_REF:
         p, states = drifting_states(ODD_N, 11)
         zones = (_thin_zones(p) + [(0, -2e-9, 2e-9), (1, 0.0, 5e-9), (2, p.h_oa + 2e-9, p.h_oa + 4e-9), (0, 0.0, p.R_oa), (1, -p.R_oa, 0.0)])[:n_zones]
-        m = REF.Mirror(zones, ODD_N)
+        m = Mirror(zones, ODD_N)
         for st in (states[0], states[10]):
             m.sample(*st[:3])
         _REDUCE_REF[n_zones] = (p, zones, (states[0], states[10]), m)
@@ -586,7 +414,7 @@ def test_reduce_shapes_equal_mirror(n_zones, blocks, monkeypatch):
     for st in states:
         eng.upload(*st)
         eng.transit_sample()
-    t = _check(eng, m)
+    t = m.check(eng)
     assert all(int(t[k, 0:3].sum()) > 0 for k in range(n_zones)) and sum(sum(_classes(t, k)) for k in range(n_zones)) > 0
     eng.close()
 
@@ -608,7 +436,7 @@ def test_reduce_adds_a_limb_pair_split_over_two_workgroups():
     L = float(sim.params.cube_x)
     zones = [(1, (0.1 + 0.1 * k) * L, (0.15 + 0.1 * k) * L) for k in range(8)]      # disjoint, in ascending order along y
     sim.enable_transits(TR.make_grid(zones), every=0)
-    m = REF.Mirror(zones, n)
+    m = Mirror(zones, n)
     # everybody below every zone, but `who`: inside zone 4 since sample 0, entered from above — above zones 0 .. 3, below 5 .. 7
     state = np.full(n, 0x11111111, dtype=np.uint32)
     state[who] = 0x11100000 | (2 | 1 << 2) << 16 | 0x3333
@@ -621,7 +449,7 @@ def test_reduce_adds_a_limb_pair_split_over_two_workgroups():
     y[who] = 0.57 * L                   # above zone 4, still below zone 5: nobody else's position word changes
     m.sample(*_set_y(sim, n, L, y))
     sim.transits_sample()
-    t = _check(sim.engine, m)
+    t = m.check(sim.engine)
     c = COL(1, 1)
     want = np.zeros((8, REF.COLUMNS), dtype=object)
     want[zone, c], want[zone, c + 1], want[zone, c + 2], want[zone, c + 3 + 17] = 1, 2 ** 17, 2 ** 34, 1

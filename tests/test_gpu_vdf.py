@@ -1,9 +1,9 @@
 """GPU (-m gpu): sampled velocity distributions (include/argonmc_vdf.h).  The device's integer counts must equal the NumPy
 reference (tests/vdf_ref.py) on the downloaded states bit for bit, whatever the launch configuration or the way the steps were
-driven, and sampling must change nothing else."""
+driven, and sampling must change nothing else.  What the distributions share with the other streaming samplers — two ranks, odd
+index ranges, the reduce's shapes, sampling changes nothing else — is in tests/test_gpu_sampler_protocol.py, and the body of
+run(k) against k timesteps in tests/sampler_protocol.py."""
 import math
-import os
-import random
 
 import numpy as np
 import pytest
@@ -12,51 +12,15 @@ from argon_monte_carlo_amd import distributions as VD
 from argon_monte_carlo_amd import fields as FL
 from argon_monte_carlo_amd import ic as IC
 from argon_monte_carlo_amd import params as PR
+from tests import sampler_protocol as SP
 from tests import vdf_ref as REF
-from tests.sampler_states import ODD_N, ODD_SHARDS, drifting_states
+from tests.sampler_protocol import VdfMirror as Totals
+from tests.sampler_protocol import make_sim as _sim
+from tests.sampler_protocol import vdf_slab_columns as _slab_columns
 
 pytestmark = pytest.mark.gpu
 
-KEYS = ["x", "y", "z", "vx", "vy", "vz", "d", "dx", "dy", "dz", "flag"]
-N = 20_011                              # odd: the unpaired tail; three workgroups
-
-
-def _sim(kind, n, seed=11):
-    from argon_monte_carlo_amd.sim import Simulation
-    sim = Simulation(kind, n=n)
-    gen = IC.cube_ic if kind == "cube" else IC.pore_ic
-    sim.set_state(*gen(sim.params, sim.consts, seed))
-    return sim
-
-
-# regions and histogram bins per named grid: W = regions * (4 H + 8) columns and the outside column make W + 1 slab columns
-_SHAPES = {"one": ((1, 1, 1), 64), "exact": ((8, 8, 6), 14), "125": ((1, 1, 1), 29), "129": ((2, 2, 2), 2), "133": ((11, 1, 1), 1)}
-
-
-def _grid(kind, p, which):
-    if which == "default":
-        return VD.default_grid(p)
-    if which == "cart":                 # a Cartesian grid in the pore, over its bounding box
-        return VD.make_grid("cartesian", (2, 2, 8), (-p.R_oa, -p.R_oa, 0.0), (p.R_oa, p.R_oa, p.H))
-    if which == "half":                 # ... and over the half x >= 0 of it: the other half of the particles is outside
-        return VD.make_grid("cartesian", (1, 2, 8), (0.0, -p.R_oa, 0.0), (p.R_oa, p.R_oa, p.H))
-    n3, H = _SHAPES[which]
-    if kind == "cube":
-        return VD.make_grid("cartesian", n3, (0, 0, 0), (p.cube_x, p.cube_y, p.cube_z), hist_bins=H)
-    return VD.make_grid("axisymmetric", (n3[2], n3[0] * n3[1]), (0, 0), (p.R_oa, p.H), hist_bins=H)
-
-
-def _slab_columns(g):
-    return VD.grid_bins(g) * VD.columns(g.hist_bins) + 1
-
-
-def _check(engine, ref):
-    """The engine's totals and counters equal the reference's; returns the totals."""
-    tot, ns, no = engine.vdf_read()
-    assert (ns, no) == (ref.n_samples, ref.n_outside), (ns, no, ref.n_samples, ref.n_outside)
-    assert tot.shape == ref.sums.shape and tot.dtype == np.int64 and np.array_equal(tot, ref.sums), np.argwhere(tot != ref.sums)[:5]
-    REF.check_invariants(engine.vdf_grid, tot)
-    return tot
+_grid = SP.DISTRIBUTIONS.grids
 
 
 # ---- 1. the totals equal the reference on the downloaded states -----------------------------------------------------------
@@ -73,7 +37,7 @@ def test_totals_equal_reference_after_timesteps(kind, n, which):
         assert _slab_columns(g) - 1 == 24_576       # the whole table in LDS
     axes = 3 if g.kind == FL.AMC_FIELDS_CARTESIAN else 2
     sim.enable_fields(FL.make_grid(g.kind, (g.n1, g.n2, g.n3)[:axes], list(g.lo)[:axes], list(g.hi)[:axes]))      # the same regions
-    ref = REF.Totals(g)
+    ref = Totals(g)
     sim.distributions_sample()          # straight after the upload
     sim.fields_sample()
     ref.add_state(sim.engine.download())
@@ -82,7 +46,7 @@ def test_totals_equal_reference_after_timesteps(kind, n, which):
         sim.distributions_sample()      # the cube's sweep results are still deferred here: read through the slot arrays
         sim.fields_sample()
         ref.add_state(sim.engine.download())
-    tot = _check(sim.engine, ref)
+    tot = ref.check(sim.engine)
     assert int(tot[:, 0].sum()) + ref.n_outside == 4 * n
     assert (ref.n_outside > 0) == (which == "half")
     f_tot, f_ns, f_no = sim.engine.fields_read()
@@ -94,27 +58,6 @@ def test_totals_equal_reference_after_timesteps(kind, n, which):
 
 
 # ---- 2. run(k) equals k timesteps, for any number of workgroups and in an overlapped run -----------------------------------
-_RUN_REF = {}
-STEPS, EVERY = 7, 2
-
-
-def _run_reference(kind, which):
-    """timesteps + distributions_sample against the reference, once per (geometry, grid): (totals, counters, final state)"""
-    if (kind, which) not in _RUN_REF:
-        sim = _sim(kind, N)
-        sim.enable_distributions(_grid(kind, sim.params, which))
-        ref = REF.Totals(sim.engine.vdf_grid)
-        for s in range(1, STEPS + 1):
-            sim.timestep()
-            if s % EVERY == 0:
-                sim.distributions_sample()
-                ref.add_state(sim.engine.download())
-        tot = _check(sim.engine, ref)
-        _RUN_REF[(kind, which)] = (tot, (ref.n_samples, ref.n_outside), sim.engine.download())
-        sim.close()
-    return _RUN_REF[(kind, which)]
-
-
 @pytest.mark.parametrize("kind,which,overlap,blocks", [
     ("cube", "default", None, None), ("pore", "default", None, None), ("cube", "default", "1", None), ("pore", "default", "1", None),
     ("cube", "125", None, "1"), ("pore", "125", None, "17"), ("cube", "129", None, "33"),
@@ -123,41 +66,9 @@ def test_run_equals_timesteps_and_reference(kind, which, overlap, blocks, monkey
     """The reduce takes 64 slab columns per workgroup.  A slab row has regions * (4 H + 8) + 1 columns, which is 1 modulo 4, so
     127 and 128 columns do not exist; the sizes around the boundary between two and three workgroups are 125 (one region, H = 29:
     three lanes short of two full workgroups), 129 (8 regions, H = 2: a third workgroup with one live lane) and 133 (11 regions,
-    H = 1, C = 12: five live lanes).  1, 17 and 33 slab rows: below, one above and two above a multiple of its sixteen waves."""
-    ref_tot, ref_cnt, ref_state = _run_reference(kind, which)
-    if overlap is not None:
-        monkeypatch.setenv("AMC_OVERLAP", overlap)
-    if blocks is not None:
-        monkeypatch.setenv("AMC_VDF_BLOCKS", blocks)
-    sim = _sim(kind, N)
-    sim.enable_distributions(_grid(kind, sim.params, which), every=EVERY)
-    if which in ("125", "129", "133"):
-        assert _slab_columns(sim.engine.vdf_grid) == int(which)
-    sim.run(STEPS)
-    tot, ns, no = sim.engine.vdf_read()
-    assert (ns, no) == ref_cnt and ns == STEPS // EVERY
-    assert np.array_equal(tot, ref_tot), np.argwhere(tot != ref_tot)[:5]
-    st = sim.engine.download()
-    for k in KEYS:
-        assert np.array_equal(st[k], ref_state[k]), k
-    sim.close()
-
-
-# ---- 3. the walk's odd ends: an index range that begins or ends inside an aligned pair ------------------------------------------
-@pytest.mark.parametrize("lo,hi", ODD_SHARDS)
-def test_index_range_with_odd_ends_equals_reference(lo, hi):
-    from argon_monte_carlo_amd.engine import ShardEngine
-    p, states = drifting_states(ODD_N, 3)
-    eng = ShardEngine(p, lo, hi)
-    eng.vdf_config(VD.default_grid(p))
-    ref = REF.Totals(eng.vdf_grid)
-    for st in states:
-        eng.upload(*st)
-        eng.vdf_sample()
-        ref.add(*(a[lo:hi] for a in st))
-    tot = _check(eng, ref)
-    assert int(tot[:, 0].sum()) + ref.n_outside == 3 * (hi - lo)
-    eng.close()
+    H = 1, C = 12: five live lanes); the shared body asserts each.  1, 17 and 33 slab rows: below, one above and two above a
+    multiple of its sixteen waves."""
+    SP.check_run(SP.DISTRIBUTIONS, monkeypatch, kind, which, overlap, blocks)
 
 
 # ---- 4. crafted edges ---------------------------------------------------------------------------------------------------------------
@@ -260,9 +171,9 @@ def test_range_edge_is_reported_with_its_index_and_the_value_below_is_counted():
     vx[601] = vy[601] = top
     sim.set_state(x, y, z, vx, vy, vz)
     sim.distributions_sample()
-    ref = REF.Totals(sim.engine.vdf_grid)
+    ref = Totals(sim.engine.vdf_grid)
     ref.add(x, y, z, vx, vy, vz)
-    s = VD.split(sim.engine.vdf_grid, _check(sim.engine, ref))
+    s = VD.split(sim.engine.vdf_grid, ref.check(sim.engine))
     assert s["under"].sum(axis=0).tolist() == [1, 0, 1] and s["over"].sum(axis=0).tolist() == [1, 1, 1] and s["over_speed"].sum() == 3
     # NaN is reported the same way ...
     vy = vy.copy()
@@ -323,45 +234,11 @@ def test_calls_before_a_config_return_state_errors():
     sim.close()
 
 
-# ---- 7. sampling changes nothing else ------------------------------------------------------------------------------------------
-def test_sampling_leaves_state_counters_histograms_and_paths_unchanged():
-    out = []
-    for on in (False, True):
-        sim = _sim("pore", N, seed=5)
-        if on:
-            sim.enable_distributions(every=2)
-        stats = [sim.run(10)]
-        sim._collect()
-        for _ in range(10):
-            stats.append(sim.timestep())
-        st = sim.engine.download()
-        counts, npaths = sim.engine.histograms()
-        out.append((st, stats, counts, npaths, list(sim.completed_paths), list(sim.completed_x_paths)))
-        if on:
-            assert sim.engine.vdf_read()[1] == 10
-        sim.close()
-    (a, sa, ca, na, pa, pxa), (b, sb, cb, nb, pb, pxb) = out
-    for k in KEYS:
-        assert np.array_equal(a[k], b[k]), k
-    assert sa == sb
-    assert na == nb and np.array_equal(ca, cb)
-    assert len(pa) > 0 and pa == pb and pxa == pxb
-
-
 # ---- 8. checkpoints ------------------------------------------------------------------------------------------------------------
 def test_checkpoint_resume_gives_the_same_totals(tmp_path):
-    from argon_monte_carlo_amd.sim import Simulation
-    ref = _sim("pore", 20_000, seed=4)
-    ref.enable_distributions(every=3)
-    ref.run(7)
-    ref.run(8)
-    ref_tot = ref.engine.vdf_read()
-    ref.close()
-    a = _sim("pore", 20_000, seed=4)
-    a.enable_distributions(every=3)
-    a.run(7)
     ck = str(tmp_path / "ck.npz")
-    a.save_checkpoint(ck)
+    ref_tot = SP.uninterrupted(SP.DISTRIBUTIONS, 20_000)
+    a = SP.checkpointed(SP.DISTRIBUTIONS, 20_000, ck)
     a.write_distributions(str(tmp_path / "distributions.npz"))
     a.close()
     zc = np.load(ck)
@@ -372,13 +249,8 @@ def test_checkpoint_resume_gives_the_same_totals(tmp_path):
     assert z["count"].shape == z["over_speed"].shape == z["T_est"].shape == z["mean_speed"].shape == (32,)
     assert z["edges_v"].shape == z["edges_speed"].shape == (65,) and z["edges_1"].shape == (2,) and z["edges_2"].shape == (33,) and "edges_3" not in z
     assert z["shape"].tolist() == [1, 32, 1] and int(z["kind"]) == 1 and int(z["n_outside"]) == 0
-    b = Simulation("pore", n=20_000)
-    b.load_checkpoint(ck)               # restores the grid, the totals and the cadence (steps 9, 12, 15 still to come)
-    b.run(8)
-    tot = b.engine.vdf_read()
-    assert tot[1] == ref_tot[1] == 5 and tot[2] == ref_tot[2]
-    assert np.array_equal(tot[0], ref_tot[0]) and int(tot[0][:, 0].sum()) == 5 * 20_000
-    b.close()
+    tot = SP.resumed(SP.DISTRIBUTIONS, 20_000, ck, ref_tot)
+    assert int(tot[0][:, 0].sum()) == 5 * 20_000
     c = _sim("pore", 20_000)            # a checkpoint without distributions: sampling is off in the resumed run
     c.run(1)
     c.save_checkpoint(str(tmp_path / "plain.npz"))
@@ -420,86 +292,20 @@ def test_load_read_round_trip_and_a_sample_adds_exactly():
 
 
 # ---- 10. energised pore: host-RNG and device-RNG steps, and the host-free run ---------------------------------------------------
-def _temp_sim(device_rng):
-    from argon_monte_carlo_amd.sim import TemperatureSimulation
-    p, c = PR.pore_params(n=20_000, energised=True)
-    sim = TemperatureSimulation(params=p, consts=c, np_rng=np.random.RandomState(3), py_rng=random.Random(3),
-                                device_rng_seed=(7 if device_rng else None))
-    sim.set_state(*IC.pore_ic(p, c, 13))
-    sim.enable_distributions(every=2)
-    return sim
-
-
 @pytest.mark.parametrize("device_rng", [False, True])
 def test_energised_pore_totals_equal_reference(device_rng, tmp_path):
-    sim = _temp_sim(device_rng)
-    ref = REF.Totals(sim.engine.vdf_grid)
-    for s in range(1, 5):
-        sim.timestep()
-        if s % 2 == 0:
-            ref.add_state(sim.engine.download())
-    tot = _check(sim.engine, ref)
+    sim, ref, tot = SP.energised_totals(SP.DISTRIBUTIONS, device_rng, every=2)
     assert ref.n_samples == 2 and int(tot[:, 0].sum()) + ref.n_outside == 40_000
     d = sim.distributions()
     assert np.isfinite(d["pdf_speed"][d["count"] >= 1]).all()
-    state = sim.engine.download()
+    read, state = sim.engine.vdf_read(), sim.engine.download()
     ck = str(tmp_path / "ck.npz")
     sim.save_checkpoint(ck)             # the energised class extends the base class's checkpoint: the distributions travel with it
     sim.close()
     z = np.load(ck)
     assert np.array_equal(z["vdf_totals"], tot) and z["vdf_counters"].tolist() == [2, ref.n_outside]
     if device_rng:                      # the host-free run takes the same samples as four single steps
-        run = _temp_sim(True)
-        run.run(4)
-        tot_run, ns, no = run.engine.vdf_read()
-        assert (ns, no) == (2, ref.n_outside) and np.array_equal(tot_run, tot)
-        st = run.engine.download()
-        for k in KEYS:
-            assert np.array_equal(st[k], state[k]), k
-        run.close()
-
-
-# ---- 11. two ranks on one GPU ---------------------------------------------------------------------------------------------------
-def _vdf_worker(rank, world, port, kind, n, steps, every, q):
-    import torch.distributed as dist
-    try:
-        os.environ["MASTER_ADDR"] = "127.0.0.1"
-        os.environ["MASTER_PORT"] = str(port)
-        dist.init_process_group("gloo", rank=rank, world_size=world)
-        try:
-            from argon_monte_carlo_amd.dist import ShardedSimulation
-            from tests.test_gpu_dist import _case
-            p, c, init = _case(kind, n)
-            sim = ShardedSimulation(p, rank, world, backend="gloo")
-            sim.upload(*init)
-            sim.enable_distributions(every=every)
-            sim.run(c["dt"], steps)
-            d = sim.distributions()
-            if rank == 0:
-                q.put(("ok", (d["totals"], d["n_samples"], d["n_outside"])))
-        finally:
-            dist.destroy_process_group()
-    except BaseException as e:
-        import traceback
-        q.put(("error", f"rank {rank}: {e!r}\n{traceback.format_exc()}"))
-        raise
-
-
-@pytest.mark.parametrize("kind,n", [("cube", 30_000), ("pore", 60_001)])
-def test_two_ranks_on_one_gpu_equal_single_engine(kind, n):
-    from argon_monte_carlo_amd.engine import Engine
-    from tests.test_gpu_dist import _case, _run_ranks
-    steps, every = 6, 2
-    p, c, init = _case(kind, n)
-    eng = Engine(p)
-    eng.upload(*init)
-    eng.vdf_config(VD.default_grid(p, every=every))
-    eng.run(c["dt"], steps)
-    ref = eng.vdf_read()
-    eng.close()
-    tot, ns, no = _run_ranks(2, (kind, n, steps, every), target=_vdf_worker)
-    assert ns == ref[1] == steps // every and no == ref[2]
-    assert np.array_equal(tot, ref[0]) and int(ref[0][:, 0].sum()) + no == 3 * n
+        SP.host_free_run(SP.DISTRIBUTIONS, read, state, every=2)
 
 
 # ---- 12. physics on a Maxwell start ---------------------------------------------------------------------------------------------
@@ -516,9 +322,9 @@ def test_maxwell_start_gives_maxwellian_histograms_and_its_temperature():
     sim.enable_distributions(g)
     sim.distributions_sample()
     st = sim.engine.download()
-    ref = REF.Totals(g)
+    ref = Totals(g)
     ref.add_state(st)
-    tot = _check(sim.engine, ref)
+    tot = ref.check(sim.engine)
     d = sim.distributions()
     m, k_b = float(p.argon_mass), VD.boltzmann_constant(p)
     assert d["n_outside"] == 0 and d["count"].tolist() == [n] and not d["under"].any() and not d["over"].any() and not d["over_speed"].any()
@@ -535,37 +341,3 @@ def test_maxwell_start_gives_maxwellian_histograms_and_its_temperature():
     print("T_est", d["T_est"][0], "T0", T0, "bound", bound)
     assert abs(d["T_est"][0] - T0) < bound
     sim.close()
-
-
-# ---- 13. the reduce at its shapes -------------------------------------------------------------------------------------------------
-_REDUCE_REF = {}
-
-
-def _reduce_case(regions):
-    """(params, grid of ``regions`` regions over the lower half of the pore's box, state, reference sums, outside), computed once"""
-    if regions not in _REDUCE_REF:
-        p, (st,) = drifting_states(ODD_N, 1, seed=29)
-        g = VD.make_grid("cartesian", (regions, 1, 1), (-p.R_oa, -p.R_oa, 0.0), (p.R_oa, p.R_oa, 0.5 * p.H), hist_bins={4: 2, 5: 1}[regions])
-        _REDUCE_REF[regions] = (p, g, st) + REF.sample(g, *st)
-    return _REDUCE_REF[regions]
-
-
-@pytest.mark.parametrize("blocks", ["1", "17", "33"])
-@pytest.mark.parametrize("regions", [4, 5])
-def test_reduce_shapes_equal_reference(regions, blocks, monkeypatch):
-    """4 regions of H = 2: W = 4 * 16 = 64 totals columns, the last one lane 63 of the reduce's first workgroup, the outside column
-    lane 0 of a second one; 5 regions of H = 1: W = 60, one partial workgroup.  1, 17 and 33 slab rows: below, one above and two
-    above a multiple of the reduce's sixteen waves."""
-    from argon_monte_carlo_amd.engine import Engine
-    p, g, st, sums, outside = _reduce_case(regions)
-    assert _slab_columns(g) - 1 == {4: 64, 5: 60}[regions] and outside > 0 and (sums[:, 0] > 0).all()
-    monkeypatch.setenv("AMC_VDF_BLOCKS", blocks)
-    eng = Engine(p)
-    eng.upload(*st)
-    eng.vdf_config(g)
-    for k in (1, 2):                    # (the second sample adds onto non-zero totals)
-        eng.vdf_sample()
-        tot, ns, no = eng.vdf_read()
-        assert ns == k and no == k * outside
-        assert np.array_equal(tot, k * sums), np.argwhere(tot != k * sums)[:5]
-    eng.close()

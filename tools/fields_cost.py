@@ -6,33 +6,16 @@ against run(100) without sampling.  Prints one JSON line per workload.
 """
 import argparse
 import json
-import os
 import statistics
-import sys
 import time
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from cost_common import WORKLOADS, make_sim
 
-from argon_monte_carlo_amd import fields as FL  # noqa: E402
-from argon_monte_carlo_amd import ic as IC  # noqa: E402
-from argon_monte_carlo_amd import params as PR  # noqa: E402
-from argon_monte_carlo_amd.sim import Simulation  # noqa: E402
-
-WORKLOADS = [("pore", 1_000_000), ("cube", 100_000)]
+from argon_monte_carlo_amd import fields as FL
 
 
 def measure(kind, n, reps, steps=100, every=10, samples=50):
-    # the benchmark's set-up (bench.py make_workload): count-and-continue on a degenerate solve, histograms only
-    if kind == "cube":
-        p, c = PR.cube_params_for_n(n)
-        init = IC.cube_ic(p, c, seed=127)
-    else:
-        p, c = PR.pore_params(n=n)
-        init = IC.pore_ic(p, c, seed=17)
-    p.reserved1 = 1
-    p.max_paths = -1
-    sim = Simulation(kind, params=p, consts=c)
-    sim.set_state(*init)
+    sim = make_sim(kind, n)
     g = FL.default_grid(sim.params)
     # 1. one sample, kernel time on the dispatch
     sim.enable_fields(g)

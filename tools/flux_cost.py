@@ -7,49 +7,17 @@ line per workload.
 """
 import argparse
 import json
-import os
 import statistics
-import sys
 import time
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from cost_common import WORKLOADS, make_sim, sample_us
 
-from argon_monte_carlo_amd import fields as FL  # noqa: E402
-from argon_monte_carlo_amd import fluxes as FX  # noqa: E402
-from argon_monte_carlo_amd import ic as IC  # noqa: E402
-from argon_monte_carlo_amd import params as PR  # noqa: E402
-from argon_monte_carlo_amd.sim import Simulation  # noqa: E402
-
-WORKLOADS = [("pore", 1_000_000), ("cube", 100_000)]
-
-
-def sample_us(sim, sample, samples):
-    """kernel time of one sample (two launches), microseconds"""
-    for _ in range(5):
-        sample()
-    sim.engine.synchronize()
-    sim.engine.profile(True)
-    ms0, launches0 = sim.engine.kernel_times()["fields"]       # (the class's times accumulate over the context's life)
-    for _ in range(samples):
-        sample()
-    sim.engine.synchronize()
-    ms, launches = sim.engine.kernel_times()["fields"]
-    sim.engine.profile(False)
-    return 1e3 * (ms - ms0) / ((launches - launches0) / 2)
+from argon_monte_carlo_amd import fields as FL
+from argon_monte_carlo_amd import fluxes as FX
 
 
 def measure(kind, n, reps, steps=100, every=10, samples=50):
-    # the benchmark's set-up (bench.py make_workload): count-and-continue on a degenerate solve, histograms only
-    if kind == "cube":
-        p, c = PR.cube_params_for_n(n)
-        init = IC.cube_ic(p, c, seed=127)
-    else:
-        p, c = PR.pore_params(n=n)
-        init = IC.pore_ic(p, c, seed=17)
-    p.reserved1 = 1
-    p.max_paths = -1
-    sim = Simulation(kind, params=p, consts=c)
-    sim.set_state(*init)
+    sim = make_sim(kind, n)
     g = FX.default_grid(sim.params)
     axes = 3 if g.kind == FL.AMC_FIELDS_CARTESIAN else 2
     # 1. one sample of the fluxes and one of the fields on the same grid, kernel time on the dispatch, alternated

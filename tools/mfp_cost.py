@@ -7,18 +7,11 @@ other class).  Median of ``--reps`` runs per setting, the settings alternated.  
 """
 import argparse
 import json
-import os
 import statistics
-import sys
 import time
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from cost_common import WORKLOADS, make_sim
 
-from argon_monte_carlo_amd import ic as IC  # noqa: E402
-from argon_monte_carlo_amd import params as PR  # noqa: E402
-from argon_monte_carlo_amd.sim import Simulation  # noqa: E402
-
-WORKLOADS = [("pore", 1_000_000), ("cube", 100_000)]
 SETTINGS = ("none", "fields_every_1", "free_paths")
 
 
@@ -32,17 +25,8 @@ def configure(sim, setting):
 
 
 def measure(kind, n, reps, steps):
-    # the benchmark's set-up (bench.py make_workload) with the path records on: the sampler reads them
-    if kind == "cube":
-        p, c = PR.cube_params_for_n(n)
-        init = IC.cube_ic(p, c, seed=127)
-    else:
-        p, c = PR.pore_params(n=n)
-        init = IC.pore_ic(p, c, seed=17)
-    p.reserved1 = 1
-    sim = Simulation(kind, params=p, consts=c)
-    sim.set_state(*init)
-    sim.run(steps)                              # warm-up: every particle has a collision behind it, paths complete
+    sim = make_sim(kind, n, keep_paths=True)    # with the path records on: the sampler reads them
+    sim.run(steps)                             # warm-up: every particle has a collision behind it, paths complete
     times = {s: [] for s in SETTINGS}
     for _ in range(reps):
         for s in SETTINGS:

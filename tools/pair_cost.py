@@ -8,49 +8,26 @@ a sample makes (from its totals); and the time of a sample on a grid at the cap 
 """
 import argparse
 import json
-import os
 import statistics
-import sys
 import time
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import cost_common
+from cost_common import make_sim
 
-from argon_monte_carlo_amd import ic as IC  # noqa: E402
-from argon_monte_carlo_amd import pairs as PA  # noqa: E402
-from argon_monte_carlo_amd import params as PR  # noqa: E402
-from argon_monte_carlo_amd.sim import Simulation  # noqa: E402
+from argon_monte_carlo_amd import pairs as PA
+from argon_monte_carlo_amd import params as PR
+from argon_monte_carlo_amd.sim import Simulation
 
-WORKLOADS = [("cube", 100_000), ("pore", 1_000_000)]
-LAUNCHES = 6
+WORKLOADS = cost_common.WORKLOADS[::-1]         # the cube first
 
 
 def sample_us(sim, samples):
-    """kernel time of one sample (six launches), microseconds"""
-    for _ in range(3):
-        sim.pairs_sample()
-    sim.engine.synchronize()
-    sim.engine.profile(True)
-    ms0, launches0 = sim.engine.kernel_times()["fields"]       # (the class's times accumulate over the context's life)
-    for _ in range(samples):
-        sim.pairs_sample()
-    sim.engine.synchronize()
-    ms, launches = sim.engine.kernel_times()["fields"]
-    sim.engine.profile(False)
-    return 1e3 * (ms - ms0) / ((launches - launches0) / LAUNCHES)
+    """kernel time of one sample (six launches, three samples of warm-up), microseconds"""
+    return cost_common.sample_us(sim, sim.pairs_sample, samples, launches=6, warmup=3)
 
 
 def measure(kind, n, reps, steps=200, samples=20):
-    # the benchmark's set-up (bench.py make_workload): count-and-continue on a degenerate solve, histograms only
-    if kind == "cube":
-        p, c = PR.cube_params_for_n(n)
-        init = IC.cube_ic(p, c, seed=127)
-    else:
-        p, c = PR.pore_params(n=n)
-        init = IC.pore_ic(p, c, seed=17)
-    p.reserved1 = 1
-    p.max_paths = -1
-    sim = Simulation(kind, params=p, consts=c)
-    sim.set_state(*init)
+    sim = make_sim(kind, n)
     g = PA.default_grid(sim.params)
     sim.run(10)
     sim.enable_pairs(g)

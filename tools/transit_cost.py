@@ -8,52 +8,16 @@ Five takes of everything: median, minimum and maximum.  Prints one JSON line per
 """
 import argparse
 import json
-import os
 import statistics
-import sys
 import time
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from cost_common import WORKLOADS, make_sim, sample_us, spread
 
-from argon_monte_carlo_amd import ic as IC  # noqa: E402
-from argon_monte_carlo_amd import params as PR  # noqa: E402
-from argon_monte_carlo_amd import transits as TR  # noqa: E402
-from argon_monte_carlo_amd.sim import Simulation  # noqa: E402
-
-WORKLOADS = [("pore", 1_000_000), ("cube", 100_000)]
-
-
-def sample_us(sim, sample, samples):
-    """kernel time of one sample (two launches), microseconds"""
-    for _ in range(5):
-        sample()
-    sim.engine.synchronize()
-    sim.engine.profile(True)
-    ms0, launches0 = sim.engine.kernel_times()["fields"]       # (the class's times accumulate over the context's life)
-    for _ in range(samples):
-        sample()
-    sim.engine.synchronize()
-    ms, launches = sim.engine.kernel_times()["fields"]
-    sim.engine.profile(False)
-    return 1e3 * (ms - ms0) / ((launches - launches0) / 2)
-
-
-def spread(v, digits):
-    return {"median": round(statistics.median(v), digits), "min": round(min(v), digits), "max": round(max(v), digits)}
+from argon_monte_carlo_amd import transits as TR
 
 
 def measure(kind, n, reps, steps=200, samples=50):
-    # the benchmark's set-up (bench.py make_workload): count-and-continue on a degenerate solve, histograms only
-    if kind == "cube":
-        p, c = PR.cube_params_for_n(n)
-        init = IC.cube_ic(p, c, seed=127)
-    else:
-        p, c = PR.pore_params(n=n)
-        init = IC.pore_ic(p, c, seed=17)
-    p.reserved1 = 1
-    p.max_paths = -1
-    sim = Simulation(kind, params=p, consts=c)
-    sim.set_state(*init)
+    sim = make_sim(kind, n)
     g = TR.default_grid(sim.params)
     sim.run(10)
     # 1. one sample of the transits, of the distributions and of the fields, each on its default grid, kernel time on the
