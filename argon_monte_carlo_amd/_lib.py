@@ -156,11 +156,16 @@ SHARD_SIGNATURES = {
     "amc_temp_shard_run_end": (C.c_int, [_ctx, C.c_int64, C.POINTER(AmcStepStats)]),
 }
 
+# ... and every symbol include/argonmc-ic.h declares (the overlap removal of a synthetic start; argonmc.h includes it)
+IC_SIGNATURES = {
+    "amc_init_separate": (C.c_int, [_ctx, C.POINTER(AmcIcConfig), C.c_double, C.c_int32, C.c_int32, _i64p]),
+}
+
 
 def all_signatures():
     """every entry point of the library: the tables above, one per header, in one dict"""
     return {**SIGNATURES, **SHARD_SIGNATURES, **CORR_SIGNATURES, **FLUX_SIGNATURES, **MFP_SIGNATURES, **VDF_SIGNATURES, **TRANSIT_SIGNATURES,
-            **PAIR_SIGNATURES}
+            **PAIR_SIGNATURES, **IC_SIGNATURES}
 
 
 class ArgonMCError(RuntimeError):
@@ -196,12 +201,13 @@ def _source_files():
     files.append(os.path.join(os.path.dirname(_HERE), "include", "argonmc_vdf.h"))
     files.append(os.path.join(os.path.dirname(_HERE), "include", "argonmc_transit.h"))
     files.append(os.path.join(os.path.dirname(_HERE), "include", "argonmc_pair.h"))
+    files.append(os.path.join(os.path.dirname(_HERE), "include", "argonmc-ic.h"))
     return files
 
 
 def source_digest():
     """sha256 over the library's sources (csrc/*.hip, csrc/*.h, the Makefile, include/argonmc.h, argonmc_shard.h, argonmc_corr.h,
-    argonmc_flux.h, argonmc_mfp.h, argonmc_vdf.h, argonmc_transit.h and argonmc_pair.h)."""
+    argonmc_flux.h, argonmc_mfp.h, argonmc_vdf.h, argonmc_transit.h, argonmc_pair.h and argonmc-ic.h)."""
     import hashlib
     h = hashlib.sha256()
     for f in _source_files():

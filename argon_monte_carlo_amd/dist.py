@@ -131,6 +131,12 @@ class ShardedSimulation(S.Controls):
         its index only, so every rank builds the identical system."""
         self.engine.init_synthetic(cfg)
 
+    def init_separate(self, cfg, min_dist, first_round=1, max_rounds=64):
+        """Overlap removal of the synthetic start (``Engine.init_separate``).  Every rank holds the whole system after
+        ``init_synthetic`` and the rule depends on nothing but the state, the seed and the regions: every rank makes the same
+        call and holds the same state afterwards, without a collective.  Returns the statistics."""
+        return self.engine.init_separate(cfg, min_dist, first_round, max_rounds)
+
     # ---- one step -------------------------------------------------------------------------------------------------------
     def timestep(self, dt, reduce_stats=True, want_stats=True):
         self.engine.mg_local(dt)

@@ -69,6 +69,16 @@ class Engine:
         """Synthetic initial conditions generated on the device (``ic.device_ic_config``); replaces ``upload``."""
         self._ck(self.lib.amc_init_synthetic(self._ctx, C.byref(cfg)))
 
+    SEPARATE_STATS = ("searches", "rounds", "redrawn", "pairs_first", "losers_first", "pairs_left", "losers_left", "next_round")
+
+    def init_separate(self, cfg, min_dist, first_round=1, max_rounds=64):
+        """Overlap removal of a synthetic start on the device (include/argonmc-ic.h): pairs closer than ``min_dist`` are searched
+        in the whole system and the atom of the higher index is redrawn from ``cfg``'s seed and regions, round after round.
+        Returns the eight statistics by name; ``pairs_left > 0``: the budget of rounds did not suffice."""
+        st = (C.c_int64 * len(self.SEPARATE_STATS))()
+        self._ck(self.lib.amc_init_separate(self._ctx, C.byref(cfg), float(min_dist), int(first_round), int(max_rounds), st))
+        return dict(zip(self.SEPARATE_STATS, (int(v) for v in st)))
+
     def download(self):
         n = self.n
         arrs = [np.empty(n) for _ in range(10)]

@@ -14,6 +14,7 @@ from . import ic as IC
 from . import outputs as OUT
 from . import params as PR
 from . import samplers as S
+from ._lib import ArgonMCError
 from .engine import Engine
 
 _NAMES = {"x_vals": "x", "y_vals": "y", "z_vals": "z", "x_velocities": "vx", "y_velocities": "vy",
@@ -64,16 +65,38 @@ class Simulation(S.Controls):
                            dist_x_since_collision, dist_y_since_collision, dist_z_since_collision, full_path_traveled)
         self._cache = None
 
-    def init_synthetic(self, seed=None, device=False):
+    def init_synthetic(self, seed=None, device=False, separate=False):
         """Seeded synthetic initial conditions — the reference's own generators are host-side, one-off.
-        ``device=True`` generates them on the GPU (counter-based generator: another random stream, no PCIe transfer)."""
+        ``device=True`` generates them on the GPU (counter-based generator: another random stream, no PCIe transfer).
+        ``separate=True`` runs ``separate_overlaps`` afterwards, behind either generator."""
         seed = seed if seed is not None else self.consts["seed"]
+        self._ic_seed = seed
         if device:
             self.engine.init_synthetic(IC.device_ic_config(self.params, self.consts, seed, "cube" if self.kind == "cube" else "pore"))
             self._cache = None
-            return
-        gen = IC.cube_ic if self.kind == "cube" else IC.pore_ic
-        self.set_state(*gen(self.params, self.consts, seed))
+        else:
+            gen = IC.cube_ic if self.kind == "cube" else IC.pore_ic
+            self.set_state(*gen(self.params, self.consts, seed))
+        if separate:
+            self.separate_overlaps()
+
+    def separate_overlaps(self, min_dist=None, max_rounds=64, seed=None):
+        """Redraw, on the GPU, every atom that overlaps one of a lower index (``Engine.init_separate``, include/argonmc-ic.h) until
+        no pair is closer than ``min_dist`` (default: the collision range).  The new positions come from the device generator
+        under ``seed`` (default: the seed of the last ``init_synthetic``) and lie in the atom's own region by its index — the
+        host generators store their atoms region by region too.  Raises ``ArgonMCError`` (AMC_ERR_CAPACITY) when pairs are left
+        after ``max_rounds`` rounds; the state is then the last round's.  Returns the statistics."""
+        if seed is None:
+            seed = getattr(self, "_ic_seed", None)
+        if seed is None:
+            seed = self.consts["seed"]
+        cfg = IC.device_ic_config(self.params, self.consts, seed, "cube" if self.kind == "cube" else "pore")
+        st = self.engine.init_separate(cfg, self.params.collision_range if min_dist is None else min_dist, 1, max_rounds)
+        self._cache = None
+        if st["pairs_left"] > 0:
+            raise ArgonMCError(-4, "separate_overlaps: %d overlapping pairs (%d atoms to redraw) are left after %d rounds "
+                                   "(%d at the start)" % (st["pairs_left"], st["losers_left"], st["rounds"], st["pairs_first"]))
+        return st
 
     def _state(self):
         if self._cache is None:
@@ -476,13 +499,16 @@ class TemperatureSimulation(Simulation):
         self.energy_transfer_cold_per_step = []       # Temp:638
         self._zero_flags = []
 
-    def init_synthetic(self, seed=None, device=False):
+    def init_synthetic(self, seed=None, device=False, separate=False):
         seed = seed if seed is not None else self.consts["seed"]
+        self._ic_seed = seed
         if device:
             self.engine.init_synthetic(IC.device_ic_config(self.params, self.consts, seed, "pore"))
             self._cache = None
-            return
-        self.set_state(*IC.pore_ic(self.params, self.consts, seed))
+        else:
+            self.set_state(*IC.pore_ic(self.params, self.consts, seed))
+        if separate:
+            self.separate_overlaps()
 
     def timestep(self, dt=None, collect_paths=True):
         if self._device_rng is not None:

@@ -535,6 +535,9 @@ int amc_wall_contacts(amc_ctx *ctx, int case_id, double *contact_xyz, size_t cap
 /* ---- the device-RNG energised pore over shards: the hits exchange and the host-free sharded run ---------------------------- */
 #include "argonmc_shard.h"
 
+/* ---- overlap removal of a synthetic start: whole-system search, losers redrawn by counter (opt-in) ------------ */
+#include "argonmc-ic.h"
+
 #ifdef __cplusplus
 }
 #endif
