@@ -82,6 +82,16 @@ class AmcTempRng(C.Structure):
                 ("gl_x", C.c_double * 32), ("gl_w", C.c_double * 32)]
 
 
+AMC_WALL_LAW_REFERENCE = 0
+AMC_WALL_LAW_MAXWELL = 1
+
+
+class AmcWallLaw(C.Structure):
+    """amc_wall_law (include/argonmc-walllaw.h): the wall law of the device-RNG energised steps."""
+    _fields_ = [("struct_size", C.c_int32), ("kind", C.c_int32), ("alpha_coated", C.c_double), ("alpha_gap", C.c_double),
+                ("reserved", C.c_double * 4)]
+
+
 AMC_FIELDS_CARTESIAN = 0
 AMC_FIELDS_AXISYMMETRIC = 1
 AMC_FIELDS_MAX_BINS = 2048

@@ -9,7 +9,7 @@ import os
 import subprocess
 
 from ._abi import (AMC_ABI_VERSION, AmcCorrGrid, AmcFieldGrid, AmcFluxGrid, AmcIcConfig, AmcMfpGrid, AmcParams, AmcPathRecord, AmcStepStats, AmcSurfaceGrid,
-                   AmcPairGrid, AmcTempRng, AmcTransitGrid, AmcVdfGrid)
+                   AmcPairGrid, AmcTempRng, AmcTransitGrid, AmcVdfGrid, AmcWallLaw)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libargonmc.so")
@@ -161,11 +161,23 @@ IC_SIGNATURES = {
     "amc_init_separate": (C.c_int, [_ctx, C.POINTER(AmcIcConfig), C.c_double, C.c_int32, C.c_int32, _i64p]),
 }
 
+# ... and every symbol include/argonmc-walllaw.h declares (the device-RNG steps' wall law; argonmc.h includes it).  A table beside
+# all_signatures(), whose size tests/test_ic_separate_host.py fixes: load() types both (typed_signatures)
+WALL_LAW_SIGNATURES = {
+    "amc_temp_wall_law": (C.c_int, [_ctx, C.POINTER(AmcWallLaw)]),
+    "amc_temp_wall_law_get": (C.c_int, [_ctx, C.POINTER(AmcWallLaw)]),
+}
+
 
 def all_signatures():
     """every entry point of the library: the tables above, one per header, in one dict"""
     return {**SIGNATURES, **SHARD_SIGNATURES, **CORR_SIGNATURES, **FLUX_SIGNATURES, **MFP_SIGNATURES, **VDF_SIGNATURES, **TRANSIT_SIGNATURES,
             **PAIR_SIGNATURES, **IC_SIGNATURES}
+
+
+def typed_signatures():
+    """what load() types: all_signatures() and the wall law's entry points"""
+    return {**all_signatures(), **WALL_LAW_SIGNATURES}
 
 
 class ArgonMCError(RuntimeError):
@@ -202,12 +214,13 @@ def _source_files():
     files.append(os.path.join(os.path.dirname(_HERE), "include", "argonmc_transit.h"))
     files.append(os.path.join(os.path.dirname(_HERE), "include", "argonmc_pair.h"))
     files.append(os.path.join(os.path.dirname(_HERE), "include", "argonmc-ic.h"))
+    files.append(os.path.join(os.path.dirname(_HERE), "include", "argonmc-walllaw.h"))
     return files
 
 
 def source_digest():
     """sha256 over the library's sources (csrc/*.hip, csrc/*.h, the Makefile, include/argonmc.h, argonmc_shard.h, argonmc_corr.h,
-    argonmc_flux.h, argonmc_mfp.h, argonmc_vdf.h, argonmc_transit.h, argonmc_pair.h and argonmc-ic.h)."""
+    argonmc_flux.h, argonmc_mfp.h, argonmc_vdf.h, argonmc_transit.h, argonmc_pair.h, argonmc-ic.h and argonmc-walllaw.h)."""
     import hashlib
     h = hashlib.sha256()
     for f in _source_files():
@@ -245,7 +258,7 @@ def load():
         raise ArgonMCError(-3, f"{LIB_PATH} does not match the sources {stale[0]}: rebuild it "
                                "(`python -c 'import __graft_entry__ as g; g.build()'`)")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in all_signatures().items():
+    for name, (res, args) in typed_signatures().items():
         fn = getattr(lib, name)          # AttributeError = missing export
         fn.restype = res
         fn.argtypes = args

@@ -236,6 +236,35 @@ static int temp_rng_check(amc_ctx *c, const amc_temp_rng *cfg)
     return amc_fail(c, AMC_ERR_INVALID, "amc_temp_rng: bad struct_size / n_gl");
 }
 
+// ---- the wall law of the device-RNG steps (include/argonmc-walllaw.h): host state, read by the launches -----------------------
+int amc_temp_wall_law(amc_ctx *c, const amc_wall_law *law)
+{
+    if (!c) return AMC_ERR_INVALID;
+    if (c->P.geometry != AMC_GEOM_PORE_ENERGISED) return amc_fail(c, AMC_ERR_STATE, "amc_temp_wall_law needs AMC_GEOM_PORE_ENERGISED");
+    if (!law) { c->wall_law = amc_wall_law{}; return AMC_OK; }
+    if (law->struct_size != (int32_t)sizeof(amc_wall_law)) return amc_fail(c, AMC_ERR_INVALID, "amc_wall_law: bad struct_size");
+    if (law->kind != AMC_WALL_LAW_REFERENCE && law->kind != AMC_WALL_LAW_MAXWELL)
+        return amc_fail(c, AMC_ERR_INVALID, "amc_wall_law: unknown kind %d", (int)law->kind);
+    if (!(law->alpha_coated >= 0.0 && law->alpha_coated <= 1.0) || !(law->alpha_gap >= 0.0 && law->alpha_gap <= 1.0))
+        return amc_fail(c, AMC_ERR_INVALID, "amc_wall_law: alpha_coated %g / alpha_gap %g outside [0, 1]", law->alpha_coated, law->alpha_gap);
+    for (int k = 0; k < 4; k++)
+        if (!(law->reserved[k] == 0.0)) return amc_fail(c, AMC_ERR_INVALID, "amc_wall_law: reserved words must be 0");
+    c->wall_law = *law;
+    return AMC_OK;
+}
+
+int amc_temp_wall_law_get(amc_ctx *c, amc_wall_law *out)
+{
+    if (!c || !out) return AMC_ERR_INVALID;
+    if (c->P.geometry != AMC_GEOM_PORE_ENERGISED) return amc_fail(c, AMC_ERR_STATE, "amc_temp_wall_law_get needs AMC_GEOM_PORE_ENERGISED");
+    if (c->wall_law.struct_size) { *out = c->wall_law; return AMC_OK; }
+    *out = amc_wall_law{};
+    out->struct_size = (int32_t)sizeof(amc_wall_law);
+    out->kind = AMC_WALL_LAW_REFERENCE;
+    out->alpha_coated = c->P.alpha_coated; out->alpha_gap = c->P.alpha_gap;
+    return AMC_OK;
+}
+
 int amc_temp_cases_device(amc_ctx *c, const amc_temp_rng *cfg)
 {
     if (!c || !c->uploaded) return AMC_ERR_STATE;

@@ -143,6 +143,8 @@ __global__ __launch_bounds__(256) void k_temp_sample(amc_params P, amc_temp_rng 
 // particle is a sequential evaluation (temp_cases_particle, amc_energised_dev.h), so with the random numbers available on
 // the device the 7 x (hits, sample, apply) kernels collapse into this one.  The per-hit records (one segment per case) are
 // still written: their z-momentum / energy changes are summed in the reference's order, tests read the draws.
+// LAW (AMC_WALL_LAW_*): the context's wall law; the Maxwell instance gets the law's two alpha in P.alpha_coated / P.alpha_gap.
+template <int LAW>
 __global__ __launch_bounds__(256) void k_temp_all(amc_state S, amc_params P, amc_out O, amc_temp_rng g, unsigned int step,
                                                   long long lo, long long hi, temp_dev_segments D, amc_dev_counters *cnt)
 {
@@ -155,22 +157,67 @@ __global__ __launch_bounds__(256) void k_temp_all(amc_state S, amc_params P, amc
     q.vx = S.vx[p]; q.vy = S.vy[p]; q.vz = S.vz[p];
     q.d = S.d[p]; q.dx = S.dx[p]; q.dy = S.dy[p]; q.dz = S.dz[p];
     q.flag = S.flag[p] != 0;
-    temp_cases_particle<false>(P, O, g, step, D, (int)p, px, py, pz, q);
+    temp_cases_particle<false, LAW>(P, O, g, step, D, (int)p, px, py, pz, q);
     S.x[p] = q.x; S.y[p] = q.y; S.z[p] = q.z; S.vx[p] = q.vx; S.vy[p] = q.vy; S.vz[p] = q.vz;
     S.d[p] = q.d; S.dx[p] = q.dx; S.dy[p] = q.dy; S.dz[p] = q.dz; S.flag[p] = q.flag ? 1 : 0;
     if (q.nwall) atomicAdd(&O.banks[amc_bank_id()].n_wall, (unsigned long long)q.nwall);
     if (q.nerr) atomicAdd(&O.banks[amc_bank_id()].n_fp_errors, (unsigned long long)q.nerr);
 }
 
+// The case-by-case form's draw and apply of one case under the Maxwell law (AMC_TEMP_UNFUSED=1): what k_temp_sample and
+// k_temp_apply do under the reference law, in one kernel, because a specular reflection needs the incoming velocity where the
+// reference's draw needs only the normal.  Same device functions, hence the same bits, as temp_cases_particle's Maxwell branch.
+__global__ __launch_bounds__(256) void k_temp_maxwell(amc_state S, amc_params P, amc_out O, amc_temp_rng g, int case_id,
+                                                      unsigned int step, temp_records R, double *__restrict__ dir,
+                                                      double *__restrict__ Es, double *__restrict__ dpz, double *__restrict__ dE)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= min(*R.count, R.cap)) return;
+    dir[3 * k] = dir[3 * k + 1] = dir[3 * k + 2] = 0.0;
+    Es[k] = 0.0; dpz[k] = 0; dE[k] = 0;
+    if (!R.ok[k]) { atomicAdd(&O.banks[amc_bank_id()].n_fp_errors, 1ULL); atomicAdd(&O.banks[amc_bank_id()].n_wall, 1ULL); return; }
+    const int p = R.idx[k];
+    const double t = R.t[k];
+    const double vx = S.vx[p], vy = S.vy[p], vz = S.vz[p];
+    double wvx, wvy, wvz, es, fx, fy, fz, mz, e;
+    temp_maxwell_draw(P, g, case_id, step, p, R.normal[3 * k], R.normal[3 * k + 1], R.normal[3 * k + 2], R.contact[3 * k + 2], vx, vy, vz,
+                      wvx, wvy, wvz, es);
+    const double v_magnitude = temp_maxwell_finish(P, vx, vy, vz, wvx, wvy, wvz, fx, fy, fz, mz, e);
+    dir[3 * k] = fx; dir[3 * k + 1] = fy; dir[3 * k + 2] = fz;
+    Es[k] = es; dpz[k] = mz; dE[k] = e;
+    if (S.flag[p])                                                                           // Temp:391-395
+        amc_emit(O, case_id + 1, 0, p, -1, 0, fabs(S.d[p] - fabs(v_magnitude * t)), fabs(S.dx[p] - fabs(vx * t)),
+                 fabs(S.dy[p] - fabs(vy * t)), fabs(S.dz[p] - fabs(vz * t)));
+    else
+        S.flag[p] = 1;
+    S.d[p] = 0; S.dx[p] = 0; S.dy[p] = 0; S.dz[p] = 0;                                       // Temp:398-401
+    S.x[p] = R.contact[3 * k]; S.y[p] = R.contact[3 * k + 1]; S.z[p] = R.contact[3 * k + 2];   // Temp:402
+    S.vx[p] = wvx; S.vy[p] = wvy; S.vz[p] = wvz;                                             // Temp:403
+    atomicAdd(&O.banks[amc_bank_id()].n_wall, 1ULL);                                         // Temp:411,482,552
+}
+
+// the context's parameters as the Maxwell instances take them: the law's alpha in place of the accommodation coefficients
+amc_params amc_wall_law_params(const amc_ctx *c)
+{
+    amc_params P = c->P;
+    if (amc_wall_law_kind(c) == AMC_WALL_LAW_MAXWELL) { P.alpha_coated = c->wall_law.alpha_coated; P.alpha_gap = c->wall_law.alpha_gap; }
+    return P;
+}
+
 hipError_t amc_launch_temp_cases_device(amc_ctx *c, const amc_temp_rng *cfg)
 {
+    const bool maxwell = amc_wall_law_kind(c) == AMC_WALL_LAW_MAXWELL;
     const long long cnt = c->hi - c->lo;
     const temp_dev_segments &D = c->TD.seg;
     hipError_t e = hipMemsetAsync(D.count, 0, sizeof(int) * 7, c->stream);
     if (e != hipSuccess || cnt <= 0) return e;
     if (!c->temp_unfused) {
-        AMC_LAUNCH(c, k_temp_all, dim3((unsigned)((cnt + 255) / 256)), dim3(256), c->S, c->P, c->out, *cfg,
-                           (unsigned int)c->out.step, c->lo, c->hi, D, c->d_cnt);
+        if (maxwell)
+            AMC_LAUNCH(c, k_temp_all<AMC_WALL_LAW_MAXWELL>, dim3((unsigned)((cnt + 255) / 256)), dim3(256), c->S, amc_wall_law_params(c),
+                               c->out, *cfg, (unsigned int)c->out.step, c->lo, c->hi, D, c->d_cnt);
+        else
+            AMC_LAUNCH(c, k_temp_all<AMC_WALL_LAW_REFERENCE>, dim3((unsigned)((cnt + 255) / 256)), dim3(256), c->S, c->P, c->out, *cfg,
+                               (unsigned int)c->out.step, c->lo, c->hi, D, c->d_cnt);
         return hipGetLastError();
     }
     const unsigned rec_blocks = (unsigned)((D.cap + 255) / 256);
@@ -182,6 +229,11 @@ hipError_t amc_launch_temp_cases_device(amc_ctx *c, const amc_temp_rng *cfg)
         R.count = D.count + s; R.cap = D.cap;
         AMC_LAUNCH(c, k_temp_hits, dim3((unsigned)((cnt + 255) / 256)), dim3(256), c->S, c->P, case_id,
                            c->lo, c->hi, R, c->d_cnt);
+        if (maxwell) {
+            AMC_LAUNCH(c, k_temp_maxwell, dim3(rec_blocks), dim3(256), c->S, amc_wall_law_params(c), c->out, *cfg, case_id,
+                               (unsigned int)c->out.step, R, D.dir + 3 * o, D.Es + o, D.dpz + o, D.dE + o);
+            continue;
+        }
         AMC_LAUNCH(c, k_temp_sample, dim3(rec_blocks), dim3(256), c->P, *cfg, case_id,
                            (unsigned int)c->out.step, R, D.dir + 3 * o, D.Es + o);
         AMC_LAUNCH(c, k_temp_apply, dim3(rec_blocks), dim3(256), c->S, c->P, c->out, case_id, -1, R,

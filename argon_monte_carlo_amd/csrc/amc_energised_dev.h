@@ -124,6 +124,66 @@ __device__ inline void temp_draw(const amc_params &P, const amc_temp_rng &g, int
                         : (amc_case_cold(case_id) ? P.E_cold : P.E_hot);
 }
 
+// ---- the Maxwell wall law (include/argonmc-walllaw.h, AMC_WALL_LAW_MAXWELL) -----------------------------------
+// New velocity of one hit: with probability alpha a diffuse re-emission from the flux-weighted half-range Maxwellian at the
+// local wall temperature, else a specular reflection.  P.alpha_coated / P.alpha_gap are the LAW's two alpha here (the launch
+// puts them in place of the reference's accommodation coefficients, which this law does not read).  Es: 2 k T_w for a diffuse
+// hit, 0.0 for a specular one.  No rejection loop, no Debye integral.
+__device__ inline void temp_maxwell_draw(const amc_params &P, const amc_temp_rng &g, int case_id, unsigned int step, int particle,
+                                         double n0, double n1, double n2, double contact_z, double vx, double vy, double vz,
+                                         double &wx, double &wy, double &wz, double &Es)
+{
+    const double pi = 3.14159265358979323846;
+    unsigned int w0[4] = {(unsigned int)particle, step, ((unsigned int)case_id << 16) | 0u, 0x414d4332u};
+    unsigned int w1[4] = {(unsigned int)particle, step, ((unsigned int)case_id << 16) | 1u, 0x414d4332u};
+    philox4x32_10(w0, g.seed);
+    const double u0 = (double)((((unsigned long long)w0[0] << 32) | w0[1]) >> 11) * (1.0 / 9007199254740992.0);
+    double t_w = amc_case_cold(case_id) ? g.t_cold : g.t_hot;
+    if (case_id == 5) {
+        const double m = (g.t_cold - g.t_hot) / g.gap_height;                        // as temp_gap_energy forms t_gap
+        t_w = m * (contact_z - g.gap_bottom_height) + g.t_hot;
+    }
+    const double alpha = (case_id == 5) ? P.alpha_gap : P.alpha_coated;
+    if (u0 < alpha) {
+        philox4x32_10(w1, g.seed);
+        const double ua = (double)((((unsigned long long)w0[2] << 32) | w0[3]) >> 11) * (1.0 / 9007199254740992.0);
+        const double ub = (double)((((unsigned long long)w1[0] << 32) | w1[1]) >> 11) * (1.0 / 9007199254740992.0);
+        const double uc = (double)((((unsigned long long)w1[2] << 32) | w1[3]) >> 11) * (1.0 / 9007199254740992.0);
+        const double s = sqrt(g.boltzman * t_w / P.argon_mass);
+        const double vn = s * sqrt(-2.0 * log1p(-ua));
+        const double rt = s * sqrt(-2.0 * log1p(-ub));
+        const double ang = (2.0 * pi) * uc;
+        const double t1 = rt * cos(ang), t2 = rt * sin(ang);
+        if (case_id == 5 || case_id == 8 || case_id == 9) {                          // cylinders: the normal lies in the xy-plane
+            wx = vn * n0 - t1 * n1; wy = vn * n1 + t1 * n0; wz = t2;
+        } else {                                                                     // planes: the normal is (0, 0, +-1)
+            wx = t1; wy = t2; wz = vn * n2;
+        }
+        Es = 2 * g.boltzman * t_w;
+    } else {
+        const double dn = (vx * n0 + vy * n1) + vz * n2;
+        const double f = 2.0 * dn;
+        wx = vx - f * n0; wy = vy - f * n1; wz = vz - f * n2;
+        Es = 0.0;
+    }
+}
+
+// energies and the recorded direction of a Maxwell hit from the old and the new velocity; returns the speed before the hit
+__device__ inline double temp_maxwell_finish(const amc_params &P, double vx, double vy, double vz, double wx, double wy, double wz,
+                                             double &d0, double &d1, double &d2, double &dpz, double &dE)
+{
+    const double m = P.argon_mass;
+    const double v_magnitude = sqrt(vx * vx + vy * vy + vz * vz);                            // as temp_accommodate
+    const double E = 0.5 * m * (v_magnitude * v_magnitude);
+    const double mag = sqrt(wx * wx + wy * wy + wz * wz);
+    const double Enew = 0.5 * m * (mag * mag);
+    dE = Enew - E;
+    dpz = m * wz - m * vz;
+    d0 = d1 = d2 = 0.0;
+    if (mag != 0.0) { d0 = wx / mag; d1 = wy / mag; d2 = wz / mag; }
+    return v_magnitude;
+}
+
 // ---- all seven cases of one particle (device-RNG mode) -----------------------------------------------------------------
 // Every case reads and writes only the particle itself and the masks are evaluated in case order, each after the
 // previous handler ran (Temp:705-758): per particle that is this sequence.  The per-hit records (one segment per case,
@@ -142,7 +202,8 @@ __device__ inline bool temp_any_mask(const amc_params &P, double x, double y, do
 }
 
 // ROLLED: the form the streaming pass inlines — the case loop stays a loop (one copy of the draw: fewer registers, less code)
-template <bool ROLLED>
+// LAW: what a hit does to the velocity (AMC_WALL_LAW_*); everything around the draw is the same under every law
+template <bool ROLLED, int LAW = AMC_WALL_LAW_REFERENCE>
 __device__ inline void temp_cases_particle(const amc_params &P, const amc_out &O, const amc_temp_rng &g, unsigned int step,
                                            const temp_dev_segments &D, int p, double px, double py, double pz,
                                            temp_particle &q)
@@ -164,9 +225,14 @@ __device__ inline void temp_cases_particle(const amc_params &P, const amc_out &O
         if (!c.ok) {
             nerr++;                                                                          // Temp:472-474
         } else {
-            temp_draw(P, g, case_id, step, p, c.n0, c.n1, c.n2, c.cz, fx, fy, fz, es);
-            double wvx, wvy, wvz;
-            const double v_magnitude = temp_accommodate(P, case_id, vx, vy, vz, es, fx, fy, fz, wvx, wvy, wvz, dpz, dE);
+            double wvx, wvy, wvz, v_magnitude;
+            if constexpr (LAW == AMC_WALL_LAW_MAXWELL) {
+                temp_maxwell_draw(P, g, case_id, step, p, c.n0, c.n1, c.n2, c.cz, vx, vy, vz, wvx, wvy, wvz, es);
+                v_magnitude = temp_maxwell_finish(P, vx, vy, vz, wvx, wvy, wvz, fx, fy, fz, dpz, dE);
+            } else {
+                temp_draw(P, g, case_id, step, p, c.n0, c.n1, c.n2, c.cz, fx, fy, fz, es);
+                v_magnitude = temp_accommodate(P, case_id, vx, vy, vz, es, fx, fy, fz, wvx, wvy, wvz, dpz, dE);
+            }
             if (flag)                                                                        // Temp:391-395
                 amc_emit(O, case_id + 1, 0, p, -1, 0, fabs(d - fabs(v_magnitude * c.t)), fabs(dx - fabs(vx * c.t)),
                          fabs(dy - fabs(vy * c.t)), fabs(dz - fabs(vz * c.t)));

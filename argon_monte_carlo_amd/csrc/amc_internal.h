@@ -468,6 +468,7 @@ struct amc_ctx {
     int *d_host_ncand;             // its device address
     amc_temp_ws T;
     amc_temp_dev_ws TD;
+    amc_wall_law wall_law = {}; // the device-RNG steps' wall law (amc_temp_wall_law; struct_size 0: never set, the reference law)
     amc_moments_ws F;           // the sampled fields
     amc_surface_ws SF;
     amc_corr_ws CR;
@@ -619,6 +620,9 @@ hipError_t amc_launch_temp_hits(amc_ctx *c, int case_id);
 hipError_t amc_launch_temp_apply(amc_ctx *c, int case_id, int n, bool park = false);
 hipError_t amc_launch_temp_velocity(amc_ctx *c, int case_id, int n);
 hipError_t amc_launch_temp_cases_device(amc_ctx *c, const amc_temp_rng *cfg);
+// the wall law of the context's device-RNG steps (amc_temp_wall_law): its kind, and the parameters its kernels are launched with
+inline int amc_wall_law_kind(const amc_ctx *c) { return c->wall_law.struct_size ? c->wall_law.kind : AMC_WALL_LAW_REFERENCE; }
+amc_params amc_wall_law_params(const amc_ctx *c);
 hipError_t amc_launch_temp_sums(amc_ctx *c, int64_t row);     // the step's sums -> row `row` of the series (one workgroup)
 // sampled surfaces (amc_surface.hip; callers test c->SF.on first): the records of all seven segments of a device-RNG step, of
 // the hand-over's current case, and the two halves of a parked case

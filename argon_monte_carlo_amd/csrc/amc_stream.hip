@@ -112,6 +112,8 @@ AMC_DEV void amc_stream_count(const amc_out &O, const amc_stream_counts &cn, int
 #define AMC_LD(p) __builtin_nontemporal_load(&(p))
 #define AMC_ST(p, v) __builtin_nontemporal_store((v), &(p))
 
+// TEMP: 0 without the energised stage, else 1 + the wall law of its hits (AMC_WALL_LAW_*; the Maxwell instance gets the law's two
+// alpha in P.alpha_coated / P.alpha_gap, which nothing else in the pass reads)
 template <int GEOM, int TEMP = 0>
 __global__ __launch_bounds__(256) void k_stream(amc_state S, amc_state S_out, amc_params P, amc_out O, double dt, int stages,
                                                 long long lo, long long hi, int keep_prior, int bounds_slot,
@@ -186,7 +188,7 @@ __global__ __launch_bounds__(256) void k_stream(amc_state S, amc_state S_out, am
             temp_particle t;
             t.x = q.x; t.y = q.y; t.z = q.z; t.vx = q.vx; t.vy = q.vy; t.vz = q.vz;
             t.d = q.d; t.dx = q.dx; t.dy = q.dy; t.dz = q.dz; t.flag = q.flag ? 1 : 0; t.nwall = 0; t.nerr = 0;
-            temp_cases_particle<true>(P, O, TP->g, (unsigned int)O.step, TP->D, (int)p, px, py, pz, t);
+            temp_cases_particle<true, TEMP - 1>(P, O, TP->g, (unsigned int)O.step, TP->D, (int)p, px, py, pz, t);
             q.x = t.x; q.y = t.y; q.z = t.z; q.vx = t.vx; q.vy = t.vy; q.vz = t.vz;
             q.d = t.d; q.dx = t.dx; q.dy = t.dy; q.dz = t.dz; q.flag = t.flag != 0;
             cn.nwall += t.nwall; cn.nerr += t.nerr;
@@ -371,6 +373,12 @@ static void launch_k_stream(amc_ctx *c, hipStream_t stream, unsigned blocks, int
                             const amc_lists &B, int build, const amc_lazy &L, const amc_commit_args &C, const amc_ovl &V)
 {
     const bool cases = (stages & AMC_ST_TEMP_CASES) != 0;
+    if (cases && amc_wall_law_kind(c) == AMC_WALL_LAW_MAXWELL) {        // (a launch of its own: every other launch is what it was)
+        AMC_LAUNCH_ON(c, stream, (k_stream<AMC_GEOM_PORE_ENERGISED, 1 + AMC_WALL_LAW_MAXWELL>), dim3(blocks), dim3(threads), S, S_out,
+                      amc_wall_law_params(c), O, dt, stages, lo, hi, keep_prior, bounds_slot, c->G, B, build, L, C, V,
+                      (const amc_temp_pass *)c->TD.pass);
+        return;
+    }
     auto *k = k_stream<AMC_GEOM_CUBE>;
     switch (c->P.geometry) {
     case AMC_GEOM_CUBE: break;

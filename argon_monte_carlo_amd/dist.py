@@ -655,6 +655,12 @@ class ShardedTemperatureSimulation(ShardedSimulation):
         if self._device_rng is None:
             raise ValueError("this ShardedTemperatureSimulation was built without device_rng_seed")
 
+    def set_wall_law(self, kind, alpha_coated=None, alpha_gap=None):
+        """``TemperatureSimulation.set_wall_law`` on this rank's context: every rank calls it with the same arguments (host state,
+        nothing is communicated)."""
+        from .energised import set_wall_law
+        set_wall_law(self.engine, self._device_rng, kind, alpha_coated, alpha_gap)
+
     def _device_step(self, dt, row):
         """cases on the shard | the hit results of all ranks, summed in ascending particle index on every rank | bounds |
         the sweep of the whole system: all enqueued, nothing waits for the host"""

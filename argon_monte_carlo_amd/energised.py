@@ -662,6 +662,43 @@ def device_rng_config(consts, seed, n_gl=32):
     return g
 
 
+WALL_LAWS = ("reference", "maxwell")         # by AMC_WALL_LAW_* (include/argonmc-walllaw.h)
+
+
+def set_wall_law(engine, device_rng, kind, alpha_coated=None, alpha_gap=None):
+    """``set_wall_law`` of the simulations: the law by name ("reference" | "maxwell" | None: as never set) on ``engine``;
+    the two alpha default to the parameters'.  Raises without a device-RNG configuration (the host hand-over is the reference's)."""
+    if device_rng is None:
+        raise ValueError("a wall law needs the device-RNG mode: build the simulation with device_rng_seed")
+    if kind is not None and kind not in WALL_LAWS:
+        raise ValueError(f"unknown wall law {kind!r}: one of {WALL_LAWS} or None")
+    engine.wall_law(None if kind is None else WALL_LAWS.index(kind), alpha_coated, alpha_gap)
+
+
+def wall_law_checkpoint(engine):
+    """what a checkpoint carries of the law in force: nothing under the reference law (a file without the key loads with it),
+    else ``wall_law`` = float64[3] (kind, alpha_coated, alpha_gap)"""
+    law = engine.wall_law_get()
+    return {} if law[0] == 0 else {"wall_law": wall_law_to_array(law)}
+
+
+def wall_law_to_array(law):
+    return np.array([float(v) for v in law], dtype=np.float64)
+
+
+def wall_law_from_array(arr):
+    arr = np.asarray(arr, dtype=np.float64)
+    return int(arr[0]), float(arr[1]), float(arr[2])
+
+
+def wall_law_restore(engine, arr=None):
+    """the inverse of ``wall_law_checkpoint``; None (a checkpoint without the key): the reference law"""
+    if arr is None:
+        engine.wall_law(None)
+    else:
+        engine.wall_law(*wall_law_from_array(arr))
+
+
 def sum_device_cases(results):
     """Per-step sums from the per-hit results of the seven cases, accumulated like drive_energised_cases does
     (left-to-right in ascending particle index within a case, cases in Temp:708-751 order).  ``results[case]`` =

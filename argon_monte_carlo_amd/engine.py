@@ -7,7 +7,7 @@ import numpy as np
 
 from . import _lib
 from . import samplers as S
-from ._abi import AMC_K_NAMES, AmcParams, AmcPathRecord, AmcStepStats, path_record_dtype
+from ._abi import AMC_K_NAMES, AmcParams, AmcPathRecord, AmcStepStats, AmcWallLaw, path_record_dtype
 
 _dp = C.POINTER(C.c_double)
 _i64p = C.POINTER(C.c_int64)
@@ -612,6 +612,25 @@ class EnergisedEngine(Engine):
     def set_step(self, step):
         """Index of the next step: the step word of the device draws (a resumed run continues the interrupted one's)."""
         self._ck(self.lib.amc_set_step(self._ctx, int(step)))
+
+    # ---- the wall law of the device-RNG steps (include/argonmc-walllaw.h, DESIGN.md 21) ------------------------------------
+    def wall_law(self, kind=None, alpha_coated=None, alpha_gap=None):
+        """Set the law the next device-RNG steps apply to a hit: ``kind`` AMC_WALL_LAW_REFERENCE / AMC_WALL_LAW_MAXWELL (None:
+        back to the reference law, as never set); the two alpha default to the parameters' ``alpha_coated`` / ``alpha_gap``."""
+        if kind is None:
+            self._ck(self.lib.amc_temp_wall_law(self._ctx, None))
+            return
+        law = AmcWallLaw()
+        law.struct_size, law.kind = C.sizeof(AmcWallLaw), int(kind)
+        law.alpha_coated = float(self.params.alpha_coated if alpha_coated is None else alpha_coated)
+        law.alpha_gap = float(self.params.alpha_gap if alpha_gap is None else alpha_gap)
+        self._ck(self.lib.amc_temp_wall_law(self._ctx, C.byref(law)))
+
+    def wall_law_get(self):
+        """(kind, alpha_coated, alpha_gap) of the law in force."""
+        law = AmcWallLaw()
+        self._ck(self.lib.amc_temp_wall_law_get(self._ctx, C.byref(law)))
+        return int(law.kind), float(law.alpha_coated), float(law.alpha_gap)
 
     def temp_timestep(self, dt, sampler, energies):
         """One iteration of Temperature_Pore_MC.py's loop (Temp:662-853)."""

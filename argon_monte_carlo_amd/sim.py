@@ -550,6 +550,21 @@ class TemperatureSimulation(Simulation):
         self.steps_done += nsteps
         return st
 
+    # ---- the wall law of the device-RNG mode ---------------------------------------------------------------
+    def set_wall_law(self, kind, alpha_coated=None, alpha_gap=None):
+        """What a hit of the energised walls does from the next step on: "reference" (the reference's recipe, the default) or
+        "maxwell" — with probability alpha a diffuse re-emission at the local wall temperature (Knudsen's cosine law), else a
+        specular reflection; None: back to the default.  ``alpha_coated`` / ``alpha_gap`` default to the parameters'.  Needs
+        ``device_rng_seed``."""
+        from .energised import set_wall_law
+        set_wall_law(self.engine, self._device_rng, kind, alpha_coated, alpha_gap)
+
+    def wall_law(self):
+        """(name, alpha_coated, alpha_gap) of the law in force."""
+        from .energised import WALL_LAWS
+        kind, ac, ag = self.engine.wall_law_get()
+        return WALL_LAWS[kind], ac, ag
+
     # ---- sampled surfaces (surface.py, DESIGN.md 11; the reference reports three sums per step) -------------------------
     def _samplers(self):
         return S.ALL
@@ -576,7 +591,9 @@ class TemperatureSimulation(Simulation):
     def _checkpoint_extra(self):
         np_state = self.sampler.np_rng.get_state()
         py_state = self.sampler.py_rng.getstate()
-        return dict(momentum=np.array([float(v) for v in self.momentum_z_change_per_step]),
+        from .energised import wall_law_checkpoint
+        return dict(**wall_law_checkpoint(self.engine),
+                    momentum=np.array([float(v) for v in self.momentum_z_change_per_step]),
                     energy_cold=np.array([float(v) for v in self.energy_transfer_cold_per_step]),
                     energy_hot=np.array([float(v) for v in self.energy_transfer_hot_per_step]),
                     zero_flags=np.array(self._zero_flags, dtype=bool).reshape(-1, 3), total_errs=int(self.total_errs),
@@ -590,6 +607,8 @@ class TemperatureSimulation(Simulation):
         self.energy_transfer_hot_per_step = z["energy_hot"].tolist()
         self._zero_flags = [tuple(bool(b) for b in row) for row in z["zero_flags"]]
         self.total_errs = int(z["total_errs"])
+        from .energised import wall_law_restore
+        wall_law_restore(self.engine, z["wall_law"] if "wall_law" in z else None)
         if self._device_rng is not None:
             # the device draws are keyed by the step index: the resumed run counts on from the checkpoint's (the cadence of the
             # sampled fields then needs no offset of its own)

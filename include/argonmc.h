@@ -538,6 +538,9 @@ int amc_wall_contacts(amc_ctx *ctx, int case_id, double *contact_xyz, size_t cap
 /* ---- overlap removal of a synthetic start: whole-system search, losers redrawn by counter (opt-in) ------------ */
 #include "argonmc-ic.h"
 
+/* ---- the wall law of the device-RNG energised pore: the reference's recipe or Maxwell's diffuse / specular model (opt-in) */
+#include "argonmc-walllaw.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,9 +3,10 @@
 kernel-class times of a separate, profiled run.  It calls nothing but ``sim.run``, so it measures whatever that is: the
 host-free run (AMC_TEMP_RUN_UNFUSED=1: with the single step's three streaming passes), or a loop of steps.  One JSON line.
 
-    python tools/temp_run_cost.py [--reps 5] [--steps 200] [--n 1000000] [--surface]
+    python tools/temp_run_cost.py [--reps 5] [--steps 200] [--n 1000000] [--surface] [--wall-law maxwell]
 
 --surface samples the surfaces on the default grid in every step of every run.
+--wall-law sets the wall law of the run (default: none is set, the reference law).
 
 AMC_COST_TREE=<directory> measures the package of another checkout (an earlier commit, built there) with this same script.
 """
@@ -29,11 +30,14 @@ def main():
     ap.add_argument("--n", type=int, default=1_000_000)
     ap.add_argument("--label", default="")
     ap.add_argument("--surface", action="store_true")
+    ap.add_argument("--wall-law", default=None)
     a = ap.parse_args()
     sim = TemperatureSimulation(n=a.n, device_rng_seed=17)
     sim.set_state(*IC.pore_ic(sim.params, sim.consts, seed=17))        # the benchmark's initial conditions
     if a.surface:
         sim.enable_surface()
+    if a.wall_law:
+        sim.set_wall_law(a.wall_law)
     sim.run(20)                                                         # warm-up (allocations, first launches)
     sim.engine.synchronize()
     times = []
@@ -54,7 +58,7 @@ def main():
     print(json.dumps(dict(workload="temp_device_rng", label=a.label, form=form, n=a.n, steps=a.steps, reps=len(times),
                           us_per_step_median=round(statistics.median(times), 2), us_per_step_min=round(min(times), 2),
                           us_per_step_max=round(max(times), 2), kernel_us_per_step=classes,
-                          steps_done=sim.steps_done, surface=bool(a.surface))))
+                          steps_done=sim.steps_done, surface=bool(a.surface), wall_law=a.wall_law or "unset")))
     sim.close()
 
 
