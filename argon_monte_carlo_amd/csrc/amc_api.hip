@@ -162,6 +162,7 @@ static void read_env(amc_ctx *c)
     c->overlap_mode = env_int("AMC_OVERLAP", 0);
     c->overlap_split = env_nonzero("AMC_OVERLAP_SPLIT");                                 // (experiment)
     c->cw_blocks_env = env_int("AMC_CW_BLOCKS", 0);
+    c->cw_dense_max = std::max(env_int("AMC_CW_DENSE_MAX", c->cw_dense_max), 0);        // (0: the list form always)
     c->ordered_always = env_nonzero("AMC_ORDERED_ALWAYS");
     c->od_max_n = env_ll("AMC_OD_MAX_N", c->od_max_n);                                   // (tests, experiments)
     c->od_ahead = std::min(std::max(env_int("AMC_OD_AHEAD", c->od_ahead), 1), 32);       // (experiments)
@@ -701,9 +702,9 @@ int amc_kernel_times(amc_ctx *c, double *total_ms, int64_t *launches)
         long long h[128];
         hipMemcpy(h, c->d_dbg, sizeof h, hipMemcpyDeviceToHost);
         const double n = h[11] > 0 ? (double)h[11] : 1.0;
-        fprintf(stderr, "[amc k_resolve phases, us/launch] count-left %.1f claim %.1f | rounds: collect %.1f pairs %.1f clusters>=3: sort+load %.1f emulate %.1f | overlay %.1f validate %.1f commit %.1f | rounds %.2f cand %.1f complex-members %.2f launches %lld (idle hand-over only %lld) | body: labels in the work space %lld moved there %lld layers in LDS %lld rounds split %lld heads shared %lld sorted %lld pool global %lld sort global %lld later %lld clusters by a wave %lld by one lane %lld most complex members %lld\n",
+        fprintf(stderr, "[amc k_resolve phases, us/launch] count-left %.1f claim %.1f | rounds: collect %.1f pairs %.1f clusters>=3: sort+load %.1f emulate %.1f | overlay %.1f validate %.1f commit %.1f | rounds %.2f cand %.1f complex-members %.2f launches %lld (idle hand-over only %lld) | body: labels in the work space %lld moved there %lld layers in LDS %lld rounds split %lld heads shared %lld sorted %lld pool global %lld sort global %lld later %lld clusters by a wave %lld by one lane %lld most complex members %lld dense sweeps linked %lld\n",
                 h[0] / n / 100.0, h[1] / n / 100.0, h[6] / n / 100.0, h[7] / n / 100.0, h[2] / n / 100.0, h[3] / n / 100.0, h[14] / n / 100.0, h[4] / n / 100.0, h[5] / n / 100.0,
-                h[8] / n, h[9] / n, h[10] / n, h[11], h[12], h[32], h[33], h[34], h[35], h[36], h[37], h[38], h[39], h[40], h[41], h[42], h[43]);
+                h[8] / n, h[9] / n, h[10] / n, h[11], h[12], h[32], h[33], h[34], h[35], h[36], h[37], h[38], h[39], h[40], h[41], h[42], h[43], h[44]);
         fprintf(stderr, "[amc host candidate count] %d (what the next launch plan is chosen from)\n", c->h_host_ncand ? (int)*c->h_host_ncand : -1);
         if (h[12] > 0)
             fprintf(stderr, "[amc k_resolve idle hand-over, us/launch] entry -> counts read %.2f, -> hand-over written %.2f, -> through the barrier %.2f (%lld launches)\n",
@@ -720,8 +721,8 @@ int amc_kernel_times(amc_ctx *c, double *total_ms, int64_t *launches)
             const double nl = h[25] > 0 ? (double)h[25] : 1.0;
             static const char *cn[8] = {"pair", "3-cluster", "4+-cluster", "not owner", "pair+again", "3-cluster+again", "4+-cluster+again", "not owner+again"};
             static const char *pn[12] = {"graph", "walk", "reserve", "small: after emulate", "pair emulate | by the wave: emulate", "publish", "grid probe", "first hop", "particles", "set-up", "overlay probe", "small: prepare"};
-            fprintf(stderr, "[amc k_clusters_wide] working waves %lld in %lld launches; launch span (first working wave in -> last out) %.2f us, last out -> ordered workgroup in %.2f us, longest wave ever %.2f us\n",
-                    s[3], h[25], h[27] / nl / 100.0, h[26] / nl / 100.0, longest / 100.0);
+            fprintf(stderr, "[amc k_clusters_wide] working waves %lld in %lld launches; launch span (first working wave in -> last out) %.2f us, last out -> ordered workgroup in %.2f us, longest wave ever %.2f us; dense scans %lld\n",
+                    s[3], h[25], h[27] / nl / 100.0, h[26] / nl / 100.0, longest / 100.0, s[125]);
             fprintf(stderr, "[three-particle path of lane 0] %lld times, %lld continued from the pair's hit; loads + slots %.2f us, emulation %.2f us\n", s[5], s[6],
                     s[7] / (double)std::max<long long>(1, s[5]) / 100.0, s[124] / (double)std::max<long long>(1, s[5]) / 100.0);
             fprintf(stderr, "[pair-wave lifetimes, 2.5 us buckets]");

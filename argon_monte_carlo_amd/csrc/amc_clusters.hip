@@ -34,6 +34,13 @@
 //      at agent scope).  Two clusters whose new positions conflict are both pushed before either probes, or one probes
 //      after the other's push: at least one of them sees the other.  That hit becomes a merge edge for the ordered
 //      workgroup, which merges, re-emulates from the pre-sweep state and validates again.
+//      That is the LIST form of the second half.  A sweep of up to A.dense_max candidates (all of them in one pass of the
+//      launch) takes the DENSE form instead: nothing is linked — the candidates' history entries of the whole sweep are one
+//      contiguous array (candidate k owns 4k .. 4k + 3), every record of it already written through, so each wave, once
+//      its own final records have left, reads that array once and tests it against its new positions (cw_scan_dense).
+//      Whichever of two conflicting clusters reads later sees the other's records; a record met half-written or superseded
+//      can only add a merge edge too many.  The ordered workgroup, whose probe walks the overlay lists, links the wide
+//      entries itself in such a sweep (amc_resolve.hip).  The choice is uniform over the launch.  DESIGN.md 4.1.
 //
 // Bound: latency — ~6 dependent memory round trips of 0.5-0.6 us and ~2,000 instructions of one lane per candidate
 //  — which is why the candidates are spread as thinly as the launch allows: CW_BLOCKS one-wave
@@ -98,6 +105,7 @@ struct cw_lds {
     cw_item item[CW_ITEMS];
     int next[CW_ITEMS];         // overlay `next` of every published item (own entries are stepped over without a load)
     int nitems;
+    int ncand;                  // the sweep's (clamped) candidate count, for the dense scan behind the loop
     int unv[64];                // the running emulation of the owner got entries the wave cannot publish
     double pool_d[10][CW_MAXM];
     int pool_tmp[CW_MAXM], pool_pidx[CW_MAXM], pool_slot[CW_MAXM];
@@ -190,6 +198,97 @@ AMC_DEV void cw_probe_overlay(const rs_args &A, rs_shared *wc, cw_lds &L, const 
         // (only final emulations are ever published, but the ordered workgroup's rounds are told apart the same way)
         if (rs_hist_gen(o) != __hip_atomic_load(amc_g((int *)&W.sl_meta[s2]) + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) continue;
         rs_add_edge(W, wc, me.p, -(s2 + 2));                    // (the other end as a slot)
+    }
+}
+
+// The DENSE form of the overlay half (sweeps of up to A.dense_max candidates; the choice is uniform over the launch).
+// Candidate k brings its history entries statically (4k .. 4k + 3), so the new positions of ALL clusters of the sweep are one
+// contiguous array of 4 ncand records, each written through by its cluster's emulation: the wave reads that array once —
+// independent, coalesced, agent-scope loads (cw_load_hist) — instead of linking its own records into per-cell lists and
+// walking the lists around every position.  Nothing is pushed: no ov_head, no ov_next, no L.next.
+//   D1: the caller has waited (vmcnt(0)) for the wave's own final records before the first load here.
+//   D2: every load of another cluster's record is a global agent-scope load.
+// Of two conflicting clusters, the one whose scan misses the other's final record scanned before that record was visible,
+// hence before the other's drain, hence before the other's scan, which therefore sees the first one's (drained) records: at
+// least one of the two adds the merge edge.  A record met half-written or superseded can only add a spurious edge (the
+// ordered workgroup then re-emulates from the pre-sweep state, with the same result), never hide one.  DESIGN.md 4.1.
+// A record counts as in cw_probe_overlay: round non-zero (the detect kernel cleared the tag words of all four entries, a
+// failed hit writes round 0), slot not in the item owner's cluster, closer than cr2i, round equal to its slot's.  Counter-
+// allocated entries (h_off and beyond) are not scanned: their clusters carry a self edge and are redone anyway.
+// A candidate's SECOND pair of entries (4k + 2, 4k + 3) is almost always empty: only its tag words are read with the first
+// pairs' records; the coordinates follow where a tag is set.
+// Shape: the wave's items are taken one after the other (the same item in every lane, its fields made scalar), the lane's
+// records tested against it without a branch — round, distance, and "not a record of the owner's first candidate", which
+// keeps a pair's own two records off the slow path — into a bit per record; what is left (a neighbour, or a larger
+// cluster's own further records) goes through ONE copy of the slot / round tests.  Written that way for the scalar
+// registers: a nest of divergent branches per record, eight times over, cost both product instantiations a dozen more
+// spilled SGPRs than tests/test_isa_addressing.py allows.
+#define CW_DENSE_U 8        // first-pair records (and second-pair tags) a lane has in flight per trip: 256 candidates per trip
+AMC_DEV void cw_dense_hit(const amc_resolve_ws &W, rs_shared *wc, cw_lds &L, int own, int p, int s2, int g2)
+{
+    const int nm = L.nm[own];
+    if ((unsigned int)s2 >= (unsigned int)W.max_slots) return;      // (every record with a round names a slot of this sweep)
+    bool mine = false;
+    for (int m = 0; m < nm; m++) mine |= L.msl[own][m] == s2;
+    if (mine || g2 != __hip_atomic_load(amc_g((int *)&W.sl_meta[s2]) + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+    rs_add_edge(W, wc, p, -(s2 + 2));                           // (the other end as a slot)
+}
+AMC_DEV void cw_scan_dense(const amc_resolve_ws &W, rs_shared *wc, cw_lds &L, int nit_in, int ncand, double cr2i, int lane)
+{
+    const int npair = 2 * ncand;            // first-pair records: index i stands for entry 4 (i / 2) + (i & 1)
+    const int nit = __builtin_amdgcn_readfirstlane(nit_in);
+    if (nit == 0) return;                   // (a wave without a candidate — most waves of a small sweep — reads nothing)
+    for (int base = 0; base < npair; base += 64 * CW_DENSE_U) {         // wave-uniform
+        double4 o[CW_DENSE_U];
+        double w2[CW_DENSE_U];
+        int gen[CW_DENSE_U];                // round of o[u]; 0 (counts for nothing) behind the end of the array
+        unsigned int second = 0;            // bit u: the second-pair entry behind o[u] has a round
+#pragma unroll
+        for (int u = 0; u < CW_DENSE_U; u++) {      // (indices clamped, not branched around: the loads go out together)
+            const int i = base + 64 * u + lane, ic = min(i, npair - 1), h = 4 * (ic >> 1) + (ic & 1);
+            o[u] = cw_load_hist(W, h);
+            w2[u] = __hip_atomic_load(amc_g((const double *)&W.hist[h + 2]) + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+#pragma unroll
+        for (int u = 0; u < CW_DENSE_U; u++) {
+            // (in range as a word of ones, by arithmetic: eight lane masks kept across the loads were sixteen scalar registers)
+            const int in = (base + 64 * u + lane - npair) >> 31;
+            gen[u] = rs_hist_gen(o[u]) & in;
+            second |= ((int)(__double_as_longlong(w2[u]) >> 32) & in) != 0 ? 1u << u : 0u;
+        }
+        for (int t = 0; t < nit; t++) {
+            const int pad = __builtin_amdgcn_readfirstlane(L.item[t].pad), own = __builtin_amdgcn_readfirstlane(L.item[t].own);
+            if ((pad & 1) || (pad >> 1) != __builtin_amdgcn_readfirstlane(L.gen[own])) continue;   // a failed hit / an item of a dropped emulation
+            const double x = L.item[t].x, y = L.item[t].y, z = L.item[t].z;
+            const int kc = __builtin_amdgcn_readfirstlane(L.cnd[own][0]);
+            unsigned int hits = 0;
+#pragma unroll
+            for (int u = 0; u < CW_DENSE_U; u++) {
+                const double ax = o[u].x - x, ay = o[u].y - y, az = o[u].z - z;
+                const bool pass = (ax * ax + ay * ay + az * az < cr2i) & (gen[u] != 0) & (((base + 64 * u + lane) >> 1) != kc);
+                hits |= pass ? 1u << u : 0u;
+            }
+            while (hits) {
+                const int u = __ffs((int)hits) - 1;
+                hits &= hits - 1;
+                int s2 = 0, g2 = 0;
+#pragma unroll
+                for (int e = 0; e < CW_DENSE_U; e++) { s2 = (e == u) ? rs_hist_slot(o[e]) : s2; g2 = (e == u) ? gen[e] : g2; }
+                cw_dense_hit(W, wc, L, own, L.item[t].p, s2, g2);
+            }
+        }
+        while (second) {                            // rare: a cluster with more hits than candidates
+            const int u = __ffs((int)second) - 1;
+            second &= second - 1;
+            const int i = base + 64 * u + lane;
+            const double4 o2 = cw_load_hist(W, 4 * (i >> 1) + (i & 1) + 2);
+            for (int t = 0; t < nit; t++) {
+                const cw_item me = L.item[t];
+                if ((me.pad & 1) || (me.pad >> 1) != L.gen[me.own]) continue;
+                const double ax = o2.x - me.x, ay = o2.y - me.y, az = o2.z - me.z;
+                if (rs_hist_gen(o2) != 0 && ax * ax + ay * ay + az * az < cr2i) cw_dense_hit(W, wc, L, me.own, me.p, rs_hist_slot(o2), rs_hist_gen(o2));
+            }
+        }
     }
 }
 
@@ -296,11 +395,21 @@ __global__ __launch_bounds__(64 * CW_WPB) void k_clusters_wide(rs_args A_in_kern
     if (wave_id == 0 && lane == 0) {
         amc_g(wc)->active = 1; amc_g(wc)->ncand = ncand;
         if (A.od_done) *amc_g(A.od_done) = A.od_tick;   // (host-mapped: how far the host may run ahead)
+        // a dense sweep leaves the candidate loop after ONE pass: a threshold the host did not cap at what a pass holds
+        // (rs_dense_max) would drop candidates silently — the step is failed instead (reported like an overflow)
+        if (ncand <= A.dense_max && ncand > nwaves * per) { amc_g(wc)->ovf = 1; rs_raise(W); }
     }
     if (ncand == 0) return;
     const int s_off = 2 * ncand;        // first counter-allocated slot of this sweep (candidate k owns slots 2k, 2k + 1)
     const int h_off = 4 * ncand;        // first counter-allocated history entry (candidate k owns the pairs 4k and 4k + 2)
     const double cr2i = A.P.collision_range * A.P.collision_range * AMC_CR2_INFLATE;
+    // The form of the overlay half (4b), dense or lists: decided from the count every wave reads from the same word after the
+    // detect kernel has finished, so uniform over the launch — a launch that mixed the two forms would break either form's
+    // argument.  The host caps dense_max at what ONE pass of this launch holds (rs_dense_max): a dense sweep leaves the loop
+    // below after its only pass and scans behind it.  (Evaluated where it is used, from the LDS copies, not kept in a flag.)
+#define CW_DENSE(n) (__builtin_amdgcn_readfirstlane((n) <= A.dense_max) != 0)
+    L.ncand = ncand;
+    if (lane == 0) L.nitems = 0;        // (a wave without a candidate has no items when it comes to the dense scan)
     rs_work K;
     K.x = L.pool_d[0]; K.y = L.pool_d[1]; K.z = L.pool_d[2]; K.vx = L.pool_d[3]; K.vy = L.pool_d[4]; K.vz = L.pool_d[5];
     K.d = L.pool_d[6]; K.dx = L.pool_d[7]; K.dy = L.pool_d[8]; K.dz = L.pool_d[9];
@@ -322,6 +431,7 @@ __global__ __launch_bounds__(64 * CW_WPB) void k_clusters_wide(rs_args A_in_kern
     if (DBG && dbg__) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); CW_STAMP(7); }      // entry -> candidate count and my first candidate have arrived
     int cat__ = 0;
     long long d_cont = 0, d_three = 0, d_t_load = 0, d_t_emu = 0;      // (diagnostic: the three-particle path of lane 0)
+    long long d_dense = 0;              // (diagnostic: this wave validated by the dense scan)
     for (int k0 = wave_id * per; k0 < ncand; k0 += nwaves * per) {       // wave-uniform trip count
         const int k = k0 + lane;
         const bool valid = lane < per && k < ncand;
@@ -566,6 +676,7 @@ __global__ __launch_bounds__(64 * CW_WPB) void k_clusters_wide(rs_args A_in_kern
         rs_wave_sync();
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // the history records (write-through stores) have left
         const int nit = L.nitems < CW_ITEMS ? L.nitems : CW_ITEMS;
+        if (CW_DENSE(ncand)) break;     // small sweep: nothing to link, its only pass ends here — the scan follows the loop
         for (int t0 = 0; t0 < nit; t0 += 64) {
             const int t = t0 + lane;
             if (t < nit) L.next[t] = -1;
@@ -605,6 +716,23 @@ __global__ __launch_bounds__(64 * CW_WPB) void k_clusters_wide(rs_args A_in_kern
         rs_wave_sync();
         CW_STAMP(10);
     }
+    asm volatile("" ::: "memory");
+    if (CW_DENSE(L.ncand)) {
+        // The DENSE form of the overlay half: the wave's final records are out (rule D1: the wait at 4b), the candidates'
+        // records of the whole sweep are read once and tested against the wave's items (cw_scan_dense).
+        // It stands behind the loop and takes everything it needs afresh — count and items from LDS, the range and the
+        // counters' address from the argument copy, the lane from the hardware — so that it lengthens no value's life across
+        // the loop: written inside the loop, or fed from the loop's variables, it cost the product instantiations 4 to 18
+        // more spilled SGPRs than tests/test_isa_addressing.py allows.
+        const int nit = L.nitems < CW_ITEMS ? L.nitems : CW_ITEMS;
+        CW_STAMP(5);
+        if (DBG) d_dense = 1;
+        const int lane_again = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+        const double cr = A.P.collision_range;
+        cw_scan_dense(W, (rs_shared *)W.wctl, L, nit, L.ncand, cr * cr * AMC_CR2_INFLATE, lane_again);
+        rs_wave_sync();
+        CW_STAMP(10);
+    }
     if (timed__) {
         // Every wave keeps its figures in 64 words of its own (plain read-modify-write: a wave id occurs once per launch and
         // launches are serial).  The first version added them to shared words with atomics: a few hundred waves hitting one
@@ -614,7 +742,7 @@ __global__ __launch_bounds__(64 * CW_WPB) void k_clusters_wide(rs_args A_in_kern
         R[0] = t_enter__; R[1] = t_exit; R[2] = A.sweep_epoch;          // (this launch: the ordered workgroup forms the span)
         R[3] += 1;
         if (life > R[4]) R[4] = life;
-        R[5] += d_three; R[6] += d_cont; R[7] += d_t_load; R[124] += d_t_emu;   // (R[124..127]: the tail of the last category's figures, never reached)
+        R[5] += d_three; R[6] += d_cont; R[7] += d_t_load; R[124] += d_t_emu; R[125] += d_dense;   // (R[124..127]: the tail of the last category's figures, never reached)
         R[8 + cat__] += life; R[16 + cat__] += 1;                       // by kind of wave
         for (int e = 0; e < 12; e++) R[32 + 12 * cat__ + e] += t_acc[e];
         if (cat__ == 0) { int bk = (int)(life / 250); if (bk > 7) bk = 7; R[24 + bk] += 1; }

@@ -53,6 +53,7 @@ struct amc_adj {
     // emulates the candidate's cluster uses them without any allocation; here they are marked empty
     int4 *sl_meta;
     int *sl_hits, *ev_gen;
+    double4 *hist;              // the tag word of the candidate's four history entries is cleared too (see amc_push_candidate)
     unsigned int epoch;
     unsigned long long *mark;
 };
@@ -89,6 +90,12 @@ AMC_DEV int amc_push_candidate(int a, int b, int max_cand, amc_dev_counters *cnt
             atomicAnd(&D.sl_hits[2 * k], 0);    // (atomics, like the increments: no value needed back)
             atomicAnd(&D.sl_hits[2 * k + 1], 0);
             *(int4 *)&D.ev_gen[4 * k] = make_int4(0, 0, 0, 0);      // (its two pairs of history / event entries: 4k .. 4k + 3)
+            // The tag word (slot | round << 32) of those four entries: the wide kernel's dense validation reads the
+            // candidates' entries of the WHOLE sweep, and what the last sweep left at 4k names slot 2k with round 1 — valid
+            // again the moment this sweep's owner initialises slot 2k, before it has written a record of its own.  Plain
+            // stores behind the others (the kernel boundary publishes them), outside the exchange chain above.
+#pragma unroll
+            for (int e = 0; e < 4; e++) D.hist[4 * k + e].w = 0.0;
         }
         return (int)k;
     }
@@ -443,7 +450,7 @@ hipError_t amc_launch_detect(amc_ctx *c)
     // workgroup itself, a large one by the wide commit kernel
     c->step.plan_split = !c->allpairs && !(c->h_host_ncand && *c->h_host_ncand <= c->plan_small);
     D.head = c->allpairs ? nullptr : c->W.adj_head; D.rec = c->W.cand4; D.sd = c->W.cand_s; D.epoch = c->step.sweep_epoch;
-    D.sl_meta = c->W.sl_meta; D.sl_hits = c->W.sl_hits; D.ev_gen = c->W.ev_gen; D.mark = c->W.cand_mark;
+    D.sl_meta = c->W.sl_meta; D.sl_hits = c->W.sl_hits; D.ev_gen = c->W.ev_gen; D.mark = c->W.cand_mark; D.hist = c->W.hist;
     amc_prof_begin(c, AMC_K_DETECT);
     if (c->detect_ap) {
         if (n >= 16 * AP2_T && c->G.ncells > 0) {       // enough tiles to fill the chip (and a grid, whose origin and extent it uses): the register-tiled form
@@ -496,7 +503,7 @@ hipError_t amc_launch_ingest(amc_ctx *c, int world)
     c->step.sweep_epoch = next_sweep_epoch(c->step.sweep_epoch);
     c->step.plan_split = !(c->h_host_ncand && *c->h_host_ncand <= c->plan_small);
     D.head = c->W.adj_head; D.rec = c->W.cand4; D.sd = c->W.cand_s; D.epoch = c->step.sweep_epoch;
-    D.sl_meta = c->W.sl_meta; D.sl_hits = c->W.sl_hits; D.ev_gen = c->W.ev_gen; D.mark = c->W.cand_mark;
+    D.sl_meta = c->W.sl_meta; D.sl_hits = c->W.sl_hits; D.ev_gen = c->W.ev_gen; D.mark = c->W.cand_mark; D.hist = c->W.hist;
     amc_prof_begin(c, AMC_K_DETECT);
     AMC_LAUNCH(c, k_ingest_candidates, dim3(16), dim3(256), (const int *)c->MG.cand_recv, world, 2 + 2 * c->MG.cand_cap, c->MG.cand_cap,
                c->W.max_cand, c->d_cnt, D, c->MG.cand_send);

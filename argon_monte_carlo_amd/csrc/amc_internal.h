@@ -417,6 +417,9 @@ struct amc_res { void *p; amc_res_kind kind; };
 #define AMC_OD_MIN_STEPS 8      // shorter runs keep the ordered workgroup in every sweep (the run ends with a synchronisation of its own)
 #define AMC_PLAN_SMALL 430      // default of amc_ctx::plan_small: measured crossover of the two launch plans (tools/plan_sweep.sh;
                                 // experiments: environment variable AMC_PLAN_SMALL)
+#define AMC_CW_DENSE_MAX 256    // default of amc_ctx::cw_dense_max: the largest of 0 / 256 / 512 / 1024 / 2048 at which the dense scan of the
+                                // wide kernel's validation was not slower than the overlay lists at N = 1e5, 3e5 and 5e5 (DESIGN.md 7,
+                                // profiles/r21_ab_wide_dense.json; environment variable AMC_CW_DENSE_MAX, 0 = lists always)
 
 // What the launchers change as they enqueue a step: everything a rewind of amc_run's on-demand loop has to put back (it keeps
 // a copy per step, together with c->B and c->out.step).  A new per-step member of the host's goes HERE.
@@ -493,6 +496,7 @@ struct amc_ctx {
     int overlap_mode;         // AMC_OVERLAP: 0 off (default), 1 two streams, 2 the same kernels in order on one stream (debug)
     bool overlap_split;       // AMC_OVERLAP_SPLIT != 0: an overlapped run builds its lists in a kernel of its own
     int cw_blocks_env;        // AMC_CW_BLOCKS (0 = default number of wide-kernel waves)
+    int cw_dense_max = AMC_CW_DENSE_MAX;   // AMC_CW_DENSE_MAX: candidates up to which a sweep's new positions are validated by a dense scan (0: lists always)
     int stream_bs;            // AMC_STREAM_BS: block size of the streaming pass (the kept-list pools are sized for it)
     int detect_bs;            // AMC_DETECT_BS: block size of the list-based detect kernel
     bool temp_unfused;        // AMC_TEMP_UNFUSED set: the device-RNG energised mode runs one kernel triple per case

@@ -199,7 +199,8 @@ __global__ __launch_bounds__(RS_T) void k_resolve(rs_args A_in_kernarg)
     V.cap = W.max_slots;
     // (debug figures of the body, exact for a single launch: [32] launches that began with the tables in the work space,
     // [33] that moved them there later, [34] layer tables in LDS, [35 ..] rounds by path, [41] / [42] clusters emulated by
-    // a wave / by one lane, [43] the largest count of complex members in a round)
+    // a wave / by one lane, [43] the largest count of complex members in a round, [44] dense sweeps whose wide entries were
+    // linked here)
     if (A.dbg && tid == 0) { A.dbg[32] += V.label != s_label; A.dbg[34] += !resolved && !A.allpairs && 3 * A.G.gz <= RS_LAY; }
     amc_grid G = A.G;
     int rounds = 0;
@@ -463,6 +464,19 @@ __global__ __launch_bounds__(RS_T) void k_resolve(rs_args A_in_kernarg)
         const int nh = sh.nhist < W.max_hist ? sh.nhist : W.max_hist;
         // ---- validate: every new position of this round against everything outside its cluster -------------------------------
         if (!A.allpairs) {
+            // A DENSE sweep (the wide kernel's predicate, on the same count): that kernel validated its new positions against
+            // each other by scanning the candidates' records and linked nothing, but rs_probe finds other clusters' new
+            // positions through the overlay lists — so the wide entries that are still valid (round non-zero and equal to
+            // their slot's: a cluster redone in this round has moved on) are linked here, once, before the first validation.
+            if (first && wide && ncand <= A.dense_max) {
+                if (A.dbg && tid == 0) A.dbg[44] += 1;
+                for (int h = tid; h < wide_nh; h += RS_T) {
+                    const double4 r = W.hist[h];
+                    const int g = rs_hist_gen(r), s = rs_hist_slot(r);
+                    if (g == 0 || s < 0 || s >= W.max_slots || g != W.sl_meta[s].z) continue;
+                    W.ov_next[h] = atomicExch(&W.ov_head[rs_hist_cell(A, G, h)], h);
+                }
+            }
             for (int h = sh.hist_begin + tid; h < nh; h += RS_T) W.ov_next[h] = atomicExch(&W.ov_head[rs_hist_cell(A, G, h)], h);
             __syncthreads();
             if (A.dbg && tid == 0) { const long long n__ = wall_clock64(); A.dbg[14] += n__ - t_last; }
@@ -605,6 +619,13 @@ static int rs_wide_per(amc_ctx *c)
     return (int)std::min<long long>(std::max<long long>(per, 1), 64);
 }
 
+// The dense form of the wide kernel's validation takes ONE pass of the launch (the scan follows the candidate loop): the
+// threshold both resolve kernels compare the sweep's candidate count with is capped at what one pass holds.
+static int rs_dense_max(amc_ctx *c, int wide_per)
+{
+    return (int)std::min<long long>(c->cw_dense_max, (long long)amc_clusters_wide_blocks(c) * wide_per);
+}
+
 template <int GEOM>
 static void rs_launch_all(amc_ctx *c, const rs_args &A)
 {
@@ -620,6 +641,7 @@ static void rs_launch_all(amc_ctx *c, const rs_args &A)
     Aw.wide_plan = 1;
     Aw.force_mono = 0;
     Aw.wide_per = rs_wide_per(c);
+    Aw.dense_max = rs_dense_max(c, Aw.wide_per);
     amc_prof_cancel(c);                 // (the caller's bracket is re-opened below, around the kernel it is named after)
     amc_prof_begin(c, AMC_K_CLUSTERS_WIDE);
     amc_launch_clusters_wide(c, Aw);
@@ -656,6 +678,7 @@ static rs_args rs_make_args(amc_ctx *c)
     A.inv_dx = c->P.dx > 0 ? 1.0 / c->P.dx : 0.0; A.inv_dy = c->P.dy > 0 ? 1.0 / c->P.dy : 0.0; A.inv_dz = c->P.dz > 0 ? 1.0 / c->P.dz : 0.0;
     A.W.raise_dev = nullptr; A.W.raise_host = nullptr; A.W.raise_tick = 0;
     A.od_stall = nullptr; A.od_stall_host = nullptr; A.od_done = nullptr; A.od_tick = 0;
+    A.dense_max = 0;            // (set with wide_per where the wide kernel is launched)
     return A;
 }
 
@@ -668,6 +691,7 @@ hipError_t amc_launch_wide_only(amc_ctx *c, rs_args *used)
     Aw.defer_commit = 1;
     Aw.wide_plan = 1;
     Aw.wide_per = rs_wide_per(c);
+    Aw.dense_max = rs_dense_max(c, Aw.wide_per);
     Aw.W.raise_dev = c->d_od; Aw.W.raise_host = c->d_od_stall_host; Aw.W.raise_tick = c->od_tick;
     Aw.od_stall = c->d_od; Aw.od_stall_host = c->d_od_stall_host; Aw.od_done = c->d_od_done_host; Aw.od_tick = c->od_tick;
     amc_prof_begin(c, AMC_K_CLUSTERS_WIDE);

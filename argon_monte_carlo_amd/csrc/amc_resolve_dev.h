@@ -52,6 +52,10 @@ struct rs_args {
     // the host through od_done that it has run; k_resolve, launched for the sweep that raised the word, clears it
     int *od_stall, *od_stall_host, *od_done;
     int od_tick;
+    // sweeps of up to this many candidates validate their new positions against each other by a dense scan of the
+    // candidates' history records instead of per-cell overlay lists (amc_clusters.hip, 4b); 0: lists always.  Both resolve
+    // kernels decide from it and the sweep's candidate count alone, so they always agree on the form
+    int dense_max;
 };
 
 // The resolve kernels' only formal parameter is this block (offset 0 of the kernarg segment).  k_clusters_wide copies it
